@@ -4,7 +4,13 @@ synthetic MVTec-3D-shaped inputs -- BASELINE.json configs[1]: DINO ViT-B/8 + Poi
 1024-group point clouds, bf16 MFMA, batch 32 per GPU, 'bagel'-sized patch libraries
 (xyz 76 518 x 768, rgb 19 129 x 768).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line: the contract fields and `config`.  Everything else the
+benchmark measures -- `roofline`, the secondary legs and `cpu_baseline` below -- runs only with --full (--no-extras and
+--no-cpu-baseline then leave out parts of it).  --dump-outputs DIR writes what the last timed step returned to its caller, the
+image scores and pixel maps of one batch, as DIR/image_scores.npy and DIR/pixel_maps.npy (float64, rank 0; the inputs are seeded,
+so two builds can be compared output for output).
 
 With N > 1 and no WORLD_SIZE in the environment this process only LAUNCHES: it starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child before anything touches the GPU and
@@ -28,8 +34,8 @@ the ranks, all-gather of every rank's 16-bit queries, per-shard distance GEMM, O
 (distance, global row) keys over RCCL -- for the bagel library and for all ten MVTec-3D class sizes (65 856 ... 113 209
 rows).  CMDIAD_FORCE_DIST=1 exercises that path with a world of one rank on a single GPU.
 
-Prints ONE JSON line (rank 0) with the fields of the bench contract plus `roofline` (dominant kernel: the xyz-library
-distance GEMM, MFMA-bound; duration from HIP events inside the timed region) and, at N = 1, `cpu_baseline` (the CPU
+Prints ONE JSON line (rank 0) with the fields of the bench contract; with --full also `roofline` (dominant kernel: the
+xyz-library distance GEMM, MFMA-bound; duration from HIP events inside the timed region) and, at N = 1, `cpu_baseline` (the CPU
 oracle pipeline timed on a bounded sample on this box's host cores: best thread count, the reference's default 6
 threads, and all cores) and `dropin_b1` (the B = 1 drop-in protocol the reference's main.py drives).
 
@@ -73,13 +79,24 @@ def _traffic_with_ratio(t, bytes_alg):
     return t
 
 
+def dump_outputs(directory, last):
+    """--dump-outputs: the last timed step's image scores [B] and pixel maps [B, 224, 224], float64 as the predictor returns them
+    (12.9 MB at batch 32)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    scores, maps = last["outputs"]
+    for name, a in (("image_scores", scores), ("pixel_maps", maps)):
+        a = np.asarray(a)
+        np.save(os.path.join(directory, name + ".npy"), a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=4)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary legs (h2d_inclusive, dropin_b1, sharded_search)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary legs (h2d_inclusive, dropin_b1, sharded_search)")
     ap.add_argument("--cpu-images", type=int, default=10)
     ap.add_argument("--workload", choices=("dino_pointmae", "mtfi"), default="dino_pointmae",
                     help="dino_pointmae = BASELINE configs[1] (both modalities extracted, the headline workload); mtfi = the "
@@ -95,8 +112,17 @@ def main():
                          "dealt to the ranks by LPT, metric dictionaries gathered at the end (cmdiad_amd/evaluate.py)")
     ap.add_argument("--class-scale", type=float, default=0.05, help="train images per class = MVTec 3D-AD count x this (1.0 = full size)")
     ap.add_argument("--class-test", type=int, default=20, help="test images per synthetic class (3 of every 10 anomalous)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: `roofline`, the secondary legs and `cpu_baseline` (a plain "
+                         "run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (image scores, pixel maps; float64) as DIR/<name>.npy")
     ap.add_argument("--selftest-launch", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.evaluate:
+        ap.error("--dump-outputs writes the outputs of the timed predict steps; --evaluate has none")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch(args.gpus, sys.argv[1:]))        # before ANY GPU call in this process
@@ -191,14 +217,17 @@ def main():
     torch.cuda.synchronize()
     pred.live_rows.zero_()
     pred.xyz_searches = 0
+    last = {}
     t0 = time.perf_counter()
-    run_steps(pred, batches, args.steps, first)
+    run_steps(pred, batches, args.steps, first, last)
     torch.cuda.synchronize()
     if group is not None:
         td.barrier()
     dt = time.perf_counter() - t0
     q_live = float(pred.live_rows.item()) / max(pred.xyz_searches, 1)   # query rows per xyz search after the exact row de-duplication
-    l2_alone_ms = isolated_xyz_search_ms(pred)                          # after the timed region: the dominant kernel alone
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+    l2_alone_ms = isolated_xyz_search_ms(pred) if args.full else None   # after the timed region: the dominant kernel alone
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
     if group is not None:
         td.all_reduce(tmax, op=td.ReduceOp.MAX)
@@ -242,21 +271,22 @@ def main():
                        "hip_graphs": bool(pred.use_graph),
                        "search_operands": ("bf16" if st["bank_xyz"].bf16.dtype == torch.bfloat16 else "fp16") + " (fp32 accumulate, exact fp32 re-score of the winner)",
                        "weights": "seeded random init (no checkpoints offline)"},
-            "roofline": {"kernel": "l2_min_pp3_kernel (xyz library distance GEMM + running min/argmin)", "bound": "mfma",
-                         "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
-                         "frac_in_pipeline": round(achieved_pipe / PEAK_BF16_TFLOPS, 4) if achieved_pipe else None,
-                         **_traffic_with_ratio(profiled_traffic(), bytes_alg),
-                         "launch_ms": round(l2_ms, 3), "launch_ms_in_pipeline": round(l2_pipe_ms, 3),
-                         "launch_ms_note": "launch_ms / frac: the step's launch repeated alone after the timed loop (HIP events, idle chip; median of ten) "
-                                           "-- the regime of the stand-alone rocprofv3 row in profiles/r5_standalone.md; "
-                                           "in_pipeline: the same launch inside the timed steps, on the second stream beside the next "
-                                           "step's extraction (shares the CUs)",
-                         "flops_per_launch": flops,
-                         "hbm_secondary": {"algorithmic_bytes": bytes_alg,
-                                           "achieved_GBs": round(bytes_alg / (l2_ms * 1e-3) / 1e9, 1),
-                                           "frac_of_8TBs": round(bytes_alg / (l2_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)}},
         }
+        if args.full:
+            out["roofline"] = {"kernel": "l2_min_pp3_kernel (xyz library distance GEMM + running min/argmin)", "bound": "mfma",
+                               "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                               "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
+                               "frac_in_pipeline": round(achieved_pipe / PEAK_BF16_TFLOPS, 4) if achieved_pipe else None,
+                               **_traffic_with_ratio(profiled_traffic(), bytes_alg),
+                               "launch_ms": round(l2_ms, 3), "launch_ms_in_pipeline": round(l2_pipe_ms, 3),
+                               "launch_ms_note": "launch_ms / frac: the step's launch repeated alone after the timed loop (HIP events, idle chip; median of ten) "
+                                                 "-- the regime of the stand-alone rocprofv3 row in profiles/r5_standalone.md; "
+                                                 "in_pipeline: the same launch inside the timed steps, on the second stream beside the next "
+                                                 "step's extraction (shares the CUs)",
+                               "flops_per_launch": flops,
+                               "hbm_secondary": {"algorithmic_bytes": bytes_alg,
+                                                 "achieved_GBs": round(bytes_alg / (l2_ms * 1e-3) / 1e9, 1),
+                                                 "frac_of_8TBs": round(bytes_alg / (l2_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)}}
         if group is not None:
             out["rccl_ranks"] = rccl_ranks_seen          # the sum RCCL's all_reduce returned over a tensor of ones
             out["world"] = world
@@ -277,7 +307,7 @@ def main():
             return None
         return legs.run(name, fn, budget or seconds, collective=collective)
 
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         n_h2d = max(8, min(args.steps, 12))
 
         # (with the row-sharded pipeline -- --bank sharded -- the H2D-fed steps are collective steps too)
@@ -306,11 +336,11 @@ def main():
             legs.store = None            # (gone with the process group; nothing collective follows)
         torn_down = "error" not in (leg("teardown", lambda: teardown() or {"ok": True}, 60, collective=True) or {})
     if rank == 0:
-        if world == 1 and not args.no_extras and args.workload == "dino_pointmae":
+        if world == 1 and args.full and not args.no_extras and args.workload == "dino_pointmae":
             del pred, batches
             torch.cuda.empty_cache()
             leg("dropin_b1", dropin_b1, 300)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             leg("cpu_baseline", lambda: cpu_baseline(args.cpu_images), 600)
         out.pop("teardown", None)
         emit_line(out)

@@ -71,9 +71,10 @@ def make_batches(rank, workload, pinned=False):
     return out
 
 
-def run_steps(pred, batches, n, first=None):
+def run_steps(pred, batches, n, first=None, last=None):
     """n pipelined steps over the rotating batches; returns the outputs and checks each against the first output seen for
-    the same batch index (`first`, filled on the way)."""
+    the same batch index (`first`, filled on the way).  `last` (a dict): receives the last step's outputs as
+    last["outputs"] = (image scores, pixel maps) and its batch index as last["batch"] (bench.py --dump-outputs)."""
     import numpy as np
     first = {} if first is None else first
     pending = []
@@ -85,6 +86,8 @@ def run_steps(pred, batches, n, first=None):
             first[j] = (s, m)
         else:
             assert np.array_equal(s, first[j][0]) and np.array_equal(m, first[j][1]), f"batch {j}: steps disagree"
+        if last is not None:        # tickets are taken in submission order: the final assignment is the last step's
+            last["outputs"], last["batch"] = (s, m), j
 
     # Tickets outstanding on the host.  The predictor's pinned output ring has 3 slots, so the ticket of step i - 3 must have been
     # consumed before step i is submitted -- not the one of step i - 2: with three outstanding the host queues step i while the

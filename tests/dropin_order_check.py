@@ -1,13 +1,14 @@
 """Helper of tests/test_host_cpu.py::test_install_dropin_is_order_independent (run as a script: a fresh interpreter per order).
-argv[1]: path_first | install_first | no_reference; argv[2]: the reference's tree.  Third-party packages that the reference's
-UNREPLACED scripts import and this image lacks (torchvision, tifffile, tensorboard) get inert stand-ins; everything else is real:
-with the drop-in installed, the reference's dataset.py, cmdiad_runner.py, main.py and hallucination_network_pretrain.py must import,
-its own utils.misc must stay its own, and the redirected names must resolve to this package."""
+argv[1]: path_first | install_first | no_reference; argv[2]: the reference's tree (the test writes a stand-in of it from G15: its
+modules' imports of each other and their top-level names).  Third-party packages that the reference's UNREPLACED scripts import and
+this image lacks (torchvision, tifffile, tensorboard) get inert stand-ins: with the drop-in installed, the reference's dataset.py,
+cmdiad_runner.py, main.py and hallucination_network_pretrain.py must import, its own utils.misc must stay its own, and the redirected
+names must resolve to this package."""
 import importlib
 import os
 import sys
 import types
-REF = sys.argv[2] if len(sys.argv) > 2 else "/root/reference"
+REF = sys.argv[2]
 sys.dont_write_bytecode=True
 order=sys.argv[1]
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -459,9 +459,56 @@ def golden_surface():
     print(list(out["names"]))
 
 
+def golden_dropin_tree():
+    """G15: the shape of the reference's tree as the drop-in meets it, data only -- every module file, the module-level imports of
+    its own modules (`from m import a, b` / `import m as x`) and each module's top-level names.  tests/test_host_cpu.py writes a
+    stand-in tree from it (imports and names, no code) and checks that install_dropin() works before or after that tree enters
+    sys.path."""
+    import ast
+    files, imports, defines = [], [], []
+    for dirpath, dirnames, filenames in os.walk(REF):
+        dirnames[:] = sorted(d for d in dirnames if not d.startswith((".", "__")))
+        for f in sorted(filenames):
+            if f.endswith(".py"):
+                files.append(os.path.relpath(os.path.join(dirpath, f), REF))
+    local = {f.split("/")[0].removesuffix(".py") for f in files}
+
+    def top(body):                          # module-level statements, through if / try blocks
+        for n in body:
+            yield n
+            for field in ("body", "orelse", "finalbody"):
+                if isinstance(n, (ast.If, ast.Try)) and getattr(n, field, None):
+                    yield from top(getattr(n, field))
+            if isinstance(n, ast.Try):
+                for h in n.handlers:
+                    yield from top(h.body)
+
+    for rel in files:
+        mod = rel.removesuffix(".py").replace("/", ".")
+        for n in top(ast.parse(open(os.path.join(REF, rel)).read()).body):
+            if isinstance(n, ast.ImportFrom) and n.level == 0 and n.module.split(".")[0] in local:
+                imports.append(f"{mod}|from|{n.module}|{','.join(a.name for a in n.names)}")
+            elif isinstance(n, ast.Import):
+                for a in n.names:
+                    if a.name.split(".")[0] in local:
+                        imports.append(f"{mod}|import|{a.name}|{a.asname or ''}")
+            elif isinstance(n, (ast.FunctionDef, ast.AsyncFunctionDef, ast.ClassDef)):
+                defines.append(f"{mod}|{n.name}")
+            elif isinstance(n, (ast.Assign, ast.AnnAssign)):
+                for t in (n.targets if isinstance(n, ast.Assign) else [n.target]):
+                    for e in (t.elts if isinstance(t, ast.Tuple) else [t]):
+                        if isinstance(e, ast.Name):
+                            defines.append(f"{mod}|{e.id}")
+    np.savez_compressed(os.path.join(HERE, "g15_dropin_tree.npz"), files=np.array(files), imports=np.array(imports),
+                        defines=np.array(sorted(set(defines))))
+    print(len(files), "files,", len(imports), "local imports,", len(set(defines)), "top-level names")
+
+
 def main():
     _install_stubs()
     sys.path.insert(0, REF)
+    if len(sys.argv) > 1 and sys.argv[1] == "g15":  # only the drop-in tree fixture
+        return golden_dropin_tree()
     if len(sys.argv) > 1 and sys.argv[1] == "g14":  # only the drop-in surface fixture
         return golden_surface()
     if len(sys.argv) > 1 and sys.argv[1] == "g13":  # only the pair-dataset fixture
@@ -739,6 +786,7 @@ def main():
     golden_coreset_tf32()
     golden_heads()
     golden_methods()
+    golden_dropin_tree()
 
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):

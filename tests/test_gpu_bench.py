@@ -28,9 +28,24 @@ def _run(extra_env, *args):
     return json.loads(lines[0])
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) prints the contract fields and nothing it would need further runs for; --dump-outputs writes the
+    last timed step's image scores and pixel maps."""
+    import numpy as np
+    d = _run({}, "--dump-outputs", str(tmp_path))
+    assert d["metric"].startswith("images/sec") and d["unit"] == "images/s" and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
+    assert d["value"] > 100 and abs(d["value"] - 32 / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"]
+    assert d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert [k for k, v in d.items() if isinstance(v, dict)] == ["config"], d.keys()      # no roofline, no secondary leg
+    s, m = np.load(tmp_path / "image_scores.npy"), np.load(tmp_path / "pixel_maps.npy")
+    assert s.shape == (32,) and m.shape == (32, 224, 224) and s.dtype == m.dtype == np.float64
+    assert np.isfinite(s).all() and np.isfinite(m).all() and len(np.unique(s)) > 1
+    assert sum(f.stat().st_size for f in tmp_path.iterdir()) <= 64 << 20
+
+
 @pytest.mark.rehearsal
 def test_bench_single_gpu_line():
-    d = _run({}, "--no-extras")
+    d = _run({}, "--full", "--no-extras")
     assert d["metric"].startswith("images/sec") and d["unit"] == "images/s" and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
     assert d["value"] > 100 and abs(d["value"] - 32 / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"]
     r = d["roofline"]
@@ -41,10 +56,10 @@ def test_bench_single_gpu_line():
 
 @slow
 def test_bench_default_line_carries_the_secondary_legs():
-    """The driver's command (no flags beyond steps): besides the headline, configs[2] (distillation training step), the conv head's
+    """`bench.py --full`: besides the headline, configs[2] (distillation training step), the conv head's
     training step (row f4), the variable-N leg, the MTFI step (the metric's "distill" term) and the class loop
     ride in the same JSON line; no leg carries an error."""
-    d = _run({})
+    d = _run({}, "--full")
     assert not [k for k, v in d.items() if isinstance(v, dict) and ("error" in v or "skipped" in v)], d
     # the headline contract (what test_bench_single_gpu_line checks on a --no-extras run)
     assert d["metric"].startswith("images/sec") and d["unit"] == "images/s" and d["n_gpus"] == 1
@@ -66,7 +81,7 @@ def test_bench_default_line_carries_the_secondary_legs():
 @slow
 @pytest.mark.rehearsal
 def test_bench_distributed_path_on_one_gpu():
-    d = _run({"CMDIAD_FORCE_DIST": "1"})
+    d = _run({"CMDIAD_FORCE_DIST": "1"}, "--full")
     assert d["rccl_ranks"] == 1 and d["world"] == 1 and d["ranks"][0]["rank"] == 0 and "device" in d["ranks"][0]
     assert not [k for k, v in d.items() if isinstance(v, dict) and ("error" in v or "skipped" in v)], d
     s = d["sharded_search"]
@@ -88,7 +103,7 @@ def test_bench_row_sharded_pipeline_on_one_gpu():
     """`--bank sharded` with CMDIAD_FORCE_DIST=1: the row-sharded search INSIDE the timed pipeline (engine.sharded_min_keys in
     BatchPredictor.search: local de-duplication, counts exchange, all-gather of the live rows, per-shard GEMM, all_reduce(MIN),
     expansion) through RCCL with a world of one rank; the searched-row count says the compaction happened before the exchange."""
-    d = _run({"CMDIAD_FORCE_DIST": "1"}, "--no-extras", "--bank", "sharded")
+    d = _run({"CMDIAD_FORCE_DIST": "1"}, "--full", "--no-extras", "--bank", "sharded")
     assert d["config"]["bank"].startswith("row-sharded") and d["value"] > 100
     rows = d["config"]["xyz_query_rows"]
     assert rows["dedup"] and 0.5 * rows["per_step"] < rows["searched_per_step"] < 0.7 * rows["per_step"]

@@ -57,7 +57,7 @@ def test_bench_line_of_n_ranks_rehearsed_on_one_gpu(world, bank):
     driver's largest -- and rank 0 prints the one line with no leg in error."""
     import time
     t0 = time.perf_counter()
-    out = _launch(world, [os.path.join(REPO, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "2", "--bank", bank,
+    out = _launch(world, [os.path.join(REPO, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "2", "--bank", bank, "--full",
                           "--classes", "cookie,bagel", "--class-scale", "0.02", "--class-test", "10"],
                   {"CMDIAD_BENCH_ONE_DEVICE": "1", "OMP_NUM_THREADS": "2"}, timeout=1500)
     print(f"[bench.py --gpus {world} --bank {bank}, {world} ranks on one device: {time.perf_counter() - t0:.0f} s]")

@@ -1109,18 +1109,40 @@ def test_resize_organized_pc_equals_the_reference(golden):
         mv.read_tiff_organized_pc("/nonexistent/file.tiff")
 
 
+def _write_standin_tree(root, g):
+    """The reference's tree as the drop-in meets it (G15, tests/golden/make_golden.py): every module file with its module-level
+    imports of the tree's own modules and its top-level names bound to None -- imports and names, no code.  A module that
+    install_dropin() redirects raises when imported from the tree: the drop-in must serve it."""
+    import cmdiad_amd
+    body = {str(f)[:-3].replace("/", "."): [] for f in g["files"]}
+    for line in g["imports"]:
+        mod, kind, target, names = str(line).split("|")
+        body[mod].append(f"from {target} import {', '.join(names.split(','))}" if kind == "from" else
+                         f"import {target}" + (f" as {names}" if names else ""))
+    for line in g["defines"]:
+        mod, name = str(line).split("|")
+        body[mod].append(f"{name} = None")
+    for mod, lines in body.items():
+        path = os.path.join(root, *mod.split(".")) + ".py"
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        if mod in cmdiad_amd._DROPIN:
+            lines = [f"raise ImportError('{mod} is redirected by install_dropin(): imported from the tree')"]
+        with open(path, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
 @pytest.mark.parametrize("order", ["path_first", "install_first", "no_reference"])
-def test_install_dropin_is_order_independent(order):
+def test_install_dropin_is_order_independent(order, tmp_path, golden):
     """install_dropin() before or after the reference's tree enters sys.path, or with no reference at all: the reference's own
     unreplaced scripts import (dataset.py star-imports a redirected module; hallucination_network_pretrain.py needs the reference's
     OWN utils.misc beside the redirected utils.lr_sched), redirected names resolve here.  Round 5: installed first, the old
-    install_dropin() registered an empty `utils` package and the reference's utils.misc was gone."""
-    ref = os.environ.get("CMDIAD_REFERENCE", "/root/reference")
-    if order != "no_reference" and not os.path.isdir(ref):
-        pytest.skip("the reference's tree is not on this machine")
+    install_dropin() registered an empty `utils` package and the reference's utils.misc was gone.  The tree is a stand-in written
+    from G15: the reference's module files with their imports of each other and their top-level names."""
+    ref = str(tmp_path / "reference")
+    _write_standin_tree(ref, golden("g15_dropin_tree.npz"))
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1", CMDIAD_ALLOW_RANDOM_INIT="1")
     out = subprocess.run([sys.executable, os.path.join(REPO, "tests", "dropin_order_check.py"), order, ref], capture_output=True, text=True,
-                         timeout=300, env=env, cwd="/tmp")
+                         timeout=300, env=env, cwd=str(tmp_path))
     assert out.returncode == 0 and f"{order} ok" in out.stdout, out.stderr[-2500:]
 
 

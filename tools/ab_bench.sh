@@ -1,13 +1,14 @@
 #!/bin/bash
 # A/B of one environment switch on the bench line (run ON the MI355X box):  tools/ab_bench.sh CMDIAD_GEMM_RES_WIDE "0 1" [repeats]
 VAR=$1; VALS=$2; REP=${3:-2}
-mkdir -p gpurun_out/ab
+D=${BENCH_RUNS:-bench_runs}/ab
+mkdir -p "$D"
 for i in $(seq $REP); do
   n=0
   for v in $VALS; do
     n=$((n+1))
-    env $VAR=$v python bench.py --no-extras --no-cpu-baseline > gpurun_out/ab/out_${n}_$i.json 2> gpurun_out/ab/err_${n}_$i.log
-    python - "$VAR=$v" gpurun_out/ab/out_${n}_$i.json gpurun_out/ab/err_${n}_$i.log <<'PY'
+    env $VAR=$v python bench.py --full --no-extras --no-cpu-baseline > "$D/out_${n}_$i.json" 2> "$D/err_${n}_$i.log"
+    python - "$VAR=$v" "$D/out_${n}_$i.json" "$D/err_${n}_$i.log" <<'PY'
 import json, sys
 tag, out, err = sys.argv[1:4]
 try:

@@ -5,7 +5,7 @@
 # run in order, each with its own log file and a line (+ the log's tail) in <out>/rc.log:
 #   suite[:extra pytest args]        python -m pytest tests -m gpu -q --durations=25
 #   pytest:<-k expression>[:files]   python -m pytest <files or tests> -m gpu -q -s -k <expression>
-#   bench[:args]                     python bench.py <args>  (default: --no-cpu-baseline) + a one-line summary of the JSON line
+#   bench[:args]                     python bench.py <args>  (default: --full --no-cpu-baseline) + a one-line summary of the JSON line
 #   ab:<VAR>:<values>[:passes]       tools/ab_bench.sh (one environment switch on the bench line, candidates interleaved)
 #   profile:<rN>                     tools/profile_round.sh rN (kernel trace + counter passes of the bench and of the stand-alone kernels)
 #   py:<script args>                 python <script args>
@@ -25,7 +25,7 @@ for step in "$@"; do
     suite)   timeout $LIM python -m pytest tests -m gpu -q --durations=25 $rest > "$log" 2>&1 ;;
     pytest)  expr=${rest%%:*}; files=tests; [ "$expr" != "$rest" ] && files=${rest#*:}
              timeout $LIM python -m pytest $files -m gpu -q -s -k "$expr" > "$log" 2>&1 ;;
-    bench)   timeout $LIM python bench.py ${rest:---no-cpu-baseline} > "$O/${n}_bench.json" 2> "$log"; rc=$?
+    bench)   timeout $LIM python bench.py ${rest:---full --no-cpu-baseline} > "$O/${n}_bench.json" 2> "$log"; rc=$?
              python - "$O/${n}_bench.json" >> "$log" 2>&1 <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 O=$PWD/gpurun_out/h2d_trace
 rm -rf "$O"; mkdir -p "$O"
 export CMDIAD_BENCH_LEGS=h2d_inclusive
-rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d "$O/t" -- python3 bench.py --no-cpu-baseline --steps 6 --warmup 3 > "$O/bench.log" 2>&1
+rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d "$O/t" -- python3 bench.py --full --no-cpu-baseline --steps 6 --warmup 3 > "$O/bench.log" 2>&1
 tail -c 600 "$O/bench.log"
 find "$O" -name "*.db" -delete
 ls -la "$O"/t/*/ | head

@@ -10,7 +10,7 @@ timeout 600 python tools/l2_runner_ab.py 3 > $O/ab.log 2>&1; echo "ab rc=$?" | t
 timeout 900 python -m pytest tests/test_gpu_fullsize.py tests/test_gpu_engine.py -x -q -s > $O/t_full.log 2>&1; echo "fullsize+engine rc=$?" | tee -a $O/rc.log; tail -n 4 $O/t_full.log | tee -a $O/rc.log
 grep "full size" $O/t_full.log | tee -a $O/rc.log
 timeout 900 python -m pytest tests/test_gpu_predictor.py tests/test_gpu_fakeworld.py tests/test_gpu_world2.py -x -q > $O/t_pred.log 2>&1; echo "predictor+fakeworld+world2 rc=$?" | tee -a $O/rc.log; tail -n 4 $O/t_pred.log | tee -a $O/rc.log
-timeout 900 python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" | tee -a $O/rc.log
+timeout 900 python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" | tee -a $O/rc.log
 python - <<'PY' | tee -a $O/rc.log
 import json
 try:
