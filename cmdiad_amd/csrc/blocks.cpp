@@ -2,7 +2,25 @@
 // caller pays one FFI call per block instead of seven (SURVEY 8b lists `vit_block_fwd` among the proposed exports; at
 // B = 1 the Python / ctypes launch path, not the GPU, bounds the drop-in).  Pure launch sequencing over the entry points
 // of gemm.hip / attention.hip / misc.hip: no kernels here, nothing allocated, stream-ordered like everything else.
+#include <stdlib.h>
+
 #include "common.h"
+
+// mlp_fused.hip: fc1 + GELU + fc2 of the folded Point-MAE block (C = 384, hidden = 1 536) as one kernel, bit-identical to the two
+// launches it replaces
+int cmdiad_pmae_mlp_fused(float* x, const uint16_t* xb, const float* rstd, const uint16_t* w1, const float* b1, const uint16_t* w2,
+                          const float* b2, int M, uint16_t* ln_xb, float* ln_part, const float* add2, cmdiad_stream_t stream);
+
+// The fused MLP keeps a 128-row tile per CU (one block of 8 waves, all 160 KiB of LDS); below ~3/4 of a chip's worth of
+// tiles the two launches, which spread smaller tiles over every CU, are at least as fast (B = 1: 8 tiles; the drop-in's
+// micro-batches of 16: 128).  CMDIAD_PMAE_MLP=1 / 0 forces it on / off wherever it is legal (A/B runs, parity tests; read per call).
+static bool pmae_mlp_fused_wanted(bool folded, int M, int C, int hidden)
+{
+    if (!folded || C != 384 || hidden != 1536) return false;
+    const char* e = getenv("CMDIAD_PMAE_MLP");
+    if (e) return e[0] != '0';
+    return M >= 192 * 128;
+}
 
 extern "C" size_t cmdiad_transformer_block_workspace_bytes(int M, int C, int hidden)
 {
@@ -53,6 +71,14 @@ extern "C" int cmdiad_transformer_block_fwd(float* x, const float* pos, const cm
     g.residual = x; g.ldr = C; g.out_f32 = x; g.ldo32 = C; g.act = CMDIAD_ACT_NONE; g.group_rows = 1; g.split_k = 1;
     if (folded) { g.ln_xb = h; g.ld_xb = C; g.ln_part = part; }
     if ((rc = cmdiad_gemm_bf16(&g, stream))) return rc;
+    if (pmae_mlp_fused_wanted(folded, M, C, hidden)) {
+        if ((rc = cmdiad_ln_stats_finalize(part, M, C / 64, eps, rstd, nullptr, stream))) return rc;
+        const bool prep = flags & CMDIAD_BLOCK_PREP_NEXT;
+        if ((rc = cmdiad_pmae_mlp_fused(x, h, rstd, w->fc1_wf, w->fc1_bf, w->fc2_w, w->fc2_b, M, prep ? h : nullptr, prep ? part : nullptr,
+                                        prep ? pos : nullptr, stream))) return rc;
+        if (prep) return cmdiad_ln_stats_finalize(part, M, C / 64, eps, rstd, nullptr, stream);
+        return CMDIAD_OK;
+    }
     cmdiad_gemm_args f1{};
     f1.A = h; f1.lda = C; f1.ldw = C; f1.M = M; f1.N = hidden; f1.K = C;
     f1.act = CMDIAD_ACT_GELU; f1.out_bf16 = m; f1.ldo16 = hidden; f1.group_rows = 1; f1.split_k = 1;
