@@ -39,11 +39,14 @@ __device__ __forceinline__ bf16_t f2bf(float v) { return (bf16_t)v; }
 
 // erf-GELU (nn.GELU() default, utils/utils.py:97, models/models.py:129):  GELU(x) = x - h for x > 0, h otherwise, with
 // h = 0.5 x erfc(|x| / sqrt 2) and erfc(z) = 2^(-q(z)), q a degree-6 polynomial fitted to -log2 erfc on [0, 4.3] (beyond it
-// erfc < 2e-9).  |error| <= 5.3e-7 absolute on the GELU value -- a tenth of a bf16 half-ulp, the same bound as the
-// Abramowitz-Stegun 7.1.26 form it replaces -- with ONE transcendental (v_exp_f32, quarter rate) instead of two (rcp + exp):
-// ~16 VALU issue slots per element instead of ~22, and the Horner steps are plain FMAs that the 4-wide form below hands to
-// v_pk_fma_f32 two elements at a time.  The fc1 epilogues run this on 77 M activations per ViT layer; in the two-group
-// persistent GEMM both waves of a SIMD evaluate it between the same two barriers, where it is not hidden by anything.
+// erfc < 2e-9).  Past the clamp (x < -4.3 sqrt 2) 2^(-q) stays at erfc(4.3), so the x that multiplies it is clamped there too
+// (NaN-propagating v_maximum3_f32, one VALU op): h then stays at -3.6e-9 for every x below instead of growing with |x| (-6e-7
+// at x = -1000, -1.8e29 at -3e38), and nothing changes for x >= -4.3 sqrt 2.  |error| <= 5.3e-7 absolute on the GELU value for
+// every finite x -- a tenth of a bf16 half-ulp, the same bound as the Abramowitz-Stegun 7.1.26 form it replaces -- with ONE
+// transcendental (v_exp_f32, quarter rate) instead of two (rcp + exp): ~17 VALU issue slots per element instead of ~22, and the
+// Horner steps are plain FMAs that the 4-wide form below hands to v_pk_fma_f32 two elements at a time.  The fc1 epilogues run
+// this on 77 M activations per ViT layer; in the two-group persistent GEMM both waves of a SIMD evaluate it between the same two
+// barriers, where it is not hidden by anything.
 #define CMDIAD_GELU_Q6 -2.3885208886e-04f
 #define CMDIAD_GELU_Q5 4.0851729330e-03f
 #define CMDIAD_GELU_Q4 -3.1410888601e-02f
@@ -51,6 +54,7 @@ __device__ __forceinline__ bf16_t f2bf(float v) { return (bf16_t)v; }
 #define CMDIAD_GELU_Q2 9.1851604883e-01f
 #define CMDIAD_GELU_Q1 1.6277476882e+00f
 #define CMDIAD_GELU_Q0 2.2232231590e-05f
+#define CMDIAD_GELU_XMIN -6.0811529f   // -4.3 sqrt 2: below it z is clamped
 
 __device__ __forceinline__ float gelu_erf(float x)
 {
@@ -61,7 +65,7 @@ __device__ __forceinline__ float gelu_erf(float x)
     q = fmaf(q, z, CMDIAD_GELU_Q2);
     q = fmaf(q, z, CMDIAD_GELU_Q1);
     q = fmaf(q, z, CMDIAD_GELU_Q0);
-    const float h = (0.5f * x) * __builtin_amdgcn_exp2f(-q);
+    const float h = (0.5f * __builtin_elementwise_maximum(x, CMDIAD_GELU_XMIN)) * __builtin_amdgcn_exp2f(-q);
     return x > 0.0f ? x - h : h;
 }
 
@@ -83,7 +87,7 @@ __device__ __forceinline__ f32x4 gelu_erf4(f32x4 x)
     q = __builtin_elementwise_fma(q, z, c2);
     q = __builtin_elementwise_fma(q, z, c1);
     q = __builtin_elementwise_fma(q, z, c0);
-    const f32x4 hx = x * 0.5f;
+    const f32x4 hx = __builtin_elementwise_maximum(x, f32x4{CMDIAD_GELU_XMIN, CMDIAD_GELU_XMIN, CMDIAD_GELU_XMIN, CMDIAD_GELU_XMIN}) * 0.5f;
     f32x4 out;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {

@@ -1067,6 +1067,16 @@ extern "C" int cmdiad_gemm_bf16(const cmdiad_gemm_args* a, cmdiad_stream_t strea
                    "cmdiad_gemm_bf16: row_scale with split_k / training terms / m_count");
     CMDIAD_REQUIRE(!a->m_count || split == 1, CMDIAD_ERR_ARG, "cmdiad_gemm_bf16: m_count with split_k > 1");
     hipStream_t s = (hipStream_t)stream;
+    if (split > 1) {
+        // a slab holds ceil(T / split) of the T K-tiles, so slabs ceil(T / per) .. split - 1 can be left without one (T = 33, split 8:
+        // slab 7); their blocks return before any store (gemm_std_kernel), and the caller sums every slab: zero those here
+        const int T = a->K / BK, per = (T + split - 1) / split, used = (T + per - 1) / per;
+        if (used < split && hipMemset2DAsync(a->out_f32 + (size_t)used * a->M * a->ldo32, (size_t)a->ldo32 * sizeof(float), 0,
+                                             (size_t)a->N * sizeof(float), (size_t)(split - used) * a->M, s) != hipSuccess) {
+            cmdiad_set_error("cmdiad_gemm_bf16: hipMemset2DAsync of the empty split-K slabs failed");
+            return CMDIAD_ERR_LAUNCH;
+        }
+    }
     const bool extras = a->out_pre_bf16 || a->dact_of;
     int rc;
 #ifdef CMDIAD_AB_VARIANTS
