@@ -59,11 +59,14 @@ SIGNATURES = {
     "cmdiad_gemm_tn_bf16": [P, I, P, I, I, I, I, I, P, I, P, P],
     "cmdiad_attention": [P, P, P, I, I, I, P, P],
     "cmdiad_encoder_tail": [P, P, P, P, P, I, I, P, P],
+    "cmdiad_encoder_tail_n": [P, P, P, P, P, I, I, I, I, P, P],
     "cmdiad_conv2d_nhwc_bf16": [POINTER(ConvArgs), P],
     "cmdiad_conv_stem": [P, P, P, I, I, I, I, I, I, P, P],
     "cmdiad_upsample_bicubic": [P, I, I, I, I, I, I, I, P, I, P, P],
     "cmdiad_transformer_block_fwd": [P, P, POINTER(BlockWeights), I, I, I, I, I, F, I, P, P, P, P, SZ, P],
     "cmdiad_layernorm": [P, P, P, P, F, I, I, P, P, I, P, P, P],
+    "cmdiad_layernorm_skip_first": [P, P, P, F, I, I, I, P, I, P],
+    "cmdiad_lead_rows": [P, P, P, P, I, I, I, P],
     "cmdiad_loss_head": [P, P, I, I, I, F, P, P, P, P],
     "cmdiad_bn_affine": [P, P, P, P, SZ, D, I, P, P, P, P, P, P, P],
     "cmdiad_bn_relu_fwd": [P, P, P, P, I, SZ, I, P, P, P],

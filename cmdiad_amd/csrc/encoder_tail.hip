@@ -12,6 +12,9 @@
 // Arithmetic order equals the two-kernel path (same bf16 rounding of h3, same K order of the fp32 accumulation), so
 // the tokens are bit-identical to gemm_bf16 + gemm_groupmax.  The group maximum is combined across the four 32-row wave
 // rows of the block through LDS; a block always owns whole groups, so every output is stored exactly once.
+// Point-BERT's encoder ends in 512 -> 256 (models/models.py:194 with encoder_channel = 256): the same kernel with the output width a
+// template parameter, NO = 2 output chunks of 128 (8 phases per chunk, 32 tiles per row tile, 64 accumulator registers per lane);
+// that form can also scatter group g's token to row g + g / seg + 1 (one leading row per cloud of seg groups: the cls row).
 #include <type_traits>
 
 #include "gemm_core.h"
@@ -71,10 +74,17 @@ struct TailParams {
 //   * the group maxima of a finished tile meet in the h3 buffer (dead until phase 3 of the next tile).
 // Same arithmetic per output element (K order per accumulator, bf16 rounding of h3): identical tokens.
 // ------------------------------------------------------------------------------------------------
-template <bool ABL>   // ABL: timing ablations (results are garbage), instantiated in the test-only build
-__global__ __launch_bounds__(TW * 64, 1) void encoder_tail_persist_kernel(GlobalTile H2, GlobalTile W3, GlobalTile W4, TailParams p, int n_tiles)
+// NO: output chunks of 128 columns (3: Point-MAE's 384, 2: Point-BERT's 256).  A chunk is PH = 4 + 2 NO phases; the schedule below
+// is written for any NO >= 2 (PH >= 8: the group-bias fetch of phase 3 and the h2 refills of phases 0-3 stay inside one chunk).
+// seg (NO != 3 only): > 0 scatters group g's token to row g + g / seg + 1 of tok, 0 stores it at row g.
+template <bool ABL, int NO = 3>   // ABL: timing ablations (results are garbage), instantiated in the test-only build
+__global__ __launch_bounds__(TW * 64, 1) void encoder_tail_persist_kernel(GlobalTile H2, GlobalTile W3, GlobalTile W4, TailParams p, int n_tiles,
+                                                                          int seg)
 {
     static_assert(NST == 4, "the schedule is written for four weight stages");
+    static_assert(NO == 2 || NO == 3, "output width 256 or 384");
+    constexpr int PH = 4 + 2 * NO;       // phases per chunk: 4 K-steps of W3b + NO output chunks x 2 K-steps of W4
+    constexpr int NOUT = NO * 128;
     extern __shared__ __attribute__((aligned(16))) char lds[];
     char* A2 = lds;
     char* A3 = lds + A2_BYTES;
@@ -100,8 +110,8 @@ __global__ __launch_bounds__(TW * 64, 1) void encoder_tail_persist_kernel(Global
         asm volatile("s_mov_b64 %0, %2\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0"
                      : "=&s"(sb) : "v"(voff), "s"(ubase), "s"(lds_addr) : "memory");
     };
-    // weight tile (c, u) of the 40-tile sequence: u < 4 -> W3b rows [128 c, +128), K-step u; else v = u - 4: K-step k2 = v / 3 of
-    // W4 rows [128 (v % 3), +128), columns 128 c + 64 k2
+    // weight tile (c, u) of the 4 PH-tile sequence: u < 4 -> W3b rows [128 c, +128), K-step u; else v = u - 4: K-step k2 = v / NO of
+    // W4 rows [128 (v % NO), +128), columns 128 c + 64 k2
     auto stage_w = [&](int c, int u, int slot) {   // wave-uniform arguments
         const unsigned dst = lds0 + A2_BYTES + A3_BYTES + slot * W_STAGE + (wave & 3) * 32 * 128;
         if (u < 4) {
@@ -109,7 +119,7 @@ __global__ __launch_bounds__(TW * 64, 1) void encoder_tail_persist_kernel(Global
 #pragma unroll
             for (int j = 0; j < 4; ++j) dma(ub + j * 8 * 512, off3, dst + j * 8 * 128);
         } else {
-            const int v = u - 4, k2 = v >= 3 ? 1 : 0, o = v - 3 * k2;
+            const int v = u - 4, k2 = v >= NO ? 1 : 0, o = v - NO * k2;
             const char* ub = reinterpret_cast<const char*>(W4.base) + ((size_t)o * 128 * 512 + c * 128 + k2 * BK) * 2;
 #pragma unroll
             for (int j = 0; j < 4; ++j) dma(ub + j * 8 * 1024, off4, dst + j * 8 * 128);
@@ -129,6 +139,12 @@ __global__ __launch_bounds__(TW * 64, 1) void encoder_tail_persist_kernel(Global
     //   any chunk but the last (and the last one... see `zone`):  8 8 8 8 12 12 12 8 8 8
     //   last chunk, a row tile follows:                           8 12 16 20 24 20 16 8 8 8
     //   last chunk of the last row tile (stream ends at tile 39, no group-bias fetch):  8 x 7, then 4, 0, no wait
+    // Re-derived for PH = 8 (NO = 2) with the same counting (the tile of phase u + 1 was issued at phase u - 3; count the pieces of
+    // phase u - 3 after its weight tile and all of phases u - 2, u - 1):
+    //   any chunk but the last:                                   8 8 8 8 12 12 12 8       (group bias of phase 3 in u = 4..6)
+    //   last chunk, a row tile follows:                           8 12 16 20 24 20 16 8   (h2 refills in phases 0-3)
+    //   last chunk of the last row tile (stream ends at tile 31): 8 x 5, then 4, 0, no wait
+    // i.e. the first two rows do not depend on PH (>= 8), and the last one is 8 up to u = PH - 4, then 4, 0.
     auto wait_next = [&](auto UC, int zone) {   // zone 0 / 1 / 2 as listed, wave-uniform
         constexpr int u = decltype(UC)::value;
         constexpr int generic = (u >= 4 && u <= 6) ? 12 : 8;
@@ -144,9 +160,9 @@ __global__ __launch_bounds__(TW * 64, 1) void encoder_tail_persist_kernel(Global
             else asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
         };
         if (zone == 2) {
-            if constexpr (u <= 6) w(std::integral_constant<int, 8>{});
-            else if constexpr (u == 7) w(std::integral_constant<int, 4>{});
-            else if constexpr (u == 8) w(std::integral_constant<int, 0>{});
+            if constexpr (u <= PH - 4) w(std::integral_constant<int, 8>{});
+            else if constexpr (u == PH - 3) w(std::integral_constant<int, 4>{});
+            else if constexpr (u == PH - 2) w(std::integral_constant<int, 0>{});
         } else if (zone == 1) w(std::integral_constant<int, with_next>{});
         else w(std::integral_constant<int, generic>{});
     };
@@ -193,8 +209,8 @@ __global__ __launch_bounds__(TW * 64, 1) void encoder_tail_persist_kernel(Global
     block_barrier();
     read_half(0, A2, true, WS);
 
-    float* s_part = reinterpret_cast<float*>(A3);  // [4 row blocks][384]: the h3 buffer is dead between two row tiles
-    f32x4 acc3[2][4], acco[3][2][4];
+    float* s_part = reinterpret_cast<float*>(A3);  // [4 row blocks][NOUT]: the h3 buffer is dead between two row tiles
+    f32x4 acc3[2][4], acco[NO][2][4];
 
 #pragma unroll 1
     for (int k = 0; k < my; ++k) {
@@ -202,13 +218,13 @@ __global__ __launch_bounds__(TW * 64, 1) void encoder_tail_persist_kernel(Global
         const bool has_next = k + 1 < my;
         const int m0n = m0 + (int)gridDim.x * TM;
 #pragma unroll
-        for (int o = 0; o < 3; ++o)
+        for (int o = 0; o < NO; ++o)
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) acco[o][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-        // one chunk = ten phases; S0 = stage of its first weight tile ((10 c) & 3: 0 for even c, 2 for odd c)
+        // one chunk = PH phases; S0 = stage of its first weight tile ((PH c) & 3: 0 for even c, PH & 3 for odd c)
         auto chunk = [&](auto S0C, int c) {
             constexpr int S0 = decltype(S0C)::value;
             const int zone = c < 3 ? 0 : has_next ? 1 : 2;
@@ -219,24 +235,24 @@ __global__ __launch_bounds__(TW * 64, 1) void encoder_tail_persist_kernel(Global
             auto phase = [&](auto UC) {
                 constexpr int u = decltype(UC)::value;
                 const int slot = (S0 + u) & 3;
-                const char* ta = u < 4 ? A2 + u * KB_BYTES : A3 + ((u - 4) / 3) * KB_BYTES;
-                const bool load_a = u < 4 || (u - 4) % 3 == 0;
+                const char* ta = u < 4 ? A2 + u * KB_BYTES : A3 + ((u - 4) / NO) * KB_BYTES;
+                const bool load_a = u < 4 || (u - 4) % NO == 0;
                 const char* tw = WS + slot * W_STAGE;
                 // the phase after this one: (c, u + 1), or phase 0 of the next chunk / the next row tile
-                const int un = u == 9 ? 0 : u + 1;
-                const char* tan = un < 4 ? A2 + un * KB_BYTES : A3 + ((un - 4) / 3) * KB_BYTES;
-                const bool load_an = un < 4 || (un - 4) % 3 == 0;
+                const int un = u == PH - 1 ? 0 : u + 1;
+                const char* tan = un < 4 ? A2 + un * KB_BYTES : A3 + ((un - 4) / NO) * KB_BYTES;
+                const bool load_an = un < 4 || (un - 4) % NO == 0;
                 const char* twn = WS + ((slot + 1) & 3) * W_STAGE;
 
                 read_half(1, ta, load_a, tw);
                 if (u < 4) mfma_half(0, acc3);
-                else mfma_half(0, acco[(u - 4) % 3]);
+                else mfma_half(0, acco[(u - 4) % NO]);
                 if (lead && !(ABL && (p.ablate & 1))) wait_next(UC, zone);
                 if (!(ABL && (p.ablate & 16))) block_barrier();
                 if (lead && !(ABL && (p.ablate & 1))) {
                     // every wave holds all of this phase's tile in registers: its stage takes the tile four ahead -- (c, u + 4),
-                    // (c + 1, u - 6), or the next row tile's (0, u - 6); K-block u of the h2 tile is dead in the last chunk
-                    const int ic = u + 4 < 10 ? c : c + 1, iu = u + 4 < 10 ? u + 4 : u - 6;
+                    // (c + 1, u + 4 - PH), or the next row tile's (0, u + 4 - PH); K-block u of the h2 tile is dead in the last chunk
+                    const int ic = u + 4 < PH ? c : c + 1, iu = u + 4 < PH ? u + 4 : u + 4 - PH;
                     if (ic < 4) stage_w(ic, iu, slot);
                     else if (has_next) stage_w(0, iu, slot);
                     if (c == 3 && u < 4 && has_next) stage_h(m0n, u);
@@ -244,7 +260,7 @@ __global__ __launch_bounds__(TW * 64, 1) void encoder_tail_persist_kernel(Global
                 if (u != 3) {
                     read_half(0, tan, load_an, twn);
                     if (u < 4) mfma_half(1, acc3);
-                    else mfma_half(1, acco[(u - 4) % 3]);
+                    else mfma_half(1, acco[(u - 4) % NO]);
                 } else {
                     mfma_half(1, acc3);
                     // h3 chunk c: + group bias, ReLU, bf16, into LDS in the A-operand layout of the next product.  The group bias was
@@ -270,36 +286,37 @@ __global__ __launch_bounds__(TW * 64, 1) void encoder_tail_persist_kernel(Global
             };
             phase(std::integral_constant<int, 0>{}); phase(std::integral_constant<int, 1>{}); phase(std::integral_constant<int, 2>{});
             phase(std::integral_constant<int, 3>{}); phase(std::integral_constant<int, 4>{}); phase(std::integral_constant<int, 5>{});
-            phase(std::integral_constant<int, 6>{}); phase(std::integral_constant<int, 7>{}); phase(std::integral_constant<int, 8>{});
-            phase(std::integral_constant<int, 9>{});
+            phase(std::integral_constant<int, 6>{}); phase(std::integral_constant<int, 7>{});
+            if constexpr (PH > 8) { phase(std::integral_constant<int, 8>{}); phase(std::integral_constant<int, 9>{}); }
         };
 #pragma unroll 1
-        for (int cc = 0; cc < 2; ++cc) {   // (rolled: 20 phases of code, not 40)
+        for (int cc = 0; cc < 2; ++cc) {   // (rolled: 2 PH phases of code, not 4 PH)
             chunk(std::integral_constant<int, 0>{}, 2 * cc);
-            chunk(std::integral_constant<int, 2>{}, 2 * cc + 1);
+            chunk(std::integral_constant<int, PH & 3>{}, 2 * cc + 1);
         }
 
         // ---- group maximum of the finished tile: in-lane over the wave's two 16-row blocks, over the 16 row lanes by DPP, the
         // four 32-row partial maxima through LDS; waves 4-7 combine and store (the first four go on to issue).  A block owns whole
         // groups (Mg | 128): every output is stored exactly once.  The conv4 bias of a thread's (up to six) outputs is fetched by
         // inline asm BEFORE the reduction: a load at its use would put an L2 round trip between two row tiles.
-        // Thread te of waves 4-7 owns output columns te and te + 256 (< 384) of every group in the tile.
+        // Thread te of waves 4-7 owns output columns te and te + 256 (< NOUT) of every group in the tile.
+        constexpr int NQ = (NOUT + 255) / 256;
         float b4r[2] = {0.f, 0.f};
         int te = tid - 256;
         asm volatile("" : "+v"(te));   // (opaque per row tile: otherwise the offsets are hoisted out of the tile loop and spilled)
         if (!lead && !(ABL && (p.ablate & (64 | 128)))) {
 #pragma unroll
-            for (int q = 0; q < 2; ++q)   // unconditional (second column wrapped into the table) and early-clobber: the result register
+            for (int q = 0; q < NQ; ++q)   // unconditional (second column wrapped into the table) and early-clobber: the result register
                                           // is written when the load returns -- it must not double as an address or pass through a copy
             {
                 unsigned long long sb;   // (SALU copy of the base: see dma())
                 asm volatile("s_mov_b64 %1, %3\n\tglobal_load_dword %0, %2, %1"
-                             : "=&v"(b4r[q]), "=&s"(sb) : "v"((unsigned)((te + q * 256) % 384) * 4u), "s"(p.b4) : "memory");
+                             : "=&v"(b4r[q]), "=&s"(sb) : "v"((unsigned)((te + q * 256) % NOUT) * 4u), "s"(p.b4) : "memory");
             }
         }
         if (!(ABL && (p.ablate & 64)))
 #pragma unroll
-        for (int o = 0; o < 3; ++o) {
+        for (int o = 0; o < NO; ++o) {
             float red[16];   // the lane's 4 x 4 columns of this output chunk, maximum over its two 16-row blocks
 #pragma unroll
             for (int q = 0; q < 16; ++q) red[q] = fmaxf(acco[o][0][q >> 2][q & 3], acco[o][1][q >> 2][q & 3]);
@@ -307,13 +324,29 @@ __global__ __launch_bounds__(TW * 64, 1) void encoder_tail_persist_kernel(Global
             if ((lane & 15) == 0) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    *reinterpret_cast<f32x4*>(s_part + wr * 384 + o * 128 + wc * 64 + j * 16 + (lane >> 4) * 4) =
+                    *reinterpret_cast<f32x4*>(s_part + wr * NOUT + o * 128 + wc * 64 + j * 16 + (lane >> 4) * 4) =
                         f32x4{red[4 * j], red[4 * j + 1], red[4 * j + 2], red[4 * j + 3]};
             }
         }
         if (!lead) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the bias values (and nothing else of these waves)
         block_barrier();
-        if (!lead && !(ABL && (p.ablate & (64 | 256)))) {
+        if constexpr (NO != 3) {   // 256 columns: one per thread; group k of the tile -> its (possibly scattered) token row
+            if (!lead) {
+                const int Mg = p.Mg, n = te, g0 = m0 / Mg;
+                auto out = [&](int k) { const int g = g0 + k; return p.tok + (size_t)(seg > 0 ? g + g / seg + 1 : g) * NOUT + n; };
+                const float v0 = s_part[n], v1 = s_part[NOUT + n], v2 = s_part[2 * NOUT + n], v3 = s_part[3 * NOUT + n], b = b4r[0];
+                if (Mg == 128) *out(0) = fmaxf(fmaxf(v0, v1), fmaxf(v2, v3)) + b;
+                else if (Mg == 64) {
+                    *out(0) = fmaxf(v0, v1) + b;
+                    if (m0 + 64 < p.M) *out(1) = fmaxf(v2, v3) + b;
+                } else {
+                    *out(0) = v0 + b;
+                    if (m0 + 32 < p.M) *out(1) = v1 + b;
+                    if (m0 + 64 < p.M) *out(2) = v2 + b;
+                    if (m0 + 96 < p.M) *out(3) = v3 + b;
+                }
+            }
+        } else if (!lead && !(ABL && (p.ablate & (64 | 256)))) {
             const int Mg = p.Mg;                           // 32, 64 or 128: one, two or four 32-row blocks per group
             float* out = p.tok + (size_t)(m0 / Mg) * 384;
 #pragma unroll
@@ -377,10 +410,39 @@ extern "C" int cmdiad_encoder_tail(const uint16_t* h2, const float* gb, const ui
     else if (e && e[0] == '1') {
         if (p.ablate) hipLaunchKernelGGL(encoder_tail_pp_kernel<true>, dim3(n_tiles), block, TAIL_LDS, s, H2, W3, W4t, p);
         else hipLaunchKernelGGL(encoder_tail_pp_kernel<false>, dim3(n_tiles), block, TAIL_LDS, s, H2, W3, W4t, p);
-    } else if (p.ablate) hipLaunchKernelGGL(encoder_tail_persist_kernel<true>, grid_p, block, TAIL_LDS, s, H2, W3, W4t, p, n_tiles);
+    } else if (p.ablate) hipLaunchKernelGGL(encoder_tail_persist_kernel<true>, grid_p, block, TAIL_LDS, s, H2, W3, W4t, p, n_tiles, 0);
     else
 #endif
-    hipLaunchKernelGGL(encoder_tail_persist_kernel<false>, grid_p, block, TAIL_LDS, s, H2, W3, W4t, p, n_tiles);
+    hipLaunchKernelGGL(encoder_tail_persist_kernel<false>, grid_p, block, TAIL_LDS, s, H2, W3, W4t, p, n_tiles, 0);
+    CMDIAD_CHECK_LAUNCH();
+    return CMDIAD_OK;
+}
+
+extern "C" int cmdiad_encoder_tail_n(const uint16_t* h2, const float* gb, const uint16_t* W3b, const uint16_t* W4, const float* b4,
+                                     int groups, int Mg, int n_out, int seg, float* tok_out, cmdiad_stream_t stream)
+{
+    CMDIAD_REQUIRE(h2 && gb && W3b && W4 && b4 && tok_out, CMDIAD_ERR_ARG, "cmdiad_encoder_tail_n: null pointer");
+    CMDIAD_REQUIRE(groups > 0 && (Mg == 32 || Mg == 64 || Mg == 128), CMDIAD_ERR_ARG, "cmdiad_encoder_tail_n: Mg in {32,64,128} (Mg=%d)", Mg);
+    CMDIAD_REQUIRE(n_out == 256 || n_out == 384, CMDIAD_ERR_ARG, "cmdiad_encoder_tail_n: n_out in {256,384} (n_out=%d)", n_out);
+    CMDIAD_REQUIRE(seg >= 0 && (seg == 0 || (n_out == 256 && groups % seg == 0)), CMDIAD_ERR_ARG,
+                   "cmdiad_encoder_tail_n: seg must be 0, or (n_out 256) divide groups (groups=%d seg=%d)", groups, seg);
+    if (n_out == 384) return cmdiad_encoder_tail(h2, gb, W3b, W4, b4, groups, Mg, tok_out, stream);
+    CMDIAD_REQUIRE(((((uintptr_t)h2 | (uintptr_t)W3b | (uintptr_t)W4 | (uintptr_t)gb | (uintptr_t)b4) & 15) == 0), CMDIAD_ERR_ARG,
+                   "cmdiad_encoder_tail_n: 16-byte alignment");
+    static bool attr = false;
+    if (!attr) {
+        if (hipFuncSetAttribute((const void*)encoder_tail_persist_kernel<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, TAIL_LDS) != hipSuccess) {
+            cmdiad_set_error("cmdiad_encoder_tail_n: hipFuncSetAttribute failed");
+            return CMDIAD_ERR_LAUNCH;
+        }
+        attr = true;
+    }
+    const int M = groups * Mg;
+    GlobalTile H2{(const bf16_t*)h2, 256, M}, W3{(const bf16_t*)W3b, 256, 512}, W4t{(const bf16_t*)W4, 512, 256};
+    TailParams p{M, Mg, gb, b4, tok_out, 0};
+    const int n_tiles = (M + TM - 1) / TM;
+    hipLaunchKernelGGL((encoder_tail_persist_kernel<false, 2>), dim3((unsigned)(n_tiles < kTailCUs ? n_tiles : kTailCUs)), dim3(TW * 64), TAIL_LDS,
+                       (hipStream_t)stream, H2, W3, W4t, p, n_tiles, seg);
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
 }

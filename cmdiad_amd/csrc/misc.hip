@@ -248,6 +248,61 @@ __global__ __launch_bounds__(256) void linear3_kernel(const float* __restrict__ 
 
 unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256); }
 
+// Point-BERT's fetch LayerNorm without the cls rows (models/models.py:348 `self.norm(x)[:, 1:]`): output row r = b (T - 1) + t - 1
+// normalises input row b T + t, t >= 1, into out_f32 (leading dimension ldo32: a tap's column block of the [B, G, 768] features).
+// The arithmetic of layernorm_kernel's float2 form step for step: the same rows give the same bits as cmdiad_layernorm.
+template <int PAIRS>
+__global__ __launch_bounds__(256) void layernorm_skip_first_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                                   const float* __restrict__ beta, float eps, int rows, int T,
+                                                                   float* __restrict__ out_f32, int ldo32)
+{
+    constexpr int C = PAIRS * 128;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const float* xr = x + ((size_t)row + row / (T - 1) + 1) * C;
+    float2 v[PAIRS];
+    float s = 0.0f;
+#pragma unroll
+    for (int e = 0; e < PAIRS; ++e) {
+        v[e] = *reinterpret_cast<const float2*>(xr + 2 * (lane + 64 * e));
+        s += v[e].x + v[e].y;
+    }
+    s = wave_sum(s);
+    const float mean = s / C;
+    float q = 0.0f;
+#pragma unroll
+    for (int e = 0; e < PAIRS; ++e) {
+        const float a = v[e].x - mean, b = v[e].y - mean;
+        q += a * a + b * b;
+    }
+    q = wave_sum(q);
+    const float rstd = rsqrtf(q / C + eps);
+#pragma unroll
+    for (int e = 0; e < PAIRS; ++e) {
+        const int c = 2 * (lane + 64 * e);
+        const float2 g = *reinterpret_cast<const float2*>(gamma + c);
+        const float2 bb = *reinterpret_cast<const float2*>(beta + c);
+        const float y0 = (v[e].x - mean) * rstd * g.x + bb.x;
+        const float y1 = (v[e].y - mean) * rstd * g.y + bb.y;
+        *reinterpret_cast<float2*>(out_f32 + (size_t)row * ldo32 + c) = make_float2(y0, y1);
+    }
+}
+
+// row b T of x <- lead_x, of pos <- lead_pos (Point-BERT's cls token and cls_pos, models/models.py:338-344): every other row of the two
+// streams is written by the products in front (their token rows are laid out with the gap already)
+__global__ __launch_bounds__(256) void lead_rows_kernel(float* __restrict__ x, float* __restrict__ pos, const float* __restrict__ lead_x,
+                                                        const float* __restrict__ lead_pos, int B, int T, int C)
+{
+    const int c4 = C / 4;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * c4) return;
+    const int b = i / c4, c = (i % c4) * 4;
+    const size_t o = (size_t)b * T * C + c;
+    *reinterpret_cast<float4*>(x + o) = *reinterpret_cast<const float4*>(lead_x + c);
+    if (pos) *reinterpret_cast<float4*>(pos + o) = *reinterpret_cast<const float4*>(lead_pos + c);
+}
+
 }  // namespace
 
 
@@ -343,6 +398,41 @@ extern "C" int cmdiad_layernorm(float* x, const float* add, const float* gamma, 
         LN_CASE(1) LN_CASE(2) LN_CASE(3) LN_CASE(4) LN_CASE(5) LN_CASE(6) LN_CASE(7) LN_CASE(8)
     }
 #undef LN_CASE
+    CMDIAD_CHECK_LAUNCH();
+    return CMDIAD_OK;
+}
+
+extern "C" int cmdiad_layernorm_skip_first(const float* x, const float* gamma, const float* beta, float eps, int B, int T, int C,
+                                           float* out_f32, int ldo32, cmdiad_stream_t stream)
+{
+    CMDIAD_REQUIRE(x && gamma && beta && out_f32, CMDIAD_ERR_ARG, "cmdiad_layernorm_skip_first: null pointer");
+    CMDIAD_REQUIRE(B > 0 && T >= 2 && (size_t)B * T < (1u << 31) && C % 128 == 0 && C >= 128 && C <= 1024 && ldo32 >= C && ldo32 % 2 == 0,
+                   CMDIAD_ERR_ARG, "cmdiad_layernorm_skip_first: need B > 0, T >= 2, C%%128==0, 128<=C<=1024, ldo32 >= C even "
+                   "(B=%d T=%d C=%d ldo32=%d)", B, T, C, ldo32);
+    CMDIAD_REQUIRE((((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)out_f32) & 7) == 0, CMDIAD_ERR_ARG,
+                   "cmdiad_layernorm_skip_first: alignment");
+    const int rows = B * (T - 1);
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid((rows + 3) / 4), block(256);
+#define LNS_CASE(P) case P: hipLaunchKernelGGL(layernorm_skip_first_kernel<P>, grid, block, 0, s, x, gamma, beta, eps, rows, T, out_f32, ldo32); break;
+    switch (C / 128) {
+        LNS_CASE(1) LNS_CASE(2) LNS_CASE(3) LNS_CASE(4) LNS_CASE(5) LNS_CASE(6) LNS_CASE(7) LNS_CASE(8)
+    }
+#undef LNS_CASE
+    CMDIAD_CHECK_LAUNCH();
+    return CMDIAD_OK;
+}
+
+extern "C" int cmdiad_lead_rows(float* x, float* pos, const float* lead_x, const float* lead_pos, int B, int T, int C,
+                                cmdiad_stream_t stream)
+{
+    CMDIAD_REQUIRE(x && lead_x && (!pos == !lead_pos), CMDIAD_ERR_ARG, "cmdiad_lead_rows: null pointer");
+    CMDIAD_REQUIRE(B > 0 && T > 0 && C > 0 && C % 4 == 0 && (size_t)B * (C / 4) < (1u << 31), CMDIAD_ERR_ARG,
+                   "cmdiad_lead_rows: bad sizes (B=%d T=%d C=%d)", B, T, C);
+    CMDIAD_REQUIRE((((uintptr_t)x | (uintptr_t)pos | (uintptr_t)lead_x | (uintptr_t)lead_pos) & 15) == 0, CMDIAD_ERR_ARG,
+                   "cmdiad_lead_rows: 16-byte alignment");
+    hipLaunchKernelGGL(lead_rows_kernel, dim3(blocks_for((size_t)B * (C / 4))), dim3(256), 0, (hipStream_t)stream, x, pos, lead_x, lead_pos,
+                       B, T, C);
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
 }

@@ -129,10 +129,14 @@ def load_backbone_weights(module, state_dict, what, ignore_unexpected=("head.", 
     return res
 
 
+POINTMAE_CHECKPOINT = "checkpoints/pointmae_pretrain.pth"
+POINTBERT_CHECKPOINT = "checkpoints/Point-BERT.pth"
+
+
 class Model(torch.nn.Module):
     def __init__(self, device, rgb_backbone_name='vit_base_patch8_224_dino', out_indices=None, checkpoint_path='',
                  pool_last=False, xyz_backbone_name='Point_MAE', group_size=128, num_group=1024,
-                 xyz_checkpoint_path="checkpoints/pointmae_pretrain.pth"):
+                 xyz_checkpoint_path=POINTMAE_CHECKPOINT):
         super().__init__()
         self.device = device
         self.rgb_backbone_name = rgb_backbone_name
@@ -151,10 +155,16 @@ class Model(torch.nn.Module):
         else:
             raise RuntimeError("no ViT-B/8 weights: pass checkpoint_path= / set CMDIAD_VIT_CHECKPOINT to a timm "
                                f"{rgb_backbone_name} state_dict, or opt in to random weights with CMDIAD_ALLOW_RANDOM_INIT=1")
-        if xyz_backbone_name != 'Point_MAE':
-            raise NotImplementedError("cmdiad_amd implements the Point_MAE xyz backbone only")
-        self.xyz_backbone = PointTransformer(group_size=group_size, num_group=num_group)
-        self.xyz_backbone.load_model_from_ckpt(os.environ.get("CMDIAD_POINTMAE_CHECKPOINT", xyz_checkpoint_path))
+        if xyz_backbone_name == 'Point_MAE':
+            self.xyz_backbone = PointTransformer(group_size=group_size, num_group=num_group)
+            self.xyz_backbone.load_model_from_ckpt(os.environ.get("CMDIAD_POINTMAE_CHECKPOINT", xyz_checkpoint_path))
+        elif xyz_backbone_name == 'Point_Bert':  # models/models.py:31-33
+            # (xyz_checkpoint_path defaults to the Point-MAE file; an explicitly different path is taken for Point-BERT too)
+            path = xyz_checkpoint_path if xyz_checkpoint_path != POINTMAE_CHECKPOINT else POINTBERT_CHECKPOINT
+            self.xyz_backbone = PointTransformer(group_size=group_size, num_group=num_group, encoder_dims=256)
+            self.xyz_backbone.load_model_from_pb_ckpt(os.environ.get("CMDIAD_POINTBERT_CHECKPOINT", path))
+        else:
+            raise NotImplementedError(f"cmdiad_amd implements the Point_MAE and Point_Bert xyz backbones only (got {xyz_backbone_name})")
         self._vit_packed = None
 
     def _vit(self):
@@ -227,12 +237,16 @@ class TransformerEncoder(nn.Module):
 class PointTransformer(torch.nn.Module):
     def __init__(self, group_size=128, num_group=1024, encoder_dims=384):
         super().__init__()
-        if encoder_dims != 384:
-            raise NotImplementedError("cmdiad_amd implements Point_MAE (encoder_dims=384); Point_Bert is out of scope")
+        if encoder_dims not in (384, 256):
+            raise NotImplementedError(f"cmdiad_amd implements Point_MAE (encoder_dims=384) and Point_Bert (256), not {encoder_dims}")
         self.trans_dim, self.depth, self.drop_path_rate, self.num_heads = 384, 12, 0.1, 6
         self.group_size, self.num_group = group_size, num_group
         self.group_divider = Group(num_group=self.num_group, group_size=self.group_size)
         self.encoder_dims = encoder_dims
+        if self.encoder_dims != self.trans_dim:  # Point-BERT (models/models.py:259-264): registered before the encoder, as there
+            self.cls_token = torch.nn.Parameter(torch.zeros(1, 1, self.trans_dim))
+            self.cls_pos = torch.nn.Parameter(torch.randn(1, 1, self.trans_dim))
+            self.reduce_dim = torch.nn.Linear(self.encoder_dims, self.trans_dim)
         self.encoder = Encoder(encoder_channel=self.encoder_dims)
         self.pos_embed = nn.Sequential(nn.Linear(3, 128), nn.GELU(), nn.Linear(128, self.trans_dim))
         self.blocks = TransformerEncoder(embed_dim=self.trans_dim, depth=self.depth, num_heads=self.num_heads)
@@ -259,14 +273,35 @@ class PointTransformer(torch.nn.Module):
         load_backbone_weights(self, base, f"Point-MAE checkpoint {bert_ckpt_path}",
                               ignore_unexpected=("MAE_decoder", "mask_token", "decoder_pos_embed", "increase_dim", "cls_"))
 
+    def load_model_from_pb_ckpt(self, bert_ckpt_path):
+        """Point-BERT checkpoint (models/models.py:297-322): the `transformer_q.` tensors except its classification heads, prefix
+        stripped (and any `base_model.` ones); the momentum encoder, the dVAE and the rest are dropped.  Unlike the reference's
+        strict=False load, a backbone tensor the file lacks is an error."""
+        if not os.path.exists(bert_ckpt_path):
+            if not allow_random_init():  # the reference fails here too (torch.load, models/models.py:298)
+                raise FileNotFoundError(f"{bert_ckpt_path} not found: place the Point-BERT checkpoint there, set "
+                                        "CMDIAD_POINTBERT_CHECKPOINT, or opt in to random weights with CMDIAD_ALLOW_RANDOM_INIT=1")
+            warnings.warn(f"{bert_ckpt_path} not found and CMDIAD_ALLOW_RANDOM_INIT=1: Point-BERT keeps its seeded random init")
+            return
+        ckpt = torch.load(bert_ckpt_path, map_location='cpu')
+        base = {k.replace("module.", ""): v for k, v in ckpt['base_model'].items()}
+        for k in list(base.keys()):  # models/models.py:301-308 key rewrite, step for step
+            if k.startswith('transformer_q') and not k.startswith('transformer_q.cls_head'):
+                base[k[len('transformer_q.'):]] = base[k]
+            elif k.startswith('base_model'):
+                base[k[len('base_model.'):]] = base[k]
+            del base[k]
+        # Point-BERT's masked transformer also carries its mask token and the dVAE-token head, which the extractor does not have
+        load_backbone_weights(self, base, f"Point-BERT checkpoint {bert_ckpt_path}", ignore_unexpected=("mask_token", "lm_head"))
+
     def packed(self):
         # BatchNorm mode: module.training selects nothing by itself (the contract of record is eval mode whatever the flag,
         # SURVEY F1 / DESIGN.md); CMDIAD_BN_BATCH_STATS=1 opts in to the reference's as-shipped batch-statistics behaviour
         ver = (_param_version(self), os.environ.get("CMDIAD_BN_BATCH_STATS", "0"))
         if self._packed is None or self._packed[0] != ver:
             dev = next(self.parameters()).device
-            self._packed = (ver, runtime.PackedPointMAE(self.state_dict(), device=dev, group_size=self.group_size,
-                                                        num_group=self.num_group))
+            cls = runtime.PackedPointMAE if self.encoder_dims == self.trans_dim else runtime.PackedPointBERT
+            self._packed = (ver, cls(self.state_dict(), device=dev, group_size=self.group_size, num_group=self.num_group))
         return self._packed[1]
 
     def forward_device(self, xyz_nc, n_valid=None):

@@ -280,6 +280,22 @@ def encoder_tail(h2, gb, W3b, W4, b4, groups, Mg):
     return tok
 
 
+def encoder_tail_n(h2, gb, W3b, W4, b4, groups, Mg, seg=0, out=None):
+    """cmdiad_encoder_tail_n: tokens [groups, N] f32 at N = W4.shape[0] (256 or 384).  seg > 0 (N = 256): group g goes to row
+    g + g // seg + 1 of out [groups + groups // seg, N], whose first row of every seg-group cloud is left unwritten."""
+    _chk(h2, torch.bfloat16, "tail.h2"); _chk(gb, torch.float32, "tail.gb")
+    N = W4.shape[0]
+    if tuple(h2.shape) != (groups * Mg, 256) or tuple(gb.shape) != (groups, 512) or tuple(W4.shape) != (N, 512) or b4.numel() != N:
+        raise ValueError(f"tail: h2 {tuple(h2.shape)}, gb {tuple(gb.shape)}, W4 {tuple(W4.shape)} for {groups} groups of {Mg}")
+    rows = groups + (groups // seg if seg else 0)
+    if out is None:
+        out = torch.empty((rows, N), dtype=torch.float32, device=h2.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (rows, N):
+        raise ValueError(f"tail.out: need a contiguous f32 [{rows}, {N}] tensor, got {out.dtype} {tuple(out.shape)}")
+    _call("cmdiad_encoder_tail_n", _p(h2), _p(gb), _p(W3b), _p(W4), _p(b4), groups, Mg, N, seg, _p(out), _stream())
+    return out
+
+
 def conv2d_nhwc(x, W, N, ksize=3, stride=1, bias=None, act=ACT_NONE, residual=None, out_f32=None, out_bf16=None,
                 want_f32=False, want_bf16=True):
     """x [B,H,W,C] bf16 NHWC, W [N, ksize*ksize*C] bf16 (tap-major) -> (out_f32 | None, out_bf16 | None), each [B,Ho,Wo,ld]
@@ -371,6 +387,28 @@ def layernorm(x, gamma, beta, eps, add=None, out_bf16=None, out_f32=None, want_b
     _call("cmdiad_layernorm", _p(x), _p(add), _p(gamma), _p(beta), float(eps), M, C, _p(out_bf16), _p(out_f32), ld,
           _p(mean_o), _p(rstd_o), _stream())
     return out_bf16
+
+
+def layernorm_skip_first(x, gamma, beta, eps, B, T, out_f32):
+    """x [B*T, C] f32 -> LN of every row but the first of each T-row segment into out_f32 [B*(T-1), >= C] (a column slice is fine)."""
+    _chk(x, torch.float32, "ln_skip.x")
+    C = x.shape[1]
+    if x.shape[0] != B * T or gamma.numel() != C or beta.numel() != C:
+        raise ValueError(f"ln_skip: x {tuple(x.shape)} is not [{B} x {T}, C] or gamma / beta are not [C]")
+    if out_f32.dtype != torch.float32 or out_f32.stride(1) != 1 or out_f32.shape[0] != B * (T - 1) or out_f32.shape[1] != C:
+        raise ValueError(f"ln_skip.out_f32: need f32 [{B * (T - 1)}, {C}] with unit column stride")
+    _call("cmdiad_layernorm_skip_first", _p(x), _p(gamma), _p(beta), float(eps), B, T, C, _p(out_f32), out_f32.stride(0), _stream())
+    return out_f32
+
+
+def lead_rows(x, pos, lead_x, lead_pos, B, T):
+    """Row b*T of x (and of pos) <- lead_x (lead_pos), in place; x, pos [B*T, C] f32."""
+    _chk(x, torch.float32, "lead.x"); _chk(pos, torch.float32, "lead.pos")
+    C = x.shape[1]
+    if x.shape[0] != B * T or (pos is not None and pos.shape != x.shape) or lead_x.numel() != C or (pos is not None and lead_pos.numel() != C):
+        raise ValueError(f"lead: x {tuple(x.shape)} is not [{B} x {T}, C], or pos / the lead rows do not match it")
+    _call("cmdiad_lead_rows", _p(x), _p(pos), _p(lead_x), _p(lead_pos), B, T, x.shape[1], _stream())
+    return x
 
 
 def col_moments(x):

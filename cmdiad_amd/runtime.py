@@ -4,7 +4,7 @@ eval-mode BatchNorm folded into the 1x1 convolutions) from a ``state_dict`` that
 reference's parameter names, so real checkpoints and synthetic weights load the same way.
 
 Reference anchors: ViT-B/8 models/models.py:35-53 (timm VisionTransformer [external]);
-Point-MAE models/models.py:183-243, 352-373; hallucination MLP models/hallucination_network.py:34-45,
+Point-MAE models/models.py:183-243, 352-373; Point-BERT (encoder_dims 256) models/models.py:259-264, 326-352; hallucination MLP models/hallucination_network.py:34-45,
 utils/utils.py:86-115.
 """
 import os
@@ -235,35 +235,43 @@ class PackedPointMAE:
           BN2: a statistics pass evaluates conv3's pre-activation z = W3b . h2 + (W3a . gmax + b3) in fp32 and reduces its
                column moments (cmdiad_col_moments); then scale = gamma / sqrt(var + eps) goes into W3b and the group bias."""
         B, G, Mg, _ = neighborhood.shape
-        e, r = self.enc, self.enc_raw
+        e = self.enc
         toks = []
         for b in range(B):
-            pts = neighborhood[b].reshape(-1, 3).contiguous()
-            mu, cov = ops.moments3(pts)
-            w1 = r["w1"].double()
-            mean1 = w1 @ mu + r["b1"].double()
-            var1 = ((w1 @ cov) * w1).sum(1).clamp_min(0.0)
-            s1 = r["g1"].double() / torch.sqrt(var1 + eps)
-            w1b1 = torch.cat([w1 * s1[:, None], ((r["b1"].double() - mean1) * s1 + r["be1"].double())[:, None]], 1).float().contiguous()
-            h2, _, g16 = ops.encoder_stage1(pts, w1b1, e["W2"], e["b2"], G, Mg)
-            gb_raw, _ = ops.gemm(g16, e["W3a_raw"], bias=r["b3"], want_f32=True, want_bf16=False)
-            z, _ = ops.gemm(h2, e["W3b_raw"], group_bias=gb_raw, group_rows=Mg, want_f32=True, want_bf16=False)
-            mean2, var2 = ops.col_moments(z)
-            del z
-            s2 = r["g2"].double() / torch.sqrt(var2.clamp_min(0.0) + eps)
-            w3b = ops.cast_bf16((r["w3"][:, 256:].double() * s2[:, None]).float().contiguous())
-            gb = ((gb_raw.double() - mean2) * s2 + r["be2"].double()).float().contiguous()
+            h2, gb, w3b = self.batch_stats_fold(neighborhood[b], eps)
             toks.append(ops.encoder_tail(h2, gb, w3b, e["W4"], e["b4"], G, Mg))
         return torch.cat(toks, 0)
+
+    def batch_stats_fold(self, nb, eps=1e-5):
+        """One sample's neighbourhoods nb [G,Mg,3] -> (h2, group bias, W3b) with both BatchNorms folded in from the sample's own
+        statistics (encode_batch_stats); the encoder tail finishes the encoder on them."""
+        G, Mg, _ = nb.shape
+        e, r = self.enc, self.enc_raw
+        if "W3a_raw" not in e:
+            e["W3a_raw"] = ops.cast_bf16(r["w3"][:, :256].contiguous())
+            e["W3b_raw"] = ops.cast_bf16(r["w3"][:, 256:].contiguous())
+        pts = nb.reshape(-1, 3).contiguous()
+        mu, cov = ops.moments3(pts)
+        w1 = r["w1"].double()
+        mean1 = w1 @ mu + r["b1"].double()
+        var1 = ((w1 @ cov) * w1).sum(1).clamp_min(0.0)
+        s1 = r["g1"].double() / torch.sqrt(var1 + eps)
+        w1b1 = torch.cat([w1 * s1[:, None], ((r["b1"].double() - mean1) * s1 + r["be1"].double())[:, None]], 1).float().contiguous()
+        h2, _, g16 = ops.encoder_stage1(pts, w1b1, e["W2"], e["b2"], G, Mg)
+        gb_raw, _ = ops.gemm(g16, e["W3a_raw"], bias=r["b3"], want_f32=True, want_bf16=False)
+        z, _ = ops.gemm(h2, e["W3b_raw"], group_bias=gb_raw, group_rows=Mg, want_f32=True, want_bf16=False)
+        mean2, var2 = ops.col_moments(z)
+        del z
+        s2 = r["g2"].double() / torch.sqrt(var2.clamp_min(0.0) + eps)
+        w3b = ops.cast_bf16((r["w3"][:, 256:].double() * s2[:, None]).float().contiguous())
+        gb = ((gb_raw.double() - mean2) * s2 + r["be2"].double()).float().contiguous()
+        return h2, gb, w3b
 
     def encode(self, neighborhood):
         """neighborhood [B,G,Mg,3] f32 -> tokens [B*G, 384] f32 (models/models.py:200-215)."""
         B, G, Mg, _ = neighborhood.shape
         e = self.enc
         if self.bn_batch_stats:
-            if "W3a_raw" not in e:
-                e["W3a_raw"] = ops.cast_bf16(self.enc_raw["w3"][:, :256].contiguous())
-                e["W3b_raw"] = ops.cast_bf16(self.enc_raw["w3"][:, 256:].contiguous())
             return self.encode_batch_stats(neighborhood)
         h2, _, g16 = ops.encoder_stage1(neighborhood.reshape(-1, 3), e["w1b1"], e["W2"], e["b2"], B * G, Mg)
         gb, _ = ops.gemm(g16, e["W3a"], bias=e["b3"], want_f32=True, want_bf16=False)
@@ -307,6 +315,64 @@ class PackedPointMAE:
         tok = self.encode(nb)
         feats = self.transform(tok, center)
         return feats, center, ori_idx, center_idx
+
+
+# ------------------------------------------------------------------------------------------- Point-BERT
+class PackedPointBERT(PackedPointMAE):
+    """Point-BERT as the reference runs it (PointTransformer(encoder_dims=256), models/models.py:246-352): Point-MAE's grouping and
+    encoder with a 256-wide last conv, reduce_dim 256 -> 384, a cls token in front of every cloud (T = G + 1) with its own
+    positional row, and fetch LayerNorms that drop the cls row.  Same sample() / forward() contract as PackedPointMAE.
+    Rows of the residual and positional streams: cloud b's cls at b*(G+1), its token g at b*(G+1) + 1 + g.  The encoder tail
+    scatters its tokens to that layout (cls rows left unwritten), reduce_dim and pos_embed.2 run over all B*(G+1) rows, then
+    cmdiad_lead_rows overwrites the B cls rows with cls_token / cls_pos: the streams are never copied or concatenated.
+    The encoder always runs as the fused tail (CMDIAD_ENCODER_TAIL only selects Point-MAE's path)."""
+
+    def __init__(self, sd, prefix="", device="cuda", **kw):
+        super().__init__(sd, prefix, device, **kw)
+        self.enc_dim = self.enc["W4"].shape[0]                       # 256
+        self.dim = sd[prefix + "reduce_dim.weight"].shape[0]         # 384: the transformer's width
+        if self.enc_dim != 256 or sd[prefix + "reduce_dim.weight"].shape[1] != 256:
+            raise ValueError(f"PackedPointBERT: encoder width {self.enc_dim}, reduce_dim {tuple(sd[prefix + 'reduce_dim.weight'].shape)}: "
+                             "need 256 -> 384")
+        self.red_w = _bf(sd[prefix + "reduce_dim.weight"], device)
+        self.red_b = _dev(sd[prefix + "reduce_dim.bias"], device)
+        self.cls = _dev(sd[prefix + "cls_token"].reshape(-1), device)
+        self.cls_pos = _dev(sd[prefix + "cls_pos"].reshape(-1), device)
+
+    def encode(self, neighborhood):
+        """neighborhood [B,G,Mg,3] f32 -> encoder tokens [B*(G+1), 256] f32 in the cls-row layout; the B cls rows are NOT written
+        (models/models.py:330; reduce_dim's output on them is overwritten by cls_token)."""
+        B, G, Mg, _ = neighborhood.shape
+        e = self.enc
+        out = torch.empty((B * (G + 1), self.enc_dim), dtype=torch.float32, device=neighborhood.device)
+        if self.bn_batch_stats:
+            for b in range(B):
+                h2, gb, w3b = self.batch_stats_fold(neighborhood[b])
+                ops.encoder_tail_n(h2, gb, w3b, e["W4"], e["b4"], G, Mg, seg=G, out=out[b * (G + 1):(b + 1) * (G + 1)])
+            return out
+        h2, _, g16 = ops.encoder_stage1(neighborhood.reshape(-1, 3), e["w1b1"], e["W2"], e["b2"], B * G, Mg)
+        gb, _ = ops.gemm(g16, e["W3a"], bias=e["b3"], want_f32=True, want_bf16=False)
+        return ops.encoder_tail_n(h2, gb, e["W3b"], e["W4"], e["b4"], B * G, Mg, seg=G, out=out)
+
+    def transform(self, tokens, center):
+        """tokens [B*(G+1),256] f32 (encode()), center [B,G,3] -> feats [B, G, 768] f32, centre-major (models/models.py:335-352)."""
+        B, G, _ = center.shape
+        T, C = G + 1, self.dim
+        x, _ = ops.gemm(ops.cast_bf16(tokens), self.red_w, bias=self.red_b, want_f32=True, want_bf16=False)   # [B*T, 384]
+        cen = center.new_zeros((B, T, 3))   # (the cls rows' positions are placeholders: cls_pos replaces their embedding)
+        cen[:, 1:] = center
+        p1 = ops.linear3(cen.view(-1, 3), self.pos0, ops.ACT_GELU)
+        pos, _ = ops.gemm(p1, self.pos2_w, bias=self.pos2_b, want_f32=True, want_bf16=False)
+        ops.lead_rows(x, pos, self.cls, self.cls_pos, B, T)
+        feats = torch.empty((B * G, C * len(self.taps)), dtype=torch.float32, device=tokens.device)
+        t = 0
+        n = len(self.blocks)
+        for i, blk in enumerate(self.blocks):
+            transformer_block(x, blk, B, T, self.heads, 1e-5, self.bufs, pos=pos, flags=block_flags(i, n, "qkv_wf" in blk, self.taps))
+            if i in self.taps:
+                ops.layernorm_skip_first(x, self.norm_w, self.norm_b, 1e-5, B, T, feats[:, t * C:(t + 1) * C])
+                t += 1
+        return feats.view(B, G, -1)
 
 
 # ------------------------------------------------------------------------------------------- hallucination MLP

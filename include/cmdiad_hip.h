@@ -210,12 +210,30 @@ int cmdiad_layernorm(float* x, const float* add, const float* gamma, const float
                      int C, uint16_t* out_bf16, float* out_f32, int ldo32, float* mean_out, float* rstd_out,
                      cmdiad_stream_t stream);
 
+/* LayerNorm of every row but the first of each of B segments of T rows (Point-BERT's fetch layers drop the cls row,
+ * models/models.py:348): x [B*T, C] f32 -> out_f32 row b*(T-1) + t-1 (leading dimension ldo32) = LN(x row b*T + t), t >= 1.
+ * Same arithmetic as cmdiad_layernorm's float2 form.  C % 128 == 0, 128 <= C <= 1024, T >= 2. */
+int cmdiad_layernorm_skip_first(const float* x, const float* gamma, const float* beta, float eps, int B, int T, int C,
+                                float* out_f32, int ldo32, cmdiad_stream_t stream);
+
+/* Row b*T of x [B*T, C] <- lead_x [C] and of pos <- lead_pos [C] (pos and lead_pos: both or neither), for b < B: Point-BERT's cls
+ * token and cls_pos (models/models.py:338-344) in front of each cloud's token rows. */
+int cmdiad_lead_rows(float* x, float* pos, const float* lead_x, const float* lead_pos, int B, int T, int C, cmdiad_stream_t stream);
+
 /* Second half of the Point-MAE encoder in one kernel (models/models.py:204-215): h3 = ReLU(W3b . h2 + gb[group]) is produced
  * and consumed in LDS, tok[g] = max over the group's rows of (W4 . h3 + b4).  h2 [groups*Mg, 256] bf16 and gb [groups, 512] f32
  * (= W3a . groupmax(h2) + b3) as produced by cmdiad_encoder_stage1 + cmdiad_gemm_bf16; W3b [512,256], W4 [384,512] bf16;
  * tok_out [groups, 384] f32.  Bit-identical to cmdiad_gemm_bf16(ReLU, group_bias) followed by cmdiad_gemm_groupmax. */
 int cmdiad_encoder_tail(const uint16_t* h2, const float* gb, const uint16_t* W3b, const uint16_t* W4, const float* b4,
                         int groups, int Mg, float* tok_out, cmdiad_stream_t stream);
+
+/* The same kernel at n_out output columns: 384 (= cmdiad_encoder_tail) or 256 (Point-BERT's encoder, models/models.py:31-33 with
+ * encoder_dims = 256: W4 [256,512], b4 [256]).  seg = 0: tok_out [groups, n_out]; seg > 0 (n_out 256 only, seg | groups): group g's
+ * token goes to row g + g / seg + 1 of tok_out [groups + groups / seg, n_out], i.e. every cloud of seg groups gets one leading row
+ * that is NOT written (Point-BERT's cls row, filled after reduce_dim by cmdiad_lead_rows).  Bit-identical to
+ * cmdiad_gemm_bf16(ReLU, group_bias) + cmdiad_gemm_groupmax at N = n_out. */
+int cmdiad_encoder_tail_n(const uint16_t* h2, const float* gb, const uint16_t* W3b, const uint16_t* W4, const float* b4,
+                          int groups, int Mg, int n_out, int seg, float* tok_out, cmdiad_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Convolution heads of the distillation networks: models/hallucination_network.py:72-143
