@@ -110,6 +110,8 @@ SIGNATURES = {
     "cmdiad_normalize_cast": [P, SZ, I, F, F, P, P, P, I, P],
     "cmdiad_normalize_cast_rows": [P, SZ, I, I, I, F, F, P, P, P, I, P],
     "cmdiad_im2col_patch8": [P, I, I, P, P],
+    "cmdiad_im2col_patch14": [P, I, I, P, P],
+    "cmdiad_token_pool56": [P, I, I, I, P, P],
     "cmdiad_im2col3x3_bf16": [P, I, I, I, I, I, I, P, P],
     "cmdiad_vit_assemble": [P, P, P, I, I, I, P, P],
     "cmdiad_bilinear_up": [P, I, I, I, P, P],

@@ -160,6 +160,63 @@ __global__ __launch_bounds__(256) void im2col3x3_kernel(const float* __restrict_
     *reinterpret_cast<bf16x8*>(cols + pix * ld + ch * 8) = o;
 }
 
+// DINOv2's 14 x 14 patch embedding as a GEMM operand: rgb [B,3,S,S] f32 -> patches [B*(S/14)^2, 640] bf16, column
+// k = c*196 + dy*14 + dx (conv weight [768,3,14,14] flattened), columns 588..639 zero (the GEMM core needs K % 64 == 0).  A 14-float
+// image row is only 8-byte aligned at odd patch columns, so this is im2col3x3_kernel's scheme: one thread per (patch, 8 columns),
+// scalar reads, one 16-byte store.
+__global__ __launch_bounds__(256) void im2col_patch14_kernel(const float* __restrict__ rgb, int B, int S, bf16_t* __restrict__ patches)
+{
+    constexpr int kCols = 640, kChunks = kCols / 8, kTaps = 3 * 14 * 14;
+    const int P = S / 14;
+    const size_t total = (size_t)B * P * P * kChunks;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int ch = (int)(i % kChunks);
+    const size_t pi = i / kChunks;
+    const int px = (int)(pi % P), py = (int)((pi / P) % P), b = (int)(pi / ((size_t)P * P));
+    bf16x8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int k = ch * 8 + e;
+        float v = 0.0f;
+        if (k < kTaps) {
+            const int c = k / 196, dy = (k % 196) / 14, dx = k % 14;
+            v = rgb[(((size_t)b * 3 + c) * S + (py * 14 + dy)) * S + px * 14 + dx];
+        }
+        o[e] = f2bf(v);
+    }
+    *reinterpret_cast<bf16x8*>(patches + pi * kCols + ch * 8) = o;
+}
+
+// torch.nn.AdaptiveAvgPool2d((56, 56)) of the s x s patch-token grid (features.py:165-166), read in place from the tokens
+// [B, 1 + s*s, C] (row 0 of every image, the cls token, is skipped) -> out [B, 56*56, C] f32.  Window of output cell i on an axis:
+// [floor(i s / 56), ceil((i + 1) s / 56)).  ATen's CPU kernel step for step (cpu_adaptive_avg_pool2d): sum = 0, += the window
+// row-major, then sum / kh / kw -- the same roundings, so the same bits.  One thread per (output cell, 4 channels).
+__global__ __launch_bounds__(256) void token_pool56_kernel(const float* __restrict__ tokens, int B, int s, int C, float* __restrict__ out)
+{
+    constexpr int O = 56;
+    const int c4 = C / 4;
+    const size_t total = (size_t)B * O * O * c4;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int c = (int)(i % c4) * 4;
+    const size_t cell = i / c4;
+    const int ox = (int)(cell % O), oy = (int)((cell / O) % O);
+    const size_t b = cell / (O * O);
+    const int y0 = oy * s / O, y1 = ((oy + 1) * s + O - 1) / O;
+    const int x0 = ox * s / O, x1 = ((ox + 1) * s + O - 1) / O;
+    const float* img = tokens + (b * ((size_t)s * s + 1) + 1) * C + c;
+    float4 sum = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (int y = y0; y < y1; ++y)
+        for (int x = x0; x < x1; ++x) {
+            const float4 v = *reinterpret_cast<const float4*>(img + ((size_t)y * s + x) * C);
+            sum.x += v.x; sum.y += v.y; sum.z += v.z; sum.w += v.w;
+        }
+    const float kh = (float)(y1 - y0), kw = (float)(x1 - x0);
+    *reinterpret_cast<float4*>(out + cell * C + c) =
+        make_float4(sum.x / kh / kw, sum.y / kh / kw, sum.z / kh / kw, sum.w / kh / kw);
+}
+
 // tokens[b][0] = cls + pos[0]; tokens[b][1+i] = patch_out[b][i] + pos[1+i]
 __global__ __launch_bounds__(256) void vit_assemble_kernel(const float* __restrict__ patch_out, const float* __restrict__ cls,
                                                            const float* __restrict__ pos, int B, int P, int C,
@@ -456,6 +513,30 @@ extern "C" int cmdiad_im2col3x3_bf16(const float* img, int B, int C, int H, int 
     const size_t total = (size_t)B * Ho * Wo * (ld / 8);
     hipLaunchKernelGGL(im2col3x3_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, img, B, C, H, W, stride, Ho, Wo, ld,
                        (bf16_t*)cols);
+    CMDIAD_CHECK_LAUNCH();
+    return CMDIAD_OK;
+}
+
+extern "C" int cmdiad_im2col_patch14(const float* rgb, int B, int S, uint16_t* patches, cmdiad_stream_t stream)
+{
+    CMDIAD_REQUIRE(rgb && patches, CMDIAD_ERR_ARG, "cmdiad_im2col_patch14: null pointer");
+    CMDIAD_REQUIRE(B > 0 && B <= (1 << 16) && S >= 14 && S % 14 == 0 && S <= 14 * 1024, CMDIAD_ERR_ARG,
+                   "cmdiad_im2col_patch14: need 0 < B <= 65536, S %% 14 == 0, 14 <= S <= 14336 (B=%d S=%d)", B, S);
+    CMDIAD_REQUIRE((((uintptr_t)rgb & 3) | ((uintptr_t)patches & 15)) == 0, CMDIAD_ERR_ARG, "cmdiad_im2col_patch14: alignment");
+    const size_t total = (size_t)B * (S / 14) * (S / 14) * 80;
+    hipLaunchKernelGGL(im2col_patch14_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, rgb, B, S, (bf16_t*)patches);
+    CMDIAD_CHECK_LAUNCH();
+    return CMDIAD_OK;
+}
+
+extern "C" int cmdiad_token_pool56(const float* tokens, int B, int s, int C, float* out, cmdiad_stream_t stream)
+{
+    CMDIAD_REQUIRE(tokens && out, CMDIAD_ERR_ARG, "cmdiad_token_pool56: null pointer");
+    CMDIAD_REQUIRE(B > 0 && B <= (1 << 16) && s > 0 && s <= 1024 && C > 0 && C % 4 == 0 && C <= 65536, CMDIAD_ERR_ARG,
+                   "cmdiad_token_pool56: need 0 < B <= 65536, 0 < s <= 1024, 0 < C <= 65536, C %% 4 == 0 (B=%d s=%d C=%d)", B, s, C);
+    CMDIAD_REQUIRE((((uintptr_t)tokens | (uintptr_t)out) & 15) == 0, CMDIAD_ERR_ARG, "cmdiad_token_pool56: 16-byte alignment");
+    const size_t total = (size_t)B * 56 * 56 * (C / 4);
+    hipLaunchKernelGGL(token_pool56_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, tokens, B, s, C, out);
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
 }

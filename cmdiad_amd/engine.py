@@ -544,16 +544,20 @@ class Engine:
 
     @staticmethod
     def rgb_patch(ex):
-        """[B,784,768] view of the ViT tokens without cls (features.py:160-162)."""
+        """[B,s*s,768] view of the ViT tokens without cls (features.py:160-162): 784 rows (ViT-B/8), 1 369 (DINOv2)."""
         return ex.rgb_tokens[:, 1:]
 
     @staticmethod
     def rgb_patch56(ex):
-        """features.py:165-166: AdaptiveAvgPool2d 28->56 == exact 2x nearest replication."""
+        """features.py:165-166: AdaptiveAvgPool2d((56, 56)) of the s x s token grid, s from the token count.  s = 28 (ViT-B/8):
+        exact 2x nearest replication, a view that costs nothing; any other grid (DINOv2's 37 x 37): cmdiad_token_pool56,
+        the bits of torch's adaptive_avg_pool2d."""
+        B, T, C = ex.rgb_tokens.shape
+        s = int(math.isqrt(T - 1))
+        if s != 28:
+            return ops.token_pool56(ex.rgb_tokens)
         p = ex.rgb_tokens[:, 1:]
-        B, T, C = p.shape
-        s = int(math.isqrt(T))
-        return p.reshape(B, s, 1, s, 1, C).expand(B, s, 2, s, 2, C).reshape(B, 4 * T, C)
+        return p.reshape(B, s, 1, s, 1, C).expand(B, s, 2, s, 2, C).reshape(B, 4 * (T - 1), C)
 
 
 def predict_batch(engine, rgb, pcs, bank_xyz, bank_second, stats, det, seg, **kw):

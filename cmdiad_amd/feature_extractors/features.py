@@ -22,7 +22,7 @@ from sklearn.metrics import roc_auc_score
 
 from .. import engine as eng
 from .. import ops
-from ..models.models import Model
+from ..models.models import DINOV2_NAME, DINOV2_SIZE, Model
 from ..utils.utils import KNNGaussianBlur, set_seeds
 
 
@@ -115,6 +115,7 @@ class Features(torch.nn.Module):
         loading the frozen backbones again -- the reference's class loop builds a fresh object, i.e. re-loads both checkpoints,
         for every class (main.py:23); cmdiad_amd.evaluate hands the rank's extractor from class to class."""
         super().__init__()
+        self._refuse(args)
         from .. import _native
         _native.lib()  # fail loudly at construction when libcmdiad_hip.so is missing
         self.device = "cuda" if torch.cuda.is_available() else "cpu"
@@ -185,6 +186,14 @@ class Features(torch.nn.Module):
         self._engine = eng.Engine(self.deep_feature_extractor._vit, self.deep_feature_extractor.xyz_backbone.packed,
                                   size=self.xyz_size)
         self._banks = {}
+
+    @classmethod
+    def _refuse(cls, args):
+        """Configurations the reference itself cannot run, refused when the method object is built (NotImplementedError naming the
+        reason, as every other refusal of the package) instead of deep inside a kernel.  Subclasses add their own."""
+        if getattr(args, "rgb_backbone_name", "") == DINOV2_NAME and getattr(args, "rgb_size", DINOV2_SIZE) != DINOV2_SIZE:
+            raise NotImplementedError(f"{DINOV2_NAME} takes {DINOV2_SIZE} x {DINOV2_SIZE} images (timm's PatchEmbed asserts it, "
+                                      f"models/models.py:23-25): run it with --rgb_size {DINOV2_SIZE}, not {args.rgb_size}")
 
     # ------------------------------------------------------------------------------------ extraction
     def __call__(self, rgb=None, xyz=None, out_type="rgb+xyz"):
@@ -262,14 +271,17 @@ class Features(torch.nn.Module):
         return ex
 
     def get_rgb_patch(self, rgb_feature_maps):
-        """features.py:160-167 -> (rgb_patch [784,768], rgb_patch2 [3136,768]) on the GPU."""
+        """features.py:160-167 -> (rgb_patch [s*s,768], rgb_patch2 [3136,768]) on the GPU (s = 28 for ViT-B/8, 37 for DINOv2)."""
         ex = getattr(rgb_feature_maps[0], "_cmdiad", None)
         if ex is not None and len(rgb_feature_maps) == 1:
             return eng.Engine.rgb_patch(ex)[0], eng.Engine.rgb_patch56(ex)[0]
         fm = torch.cat(rgb_feature_maps, 1).to(self.device)
         p = fm.reshape(fm.shape[1], -1).T.contiguous()
         s = int(math.isqrt(p.shape[0]))
-        p2 = p.reshape(s, 1, s, 1, -1).expand(s, 2, s, 2, -1).reshape(4 * s * s, -1)
+        if s == 28:
+            p2 = p.reshape(s, 1, s, 1, -1).expand(s, 2, s, 2, -1).reshape(4 * s * s, -1)
+        else:   # the pooling kernel reads [1, 1 + s*s, C] tokens: a row in front stands in for the cls token it skips
+            p2 = ops.token_pool56(torch.cat([p.new_zeros((1, p.shape[1])), p.float()], 0).unsqueeze(0))[0]
         return p, p2
 
     def get_xyz_patch(self, xyz_feature_maps, interpolated_pc, nonzero_indices, get_2828=False):

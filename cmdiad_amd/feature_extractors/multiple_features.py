@@ -19,6 +19,7 @@ import torch
 
 from .. import engine as eng
 from .. import ops
+from ..models.models import DINOV2_NAME, DINOV2_SIZE
 from .features import Features
 
 
@@ -398,9 +399,10 @@ class DoubleRGBPointFeatures(_MethodBase):
                 for sp in ("train", "test"):
                     os.makedirs(os.path.join(a.save_path_rgb_fxyz, sp, sub), exist_ok=True)
             low = self._engine.xyz_patch(ex, P=28)          # get_xyz_patch(..., get_2828=True), features.py:169-184
+            size = getattr(self, "rgb_size", 224)           # (518 with DINOv2: the image is saved at the size it has)
             for smp, hi, lo in zip(samples, xyz_patch, low):
                 img = smp[0].squeeze()
-                assert tuple(lo.shape) == (784, 768) and tuple(hi.shape) == (3136, 768) and tuple(img.shape) == (3, 224, 224)
+                assert tuple(lo.shape) == (784, 768) and tuple(hi.shape) == (3136, 768) and tuple(img.shape) == (3, size, size)
                 stem = self.class_name + str(self.ins_id3)
                 torch.save(hi.cpu(), os.path.join(a.save_path_rgb_fxyz, split, 'fxyz', stem + '_hfxyz.pt'))
                 torch.save(lo.cpu(), os.path.join(a.save_path_rgb_fxyz, split, 'fxyz', stem + '_lfxyz.pt'))
@@ -447,6 +449,15 @@ class RGBorXYZWithOneHallucination(_MethodBase):
     """MTFI with one real and one hallucinated modality (multiple_features.py:312-573): the main modality's real features
     plus the other modality's features hallucinated either from the main modality's FEATURES (``--use_hn``: the FtoF MLP, or
     the FtoF conv head when ``--use_hn_conv`` is given as well) or from the main modality's INPUT (``--use_hrnet``, ItoF)."""
+
+    @classmethod
+    def _refuse(cls, args):
+        super()._refuse(args)
+        if (getattr(args, "rgb_backbone_name", "") == DINOV2_NAME and getattr(args, "use_hrnet", False)
+                and getattr(args, "main_modality", "") == "rgb"):
+            raise NotImplementedError(f"--use_hrnet with main_modality 'rgb' and {DINOV2_NAME}: the reference runs HRNet on the "
+                                      f"{DINOV2_SIZE} x {DINOV2_SIZE} image and asserts a 56 x 56 output (multiple_features.py:326-330), "
+                                      "which fails")
 
     def _hallucinate(self, samples, xyz_patch, rgb_patch2):
         """-> [B, 3136, 768] hallucinated features of the OTHER modality."""
@@ -514,6 +525,14 @@ class RGBorXYZWithOneHallucinationFromFeature(RGBorXYZWithOneHallucination):
     As in the reference, with main_modality == 'rgb' the real point cloud is only read while the memory bank is built
     (its patches feed the cross-wired statistics, :582,605,612-618); late fusion and predict never touch it (:651-663,
     :701-719), so the 3-D branch of the extractor is skipped there."""
+
+    @classmethod
+    def _refuse(cls, args):
+        super()._refuse(args)
+        if getattr(args, "rgb_backbone_name", "") == DINOV2_NAME and getattr(args, "main_modality", "") == "xyz":
+            raise NotImplementedError(f"feature-to-input heads with main_modality 'xyz' and {DINOV2_NAME}: the reference feeds the "
+                                      f"head's 224 x 224 image to a backbone that takes {DINOV2_SIZE} x {DINOV2_SIZE} and asserts the "
+                                      "sample's shape (multiple_features.py:597-603), which fails")
 
     def _patches(self, samples, fit=False):
         a = self.args

@@ -52,6 +52,26 @@ class Block(nn.Module):
         self.attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias, qk_scale=qk_scale)
 
 
+class LayerScale(nn.Module):
+    def __init__(self, dim, init_values=1e-5):
+        super().__init__()
+        self.gamma = nn.Parameter(init_values * torch.ones(dim))
+
+
+class LayerScaleBlock(nn.Module):
+    """timm's ``Block`` with LayerScale (``init_values`` set, as in ``vit_base_patch14_dinov2``): x + ls1.gamma * attn(norm1(x)),
+    then x + ls2.gamma * mlp(norm2(x)).  Registered in timm's order."""
+
+    def __init__(self, dim, num_heads, mlp_ratio=4., init_values=1e-5):
+        super().__init__()
+        self.norm1 = nn.LayerNorm(dim, eps=1e-6)
+        self.attn = Attention(dim, num_heads=num_heads, qkv_bias=True)
+        self.ls1 = LayerScale(dim, init_values)
+        self.norm2 = nn.LayerNorm(dim, eps=1e-6)
+        self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio))
+        self.ls2 = LayerScale(dim, init_values)
+
+
 class _PatchEmbed(nn.Module):
     def __init__(self, dim, patch):
         super().__init__()
@@ -59,16 +79,20 @@ class _PatchEmbed(nn.Module):
 
 
 class VisionTransformer(nn.Module):
-    """Parameter layout of timm's ``vit_base_patch8_224(_dino)`` (timm==0.9.12 [external])."""
+    """Parameter layout of timm's ``vit_base_patch8_224(_dino)`` (timm==0.9.12 [external]); with ``init_values`` (LayerScale in
+    every block) that of ``vit_base_patch14_dinov2.lvd142m``: img_size 518, patch 14, a 37 x 37 grid."""
 
-    def __init__(self, img_size=224, patch=8, dim=768, depth=12, num_heads=12):
+    def __init__(self, img_size=224, patch=8, dim=768, depth=12, num_heads=12, init_values=None):
         super().__init__()
         self.num_heads, self.depth = num_heads, depth
         n = (img_size // patch) ** 2
         self.cls_token = nn.Parameter(torch.zeros(1, 1, dim))
         self.pos_embed = nn.Parameter(torch.zeros(1, n + 1, dim))
         self.patch_embed = _PatchEmbed(dim, patch)
-        self.blocks = nn.Sequential(*[Block(dim, num_heads, 4.0, qkv_bias=True) for _ in range(depth)])
+        if init_values is None:
+            self.blocks = nn.Sequential(*[Block(dim, num_heads, 4.0, qkv_bias=True) for _ in range(depth)])
+        else:
+            self.blocks = nn.Sequential(*[LayerScaleBlock(dim, num_heads, 4.0, init_values) for _ in range(depth)])
         self.norm = nn.LayerNorm(dim, eps=1e-6)
         nn.init.trunc_normal_(self.pos_embed, std=0.02)
         nn.init.normal_(self.cls_token, std=1e-6)
@@ -129,6 +153,20 @@ def load_backbone_weights(module, state_dict, what, ignore_unexpected=("head.", 
     return res
 
 
+VIT_B8_NAMES = ('vit_base_patch8_224_dino', 'vit_base_patch8_224', 'vit_base_patch8_224_in21k')
+DINOV2_NAME = 'vit_base_patch14_dinov2.lvd142m'
+DINOV2_SIZE = 518     # timm's PatchEmbed asserts this input size: the reference runs DINOv2 with --rgb_size 518 only
+
+
+def rgb_backbone(name):
+    """An RGB backbone name the package implements -> an unloaded VisionTransformer of its layout."""
+    if name in VIT_B8_NAMES:
+        return VisionTransformer()
+    if name == DINOV2_NAME:   # models/models.py:35-38: img_size 518, patch 14, LayerScale init_values 1e-5
+        return VisionTransformer(img_size=DINOV2_SIZE, patch=14, init_values=1e-5)
+    raise NotImplementedError(f"cmdiad_amd implements the ViT-B/8 backbones and {DINOV2_NAME} only (got {name})")
+
+
 POINTMAE_CHECKPOINT = "checkpoints/pointmae_pretrain.pth"
 POINTBERT_CHECKPOINT = "checkpoints/Point-BERT.pth"
 
@@ -140,20 +178,20 @@ class Model(torch.nn.Module):
         super().__init__()
         self.device = device
         self.rgb_backbone_name = rgb_backbone_name
-        if rgb_backbone_name not in ('vit_base_patch8_224_dino', 'vit_base_patch8_224', 'vit_base_patch8_224_in21k'):
-            raise NotImplementedError(f"cmdiad_amd implements the ViT-B/8 backbones only (got {rgb_backbone_name})")
-        self.rgb_backbone = VisionTransformer()
+        self.rgb_backbone = rgb_backbone(rgb_backbone_name)
         # timm downloads `pretrained=True` weights from the hub (models/models.py:23); offline the same state_dict comes from
         # a file: the `checkpoint_path` argument (timm's own name for it) or CMDIAD_VIT_CHECKPOINT
         checkpoint_path = checkpoint_path or os.environ.get("CMDIAD_VIT_CHECKPOINT", "")
         if checkpoint_path:
+            # (Meta's own dinov2_vitb14 file also carries the masked-modelling token, which the extractor does not use)
+            extras = ("head.", "fc_norm.", "pre_logits.") + (("mask_token",) if rgb_backbone_name == DINOV2_NAME else ())
             load_backbone_weights(self.rgb_backbone, unwrap_checkpoint(torch.load(checkpoint_path, map_location='cpu')),
-                                  f"ViT checkpoint {checkpoint_path}")
+                                  f"ViT checkpoint {checkpoint_path}", ignore_unexpected=extras)
         elif allow_random_init():
             warnings.warn("CMDIAD_ALLOW_RANDOM_INIT=1: rgb_backbone keeps its seeded random init "
                           "(load a timm state_dict with rgb_backbone.load_state_dict)")
         else:
-            raise RuntimeError("no ViT-B/8 weights: pass checkpoint_path= / set CMDIAD_VIT_CHECKPOINT to a timm "
+            raise RuntimeError(f"no {'DINOv2 ViT-B/14' if rgb_backbone_name == DINOV2_NAME else 'ViT-B/8'} weights: pass checkpoint_path= / set CMDIAD_VIT_CHECKPOINT to a timm "
                                f"{rgb_backbone_name} state_dict, or opt in to random weights with CMDIAD_ALLOW_RANDOM_INIT=1")
         if xyz_backbone_name == 'Point_MAE':
             self.xyz_backbone = PointTransformer(group_size=group_size, num_group=num_group)
@@ -175,10 +213,12 @@ class Model(torch.nn.Module):
         return self._vit_packed[1]
 
     def forward_rgb_tokens(self, x):
-        """[B,3,224,224] -> final-LN tokens [B,785,768] (device-resident fast path)."""
+        """[B,3,S,S] -> final-LN tokens [B,1+(S/p)^2,768] (device-resident fast path): [B,785,768] for ViT-B/8 at 224, [B,1370,768]
+        for DINOv2 at 518."""
         return self._vit().forward_tokens(x.float().contiguous())
 
     def forward_rgb_features(self, x):
+        """models/models.py:35-53 -> [B,768,s,s]: s = 28 (ViT-B/8), 37 (DINOv2, `forward_features` in eval mode)."""
         tok = self.forward_rgb_tokens(x)
         B, T, C = tok.shape
         s = int((T - 1) ** 0.5)

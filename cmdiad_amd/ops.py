@@ -3,6 +3,7 @@ libcmdiad_hip.so kernels underneath.  Every op raises if the tensors are not on 
 native library is missing -- there is no eager / CPU fallback here by design.
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -756,6 +757,28 @@ def im2col_patch8(rgb):
     B, _, S, _ = rgb.shape
     out = torch.empty((B * (S // 8) ** 2, 192), dtype=torch.bfloat16, device=rgb.device)
     _call("cmdiad_im2col_patch8", _p(rgb), B, S, _p(out), _stream())
+    return out
+
+
+def im2col_patch14(rgb):
+    """rgb [B,3,S,S] f32, S % 14 == 0 -> DINOv2's patch operand [B*(S/14)^2, 640] bf16: column c*196 + dy*14 + dx, 588.. zero."""
+    _chk(rgb, torch.float32, "im2col14.rgb")
+    B, _, S, _ = rgb.shape
+    out = torch.empty((B * (S // 14) ** 2, 640), dtype=torch.bfloat16, device=rgb.device)
+    _call("cmdiad_im2col_patch14", _p(rgb), B, S, _p(out), _stream())
+    return out
+
+
+def token_pool56(tokens):
+    """tokens [B, 1 + s*s, C] f32 (cls row first) -> AdaptiveAvgPool2d((56, 56)) of the s x s patch grid, [B, 3136, C] f32, read in
+    place (cmdiad_token_pool56: the bits of torch's CPU adaptive_avg_pool2d)."""
+    _chk(tokens, torch.float32, "token_pool56.tokens")
+    B, T, C = tokens.shape
+    s = math.isqrt(T - 1)
+    if s * s != T - 1:
+        raise ValueError(f"token_pool56: {T - 1} patch tokens are not a square grid")
+    out = torch.empty((B, 56 * 56, C), dtype=torch.float32, device=tokens.device)
+    _call("cmdiad_token_pool56", _p(tokens), B, s, C, _p(out), _stream())
     return out
 
 

@@ -13,6 +13,7 @@ into a ring of pinned buffers.  Two complete buffer sets alternate: the scoring 
 stream beside the extraction of step i+1, and the inputs of step i+1 are copied (H2D from pinned host memory, or
 D2D from resident batches) into the other set's static input buffers on a copy stream while step i computes.
 """
+import math
 import os
 import sys
 
@@ -100,7 +101,7 @@ class BatchPredictor:
 
     def __init__(self, engine, bank_xyz, bank_second, stats, det, seg, lambdas=(1.0, 1.0, 0.1, 0.1), batch=32, n_max=None,
                  workload="dino_pointmae", halluc=None, group=None, use_graph=True, timers=None, ring=3, size=224,
-                 gt_size=224, blur_radius=4.0):
+                 gt_size=224, blur_radius=4.0, rgb_size=None):
         if workload not in ("dino_pointmae", "mtfi"):
             raise ValueError(f"unknown workload {workload!r}")
         if workload == "mtfi" and halluc is None:
@@ -109,6 +110,7 @@ class BatchPredictor:
         self.det, self.seg, self.lambdas = det, seg, tuple(float(v) for v in lambdas)
         self.B, self.n_max, self.workload, self.halluc, self.group = batch, n_max, workload, halluc, group
         self.size, self.gt, self.blur_radius = size, gt_size, float(blur_radius)
+        self.rgb_size = rgb_size or size     # the RGB backbone's input (518 for DINOv2); `size` is the point map's
         self.timers = timers or {}
         self.use_graph = use_graph
         dev = bank_xyz.f32.device
@@ -157,7 +159,7 @@ class BatchPredictor:
 
     def _new_inputs(self):
         want_rgb = self.workload == "dino_pointmae"
-        return dict(rgb=torch.zeros((self.B, 3, self.size, self.size), dtype=torch.float32, device=self.dev) if want_rgb else None,
+        return dict(rgb=torch.zeros((self.B, 3, self.rgb_size, self.rgb_size), dtype=torch.float32, device=self.dev) if want_rgb else None,
                     pcs=torch.zeros((self.B, 3, self.size, self.size), dtype=torch.float32, device=self.dev),
                     ready=None, free=None, staged=None)
 
@@ -295,7 +297,8 @@ class BatchPredictor:
     def stage2(self, qs, keys):
         lam = self.lambdas
         gt = self.gt
-        side = (56, 56) if self.workload == "mtfi" else (28, 28)
+        s_rgb = math.isqrt(qs["rgb"][0].shape[1])      # the second library's grid: 56 (MTFI), 28 (ViT-B/8), 37 (DINOv2)
+        side = (s_rgb, s_rgb)
         rx, rr = eng.score_patches_from_keys_pair(qs["xyz"][0], keys["xyz"].contiguous(), self.bank_xyz, (56, 56),
                                                   qs["rgb"][0], keys["rgb"].contiguous(), self.bank_second, side, gt, self.group)
         s = torch.stack([rx["s"], rr["s"]], 1)                                   # [B,2]

@@ -3,7 +3,7 @@ in ops.py.  Weights are packed once (bf16 GEMM operands, fp32 biases / LayerNorm
 eval-mode BatchNorm folded into the 1x1 convolutions) from a ``state_dict`` that uses the
 reference's parameter names, so real checkpoints and synthetic weights load the same way.
 
-Reference anchors: ViT-B/8 models/models.py:35-53 (timm VisionTransformer [external]);
+Reference anchors: ViT-B/8 and DINOv2 ViT-B/14 models/models.py:35-53 (timm VisionTransformer [external]);
 Point-MAE models/models.py:183-243, 352-373; Point-BERT (encoder_dims 256) models/models.py:259-264, 326-352; hallucination MLP models/hallucination_network.py:34-45,
 utils/utils.py:86-115.
 """
@@ -41,16 +41,29 @@ def ln_fold_enabled(net=""):
     return v == "1" or (v not in ("0", "1") and v == net)
 
 
+def layer_scale_fold(sd, p, linear, ls):
+    """(weight, bias) of the Linear `linear` of block p with the LayerScale `ls` behind it folded in (timm's LayerScale, DINOv2):
+    x + g * (W a + b) = x + (g W) a + g b.  In fp32, before the weight's one bf16 rounding; the residual epilogue is unchanged.
+    Without a `<ls>.gamma` in the state_dict the Linear's own tensors, untouched."""
+    w, b = sd[p + linear + ".weight"], sd[p + linear + ".bias"]
+    if p + ls + ".gamma" not in sd:
+        return w, b
+    g = sd[p + ls + ".gamma"].detach().float().cpu()
+    return w.detach().float().cpu() * g[:, None], b.detach().float().cpu() * g
+
+
 def _pack_block(sd, p, device, qkv_bias, net=""):
     g = lambda k: sd[p + k]  # noqa: E731
+    proj_w, proj_b = layer_scale_fold(sd, p, "attn.proj", "ls1")
+    fc2_w, fc2_b = layer_scale_fold(sd, p, "mlp.fc2", "ls2")
     blk = dict(
         ln1_w=_dev(g("norm1.weight"), device), ln1_b=_dev(g("norm1.bias"), device),
         ln2_w=_dev(g("norm2.weight"), device), ln2_b=_dev(g("norm2.bias"), device),
         qkv_w=_bf(g("attn.qkv.weight"), device),
         qkv_b=_dev(g("attn.qkv.bias"), device) if qkv_bias else None,
-        proj_w=_bf(g("attn.proj.weight"), device), proj_b=_dev(g("attn.proj.bias"), device),
+        proj_w=_bf(proj_w, device), proj_b=_dev(proj_b, device),
         fc1_w=_bf(g("mlp.fc1.weight"), device), fc1_b=_dev(g("mlp.fc1.bias"), device),
-        fc2_w=_bf(g("mlp.fc2.weight"), device), fc2_b=_dev(g("mlp.fc2.bias"), device))
+        fc2_w=_bf(fc2_w, device), fc2_b=_dev(fc2_b, device))
     if ln_fold_enabled(net):
         wq, bq = ln_fold(g("attn.qkv.weight"), g("attn.qkv.bias") if qkv_bias else None, g("norm1.weight"), g("norm1.bias"))
         w1, b1 = ln_fold(g("mlp.fc1.weight"), g("mlp.fc1.bias"), g("norm2.weight"), g("norm2.bias"))
@@ -135,13 +148,24 @@ def transformer_block_unfused(x, blk, B, T, H, eps, bufs, pos=None, flags=0, sta
     return x
 
 
-# ------------------------------------------------------------------------------------------- ViT-B/8
+# ------------------------------------------------------------------------------------------- ViT-B/8, DINOv2 ViT-B/14
 class PackedViT:
+    """ViT-B/8 (patch 8, 224) or DINOv2 ViT-B/14 (patch 14, 518, LayerScale folded into proj / fc2 by _pack_block): the patch size
+    comes from the patch-embedding weight, the token count from pos_embed."""
+
     def __init__(self, sd, prefix="", device="cuda", depth=12, num_heads=12):
         self.device, self.depth, self.heads = device, depth, num_heads
         w = sd[prefix + "patch_embed.proj.weight"]
-        self.dim = w.shape[0]
-        self.patch_w = _bf(w.reshape(self.dim, -1), device)  # [768, 3*8*8], k = (c, dy, dx)
+        self.dim, self.patch = w.shape[0], w.shape[-1]
+        if self.patch == 8:
+            self.patch_w = _bf(w.reshape(self.dim, -1), device)  # [768, 3*8*8], k = (c, dy, dx)
+        elif self.patch == 14:
+            # [768, 640]: k = (c, dy, dx) over 588 columns, then zeros to K % 64 == 0 (cmdiad_im2col_patch14 writes zeros there too)
+            wp = torch.zeros((self.dim, 640), dtype=torch.float32)
+            wp[:, :588] = w.detach().float().cpu().reshape(self.dim, -1)
+            self.patch_w = _bf(wp, device)
+        else:
+            raise NotImplementedError(f"PackedViT: patch size {self.patch} (implemented: 8, 14)")
         self.patch_b = _dev(sd[prefix + "patch_embed.proj.bias"], device)
         self.cls = _dev(sd[prefix + "cls_token"].reshape(-1), device)
         self.pos = _dev(sd[prefix + "pos_embed"].reshape(-1, self.dim), device)
@@ -150,11 +174,14 @@ class PackedViT:
         self.bufs = _QkvBuffers()
 
     def forward_tokens(self, rgb):
-        """rgb [B,3,224,224] f32 cuda -> final-LayerNorm tokens [B, 785, 768] f32 (cls at index 0)."""
+        """rgb [B,3,S,S] f32 cuda -> final-LayerNorm tokens [B, 1 + (S/p)^2, 768] f32 (cls at index 0): [B, 785, 768] for ViT-B/8
+        at 224, [B, 1370, 768] for DINOv2 at 518."""
         B, _, S, _ = rgb.shape
-        P = (S // 8) ** 2
+        P = (S // self.patch) ** 2
         T = P + 1
-        patches = ops.im2col_patch8(rgb.contiguous())
+        if S % self.patch or T != self.pos.shape[0]:
+            raise ValueError(f"PackedViT: a {S} x {S} image gives {T} tokens at patch {self.patch}; pos_embed has {self.pos.shape[0]}")
+        patches = ops.im2col_patch8(rgb.contiguous()) if self.patch == 8 else ops.im2col_patch14(rgb.contiguous())
         po, _ = ops.gemm(patches, self.patch_w, bias=self.patch_b, want_f32=True, want_bf16=False)
         x = ops.vit_assemble(po, self.cls, self.pos, B, P, self.dim)
         n = len(self.blocks)
@@ -165,7 +192,7 @@ class PackedViT:
         return out.view(B, T, self.dim)
 
     def forward(self, rgb):
-        """-> [B,768,28,28] view, the reference's layout (models/models.py:52)."""
+        """-> [B,768,s,s] view, the reference's layout (models/models.py:38,52): s = 28 (ViT-B/8) or 37 (DINOv2)."""
         tok = self.forward_tokens(rgb)
         B, T, C = tok.shape
         s = int((T - 1) ** 0.5)

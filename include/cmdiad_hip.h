@@ -499,6 +499,16 @@ int cmdiad_normalize_cast_rows(const float* x, size_t rows, int D, int group_row
 /* ViT patch embedding as a GEMM operand: rgb [B,3,S,S] f32 -> patches [B*(S/8)^2, 192] bf16 with
  * k = (c, dy, dx) matching conv weight [768,3,8,8] flattened (timm PatchEmbed, models/models.py:41). */
 int cmdiad_im2col_patch8(const float* rgb, int B, int S, uint16_t* patches, cmdiad_stream_t stream);
+/* DINOv2 ViT-B/14 patch embedding as a GEMM operand (ABI 6, additive): rgb [B,3,S,S] f32, S % 14 == 0 (518 for
+ * vit_base_patch14_dinov2.lvd142m) -> patches [B*(S/14)^2, 640] bf16, column k = c*196 + dy*14 + dx (conv weight [768,3,14,14]
+ * flattened), columns 588..639 zero (the packed patch weight carries the same zero columns: K % 64 == 0). */
+int cmdiad_im2col_patch14(const float* rgb, int B, int S, uint16_t* patches, cmdiad_stream_t stream);
+/* AdaptiveAvgPool2d((56, 56)) of the patch-token grid (features.py:165-166, `rgb_patch2`), ABI 6, additive: tokens [B, 1 + s*s, C]
+ * f32 read in place (the cls row of every image skipped), s x s row-major grid -> out [B, 3136, C] f32.  Windows
+ * [floor(i s / 56), ceil((i + 1) s / 56)) per axis, summed from 0 in row-major order, divided by the window height and then by its
+ * width, as ATen's CPU kernel does: the output equals torch.nn.functional.adaptive_avg_pool2d on the CPU BIT FOR BIT (at s = 28
+ * every window is one cell: the exact 2x replication).  0 < s <= 1024, C % 4 == 0, 16-byte aligned buffers. */
+int cmdiad_token_pool56(const float* tokens, int B, int s, int C, float* out, cmdiad_stream_t stream);
 /* 3 x 3 im2col with padding 1 and stride 1 | 2 (hrnet.py:152, the trunk's stem convolution as a GEMM in the hand-written training
  * step): img [B,C,H,W] f32 -> cols [B*Ho*Wo, ld] bf16, column c * 9 + ky * 3 + kx (the order of the flattened Conv2d weight and of
  * torch.nn.functional.unfold), columns 9 C .. ld - 1 zero.  ld % 8 == 0, ld >= 9 C. */
