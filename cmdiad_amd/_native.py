@@ -123,6 +123,10 @@ SIGNATURES = {
     "cmdiad_linear3": [P, P, SZ, I, I, P, P],
     "cmdiad_cast_bf16": [P, SZ, P, P],
     "cmdiad_transpose_bf16": [P, I, I, P, P],
+    "cmdiad_plane_ransac": [P, I, I, I, D, U32, P, P, P, SZ, P],
+    "cmdiad_plane_mask": [P, P, SZ, I, P, D, P],
+    "cmdiad_dbscan": [P, I, D, I, P, P, P, SZ, P],
+    "cmdiad_label_histogram": [P, I, P, I, P],
 }
 SIZE_QUERIES = {
     "cmdiad_gemm_streamk_workspace_bytes": [],
@@ -138,6 +142,8 @@ SIZE_QUERIES = {
     "cmdiad_knn_workspace_bytes": [I, I],
     "cmdiad_interp3nn_workspace_bytes": [I, I],
     "cmdiad_transformer_block_workspace_bytes": [I, I, I],
+    "cmdiad_plane_ransac_workspace_bytes": [I],
+    "cmdiad_dbscan_workspace_bytes": [I],
 }
 
 

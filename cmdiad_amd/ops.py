@@ -843,3 +843,66 @@ def transpose_bf16(x):
     out = torch.empty((c, r), dtype=torch.bfloat16, device=x.device)
     _call("cmdiad_transpose_bf16", _p(x), r, c, _p(out), _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------ scan preprocessing (docs/preprocessing.md)
+def plane_ransac(points, n=50, iterations=1000, distance_threshold=0.004, seed=0):
+    """points [E,3] f32 -> (plane [4] f64 = (a, b, c, d) with unit normal and c >= 0, info [2] int32 = {inliers, winning hypothesis}),
+    both on the device.  get_plane_eq of utils/preprocessing.py:30-33 under this project's RANSAC contract."""
+    _chk(points, torch.float32, "plane_ransac.points")
+    E = points.shape[0]
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"plane_ransac: points must be [E,3], got {tuple(points.shape)}")
+    if E < n:
+        raise ValueError(f"plane_ransac: {E} points, {n} needed for one sample")
+    plane = torch.empty(4, dtype=torch.float64, device=points.device)
+    info = torch.empty(2, dtype=torch.int32, device=points.device)
+    wsb = nat.lib().cmdiad_plane_ransac_workspace_bytes(int(iterations))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=points.device)
+    _call("cmdiad_plane_ransac", _p(points), E, int(n), int(iterations), float(distance_threshold), int(seed) & 0xFFFFFFFF,
+          _p(plane), _p(info), _p(ws), wsb, _stream())
+    return plane, info
+
+
+def plane_mask(pc, rgb, plane, distance_threshold=0.005):
+    """In place: pc [...,3] f32 and rgb [..., C] (any dtype, None = xyz only) are zeroed where the point is closer to `plane`
+    ([4] f64 on the device) than distance_threshold (strict).  utils/preprocessing.py:46-50."""
+    _chk(pc, torch.float32, "plane_mask.pc"); _chk(plane, torch.float64, "plane_mask.plane")
+    n = pc.numel() // 3
+    rgb_bytes = 0
+    if rgb is not None:
+        if not rgb.is_cuda:
+            raise nat.NativeError("plane_mask.rgb: tensor must live on the GPU (cmdiad_amd has no CPU path)")
+        if not rgb.is_contiguous():
+            raise ValueError("plane_mask.rgb: tensor must be contiguous")
+        if n == 0 or (rgb.numel() * rgb.element_size()) % n or rgb.numel() // n * n != rgb.numel():
+            raise ValueError(f"plane_mask: rgb {tuple(rgb.shape)} does not match pc {tuple(pc.shape)}")
+        rgb_bytes = rgb.numel() * rgb.element_size() // n
+    _call("cmdiad_plane_mask", _p(pc), _p(rgb), n, rgb_bytes, _p(plane), float(distance_threshold), _stream())
+    return pc, rgb
+
+
+def dbscan(points, eps=0.006, min_points=30):
+    """points [N,3] f32 -> (labels [N] int32, n_clusters [1] int32) on the device: scikit-learn's DBSCAN labels (docs/preprocessing.md)."""
+    _chk(points, torch.float32, "dbscan.points")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"dbscan: points must be [N,3], got {tuple(points.shape)}")
+    N = points.shape[0]
+    labels = torch.empty(N, dtype=torch.int32, device=points.device)
+    ncl = torch.zeros(1, dtype=torch.int32, device=points.device)
+    if N == 0:      # (an empty tensor has no address to pass)
+        return labels, ncl
+    wsb = nat.lib().cmdiad_dbscan_workspace_bytes(N)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=points.device)
+    _call("cmdiad_dbscan", _p(points), N, float(eps), int(min_points), _p(labels), _p(ncl), _p(ws), wsb, _stream())
+    return labels, ncl
+
+
+def label_histogram(labels, bins):
+    """labels [N] int32 -> hist [bins] int32 with hist[b] = count of label b - 1 (bin 0 = noise)."""
+    _chk(labels, torch.int32, "label_histogram.labels")
+    hist = torch.zeros(int(bins), dtype=torch.int32, device=labels.device)
+    if labels.numel() == 0:
+        return hist
+    _call("cmdiad_label_histogram", _p(labels), labels.numel(), _p(hist), int(bins), _stream())
+    return hist

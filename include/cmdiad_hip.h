@@ -639,6 +639,34 @@ int cmdiad_adam_step(float* p, const float* g, float* m, float* v, size_t n, flo
 int cmdiad_cast_bf16(const float* x, size_t n, uint16_t* out, cmdiad_stream_t stream);
 int cmdiad_transpose_bf16(const uint16_t* in, int rows, int cols, uint16_t* out, cmdiad_stream_t stream);
 
+/* ---- scan preprocessing (utils/preprocessing.py:30-92: the reference calls open3d's segment_plane and cluster_dbscan; the
+ * contract of both stages is this project's own, docs/preprocessing.md; additions are backwards compatible, the ABI stays 6) ---- */
+
+/* RANSAC plane of `points` [E,3] f32: `iterations` hypotheses, hypothesis h fits the least-squares plane (float64) of n distinct
+ * points drawn from a counter-based hash of (seed, h, draw counter); inliers: |a x + b y + c z + d| < distance_threshold in
+ * float64; the winner has the most inliers (ties: the lowest h) and is refitted over all its inliers.
+ * plane_out [4] f64 (device): unit normal with c >= 0, and d; info_out [2] int32 (device): {inliers of the winner, winner h}.
+ * 3 <= n <= 64, n <= E.  workspace: cmdiad_plane_ransac_workspace_bytes(iterations). */
+size_t cmdiad_plane_ransac_workspace_bytes(int iterations);
+int cmdiad_plane_ransac(const float* points, int E, int n, int iterations, double distance_threshold, uint32_t seed,
+                        double* plane_out, int32_t* info_out, void* workspace, size_t workspace_bytes, cmdiad_stream_t stream);
+
+/* remove_plane (utils/preprocessing.py:46-50), in place: pc [n_points,3] f32 and rgb [n_points, rgb_bytes] bytes (NULL with
+ * rgb_bytes = 0: xyz only) are zeroed where |plane . (x, y, z, 1)| < distance_threshold (float64, strict).  plane [4] f64 (device). */
+int cmdiad_plane_mask(float* pc, uint8_t* rgb, size_t n_points, int rgb_bytes, const double* plane, double distance_threshold,
+                      cmdiad_stream_t stream);
+
+/* DBSCAN labels of points [N,3] f32 (cluster_dbscan at utils/preprocessing.py:67; the labels are scikit-learn's): neighbours iff
+ * dx^2 + dy^2 + dz^2 <= eps^2 in float64, core iff >= min_points neighbours counting itself, clusters = connected components of
+ * the core points, numbered 0, 1, ... by their lowest core index; a non-core point with core neighbours takes the lowest cluster
+ * number among them; everything else is -1.  labels [N] int32, n_clusters [1] int32 (both device).  N <= 2^24. */
+size_t cmdiad_dbscan_workspace_bytes(int N);
+int cmdiad_dbscan(const float* points, int N, double eps, int min_points, int32_t* labels, int32_t* n_clusters,
+                  void* workspace, size_t workspace_bytes, cmdiad_stream_t stream);
+
+/* hist[b] = number of labels equal to b - 1, b in [0, bins): bin 0 counts the noise label -1.  hist [bins] int32 (device). */
+int cmdiad_label_histogram(const int32_t* labels, int N, int32_t* hist, int bins, cmdiad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
