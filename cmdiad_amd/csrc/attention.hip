@@ -14,9 +14,8 @@
 //          8-byte LDS reads.  The online-softmax rescale of O^T is a per-lane scalar multiply.
 // Q is pre-scaled by head_dim^-0.5 * log2(e) and V arrives transposed ([B,H,64,Tp]) from cmdiad_gemm_qkv.
 // LDS tiles are padded (K rows 144 B, V^T rows 136 B) so the fragment reads are bank-conflict-free.
-#include <stdlib.h>
-
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -226,7 +225,7 @@ extern "C" int cmdiad_attention(const uint16_t* q, const uint16_t* k, const uint
     const int Tp = (T + 63) / 64 * 64;
     const int BH = B * H, nq = (T + 127) / 128;
     dim3 grid((unsigned)((BH + 7) / 8 * 8 * nq));
-    static const int occ = getenv("CMDIAD_ATT_OCC") ? atoi(getenv("CMDIAD_ATT_OCC")) : 4;  // 128 VGPRs, 4 waves/SIMD: +5 % on the Point-MAE shape, neutral on ViT
+    static const int occ = env_int("CMDIAD_ATT_OCC", 4);  // 128 VGPRs, 4 waves/SIMD: +5 % on the Point-MAE shape, neutral on ViT
     auto kern = occ == 4 ? attention_kernel<4> : occ == 3 ? attention_kernel<3> : attention_kernel<2>;
     hipLaunchKernelGGL(kern, grid, dim3(kThreads), 0, (hipStream_t)stream, (const bf16_t*)q, (const bf16_t*)k,
                        (const bf16_t*)vt, BH, H, T, Tp, (bf16_t*)out);

@@ -2,9 +2,7 @@
 // caller pays one FFI call per block instead of seven (SURVEY 8b lists `vit_block_fwd` among the proposed exports; at
 // B = 1 the Python / ctypes launch path, not the GPU, bounds the drop-in).  Pure launch sequencing over the entry points
 // of gemm.hip / attention.hip / misc.hip: no kernels here, nothing allocated, stream-ordered like everything else.
-#include <stdlib.h>
-
-#include "common.h"
+#include "launch.h"
 
 // mlp_fused.hip: fc1 + GELU + fc2 of the folded Point-MAE block (C = 384, hidden = 1 536) as one kernel, bit-identical to the two
 // launches it replaces
@@ -13,12 +11,11 @@ int cmdiad_pmae_mlp_fused(float* x, const uint16_t* xb, const float* rstd, const
 
 // The fused MLP keeps a 128-row tile per CU (one block of 8 waves, all 160 KiB of LDS); below ~3/4 of a chip's worth of
 // tiles the two launches, which spread smaller tiles over every CU, are at least as fast (B = 1: 8 tiles; the drop-in's
-// micro-batches of 16: 128).  CMDIAD_PMAE_MLP=1 / 0 forces it on / off wherever it is legal (A/B runs, parity tests; read per call).
+// micro-batches of 16: 128).  CMDIAD_PMAE_MLP=1 / 0 forces it on / off wherever it is legal (A/B runs, parity tests).
 static bool pmae_mlp_fused_wanted(bool folded, int M, int C, int hidden)
 {
     if (!folded || C != 384 || hidden != 1536) return false;
-    const char* e = getenv("CMDIAD_PMAE_MLP");
-    if (e) return e[0] != '0';
+    if (env_set("CMDIAD_PMAE_MLP")) return !env_is("CMDIAD_PMAE_MLP", '0');
     return M >= 192 * 128;
 }
 

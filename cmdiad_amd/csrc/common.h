@@ -13,6 +13,9 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 #define CMDIAD_WAVE 64
+constexpr int kPersistCUs = 256;   // one persistent block per CU (MI355X)
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // Last error text, returned through cmdiad_last_error().  Never throws across the C ABI.
 void cmdiad_set_error(const char* fmt, ...);

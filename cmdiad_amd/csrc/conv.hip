@@ -10,10 +10,8 @@
 // per K-step from the shifted pixel -- K-step kt covers channels c0..c0+63 of ONE tap (C % 64 == 0), so the LDS-DMA
 // source of a tile row is just another 128-byte run; rows whose tap falls into the zero padding read a zero line.
 // Weights are packed by the host as [Cout][tap][C] bf16 (K-contiguous, like nn.Linear), BatchNorm folded.
-#include <mutex>
-#include <set>
-
 #include "gemm_core.h"
+#include "launch.h"
 
 namespace {
 
@@ -135,23 +133,10 @@ __global__ __launch_bounds__(S::THREADS, S::WAVES_PER_SIMD) void conv_igemm_kern
     });
 }
 
-template <class Kern>
-int launch_conv(Kern kernel, unsigned blocks, hipStream_t s, const GlobalTile& W, const ConvParams& p)
+template <int ACT>
+int launch_conv(unsigned blocks, hipStream_t s, const GlobalTile& W, const ConvParams& p)
 {
-    static std::mutex mu;
-    static std::set<const void*> configured;
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        if (!configured.count((const void*)kernel)) {
-            if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, S128::LDS_BYTES) != hipSuccess) {
-                cmdiad_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d) failed", S128::LDS_BYTES);
-                return CMDIAD_ERR_LAUNCH;
-            }
-            configured.insert((const void*)kernel);
-        }
-    }
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(S128::THREADS), S128::LDS_BYTES, s, W, p);
-    return CMDIAD_OK;
+    return launch_lds<conv_igemm_kernel<S128, ACT>>("cmdiad_conv2d_nhwc_bf16", dim3(blocks), dim3(S128::THREADS), S128::LDS_BYTES, s, W, p);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -328,8 +313,6 @@ __global__ __launch_bounds__(256) void bicubic4x_kernel(const float* __restrict_
         }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int cmdiad_conv2d_nhwc_bf16(const cmdiad_conv_args* a, cmdiad_stream_t stream)
@@ -360,9 +343,9 @@ extern "C" int cmdiad_conv2d_nhwc_bf16(const cmdiad_conv_args* a, cmdiad_stream_
     GlobalTile W{(const bf16_t*)a->W, KT * 64, a->N};
     const unsigned blocks = (unsigned)(((p.M + S128::BM - 1) / S128::BM) * ((p.N + S128::BN - 1) / S128::BN));
     hipStream_t s = (hipStream_t)stream;
-    const int rc = a->act == CMDIAD_ACT_RELU        ? launch_conv(conv_igemm_kernel<S128, CMDIAD_ACT_RELU>, blocks, s, W, p)
-                   : a->act == CMDIAD_ACT_RELU_POST ? launch_conv(conv_igemm_kernel<S128, CMDIAD_ACT_RELU_POST>, blocks, s, W, p)
-                                                    : launch_conv(conv_igemm_kernel<S128, CMDIAD_ACT_NONE>, blocks, s, W, p);
+    const int rc = a->act == CMDIAD_ACT_RELU        ? launch_conv<CMDIAD_ACT_RELU>(blocks, s, W, p)
+                   : a->act == CMDIAD_ACT_RELU_POST ? launch_conv<CMDIAD_ACT_RELU_POST>(blocks, s, W, p)
+                                                    : launch_conv<CMDIAD_ACT_NONE>(blocks, s, W, p);
     if (rc) return rc;
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;

@@ -17,9 +17,8 @@
 // load instruction of a wave is one contiguous 1 KiB piece and a row's sum of squares lives in ONE lane: no cross-lane
 // reduction per row (round 1's wave-per-row form spent a 6-step butterfly per 668 bytes and reached 2.3 TB/s).
 #include <hip/hip_fp16.h>
-#include <stdlib.h>
-
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -378,8 +377,7 @@ extern "C" int cmdiad_coreset_greedy(const float* z32, int n, int d, int n_selec
     }
     hipLaunchKernelGGL(coreset_init_kernel, dim3(2048), dim3(256), 0, s, z32, n, n4, d, first_idx, z16, zT, min_d);
     const int grid = (n4 + 255) / 256;
-    const char* ee = getenv("CMDIAD_CORESET_EARLY");   // =0: every row reads all its dimensions every round (A/B runs; read per call)
-    const bool early = !(ee && ee[0] == '0');
+    const bool early = !env_is("CMDIAD_CORESET_EARLY", '0');   // =0: every row reads all its dimensions every round (A/B runs)
     for (int r = 0; r + 1 < n_select; ++r) {
         if (early) hipLaunchKernelGGL(coreset_round_kernel<true>, dim3(grid), dim3(256), 0, s, z16, (const uint4*)zT, n, n4, d / 2, min_d,
                                       r == 0 ? nullptr : best + (r - 1), best + r, first_idx, 0, n4);

@@ -25,7 +25,6 @@
 namespace {
 
 constexpr int kPlanThreads = 1024;
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 __global__ __launch_bounds__(256) void hash_rows_kernel(const uint16_t* __restrict__ q, int Q, int D, unsigned* __restrict__ tag)
 {

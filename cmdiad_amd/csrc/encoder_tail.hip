@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "gemm_core.h"
+#include "launch.h"
 
 namespace {
 
@@ -36,7 +37,6 @@ constexpr int NST = CMDIAD_TAIL_STAGES;         // weight stages in LDS: NST - 1
 [[maybe_unused]] constexpr int AHEAD = NST - 1;  // (test-only kernels)
 constexpr int TAIL_LDS = A2_BYTES + A3_BYTES + NST * W_STAGE;  // 160 KiB at 4 stages
 static_assert(NST >= 2 && NST <= 4 && TAIL_LDS <= 160 * 1024, "weight stages");
-constexpr int kTailCUs = 256;                   // one persistent block per CU (MI355X)
 
 __device__ __forceinline__ void pp_barrier() { asm volatile("s_barrier" ::: "memory"); }
 
@@ -370,6 +370,36 @@ __global__ __launch_bounds__(TW * 64, 1) void encoder_tail_persist_kernel(Global
     }
 }
 
+// The launcher of both entry points (who): NO = 3 writes Point-MAE's 384 columns, NO = 2 Point-BERT's 256 (and knows seg).
+template <int NO>
+int tail_launch(const char* who, const uint16_t* h2, const float* gb, const uint16_t* W3b, const uint16_t* W4, const float* b4, int groups, int Mg,
+                int seg, float* tok_out, hipStream_t s)
+{
+    CMDIAD_REQUIRE(((((uintptr_t)h2 | (uintptr_t)W3b | (uintptr_t)W4 | (uintptr_t)gb | (uintptr_t)b4) & 15) == 0), CMDIAD_ERR_ARG,
+                   "%s: 16-byte alignment", who);
+    const int M = groups * Mg;
+    GlobalTile H2{(const bf16_t*)h2, 256, M}, W3{(const bf16_t*)W3b, 256, 512}, W4t{(const bf16_t*)W4, 512, NO * 128};
+    TailParams p{M, Mg, gb, b4, tok_out, 0};
+    const int n_tiles = (M + TM - 1) / TM;
+    const dim3 grid_p((unsigned)(n_tiles < kPersistCUs ? n_tiles : kPersistCUs)), block(TW * 64);
+    int rc;
+#ifdef CMDIAD_AB_VARIANTS
+    // test-only build, NO = 3 only: CMDIAD_TAIL_PP=0 the lock-step kernel, =1 the two-group kernel with one block per row tile (A/B
+    // runs, identity test); CMDIAD_TAIL_ABLATE=bits timing ablations of the persistent (or, with CMDIAD_TAIL_PP=1, that) kernel
+    const bool pp0 = NO == 3 && env_is("CMDIAD_TAIL_PP", '0'), pp1 = NO == 3 && env_is("CMDIAD_TAIL_PP", '1');
+    if (NO == 3) p.ablate = env_int("CMDIAD_TAIL_ABLATE", 0);
+    if (pp0) rc = launch_lds<encoder_tail_kernel>(who, dim3(n_tiles), block, TAIL_LDS, s, H2, W3, W4t, p);
+    else if (pp1 && p.ablate) rc = launch_lds<encoder_tail_pp_kernel<true>>(who, dim3(n_tiles), block, TAIL_LDS, s, H2, W3, W4t, p);
+    else if (pp1) rc = launch_lds<encoder_tail_pp_kernel<false>>(who, dim3(n_tiles), block, TAIL_LDS, s, H2, W3, W4t, p);
+    else if (p.ablate) rc = launch_lds<encoder_tail_persist_kernel<true>>(who, grid_p, block, TAIL_LDS, s, H2, W3, W4t, p, n_tiles, 0);
+    else
+#endif
+    rc = launch_lds<encoder_tail_persist_kernel<false, NO>>(who, grid_p, block, TAIL_LDS, s, H2, W3, W4t, p, n_tiles, seg);
+    if (rc) return rc;
+    CMDIAD_CHECK_LAUNCH();
+    return CMDIAD_OK;
+}
+
 }  // namespace
 
 extern "C" int cmdiad_encoder_tail(const uint16_t* h2, const float* gb, const uint16_t* W3b, const uint16_t* W4, const float* b4,
@@ -377,45 +407,7 @@ extern "C" int cmdiad_encoder_tail(const uint16_t* h2, const float* gb, const ui
 {
     CMDIAD_REQUIRE(h2 && gb && W3b && W4 && b4 && tok_out, CMDIAD_ERR_ARG, "cmdiad_encoder_tail: null pointer");
     CMDIAD_REQUIRE(groups > 0 && (Mg == 32 || Mg == 64 || Mg == 128), CMDIAD_ERR_ARG, "cmdiad_encoder_tail: Mg in {32,64,128} (Mg=%d)", Mg);
-    CMDIAD_REQUIRE(((((uintptr_t)h2 | (uintptr_t)W3b | (uintptr_t)W4 | (uintptr_t)gb | (uintptr_t)b4) & 15) == 0), CMDIAD_ERR_ARG,
-                   "cmdiad_encoder_tail: 16-byte alignment");
-    static bool attr = false;
-    if (!attr) {
-        bool ok = hipFuncSetAttribute((const void*)encoder_tail_persist_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, TAIL_LDS) == hipSuccess;
-#ifdef CMDIAD_AB_VARIANTS
-        ok = ok && hipFuncSetAttribute((const void*)encoder_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TAIL_LDS) == hipSuccess &&
-             hipFuncSetAttribute((const void*)encoder_tail_pp_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, TAIL_LDS) == hipSuccess &&
-             hipFuncSetAttribute((const void*)encoder_tail_pp_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, TAIL_LDS) == hipSuccess &&
-             hipFuncSetAttribute((const void*)encoder_tail_persist_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, TAIL_LDS) == hipSuccess;
-#endif
-        if (!ok) {
-            cmdiad_set_error("cmdiad_encoder_tail: hipFuncSetAttribute failed");
-            return CMDIAD_ERR_LAUNCH;
-        }
-        attr = true;
-    }
-    const int M = groups * Mg;
-    hipStream_t s = (hipStream_t)stream;
-    GlobalTile H2{(const bf16_t*)h2, 256, M}, W3{(const bf16_t*)W3b, 256, 512}, W4t{(const bf16_t*)W4, 512, 384};
-    TailParams p{M, Mg, gb, b4, tok_out, 0};
-    const int n_tiles = (M + TM - 1) / TM;
-    const dim3 grid_p((unsigned)(n_tiles < kTailCUs ? n_tiles : kTailCUs)), block(TW * 64);
-#ifdef CMDIAD_AB_VARIANTS
-    // test-only build: CMDIAD_TAIL_PP=0 the lock-step kernel, =1 the two-group kernel with one block per row tile (A/B runs,
-    // identity test); CMDIAD_TAIL_ABLATE=bits timing ablations of the persistent (or, with CMDIAD_TAIL_PP=1, that) kernel
-    const char* e = getenv("CMDIAD_TAIL_PP");
-    const char* ea = getenv("CMDIAD_TAIL_ABLATE");
-    p.ablate = ea ? atoi(ea) : 0;
-    if (e && e[0] == '0') hipLaunchKernelGGL(encoder_tail_kernel, dim3(n_tiles), block, TAIL_LDS, s, H2, W3, W4t, p);
-    else if (e && e[0] == '1') {
-        if (p.ablate) hipLaunchKernelGGL(encoder_tail_pp_kernel<true>, dim3(n_tiles), block, TAIL_LDS, s, H2, W3, W4t, p);
-        else hipLaunchKernelGGL(encoder_tail_pp_kernel<false>, dim3(n_tiles), block, TAIL_LDS, s, H2, W3, W4t, p);
-    } else if (p.ablate) hipLaunchKernelGGL(encoder_tail_persist_kernel<true>, grid_p, block, TAIL_LDS, s, H2, W3, W4t, p, n_tiles, 0);
-    else
-#endif
-    hipLaunchKernelGGL(encoder_tail_persist_kernel<false>, grid_p, block, TAIL_LDS, s, H2, W3, W4t, p, n_tiles, 0);
-    CMDIAD_CHECK_LAUNCH();
-    return CMDIAD_OK;
+    return tail_launch<3>("cmdiad_encoder_tail", h2, gb, W3b, W4, b4, groups, Mg, 0, tok_out, (hipStream_t)stream);
 }
 
 extern "C" int cmdiad_encoder_tail_n(const uint16_t* h2, const float* gb, const uint16_t* W3b, const uint16_t* W4, const float* b4,
@@ -426,23 +418,7 @@ extern "C" int cmdiad_encoder_tail_n(const uint16_t* h2, const float* gb, const 
     CMDIAD_REQUIRE(n_out == 256 || n_out == 384, CMDIAD_ERR_ARG, "cmdiad_encoder_tail_n: n_out in {256,384} (n_out=%d)", n_out);
     CMDIAD_REQUIRE(seg >= 0 && (seg == 0 || (n_out == 256 && groups % seg == 0)), CMDIAD_ERR_ARG,
                    "cmdiad_encoder_tail_n: seg must be 0, or (n_out 256) divide groups (groups=%d seg=%d)", groups, seg);
-    if (n_out == 384) return cmdiad_encoder_tail(h2, gb, W3b, W4, b4, groups, Mg, tok_out, stream);
-    CMDIAD_REQUIRE(((((uintptr_t)h2 | (uintptr_t)W3b | (uintptr_t)W4 | (uintptr_t)gb | (uintptr_t)b4) & 15) == 0), CMDIAD_ERR_ARG,
-                   "cmdiad_encoder_tail_n: 16-byte alignment");
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)encoder_tail_persist_kernel<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, TAIL_LDS) != hipSuccess) {
-            cmdiad_set_error("cmdiad_encoder_tail_n: hipFuncSetAttribute failed");
-            return CMDIAD_ERR_LAUNCH;
-        }
-        attr = true;
-    }
-    const int M = groups * Mg;
-    GlobalTile H2{(const bf16_t*)h2, 256, M}, W3{(const bf16_t*)W3b, 256, 512}, W4t{(const bf16_t*)W4, 512, 256};
-    TailParams p{M, Mg, gb, b4, tok_out, 0};
-    const int n_tiles = (M + TM - 1) / TM;
-    hipLaunchKernelGGL((encoder_tail_persist_kernel<false, 2>), dim3((unsigned)(n_tiles < kTailCUs ? n_tiles : kTailCUs)), dim3(TW * 64), TAIL_LDS,
-                       (hipStream_t)stream, H2, W3, W4t, p, n_tiles, seg);
-    CMDIAD_CHECK_LAUNCH();
-    return CMDIAD_OK;
+    // (the 384-wide form reports as cmdiad_encoder_tail, the entry point it has always been served by)
+    if (n_out == 384) return tail_launch<3>("cmdiad_encoder_tail", h2, gb, W3b, W4, b4, groups, Mg, 0, tok_out, (hipStream_t)stream);
+    return tail_launch<2>("cmdiad_encoder_tail_n", h2, gb, W3b, W4, b4, groups, Mg, seg, tok_out, (hipStream_t)stream);
 }

@@ -13,9 +13,8 @@
 // per lane, a 6-step wave64 shuffle reduction of a packed (value, ~index) key, one LDS
 // hand-off across the 16 waves (double-buffered, so ONE barrier per round) and a scalar
 // (SGPR) fetch of the winner's coordinates.
-#include <stdlib.h>
-
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -326,12 +325,10 @@ extern "C" int cmdiad_fps(const float* xyz, const int32_t* n_valid, int B, int N
     if (B == 0 || G == 0) return CMDIAD_OK;
     hipStream_t s = (hipStream_t)stream;
 #ifdef CMDIAD_AB_VARIANTS
-    // test-only build: CMDIAD_FPS_PK=0 selects the first formulation (A/B runs and the parity tests; read per call),
+    // test-only build: CMDIAD_FPS_PK=0 selects the first formulation (A/B runs and the parity tests),
     // CMDIAD_FPS_RAGGED=0 the dispatch on the padded length with the memory-resident loop above 28 672 points
-    const char* e = getenv("CMDIAD_FPS_PK");
-    const bool pk = !(e && e[0] == '0');
-    const char* er = getenv("CMDIAD_FPS_RAGGED");
-    const bool ragged_ok = !(er && er[0] == '0');
+    const bool pk = !env_is("CMDIAD_FPS_PK", '0');
+    const bool ragged_ok = !env_is("CMDIAD_FPS_RAGGED", '0');
 #define FPS_LAUNCH(T, P)                                                                                                      \
     do {                                                                                                                      \
         if (pk) hipLaunchKernelGGL((fps_pk_kernel<T, P>), dim3(B), dim3(T), 0, s, xyz, n_valid, N, G, idx_out, center_out);   \
@@ -350,17 +347,9 @@ extern "C" int cmdiad_fps(const float* xyz, const int32_t* n_valid, int B, int N
         const size_t need = cmdiad_fps_workspace_bytes(B, N);
         CMDIAD_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), CMDIAD_ERR_WORKSPACE,
                        "cmdiad_fps: N=%d needs %zu workspace bytes", N, need);
-        static bool attr = false;
-        if (!attr) {
-            if (hipFuncSetAttribute((const void*)fps_ragged_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    kMaxLdsPoints * (int)sizeof(float4)) != hipSuccess) {
-                cmdiad_set_error("cmdiad_fps: hipFuncSetAttribute failed");
-                return CMDIAD_ERR_LAUNCH;
-            }
-            attr = true;
-        }
-        hipLaunchKernelGGL(fps_ragged_kernel, dim3(B), dim3(kRaggedThreads), (size_t)lds_cap * sizeof(float4), s, xyz, n_valid, N, G,
-                           lds_cap, need ? (float*)workspace : nullptr, idx_out, center_out);
+        if (const int rc = launch_lds<fps_ragged_kernel>("cmdiad_fps", dim3(B), dim3(kRaggedThreads), (size_t)lds_cap * sizeof(float4), s, xyz, n_valid,
+                                                         N, G, lds_cap, need ? (float*)workspace : nullptr, idx_out, center_out))
+            return rc;
     }
     else if (N <= 1024 * 4) FPS_LAUNCH(1024, 4);
     else if (N <= 1024 * 8) FPS_LAUNCH(1024, 8);

@@ -1,9 +1,6 @@
 // GEMM entry points built on gemm_core.h: generic Linear with fused epilogue, QKV with head-split
 // stores, and the Point-MAE encoder stages (on-the-fly first conv, per-group max pooling).
-#include <stdlib.h>
-
-#include <mutex>
-#include <set>
+#include <type_traits>
 
 #ifdef CMDIAD_AB_VARIANTS
 #include "gemm_wide.h"  // 4-wave 256-row shapes: A/B references, test-only build (make ab)
@@ -11,6 +8,7 @@
 #include "gemm_core.h"
 #endif
 #include "gemm_pp3.h"
+#include "launch.h"
 
 namespace {
 
@@ -921,28 +919,17 @@ __global__ __launch_bounds__(256) void ln_stats_finalize_kernel(const float2* __
     rstd[m] = ln_merge_chunks(part, M, chunks, m, eps, mean_out ? mean_out + m : nullptr);
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // Every network GEMM runs the 128 x 128 shape: the tile sweep on MI355X (profiles/r1_notes.md) had it ahead of
 // 256x128x3-stage and 256x256 on every ViT / Point-MAE shape; the larger shapes serve the distance GEMM only (l2min.hip).
-// one launcher per kernel instantiation: sets the dynamic-LDS attribute once
-template <class S, class Kern, class... Args>
-int launch(Kern kernel, dim3 grid, int lds, hipStream_t s, Args... args)
+constexpr int kLdsStd = S128::LDS_BYTES + S128::WAVES * kRowStoreScratch;
+
+// the run-time activation (none, GELU, ReLU) as a compile-time constant: f(std::integral_constant<int, CMDIAD_ACT_*>)
+template <class F>
+int with_act(int act, F f)
 {
-    // several kernels share one signature (the epilogue variants): remember the attribute per function, not per type
-    static std::mutex mu;
-    static std::set<const void*> configured;
-    std::lock_guard<std::mutex> lock(mu);
-    bool done = configured.count((const void*)kernel) != 0;
-    if (!done) {
-        if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            cmdiad_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d) failed", lds);
-            return CMDIAD_ERR_LAUNCH;
-        }
-        configured.insert((const void*)kernel);
-    }
-    hipLaunchKernelGGL(kernel, grid, dim3(S::THREADS), lds, s, args...);
-    return CMDIAD_OK;
+    return act == CMDIAD_ACT_GELU   ? f(std::integral_constant<int, CMDIAD_ACT_GELU>{})
+           : act == CMDIAD_ACT_RELU ? f(std::integral_constant<int, CMDIAD_ACT_RELU>{})
+                                    : f(std::integral_constant<int, CMDIAD_ACT_NONE>{});
 }
 
 // N tiles per block.  Short-K, tall-M products (the Point-MAE encoder: M = 4.2 M rows, K <= 512) are bound by the
@@ -952,27 +939,24 @@ int launch(Kern kernel, dim3 grid, int lds, hipStream_t s, Args... args)
 // M tiles per L2 group of the block order (Coord); CMDIAD_GEMM_GROUPM=1 restores the row-major order (A/B runs)
 int group_m_tiles()
 {
-    const char* e = getenv("CMDIAD_GEMM_GROUPM");
-    const int g = e ? atoi(e) : 8;
+    const int g = env_int("CMDIAD_GEMM_GROUPM", 8);
     return g < 1 ? 1 : g;
 }
 
 template <class S>
 int panel_tiles(long M, long N, long K, int split)
 {
-    const char* e = getenv("CMDIAD_GEMM_PANEL_MIN");
-    const long min_mt = e ? atol(e) : 2048;
+    const long min_mt = env_long("CMDIAD_GEMM_PANEL_MIN", 2048);
     const long mt = (M + S::BM - 1) / S::BM, ntl = (N + S::BN - 1) / S::BN;
     if (split > 1 || ntl == 1 || K > 512 || mt < min_mt) return 1;
     return (int)(ntl < 8 ? ntl : 8);
 }
 
-constexpr int kPersistCUs = 256;   // one persistent block per CU (MI355X)
 unsigned persist_blocks(long M, long N)
 {
     const long jobs = ((M + 255) / 256) * (N / 256);
 #ifdef CMDIAD_AB_VARIANTS
-    if (const char* e = getenv("CMDIAD_PP3_GRID")) { const long g = atol(e); if (g > 0) return (unsigned)(jobs < g ? jobs : g); }
+    if (const long g = env_long("CMDIAD_PP3_GRID", 0); g > 0) return (unsigned)(jobs < g ? jobs : g);
 #endif
     // as many blocks as give every block the same number of tiles (+-1) at the same number of rounds: 1 188 tiles are five
     // rounds on 256 CUs and on 238; the smaller grid is 1-2 % faster (fewer CUs share the fabric in the last round;
@@ -986,37 +970,24 @@ unsigned persist_blocks(long M, long N)
 // (profiles/r1_notes.md): the 4-wave shapes pay for issuing all LDS-DMA pieces from the MFMA-issuing wave; the only shape
 // they win as a bare product (4.2M x 512 x 256: 2.34 vs 2.57 ms) they lose again inside the encoder, where that GEMM
 // carries the group-bias + ReLU epilogue (encoder 8.6-8.9 vs 7.9 ms).  So no network GEMM selects them; the distance GEMM
-// does (l2min.hip).  CMDIAD_GEMM_WIDE=4 / =8 force a shape (A/B runs and the parity tests; read per call).
+// does (l2min.hip).  CMDIAD_GEMM_WIDE=4 / =8 force a shape (A/B runs and the parity tests).
 int wide_choice(long M, long N, long K, bool plain_epilogue, int split)
 {
-    const char* e = getenv("CMDIAD_GEMM_WIDE");
-    const int force = e ? atoi(e) : -1;
+    const int force = env_int("CMDIAD_GEMM_WIDE", -1);
     if (!plain_epilogue || split > 1 || force == 0) return 0;
     if (force == 4 || force == 8) return force;
     (void)M; (void)N; (void)K;
     return 0;
 }
 
-template <class SW, class Kern, class P>
-int launch_wide(Kern kernel, long M, long N, long K, P& p, const GlobalTile& A, const GlobalTile& W, hipStream_t s)
+template <int NJ, auto Kernel, class P>
+int launch_wide(const char* who, long M, long N, long K, P& p, const GlobalTile& A, const GlobalTile& W, hipStream_t s)
 {
+    using SW = WideShape<NJ>;
     const long ntl = (N + SW::BN - 1) / SW::BN;
     p.panel = (K <= 512 && ntl <= 8) ? (int)ntl : 1;  // short K: walk the whole N panel in one block
     const long blocks = ((M + SW::BM - 1) / SW::BM) * ((ntl + p.panel - 1) / p.panel);
-    static std::mutex mu;
-    static std::set<const void*> configured;
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        if (!configured.count((const void*)kernel)) {
-            if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SW::LDS_BYTES) != hipSuccess) {
-                cmdiad_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d) failed", SW::LDS_BYTES);
-                return CMDIAD_ERR_LAUNCH;
-            }
-            configured.insert((const void*)kernel);
-        }
-    }
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), SW::LDS_BYTES, s, A, W, p);
-    return CMDIAD_OK;
+    return launch_lds<Kernel>(who, dim3((unsigned)blocks), dim3(256), SW::LDS_BYTES, s, A, W, p);
 }
 #endif  // CMDIAD_AB_VARIANTS
 
@@ -1082,10 +1053,11 @@ extern "C" int cmdiad_gemm_bf16(const cmdiad_gemm_args* a, cmdiad_stream_t strea
 #ifdef CMDIAD_AB_VARIANTS
     const int wide = a->m_count ? 0 : wide_choice(a->M, a->N, a->K, !extras && !a->residual && !a->row_scale && !ln_out && a->ldo16 % 4 == 0, split);   // (the wide kernels know neither row_scale nor the LayerNorm outputs)
     if (wide) {
-#define CMDIAD_WIDE(NJ, ACT) launch_wide<WideShape<NJ>>(gemm_std_wide_kernel<NJ, ACT>, a->M, a->N, a->K, p, A, W, s)
-        if (wide == 8) rc = a->act == CMDIAD_ACT_GELU ? CMDIAD_WIDE(8, CMDIAD_ACT_GELU) : a->act == CMDIAD_ACT_RELU ? CMDIAD_WIDE(8, CMDIAD_ACT_RELU) : CMDIAD_WIDE(8, CMDIAD_ACT_NONE);
-        else rc = a->act == CMDIAD_ACT_GELU ? CMDIAD_WIDE(4, CMDIAD_ACT_GELU) : a->act == CMDIAD_ACT_RELU ? CMDIAD_WIDE(4, CMDIAD_ACT_RELU) : CMDIAD_WIDE(4, CMDIAD_ACT_NONE);
-#undef CMDIAD_WIDE
+        rc = with_act(a->act, [&](auto act) {
+            constexpr int ACT = decltype(act)::value;
+            return wide == 8 ? launch_wide<8, gemm_std_wide_kernel<8, ACT>>("cmdiad_gemm_bf16", a->M, a->N, a->K, p, A, W, s)
+                             : launch_wide<4, gemm_std_wide_kernel<4, ACT>>("cmdiad_gemm_bf16", a->M, a->N, a->K, p, A, W, s);
+        });
         if (rc) return rc;
         CMDIAD_CHECK_LAUNCH();
         return CMDIAD_OK;
@@ -1093,49 +1065,31 @@ extern "C" int cmdiad_gemm_bf16(const cmdiad_gemm_args* a, cmdiad_stream_t strea
 #endif
     {
         // residual products (out_f32 = A.W^T + bias + residual) on the two-group 256 x 256 kernel, one tile per block (gemm_sk.hip)
-        const char* er = getenv("CMDIAD_GEMM_RES_WIDE");
         const bool legal = a->residual && a->out_f32 && !a->out_bf16 && a->bias && !extras && !ln_out && !a->group_bias && split == 1 &&
                            a->act == CMDIAD_ACT_NONE && !a->m_count && !a->row_scale && a->N % 256 == 0 && a->K >= 192;
-        if (legal && er && er[0] == '1') return gemm_residual_tiles_launch(a, s);
+        if (legal && env_is("CMDIAD_GEMM_RES_WIDE", '1')) return gemm_residual_tiles_launch(a, s);
     }
     {
         // two-group persistent kernel: whole 256-column tiles, bias, bf16-only output; chosen when every CU gets >= 2 tiles of
-        // a wide product.  CMDIAD_GEMM_PP3=1 / 0 forces it on / off wherever it is legal (A/B runs, parity tests; read per call)
-        const char* e3 = getenv("CMDIAD_GEMM_PP3");
+        // a wide product.  CMDIAD_GEMM_PP3=1 / 0 forces it on / off wherever it is legal (A/B runs, parity tests)
         const bool plain3 = !extras && !ln_out && !a->group_bias && split == 1 && a->N % 256 == 0 && a->K % 64 == 0 && a->K >= 192 && a->bias &&
                             !a->residual && !a->out_f32 && a->out_bf16 && a->ldo16 % 8 == 0 && aligned16(a->out_bf16);
-        const bool want3 = e3 ? e3[0] != '0' : (a->N >= 1536 && ((long)(a->M + 255) / 256) * (a->N / 256) >= 2 * kPersistCUs);
+        const bool want3 = env_set("CMDIAD_GEMM_PP3") ? !env_is("CMDIAD_GEMM_PP3", '0')
+                                                      : (a->N >= 1536 && ((long)(a->M + 255) / 256) * (a->N / 256) >= 2 * kPersistCUs);
         if (plain3 && want3) {
-            static std::mutex mu3;
-            static std::set<const void*> done3;
             constexpr int kLds3 = SPP3::LDS_BYTES + 8 * kPp3Scratch;
-            auto go = [&](auto kernel) -> int {
-                {
-                    std::lock_guard<std::mutex> lock(mu3);
-                    if (!done3.count((const void*)kernel)) {
-                        if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLds3) != hipSuccess) {
-                            cmdiad_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d) failed", kLds3);
-                            return CMDIAD_ERR_LAUNCH;
-                        }
-                        done3.insert((const void*)kernel);
-                    }
-                }
-                hipLaunchKernelGGL(kernel, dim3(persist_blocks(a->M, a->N)), dim3(512), kLds3, s, A, W, p);
-                return CMDIAD_OK;
-            };
+            const dim3 grid(persist_blocks(a->M, a->N));
             p.group_m = 1;
-            if (a->row_scale)
-                rc = a->act == CMDIAD_ACT_GELU ? go(gemm_std_pp3_kernel<CMDIAD_ACT_GELU, true>)
-                   : a->act == CMDIAD_ACT_RELU ? go(gemm_std_pp3_kernel<CMDIAD_ACT_RELU, true>) : go(gemm_std_pp3_kernel<CMDIAD_ACT_NONE, true>);
-            else
-            rc = a->act == CMDIAD_ACT_GELU ? go(gemm_std_pp3_kernel<CMDIAD_ACT_GELU>)
-               : a->act == CMDIAD_ACT_RELU ? go(gemm_std_pp3_kernel<CMDIAD_ACT_RELU>) : go(gemm_std_pp3_kernel<CMDIAD_ACT_NONE>);
+            rc = with_act(a->act, [&](auto act) {
+                constexpr int ACT = decltype(act)::value;
+                if (a->row_scale) return launch_lds<gemm_std_pp3_kernel<ACT, true>>("cmdiad_gemm_bf16", grid, dim3(512), kLds3, s, A, W, p);
+                return launch_lds<gemm_std_pp3_kernel<ACT>>("cmdiad_gemm_bf16", grid, dim3(512), kLds3, s, A, W, p);
+            });
             if (rc) return rc;
             CMDIAD_CHECK_LAUNCH();
             return CMDIAD_OK;
         }
     }
-#define CMDIAD_STD(SH, ACT, EX) launch<SH>(gemm_std_kernel<SH, ACT, EX>, grid_for<SH>(a->M, a->N, split, p.panel), SH::LDS_BYTES + SH::WAVES * kRowStoreScratch, s, A, W, p)
     p.panel = panel_tiles<S128>(a->M, a->N, a->K, split);
     p.group_m = p.panel == 1 && split == 1 ? group_m_tiles() : 1;
     // fp32 residual stream in place (proj / fc2): out_f32 = acc + bias + residual through the row-contiguous epilogue
@@ -1144,15 +1098,14 @@ extern "C" int cmdiad_gemm_bf16(const cmdiad_gemm_args* a, cmdiad_stream_t strea
     CMDIAD_REQUIRE(!ln_out || (res_rows && !a->row_scale && !a->m_count), CMDIAD_ERR_ARG,
                    "cmdiad_gemm_bf16: ln_xb / ln_part need the in-place residual form (bias, residual, out_f32 only, N%%64==0)");
     CMDIAD_REQUIRE(!a->row_scale || !res_rows, CMDIAD_ERR_ARG, "cmdiad_gemm_bf16: row_scale with the residual-row form");
-    if (res_rows && ln_out) rc = launch<S128>(gemm_std_kernel<S128, CMDIAD_ACT_NONE, false, true, true>, grid_for<S128>(a->M, a->N, split, p.panel),
-                                              S128::LDS_BYTES + S128::WAVES * kRowStoreScratch, s, A, W, p);
-    else if (res_rows) rc = launch<S128>(gemm_std_kernel<S128, CMDIAD_ACT_NONE, false, true>, grid_for<S128>(a->M, a->N, split, p.panel),
-                                    S128::LDS_BYTES + S128::WAVES * kRowStoreScratch, s, A, W, p);
-    else if (extras) rc = a->act == CMDIAD_ACT_GELU ? CMDIAD_STD(S128, CMDIAD_ACT_GELU, true)
-                   : a->act == CMDIAD_ACT_RELU ? CMDIAD_STD(S128, CMDIAD_ACT_RELU, true) : CMDIAD_STD(S128, CMDIAD_ACT_NONE, true);
-    else rc = a->act == CMDIAD_ACT_GELU ? CMDIAD_STD(S128, CMDIAD_ACT_GELU, false)
-            : a->act == CMDIAD_ACT_RELU ? CMDIAD_STD(S128, CMDIAD_ACT_RELU, false) : CMDIAD_STD(S128, CMDIAD_ACT_NONE, false);
-#undef CMDIAD_STD
+    const dim3 grid = grid_for<S128>(a->M, a->N, split, p.panel), block(S128::THREADS);
+    if (res_rows && ln_out) rc = launch_lds<gemm_std_kernel<S128, CMDIAD_ACT_NONE, false, true, true>>("cmdiad_gemm_bf16", grid, block, kLdsStd, s, A, W, p);
+    else if (res_rows) rc = launch_lds<gemm_std_kernel<S128, CMDIAD_ACT_NONE, false, true>>("cmdiad_gemm_bf16", grid, block, kLdsStd, s, A, W, p);
+    else rc = with_act(a->act, [&](auto act) {
+        constexpr int ACT = decltype(act)::value;
+        if (extras) return launch_lds<gemm_std_kernel<S128, ACT, true>>("cmdiad_gemm_bf16", grid, block, kLdsStd, s, A, W, p);
+        return launch_lds<gemm_std_kernel<S128, ACT, false>>("cmdiad_gemm_bf16", grid, block, kLdsStd, s, A, W, p);
+    });
     if (rc) return rc;
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
@@ -1177,11 +1130,12 @@ extern "C" int cmdiad_gemm_qkv(const uint16_t* A, const uint16_t* W, const float
                    CMDIAD_ERR_ARG, "cmdiad_gemm_qkv: 16-byte alignment");
     const int M = B * T;
     GlobalTile At{(const bf16_t*)A, C, M}, Wt{(const bf16_t*)W, C, 3 * C};
-    static const int v_rows = !(getenv("CMDIAD_QKV_VROWS") && getenv("CMDIAD_QKV_VROWS")[0] == '0');
+    static const int v_rows = !env_is("CMDIAD_QKV_VROWS", '0');
     QkvParams p{M, T, (T + 63) / 64 * 64, C, C / 64, group_m_tiles(), bias, (bf16_t*)q_out, (bf16_t*)k_out, (bf16_t*)vt_out, row_scale, v_rows};
     hipStream_t s = (hipStream_t)stream;
-    const int rc = row_scale ? launch<S128>(gemm_qkv_kernel<S128, true>, grid_for<S128>(M, 3 * C), S128::LDS_BYTES + S128::WAVES * kRowStoreScratch, s, At, Wt, p)
-                             : launch<S128>(gemm_qkv_kernel<S128, false>, grid_for<S128>(M, 3 * C), S128::LDS_BYTES + S128::WAVES * kRowStoreScratch, s, At, Wt, p);
+    const dim3 grid = grid_for<S128>(M, 3 * C), block(S128::THREADS);
+    const int rc = row_scale ? launch_lds<gemm_qkv_kernel<S128, true>>("cmdiad_gemm_qkv", grid, block, kLdsStd, s, At, Wt, p)
+                             : launch_lds<gemm_qkv_kernel<S128, false>>("cmdiad_gemm_qkv", grid, block, kLdsStd, s, At, Wt, p);
     if (rc) return rc;
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
@@ -1202,15 +1156,15 @@ extern "C" int cmdiad_gemm_groupmax(const uint16_t* A, const uint16_t* W, const 
 #ifdef CMDIAD_AB_VARIANTS
     const int wide = wide_choice(M, N, K, true, 1);
     if (wide) {
-        const int rcw = wide == 8 ? launch_wide<WideShape<8>>(gemm_groupmax_wide_kernel<8>, M, N, K, p, At, Wt, s)
-                                  : launch_wide<WideShape<4>>(gemm_groupmax_wide_kernel<4>, M, N, K, p, At, Wt, s);
+        const int rcw = wide == 8 ? launch_wide<8, gemm_groupmax_wide_kernel<8>>("cmdiad_gemm_groupmax", M, N, K, p, At, Wt, s)
+                                  : launch_wide<4, gemm_groupmax_wide_kernel<4>>("cmdiad_gemm_groupmax", M, N, K, p, At, Wt, s);
         if (rcw) return rcw;
         CMDIAD_CHECK_LAUNCH();
         return CMDIAD_OK;
     }
 #endif
     p.panel = panel_tiles<S128>(M, N, K, 1);
-    const int rc = launch<S128>(gemm_groupmax_kernel<S128>, grid_for<S128>(M, N, 1, p.panel), group_max_lds<S128>(), s, At, Wt, p);
+    const int rc = launch_lds<gemm_groupmax_kernel<S128>>("cmdiad_gemm_groupmax", grid_for<S128>(M, N, 1, p.panel), dim3(S128::THREADS), group_max_lds<S128>(), s, At, Wt, p);
     if (rc) return rc;
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
@@ -1234,33 +1188,21 @@ extern "C" int cmdiad_encoder_stage1(const float* neigh, const float* w1, const 
     int rc;
     bool persist = M % 128 == 0;   // the once-per-block kernel keeps the ragged case (Mg = 32 / 64 with an odd group count)
 #ifdef CMDIAD_AB_VARIANTS
-    // test-only build: CMDIAD_STAGE1_PERSIST=0 selects the once-per-block kernel, CMDIAD_STAGE1_ONCE=0 the generic pipeline
-    // (A/B runs; read per call)
-    const char* e1 = getenv("CMDIAD_STAGE1_ONCE");
-    if (getenv("CMDIAD_STAGE1_PERSIST") && getenv("CMDIAD_STAGE1_PERSIST")[0] == '0') persist = false;
-    if (e1 && e1[0] == '0') {
+    // test-only build: CMDIAD_STAGE1_PERSIST=0 selects the once-per-block kernel, CMDIAD_STAGE1_ONCE=0 the generic pipeline (A/B runs)
+    if (env_is("CMDIAD_STAGE1_PERSIST", '0')) persist = false;
+    if (env_is("CMDIAD_STAGE1_ONCE", '0')) {
         p.panel = panel_tiles<S128>(M, 256, 128, 1);
-        rc = launch<S128>(encoder_stage1_kernel<S128>, grid_for<S128>(M, 256, 1, p.panel), group_max_lds<S128>(), s, At, Wt, p);
+        rc = launch_lds<encoder_stage1_kernel<S128>>("cmdiad_encoder_stage1", grid_for<S128>(M, 256, 1, p.panel), dim3(S128::THREADS), group_max_lds<S128>(), s, At, Wt, p);
     } else
 #endif
     if (persist) {
-        static bool attr = false;
-        if (!attr) {
-            if (hipFuncSetAttribute((const void*)encoder_stage1_persist_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, Stage1Persist::LDS_BYTES) != hipSuccess ||
-                hipFuncSetAttribute((const void*)encoder_stage1_persist_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, Stage1Persist::LDS_BYTES) != hipSuccess) {
-                cmdiad_set_error("cmdiad_encoder_stage1: hipFuncSetAttribute failed");
-                return CMDIAD_ERR_LAUNCH;
-            }
-            attr = true;
-        }
         const int n_tiles = M / 128;
         const dim3 grid((unsigned)(n_tiles < kPersistCUs ? n_tiles : kPersistCUs));
-        if (Mg >= 64) hipLaunchKernelGGL(encoder_stage1_persist_kernel<true>, grid, dim3(512), Stage1Persist::LDS_BYTES, s, neigh, (const float4*)w1, (const bf16_t*)W2, p, n_tiles);
-        else hipLaunchKernelGGL(encoder_stage1_persist_kernel<false>, grid, dim3(512), Stage1Persist::LDS_BYTES, s, neigh, (const float4*)w1, (const bf16_t*)W2, p, n_tiles);
-        rc = CMDIAD_OK;
+        if (Mg >= 64) rc = launch_lds<encoder_stage1_persist_kernel<true>>("cmdiad_encoder_stage1", grid, dim3(512), Stage1Persist::LDS_BYTES, s, neigh, (const float4*)w1, (const bf16_t*)W2, p, n_tiles);
+        else rc = launch_lds<encoder_stage1_persist_kernel<false>>("cmdiad_encoder_stage1", grid, dim3(512), Stage1Persist::LDS_BYTES, s, neigh, (const float4*)w1, (const bf16_t*)W2, p, n_tiles);
     } else {
         p.panel = 1;
-        rc = launch<S128>(encoder_stage1_once_kernel, dim3((unsigned)((M + 127) / 128)), group_max_lds<S128>() + 4 * kRowStoreScratch, s, At, Wt, p);
+        rc = launch_lds<encoder_stage1_once_kernel>("cmdiad_encoder_stage1", dim3((unsigned)((M + 127) / 128)), dim3(S128::THREADS), group_max_lds<S128>() + 4 * kRowStoreScratch, s, At, Wt, p);
     }
     if (rc) return rc;
     CMDIAD_CHECK_LAUNCH();

@@ -19,11 +19,8 @@
 // coherent with the others'), the counters are agent-scope atomics; no cache-wide write-back or invalidate.
 // The partial accumulators and the epilogue's residual rows arrive by inline-asm loads with explicit counted waits: a
 // compiler-visible load inside the K loop gets an s_waitcnt vmcnt(0) in every iteration (tools/isa_lint.py).
-#include <stdlib.h>
-
-#include <mutex>
-
 #include "gemm_pp3.h"
+#include "launch.h"
 
 namespace {
 
@@ -349,9 +346,6 @@ __global__ __launch_bounds__(512, 1) void gemm_sk_kernel(GlobalTile A, GlobalTil
     else body(std::false_type{});
 }
 
-bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
-constexpr int kSkBlocks = 256;   // one block per CU (MI355X)
-
 }  // namespace
 
 // The same kernel with ONE WHOLE TILE per block (grid = tiles: every block's unit range is exactly one tile, so nothing is parked
@@ -362,29 +356,17 @@ constexpr int kSkBlocks = 256;   // one block per CU (MI355X)
 int gemm_residual_tiles_launch(const cmdiad_gemm_args* a, hipStream_t stream)
 {
     constexpr int kLds = SPP3::LDS_BYTES + 8 * kRowStoreScratch;
-    static std::mutex mu;
-    static bool attr = false;
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        if (!attr) {
-            if (hipFuncSetAttribute((const void*)gemm_sk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLds) != hipSuccess) {
-                cmdiad_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d) failed", kLds);
-                return CMDIAD_ERR_LAUNCH;
-            }
-            attr = true;
-        }
-    }
     GlobalTile A{(const bf16_t*)a->A, a->lda, a->M}, W{(const bf16_t*)a->W, a->ldw, a->N};
     SkParams p{a->M, a->N, a->K, a->bias, a->residual, a->ldr, a->out_f32, a->ldo32, nullptr, nullptr};
     const long tiles = ((long)(a->M + 255) / 256) * (a->N / 256);
-    hipLaunchKernelGGL(gemm_sk_kernel, dim3((unsigned)tiles), dim3(512), kLds, stream, A, W, p);
+    if (const int rc = launch_lds<gemm_sk_kernel>("cmdiad_gemm_bf16", dim3((unsigned)tiles), dim3(512), kLds, stream, A, W, p)) return rc;
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
 }
 
 extern "C" size_t cmdiad_gemm_streamk_workspace_bytes(void)
 {
-    return (size_t)kSkBlocks * kSkSlotFloats * sizeof(float) + (size_t)kSkBlocks * 2 * sizeof(unsigned);
+    return (size_t)kPersistCUs * kSkSlotFloats * sizeof(float) + (size_t)kPersistCUs * 2 * sizeof(unsigned);
 }
 
 extern "C" int cmdiad_gemm_streamk_eligible(int M, int N, int K)
@@ -393,7 +375,7 @@ extern "C" int cmdiad_gemm_streamk_eligible(int M, int N, int K)
     const long tiles = ((long)(M + 255) / 256) * (N / 256), KT = K / 64;
     // every block's range must be at least one tile long (no block takes over and hands over the same tile), and the split
     // must be worth it: more than one tile and less than two per CU
-    return tiles * KT / kSkBlocks >= KT && tiles > kSkBlocks && tiles < 2 * kSkBlocks ? 1 : 0;
+    return tiles * KT / kPersistCUs >= KT && tiles > kPersistCUs && tiles < 2 * kPersistCUs ? 1 : 0;
 }
 
 extern "C" int cmdiad_gemm_streamk_bf16(const cmdiad_gemm_args* a, void* workspace, size_t workspace_bytes, cmdiad_stream_t stream)
@@ -411,23 +393,11 @@ extern "C" int cmdiad_gemm_streamk_bf16(const cmdiad_gemm_args* a, void* workspa
     CMDIAD_REQUIRE(workspace_bytes >= cmdiad_gemm_streamk_workspace_bytes(), CMDIAD_ERR_WORKSPACE,
                    "cmdiad_gemm_streamk_bf16: workspace %zu < %zu bytes", workspace_bytes, cmdiad_gemm_streamk_workspace_bytes());
     constexpr int kLds = SPP3::LDS_BYTES + 8 * kRowStoreScratch;
-    static std::mutex mu;
-    static bool attr = false;
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        if (!attr) {
-            if (hipFuncSetAttribute((const void*)gemm_sk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLds) != hipSuccess) {
-                cmdiad_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d) failed", kLds);
-                return CMDIAD_ERR_LAUNCH;
-            }
-            attr = true;
-        }
-    }
     GlobalTile A{(const bf16_t*)a->A, a->lda, a->M}, W{(const bf16_t*)a->W, a->ldw, a->N};
     float* partial = (float*)workspace;
     SkParams p{a->M, a->N, a->K, a->bias, a->residual, a->ldr, a->out_f32, a->ldo32, partial,
-               (unsigned*)(partial + (size_t)kSkBlocks * kSkSlotFloats)};
-    hipLaunchKernelGGL(gemm_sk_kernel, dim3(kSkBlocks), dim3(512), kLds, (hipStream_t)stream, A, W, p);
+               (unsigned*)(partial + (size_t)kPersistCUs * kSkSlotFloats)};
+    if (const int rc = launch_lds<gemm_sk_kernel>("cmdiad_gemm_streamk_bf16", dim3(kPersistCUs), dim3(512), kLds, (hipStream_t)stream, A, W, p)) return rc;
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
 }

@@ -11,9 +11,8 @@
 // Block = 128 x 128 outputs, 4 waves of 64 x 64, K-step = 64 rows of m, 2 stages (64 KiB: two blocks per CU), split-K over
 // grid.y into fp32 slabs (cmdiad_reduce_slabs sums them).  The Q fragment is fed as the MFMA "A" operand, so a lane holds 4
 // consecutive n2 of one n1: 16-byte row-major stores.
-#include <mutex>
-
 #include "gemm_core.h"
+#include "launch.h"
 
 namespace {
 
@@ -174,13 +173,9 @@ extern "C" int cmdiad_gemm_tn_bf16(const uint16_t* P, int ldp, const uint16_t* Q
                    CMDIAD_ERR_ARG, "cmdiad_gemm_tn_bf16: operands must be 16-byte aligned with ld%%8==0 (out: ld%%4==0)");
     const int split = split_k > 1 ? split_k : 1;
     CMDIAD_REQUIRE(split <= M / 64, CMDIAD_ERR_ARG, "cmdiad_gemm_tn_bf16: split_k=%d exceeds the %d K-steps", split, M / 64);
-    static std::once_flag once;
-    static hipError_t attr = hipSuccess;
-    std::call_once(once, [] { attr = hipFuncSetAttribute((const void*)gemm_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES); });
-    CMDIAD_REQUIRE(attr == hipSuccess, CMDIAD_ERR_LAUNCH, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d) failed", LDS_BYTES);
     TnParams p{(const bf16_t*)P, ldp, (const bf16_t*)Q, ldq, M, N1, N2, out_f32, ldo, split, colsum_out};
     const unsigned blocks = (unsigned)(((N1 + TN - 1) / TN) * ((N2 + TN - 1) / TN));
-    hipLaunchKernelGGL(gemm_tn_kernel, dim3(blocks, split), dim3(256), LDS_BYTES, (hipStream_t)stream, p);
+    if (const int rc = launch_lds<gemm_tn_kernel>("cmdiad_gemm_tn_bf16", dim3(blocks, split), dim3(256), LDS_BYTES, (hipStream_t)stream, p)) return rc;
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
 }

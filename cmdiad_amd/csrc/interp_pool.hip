@@ -17,6 +17,7 @@
 // interp3nn is compiled with -ffp-contract=off and follows oracle/cmdiad_oracle.c:orc_interp3nn
 // operation by operation, so idx3 / w3 are bit-exact against the oracle.
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -534,8 +535,7 @@ extern "C" size_t cmdiad_interp3nn_workspace_bytes(int B, int S)
 extern "C" int cmdiad_interp3nn_ws(const float* xyz, const int32_t* n_valid, const float* center, int B, int N, int S,
                                    int32_t* idx3, float* w3, void* workspace, size_t workspace_bytes, cmdiad_stream_t stream)
 {
-    const char* e = getenv("CMDIAD_INTERP_GRID");
-    if ((e && e[0] == '0') || S < 64 || S > kMaxCentres || B <= 0 || N <= 0)
+    if (env_is("CMDIAD_INTERP_GRID", '0') || S < 64 || S > kMaxCentres || B <= 0 || N <= 0)
         return cmdiad_interp3nn(xyz, n_valid, center, B, N, S, idx3, w3, stream);
     CMDIAD_REQUIRE(xyz && center && idx3 && w3, CMDIAD_ERR_ARG, "cmdiad_interp3nn_ws: null pointer");
     CMDIAD_REQUIRE(workspace && workspace_bytes >= cmdiad_interp3nn_workspace_bytes(B, S) && ((uintptr_t)workspace & 15) == 0,
@@ -580,7 +580,7 @@ extern "C" int cmdiad_xyz_patch_fused(const float* feat, const int32_t* idx3, co
     // only other resident workgroups hide: the fewer waves a patch takes, the more patches a CU has in flight (32 wave slots).
     // Batch 32, 224 x 224, 56 x 56 patches, D = 768 (tools/xyz_patch_time.py, identical bits): 256 threads per patch 0.386-0.403 ms,
     // 128: 0.322-0.350, 64: 0.326-0.355.
-    static const int nt = getenv("CMDIAD_XYZ_PATCH_THREADS") ? atoi(getenv("CMDIAD_XYZ_PATCH_THREADS")) : 128;
+    static const int nt = env_int("CMDIAD_XYZ_PATCH_THREADS", 128);
     auto kern = nt == 64 ? xyz_patch_fused_kernel<64> : nt == 128 ? xyz_patch_fused_kernel<128> : xyz_patch_fused_kernel<256>;
     hipLaunchKernelGGL(kern, grid, dim3(nt == 64 ? 64 : nt == 128 ? 128 : 256), 0, (hipStream_t)stream, feat, idx3, w3, pix2pt, B, N, S, D,
                        size, P, mean, inv_std, patch_f32, (bf16_t*)patch_bf16);

@@ -16,9 +16,8 @@
 //   * chunks are visited in a coprime-strided order (see the kernel) so the threshold converges fast
 //     even though organised clouds arrive in raster order;
 //   * the final sort leaves the K winners in ascending order; the epilogue gathers p[idx] - c.
-#include <stdlib.h>
-
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -542,9 +541,8 @@ extern "C" int cmdiad_knn_group(const float* xyz, const int32_t* n_valid, const 
                    "cmdiad_knn_group: bad sizes B=%d N=%d G=%d K=%d (K<=128)", B, N, G, K);
     if (B == 0 || G == 0) return CMDIAD_OK;
 #ifdef CMDIAD_AB_VARIANTS
-    // test-only build: CMDIAD_KNN_WAVE=0 selects the block-wide formulation (A/B runs and the parity tests; read per call)
-    const char* e = getenv("CMDIAD_KNN_WAVE");
-    const bool wave_form = !(e && e[0] == '0');
+    // test-only build: CMDIAD_KNN_WAVE=0 selects the block-wide formulation (A/B runs and the parity tests)
+    const bool wave_form = !env_is("CMDIAD_KNN_WAVE", '0');
 #else
     const bool wave_form = true;
 #endif
@@ -582,8 +580,7 @@ extern "C" size_t cmdiad_knn_workspace_bytes(int B, int N)
 extern "C" int cmdiad_knn_group_ws(const float* xyz, const int32_t* n_valid, const float* center, int B, int N, int G, int K,
                                    int64_t* idx_out, float* neigh_out, void* workspace, size_t workspace_bytes, cmdiad_stream_t stream)
 {
-    const char* e = getenv("CMDIAD_KNN_GRID");
-    const bool grid = !(e && e[0] == '0') && N >= 2048 && G > 0 && B > 0 && K > 0 && K <= 128 && K <= N;
+    const bool grid = !env_is("CMDIAD_KNN_GRID", '0') && N >= 2048 && G > 0 && B > 0 && K > 0 && K <= 128 && K <= N;
     if (!grid) return cmdiad_knn_group(xyz, n_valid, center, B, N, G, K, idx_out, neigh_out, stream);
     CMDIAD_REQUIRE(xyz && center, CMDIAD_ERR_ARG, "cmdiad_knn_group_ws: null pointer");
     CMDIAD_REQUIRE(workspace && workspace_bytes >= cmdiad_knn_workspace_bytes(B, N) && ((uintptr_t)workspace & 15) == 0, CMDIAD_ERR_WORKSPACE,

@@ -14,9 +14,8 @@
 // test-only build alone (make ab, -DCMDIAD_AB_VARIANTS; CMDIAD_L2_TILE=2); all three return the same keys.  (Rounds 1-4 also kept
 // a 4-wave 128 x 128-per-wave kernel, a two-buffer two-group kernel and a 32-MFMA-per-phase kernel there: measured in
 // profiles/r1_notes.md .. r4_notes.md, removed in round 5 when the running minimum changed its definition.)
-#include <stdlib.h>
-
 #include "gemm_core.h"
+#include "launch.h"
 
 namespace {
 
@@ -560,8 +559,6 @@ __global__ __launch_bounds__(512, 1) void l2_min_pp3_kernel(GlobalTile A, Global
     else body(std::false_type{});
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 template <class S, bool F16> struct L2Kernel { static constexpr auto fn = l2_min_kernel<S, F16>; };
@@ -592,22 +589,14 @@ int launch_l2(const uint16_t* q, const float* q_sqnorm, const uint16_t* bank, co
               int D, uint32_t row_offset, unsigned long long* keys, unsigned long long* keys2, hipStream_t stream,
               const L2Live& live = L2Live())
 {
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)L2Kernel<S, F16>::fn, hipFuncAttributeMaxDynamicSharedMemorySize, S::LDS_BYTES) != hipSuccess) {
-            cmdiad_set_error("cmdiad_l2_min_keys: hipFuncSetAttribute failed");
-            return CMDIAD_ERR_LAUNCH;
-        }
-        attr = true;
-    }
     // segments: the launch is sized for every segment's cap (seg_stride rows); Q = n_seg * seg_stride
     const int nq = live.seg_counts ? live.n_seg * ((live.seg_stride + S::BM - 1) / S::BM) : (Q + S::BM - 1) / S::BM;
     const int nbt = (Nb + S::BN - 1) / S::BN;
     // enough blocks to fill the chip a few times over, but long bank ranges per block so the running
     // min stays in registers and the per-block atomics stay negligible
-    static const int env_splits = getenv("CMDIAD_L2_SPLITS") ? atoi(getenv("CMDIAD_L2_SPLITS")) : 0;
-    static const int env_qgroup = getenv("CMDIAD_L2_QGROUP") ? atoi(getenv("CMDIAD_L2_QGROUP")) : 0;
-    const char* env_seg_splits = getenv("CMDIAD_L2_SEG_SPLITS");   // read per call: tools/l2_segments.py sweeps it
+    static const int env_splits = env_int("CMDIAD_L2_SPLITS", 0);
+    static const int env_qgroup = env_int("CMDIAD_L2_QGROUP", 0);
+    const int env_seg_splits = env_int("CMDIAD_L2_SEG_SPLITS", 0);   // tools/l2_segments.py sweeps it
     // measured on the bagel xyz library (profiles/r1_notes.md): 8 bank ranges for the 8-wave shapes; the 4-wave wide
     // shape gains another 5 % from 16-32 (shorter ranges, better tail balance), as long as a range keeps >= 4 tiles.
     // Round 3 (profiles/r3_notes.md, the two-group kernel on the de-duplicated 54 401 rows): 20 ranges of 15 tiles 5.40 ms against
@@ -615,7 +604,7 @@ int launch_l2(const uint16_t* q, const float* q_sqnorm, const uint16_t* bank, co
     // tail to balance; all 100 352 rows: within 1 % from 15 to 50 ranges.
     int splits = env_splits > 0 ? env_splits : 8;
     if (env_splits <= 0 && S::BM == 256 && !std::is_same<S, S2x2>::value) splits = nbt / 4 < 1 ? 1 : (nbt / 4 > 20 ? 20 : nbt / 4);
-    if (live.seg_counts && S::BM == 256) splits = env_seg_splits && atoi(env_seg_splits) > 0 ? atoi(env_seg_splits) : segment_splits(nbt);
+    if (live.seg_counts && S::BM == 256) splits = env_seg_splits > 0 ? env_seg_splits : segment_splits(nbt);
     splits = splits > nbt ? nbt : splits;
     if ((nbt + splits - 1) / splits > 4096) splits = (nbt + 4095) / 4096;   // RowMin keeps a tile's place in 12 bits
     int qgroup = env_qgroup > 0 ? env_qgroup : 4;
@@ -624,8 +613,7 @@ int launch_l2(const uint16_t* q, const float* q_sqnorm, const uint16_t* bank, co
     L2Params p{Q, Nb, D, q_sqnorm, bank_sqnorm, row_offset, keys, keys2, nq, nbt, splits, qgroup, nullptr, -1, live.q_count,
                live.seg_counts, live.n_seg, live.seg_stride};
     const int ngroups = (nq + qgroup - 1) / qgroup;
-    hipLaunchKernelGGL((L2Kernel<S, F16>::fn), dim3(ngroups * qgroup * splits), dim3(S::THREADS), S::LDS_BYTES, stream, A, W, p);
-    return CMDIAD_OK;
+    return launch_lds<L2Kernel<S, F16>::fn>("cmdiad_l2_min_keys", dim3(ngroups * qgroup * splits), dim3(S::THREADS), S::LDS_BYTES, stream, A, W, p);
 }
 
 static int l2_min_keys_impl(const uint16_t* q, const float* q_sqnorm, const L2Live& q_count, const uint16_t* bank,
@@ -643,10 +631,9 @@ static int l2_min_keys_impl(const uint16_t* q, const float* q_sqnorm, const L2Li
     CMDIAD_REQUIRE(!keys2 || row_offset % 64 == 0, CMDIAD_ERR_ARG, "cmdiad_l2_min_keys: keys2 needs row_offset %% 64 == 0 (row_offset=%u)", row_offset);
     // production: the two-group 256 x 256 pipeline (l2_min_pp3_kernel) from Q >= 512, the 128 x 128 kernel below that, for the
     // last Nb % 256 library rows and for D < 192 (the two-group schedule assumes >= 3 K-tiles per library tile).
-    // CMDIAD_L2_TILE (read per call: the parity tests force each shape on small inputs) = 0 / 5 for those two; the test-only
+    // CMDIAD_L2_TILE (the parity tests force each shape on small inputs) = 0 / 5 for those two; the test-only
     // build (make ab) also knows 2 = the lock-step 256 x 256 shape of gemm::run.
-    const char* env_tile = getenv("CMDIAD_L2_TILE");
-    const int force = env_tile ? atoi(env_tile) : -1;
+    const int force = env_int("CMDIAD_L2_TILE", -1);
     int tile = force >= 0 ? force : (Q >= 512 ? 5 : 0);
     if (q_count.seg_counts && tile != 0) tile = 5;    // segments exist for the production shapes only
 #ifndef CMDIAD_AB_VARIANTS
@@ -728,21 +715,13 @@ extern "C" int cmdiad_l2_diag(const uint16_t* q, const float* q_sqnorm, const ui
                    "cmdiad_l2_diag: bad args");
     using S = SPingPong3;
     const int lds_bytes = S::LDS_BYTES + 2 * kDiagStamps * (int)sizeof(unsigned);
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)l2_min_pp3_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess) {
-            cmdiad_set_error("cmdiad_l2_diag: hipFuncSetAttribute failed");
-            return CMDIAD_ERR_LAUNCH;
-        }
-        attr = true;
-    }
     const int nq = (Q + S::BM - 1) / S::BM, nbt = Nb / S::BN;
     int splits = nbt / 4 < 1 ? 1 : (nbt / 4 > 32 ? 32 : nbt / 4);
     int qgroup = 4 > nq ? nq : 4;
     GlobalTile A{(const bf16_t*)q, D, Q}, W{(const bf16_t*)bank, D, Nb};
     L2Params p{Q, Nb, D, q_sqnorm, bank_sqnorm, 0u, keys, nullptr, nq, nbt, splits, qgroup, stamps, wg, nullptr};
     const int ngroups = (nq + qgroup - 1) / qgroup;
-    hipLaunchKernelGGL((l2_min_pp3_kernel<true, true>), dim3(ngroups * qgroup * splits), dim3(S::THREADS), lds_bytes, (hipStream_t)stream, A, W, p);
+    if (const int rc = launch_lds<l2_min_pp3_kernel<true, true>>("cmdiad_l2_diag", dim3(ngroups * qgroup * splits), dim3(S::THREADS), lds_bytes, (hipStream_t)stream, A, W, p)) return rc;
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
 }

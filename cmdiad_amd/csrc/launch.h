@@ -1,0 +1,52 @@
+// Host-side helpers shared by the launchers of cmdiad_amd: the launch of a kernel with dynamic LDS, and the readers of the
+// library's environment switches (listed in INTEGRATION.md, "Environment switches").
+#pragma once
+#include <stdlib.h>
+
+#include <atomic>
+#include <mutex>
+
+#include "common.h"
+
+// Launch Kernel with lds bytes of dynamic LDS.  A kernel that asks for more than 64 KiB needs
+// hipFuncAttributeMaxDynamicSharedMemorySize raised first, and the attribute belongs to the function ON THE CURRENT DEVICE:
+// one slot per (kernel instantiation, device) holds the largest size set so far.  A fixed size is set on the kernel's first
+// launch on a device, a size that depends on the arguments (scan.hip, post.hip) only when it grows.  The fast path is
+// hipGetDevice and one atomic load; the first launches of two host threads meet at the mutex, which also keeps a smaller
+// size from being set after a larger one.  Devices past kLaunchDevices are served without a slot (the attribute is set on
+// every launch).  who = the entry point, for the error text.  Returns CMDIAD_OK or, with the error text set,
+// CMDIAD_ERR_LAUNCH; the launch itself is checked by the caller (CMDIAD_CHECK_LAUNCH).
+// Kernels with static LDS only are launched with hipLaunchKernelGGL directly.
+constexpr int kLaunchDevices = 32;
+
+template <auto Kernel, class... Args>
+int launch_lds(const char* who, dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args)
+{
+    static std::atomic<size_t> set_bytes[kLaunchDevices];   // zero-initialised
+    static std::mutex mu;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) {
+        cmdiad_set_error("%s: hipGetDevice failed", who);
+        return CMDIAD_ERR_LAUNCH;
+    }
+    std::atomic<size_t>* slot = dev >= 0 && dev < kLaunchDevices ? &set_bytes[dev] : nullptr;
+    if (!slot || slot->load(std::memory_order_acquire) < lds) {
+        std::lock_guard<std::mutex> lock(mu);
+        if (!slot || slot->load(std::memory_order_relaxed) < lds) {
+            if (hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+                cmdiad_set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu) failed", who, lds);
+                return CMDIAD_ERR_LAUNCH;
+            }
+            if (slot) slot->store(lds, std::memory_order_release);
+        }
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, stream, args...);
+    return CMDIAD_OK;
+}
+
+// Environment switches.  A switch that tests and tools change between calls is read at its site on every call; one that is
+// fixed for the process is written `static const int x = env_int(...)` at its site.
+inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+inline long env_long(const char* name, long dflt) { const char* e = getenv(name); return e ? atol(e) : dflt; }
+inline bool env_set(const char* name) { return getenv(name) != nullptr; }
+inline bool env_is(const char* name, char c) { const char* e = getenv(name); return e && e[0] == c; }   // set, and starts with c

@@ -3,6 +3,7 @@
 // is needed; 8/16-byte vector accesses everywhere (guide G13).
 #include <algorithm>
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -440,7 +441,7 @@ extern "C" int cmdiad_layernorm(float* x, const float* add, const float* gamma, 
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((M + 3) / 4), block(256);
     // 16-byte form: C % 256 == 0 and every pointer it touches 16-byte (bf16 row: 8-byte) aligned; CMDIAD_LN_WIDE=0: the float2 form (A/B)
-    static const bool wide_ok = !(getenv("CMDIAD_LN_WIDE") && getenv("CMDIAD_LN_WIDE")[0] == '0');
+    static const bool wide_ok = !env_is("CMDIAD_LN_WIDE", '0');
     const bool wide = wide_ok && C % 256 == 0 && C <= 1024 && (((uintptr_t)x | (uintptr_t)add | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)out_f32) & 15) == 0 &&
                       ((uintptr_t)out_bf16 & 7) == 0 && (!out_f32 || ldo32 % 4 == 0);
     if (wide) {

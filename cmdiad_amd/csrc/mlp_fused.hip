@@ -19,11 +19,8 @@
 // arithmetic of gemm_std_kernel<..., RES_ROWS, LN_OUT> (the 64-column ln_part sums in its lane order) for the output.
 //
 // LDS: xb 8 x 12 KiB + hidden 8 x 2 KiB + ring 6 x 8 KiB = 160 KiB.
-#include <stdlib.h>
-
-#include <mutex>
-
 #include "gemm_core.h"
+#include "launch.h"
 
 namespace {
 
@@ -252,30 +249,15 @@ __global__ __launch_bounds__(512, 1) void pmae_mlp_fused_kernel(MlpParams p)
 int cmdiad_pmae_mlp_fused(float* x, const uint16_t* xb, const float* rstd, const uint16_t* w1, const float* b1, const uint16_t* w2,
                           const float* b2, int M, uint16_t* ln_xb, float* ln_part, const float* add2, cmdiad_stream_t stream)
 {
-    auto a16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
     CMDIAD_REQUIRE(x && xb && rstd && w1 && b1 && w2 && b2 && M > 0, CMDIAD_ERR_ARG, "cmdiad_pmae_mlp_fused: null operand");
-    CMDIAD_REQUIRE(a16(x) && a16(xb) && a16(w1) && a16(w2) && a16(b1) && a16(b2) && (!add2 || a16(add2)), CMDIAD_ERR_ARG,
+    CMDIAD_REQUIRE(aligned16(x) && aligned16(xb) && aligned16(w1) && aligned16(w2) && aligned16(b1) && aligned16(b2) && (!add2 || aligned16(add2)), CMDIAD_ERR_ARG,
                    "cmdiad_pmae_mlp_fused: operands must be 16-byte aligned");
     CMDIAD_REQUIRE(!ln_xb == !ln_part && (ln_xb || !add2) && (!ln_xb || (((uintptr_t)ln_xb & 7) == 0 && ((uintptr_t)ln_part & 7) == 0)),
                    CMDIAD_ERR_ARG, "cmdiad_pmae_mlp_fused: ln_xb and ln_part come together (8-byte aligned); add2 only with them");
     MlpParams p{M, (const bf16_t*)xb, rstd, (const bf16_t*)w1, b1, (const bf16_t*)w2, b2, x, (bf16_t*)ln_xb, ln_part, add2};
-    static std::mutex mu;
-    static bool attr[2] = {false, false};
-    auto go = [&](auto kernel, int which) -> int {
-        {
-            std::lock_guard<std::mutex> lock(mu);
-            if (!attr[which]) {
-                if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes) != hipSuccess) {
-                    cmdiad_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d) failed", kLdsBytes);
-                    return CMDIAD_ERR_LAUNCH;
-                }
-                attr[which] = true;
-            }
-        }
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((M + kBM - 1) / kBM)), dim3(kWaves * 64), kLdsBytes, (hipStream_t)stream, p);
-        return CMDIAD_OK;
-    };
-    const int rc = ln_xb ? go(pmae_mlp_fused_kernel<true>, 1) : go(pmae_mlp_fused_kernel<false>, 0);
+    const dim3 grid((unsigned)((M + kBM - 1) / kBM)), block(kWaves * 64);
+    const int rc = ln_xb ? launch_lds<pmae_mlp_fused_kernel<true>>("cmdiad_pmae_mlp_fused", grid, block, kLdsBytes, (hipStream_t)stream, p)
+                         : launch_lds<pmae_mlp_fused_kernel<false>>("cmdiad_pmae_mlp_fused", grid, block, kLdsBytes, (hipStream_t)stream, p);
     if (rc) return rc;
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;

@@ -14,6 +14,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -160,15 +161,7 @@ extern "C" int cmdiad_blur8_maps(const float* maps, int n_maps, int H, int W, fl
                    "cmdiad_blur8_maps: a side of %dx%d is shorter than the box window (Pillow's short-line branch is not implemented)", H, W);
     const size_t lds = cmdiad_blur8_lds_bytes(H, W);
     CMDIAD_REQUIRE(lds <= 160 * 1024 - 64, CMDIAD_ERR_ARG, "cmdiad_blur8_maps: %dx%d does not fit the 160 KiB LDS", H, W);
-    static size_t attr = 0;
-    if (lds > attr) {
-        if (hipFuncSetAttribute((const void*)blur8_maps_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            cmdiad_set_error("cmdiad_blur8_maps: hipFuncSetAttribute(%zu) failed", lds);
-            return CMDIAD_ERR_LAUNCH;
-        }
-        attr = lds;
-    }
-    hipLaunchKernelGGL(blur8_maps_kernel, dim3(n_maps), dim3(256), lds, (hipStream_t)stream, maps, H, W, r, ww, fw, out);
+    if (const int rc = launch_lds<blur8_maps_kernel>("cmdiad_blur8_maps", dim3(n_maps), dim3(256), lds, (hipStream_t)stream, maps, H, W, r, ww, fw, out)) return rc;
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
 }

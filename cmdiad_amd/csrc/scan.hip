@@ -20,6 +20,7 @@
 //     error of the third-smallest distance (libraries built without a coreset hold clusters of near-identical patches:
 //     tests/test_gpu_kernels.py::test_reweight_scan_clustered_near_duplicates).
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -29,7 +30,6 @@ constexpr int kCand = 8;         // approximate candidates kept per probe from t
 constexpr int kWaves = 8;        // waves per block: 2 per SIMD
 constexpr int kChunk = 8;        // k-steps (of 16 floats) per software-pipeline chunk: D % 128 == 0
 
-static inline bool aligned16h(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // sorted ascending list of K keys, insertion of a key known to be < t[K-1]
 template <int K>
@@ -378,7 +378,7 @@ int scan_blocks(int Nb)
 {
     const int groups = (Nb + 15) / 16;
     int blocks = (groups + 7) / 8;   // at least one group per wave
-    return blocks < 1 ? 1 : (blocks > 256 ? 256 : blocks);   // one block per CU
+    return blocks < 1 ? 1 : (blocks > kPersistCUs ? kPersistCUs : blocks);   // one block per CU
 }
 
 }  // namespace
@@ -388,7 +388,7 @@ extern "C" size_t cmdiad_bank_block16_floats(int Nb, int D) { return (size_t)((N
 extern "C" int cmdiad_bank_block16(const float* bank, int Nb, int D, float* out, cmdiad_stream_t stream)
 {
     CMDIAD_REQUIRE(bank && out, CMDIAD_ERR_ARG, "cmdiad_bank_block16: null pointer");
-    CMDIAD_REQUIRE(D % 16 == 0 && aligned16h(bank) && aligned16h(out), CMDIAD_ERR_ARG, "cmdiad_bank_block16: D%%16, alignment");
+    CMDIAD_REQUIRE(D % 16 == 0 && aligned16(bank) && aligned16(out), CMDIAD_ERR_ARG, "cmdiad_bank_block16: D%%16, alignment");
     if (Nb == 0) return CMDIAD_OK;
     const size_t n4 = cmdiad_bank_block16_floats(Nb, D) / 4;
     const unsigned blocks = (unsigned)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
@@ -406,16 +406,9 @@ extern "C" size_t cmdiad_reweight_workspace_bytes(int R, int Nb)
 static int scan_launch(ScanPair& pair, int D, hipStream_t s, const char* who)
 {
     const size_t lds = (size_t)2 * (D / 16) * 64 * 16 + kProbes * 4 + (size_t)kWaves * kProbes * kCand * 8;
-    static size_t attr = 0;
-    if (lds > attr) {
-        if (hipFuncSetAttribute((const void*)reweight_scan_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-            hipSuccess) {
-            cmdiad_set_error("%s: %zu bytes of LDS exceed the device limit", who, lds);
-            return CMDIAD_ERR_ARG;
-        }
-        attr = lds;
-    }
-    hipLaunchKernelGGL(reweight_scan_mfma_kernel, dim3(pair.p[0].blocks + pair.p[1].blocks), dim3(kWaves * 64), lds, s, pair, D);
+    // (the size grows with D: a refusal is the caller's D, not a launch failure)
+    CMDIAD_REQUIRE(launch_lds<reweight_scan_mfma_kernel>(who, dim3(pair.p[0].blocks + pair.p[1].blocks), dim3(kWaves * 64), lds, s, pair, D) == CMDIAD_OK,
+                   CMDIAD_ERR_ARG, "%s: %zu bytes of LDS exceed the device limit", who, lds);
     CMDIAD_CHECK_LAUNCH();
     hipLaunchKernelGGL(reweight_exact_merge_kernel, dim3(pair.p[0].R + pair.p[1].R), dim3(kCand * 64), 0, s, pair, D);
     CMDIAD_CHECK_LAUNCH();
@@ -427,8 +420,8 @@ extern "C" int cmdiad_reweight_scan(const float* probes, const float* bank, cons
                                     cmdiad_stream_t stream)
 {
     CMDIAD_REQUIRE(probes && bank && bank_block16 && top3, CMDIAD_ERR_ARG, "cmdiad_reweight_scan: null pointer");
-    CMDIAD_REQUIRE(R > 0 && R <= kProbes && D % (16 * kChunk) == 0 && D <= 1024 && aligned16h(probes) && aligned16h(bank) &&
-                       aligned16h(bank_block16),
+    CMDIAD_REQUIRE(R > 0 && R <= kProbes && D % (16 * kChunk) == 0 && D <= 1024 && aligned16(probes) && aligned16(bank) &&
+                       aligned16(bank_block16),
                    CMDIAD_ERR_ARG, "cmdiad_reweight_scan: 0<R<=32, D%%128==0, D<=1024, 16-byte alignment (R=%d D=%d)", R, D);
     if (Nb == 0) return CMDIAD_OK;
     CMDIAD_REQUIRE(workspace && workspace_bytes >= cmdiad_reweight_workspace_bytes(R, Nb), CMDIAD_ERR_WORKSPACE,
@@ -462,8 +455,8 @@ extern "C" int cmdiad_reweight_scan_pair(const float* probes0, const float* bank
     CMDIAD_REQUIRE(probes0 && bank0 && bank0_block16 && top3_0 && probes1 && bank1 && bank1_block16 && top3_1, CMDIAD_ERR_ARG,
                    "cmdiad_reweight_scan_pair: null pointer");
     CMDIAD_REQUIRE(R0 > 0 && R0 <= kProbes && R1 > 0 && R1 <= kProbes && Nb0 > 0 && Nb1 > 0 && D % (16 * kChunk) == 0 && D <= 1024 &&
-                       aligned16h(probes0) && aligned16h(bank0) && aligned16h(bank0_block16) && aligned16h(probes1) && aligned16h(bank1) &&
-                       aligned16h(bank1_block16),
+                       aligned16(probes0) && aligned16(bank0) && aligned16(bank0_block16) && aligned16(probes1) && aligned16(bank1) &&
+                       aligned16(bank1_block16),
                    CMDIAD_ERR_ARG, "cmdiad_reweight_scan_pair: 0<R<=32, Nb>0, D%%128==0, D<=1024, 16-byte alignment (R=%d,%d D=%d)", R0, R1, D);
     CMDIAD_REQUIRE(workspace && workspace_bytes >= cmdiad_reweight_pair_workspace_bytes(Nb0, Nb1), CMDIAD_ERR_WORKSPACE,
                    "cmdiad_reweight_scan_pair: workspace too small");

@@ -225,7 +225,6 @@ __global__ void score_final_kernel(const float* __restrict__ s_star, const float
     s_out[b] = w * s_star[b];
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
