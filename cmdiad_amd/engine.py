@@ -11,7 +11,6 @@ import os
 
 import torch
 
-from . import _native as nat
 from . import ops
 
 
@@ -270,10 +269,6 @@ def sharded_min_keys(q16, q_sq, bank, group, plan=None, timer=None, stats=None, 
     return keys, s.plan
 
 
-def _call(name, *args):
-    nat.check(getattr(nat.lib(), name)(*args), name)
-
-
 def score_patches(patch32, bank, dims, gt_size=224, group=None):
     """features.py:225-294 for a batch.  patch32 [B,Q,D] f32 cuda, ALREADY normalised.
     Returns dict(min_val [B,Q], min_idx [B,Q] int64, s_idx [B], s_star [B], s [B], s_map_pre [B,gt,gt], ...).
@@ -335,13 +330,8 @@ def _sharded_score_steps(patch32, keys, bank, dims, gt_size):
         ops.l2_rescore(flat, bank.f32, keys, min_val, scratch_idx, off) if nloc else None
         min_val = yield ("sum", min_val)
         min_idx = torch.where(keys == KEY_EMPTY, torch.full_like(keys, -1), keys & 0xFFFFFFFF)       # global rows, known everywhere
-    s_star = torch.empty((B,), dtype=torch.float32, device=dev)
-    s_idx = torch.empty((B,), dtype=torch.int32, device=dev)
-    m_test = torch.empty((B, D), dtype=torch.float32, device=dev)
     m_star = torch.zeros((B, D), dtype=torch.float32, device=dev)
-    st = ops._stream()
-    _call("cmdiad_score_head", ops._p(min_val), ops._p(min_idx), ops._p(flat), ops._p(bank.f32), B, Q, D, nloc, off,
-          ops._p(s_star), ops._p(s_idx), ops._p(m_test), ops._p(m_star), st)
+    s_star, s_idx, m_test = ops.score_head(min_val, min_idx, flat.view(B, Q, D), bank.f32, m_star, off, nloc)
     m_star = yield ("sum", m_star)
     if nloc:
         top3_local = ops.reweight_scan(m_star, bank.f32, bank.blk16, row_offset=off)
@@ -349,11 +339,9 @@ def _sharded_score_steps(patch32, keys, bank, dims, gt_size):
         top3_local = torch.full((B, 3), KEY_EMPTY, dtype=torch.int64, device=dev)
     everyone = yield ("gather", top3_local)                                                      # [W, B, 3]
     top3 = everyone.permute(1, 0, 2).reshape(B, -1).sort(1).values[:, :3].contiguous()           # keys are non-negative int64
-    knn_d = torch.zeros((B, 2), dtype=torch.float32, device=dev)
-    _call("cmdiad_score_tail", ops._p(s_star), ops._p(m_test), ops._p(top3), ops._p(bank.f32), B, D, nloc, off, ops._p(knn_d), st)
+    knn_d = ops.score_tail(s_star, m_test, top3, bank.f32, torch.zeros((B, 2), dtype=torch.float32, device=dev), off, nloc)
     knn_d = yield ("sum", knn_d)
-    s = torch.empty((B,), dtype=torch.float32, device=dev)
-    _call("cmdiad_score_final", ops._p(s_star), ops._p(knn_d), B, D, ops._p(s), st)
+    s = ops.score_final(s_star, knn_d, D)
     s_map = ops.bilinear_up(min_val.view(B, dims[0], dims[1]), gt_size)
     return dict(min_val=min_val.view(B, Q), min_idx=min_idx.view(B, Q), s_idx=s_idx, s_star=s_star, s=s,
                 s_map_pre=s_map, top3=top3, knn_d=knn_d)
@@ -381,7 +369,14 @@ def _drive_collectives(gen, group):
 
 def score_patches_from_keys(patch32, keys, bank, dims, gt_size=224, group=None):
     """Everything after the (merged) nearest-neighbour keys: exact re-score, s*, re-weighting, score map.  `group` is needed only
-    when the library's fp32 rows are sharded as well (Bank(replicate_f32=False))."""
+    when the library's fp32 rows are sharded as well (Bank(replicate_f32=False)).
+
+    Where the reference has no answer, the outputs are DEFINED by a zero prefill -- the same on the sharded path, the unsharded path
+    and the pair path, never whatever the allocator left behind (tests/test_gpu_score_tail.py pins it):
+      * a query whose key is KEY_EMPTY: min_val 0, min_idx -1;
+      * an image whose winning patch has min_idx -1 (all of its keys empty): s_idx 0, s_star 0, m_star = the zero vector, s = 0;
+      * a library of fewer than 3 rows (the reference's topk(k=3) raises, features.py:254): the missing neighbours' top3 entries
+        stay KEY_EMPTY and their knn_d entries 0, i.e. each contributes exp(0) = 1 to the re-weighting sum."""
     if getattr(bank, "f32_sharded", False):
         if group is None:
             raise ValueError("score_patches_from_keys: the library's fp32 rows are sharded -- the process group is needed")
@@ -393,19 +388,12 @@ def score_patches_from_keys(patch32, keys, bank, dims, gt_size=224, group=None):
     min_val = torch.zeros((B * Q,), dtype=torch.float32, device=dev)
     min_idx = torch.full((B * Q,), -1, dtype=torch.int64, device=dev)
     ops.l2_rescore(flat, bank.f32, keys, min_val, min_idx, 0)
-    s_star = torch.empty((B,), dtype=torch.float32, device=dev)
-    s_idx = torch.empty((B,), dtype=torch.int32, device=dev)
-    m_test = torch.empty((B, D), dtype=torch.float32, device=dev)
-    m_star = torch.empty((B, D), dtype=torch.float32, device=dev)
-    st = ops._stream()
-    _call("cmdiad_score_head", ops._p(min_val), ops._p(min_idx), ops._p(flat), ops._p(bank.f32), B, Q, D, bank.rows,
-          0, ops._p(s_star), ops._p(s_idx), ops._p(m_test), ops._p(m_star), st)
+    # zero prefill, as the sharded path: m_star of an image whose winning key is empty, knn_d of a library of fewer than 3 rows
+    m_star = torch.zeros((B, D), dtype=torch.float32, device=dev)
+    s_star, s_idx, m_test = ops.score_head(min_val, min_idx, flat.view(B, Q, D), bank.f32, m_star, 0, bank.rows)
     top3 = ops.reweight_scan(m_star, bank.f32, bank.blk16)
-    knn_d = torch.empty((B, 2), dtype=torch.float32, device=dev)
-    _call("cmdiad_score_tail", ops._p(s_star), ops._p(m_test), ops._p(top3), ops._p(bank.f32), B, D, bank.rows, 0,
-          ops._p(knn_d), st)
-    s = torch.empty((B,), dtype=torch.float32, device=dev)
-    _call("cmdiad_score_final", ops._p(s_star), ops._p(knn_d), B, D, ops._p(s), st)
+    knn_d = ops.score_tail(s_star, m_test, top3, bank.f32, torch.zeros((B, 2), dtype=torch.float32, device=dev), 0, bank.rows)
+    s = ops.score_final(s_star, knn_d, D)
     s_map = ops.bilinear_up(min_val.view(B, dims[0], dims[1]), gt_size)
     return dict(min_val=min_val.view(B, Q), min_idx=min_idx.view(B, Q), s_idx=s_idx, s_star=s_star, s=s,
                 s_map_pre=s_map, top3=top3, knn_d=knn_d)
@@ -423,7 +411,6 @@ def score_patches_from_keys_pair(patch_a, keys_a, bank_a, dims_a, patch_b, keys_
         return (score_patches_from_keys(patch_a, keys_a, bank_a, dims_a, gt_size, group),
                 score_patches_from_keys(patch_b, keys_b, bank_b, dims_b, gt_size, group))
     dev = patch_a.device
-    st = ops._stream()
     heads = []
     for patch32, keys, bank in ((patch_a, keys_a, bank_a), (patch_b, keys_b, bank_b)):
         Q = patch32.shape[1]
@@ -431,21 +418,14 @@ def score_patches_from_keys_pair(patch_a, keys_a, bank_a, dims_a, patch_b, keys_
         min_val = torch.zeros((B * Q,), dtype=torch.float32, device=dev)
         min_idx = torch.full((B * Q,), -1, dtype=torch.int64, device=dev)
         ops.l2_rescore(flat, bank.f32, keys, min_val, min_idx, 0)
-        s_star = torch.empty((B,), dtype=torch.float32, device=dev)
-        s_idx = torch.empty((B,), dtype=torch.int32, device=dev)
-        m_test = torch.empty((B, D), dtype=torch.float32, device=dev)
-        m_star = torch.empty((B, D), dtype=torch.float32, device=dev)
-        _call("cmdiad_score_head", ops._p(min_val), ops._p(min_idx), ops._p(flat), ops._p(bank.f32), B, Q, D, bank.rows,
-              0, ops._p(s_star), ops._p(s_idx), ops._p(m_test), ops._p(m_star), st)
+        m_star = torch.zeros((B, D), dtype=torch.float32, device=dev)         # zero prefill: see score_patches_from_keys
+        s_star, s_idx, m_test = ops.score_head(min_val, min_idx, flat.view(B, Q, D), bank.f32, m_star, 0, bank.rows)
         heads.append((min_val, min_idx, s_star, s_idx, m_test, m_star, Q))
     tops = ops.reweight_scan_pair(heads[0][5], bank_a.f32, bank_a.blk16, heads[1][5], bank_b.f32, bank_b.blk16)
     out = []
     for (min_val, min_idx, s_star, s_idx, m_test, m_star, Q), top3, bank, dims in zip(heads, tops, (bank_a, bank_b), (dims_a, dims_b)):
-        knn_d = torch.empty((B, 2), dtype=torch.float32, device=dev)
-        _call("cmdiad_score_tail", ops._p(s_star), ops._p(m_test), ops._p(top3), ops._p(bank.f32), B, D, bank.rows, 0,
-              ops._p(knn_d), st)
-        s = torch.empty((B,), dtype=torch.float32, device=dev)
-        _call("cmdiad_score_final", ops._p(s_star), ops._p(knn_d), B, D, ops._p(s), st)
+        knn_d = ops.score_tail(s_star, m_test, top3, bank.f32, torch.zeros((B, 2), dtype=torch.float32, device=dev), 0, bank.rows)
+        s = ops.score_final(s_star, knn_d, D)
         s_map = ops.bilinear_up(min_val.view(B, dims[0], dims[1]), gt_size)
         out.append(dict(min_val=min_val.view(B, Q), min_idx=min_idx.view(B, Q), s_idx=s_idx, s_star=s_star, s=s,
                         s_map_pre=s_map, top3=top3, knn_d=knn_d))

@@ -688,6 +688,44 @@ def l2_choose(keys, d2_pair, min_val, min_idx):
     return min_val, min_idx
 
 
+def score_head(min_val, min_idx, patch32, bank32, m_star, row_offset=0, rows=None):
+    """features.py:227-235 per image.  min_val / min_idx [B*Q], patch32 [B,Q,D], bank32 = the rows [row_offset, row_offset + rows)
+    of the library (rows: bank32.shape[0] unless given) -> (s_star [B], s_idx [B] i32, m_test [B,D]).  m_star [B,D] is the CALLER's
+    prefilled buffer: row b is written only when the winning patch's library row lies in that window (its owner shard)."""
+    B, Q, D = patch32.shape
+    for t, n in ((min_val, "min_val"), (patch32, "patch"), (bank32, "bank"), (m_star, "m_star")):
+        _chk(t, torch.float32, "score_head." + n)
+    _chk(min_idx, torch.int64, "score_head.min_idx")
+    dev = patch32.device
+    s_star = torch.empty((B,), dtype=torch.float32, device=dev)
+    s_idx = torch.empty((B,), dtype=torch.int32, device=dev)
+    m_test = torch.empty((B, D), dtype=torch.float32, device=dev)
+    _call("cmdiad_score_head", _p(min_val), _p(min_idx), _p(patch32), _p(bank32), B, Q, D, bank32.shape[0] if rows is None else rows,
+          row_offset, _p(s_star), _p(s_idx), _p(m_test), _p(m_star), _stream())
+    return s_star, s_idx, m_test
+
+
+def score_tail(s_star, m_test, top3, bank32, knn_d, row_offset=0, rows=None):
+    """features.py:285 per image: knn_d[b, k - 1] = || m_test[b] - row(top3[b, k]) ||, k = 1, 2.  knn_d [B,2] is the CALLER's
+    prefilled buffer: an entry is written only when that row lies in [row_offset, row_offset + rows) (KEY_EMPTY names none)."""
+    B, D = m_test.shape
+    for t, n in ((s_star, "s_star"), (m_test, "m_test"), (bank32, "bank"), (knn_d, "knn_d")):
+        _chk(t, torch.float32, "score_tail." + n)
+    _chk(top3, torch.int64, "score_tail.top3")
+    _call("cmdiad_score_tail", _p(s_star), _p(m_test), _p(top3), _p(bank32), B, D, bank32.shape[0] if rows is None else rows,
+          row_offset, _p(knn_d), _stream())
+    return knn_d
+
+
+def score_final(s_star, knn_d, D):
+    """features.py:286-290: s [B] = (1 - exp(s* / sqrt(D)) / (exp(knn_0 / sqrt(D)) + exp(knn_1 / sqrt(D)))) * s*."""
+    _chk(s_star, torch.float32, "score_final.s_star"); _chk(knn_d, torch.float32, "score_final.knn_d")
+    B = s_star.shape[0]
+    s = torch.empty((B,), dtype=torch.float32, device=s_star.device)
+    _call("cmdiad_score_final", _p(s_star), _p(knn_d), B, D, _p(s), _stream())
+    return s
+
+
 def bank_block16(bank32):
     """[Nb,D] f32 -> the library copy laid out for the fp32 matrix cores (cmdiad_bank_block16), a flat f32 tensor."""
     _chk(bank32, torch.float32, "bank_block16.bank")
