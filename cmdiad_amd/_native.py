@@ -127,6 +127,9 @@ SIGNATURES = {
     "cmdiad_plane_mask": [P, P, SZ, I, P, D, P],
     "cmdiad_dbscan": [P, I, D, I, P, P, P, SZ, P],
     "cmdiad_label_histogram": [P, I, P, I, P],
+    "cmdiad_resize_bicubic_u8": [P, I, I, I, I, I, P, P, I, P, P, I, P, P, P, P, P],
+    "cmdiad_organized_pc_prep": [P, I, I, I, P, P, I, P, P, I, P, P, P, P],
+    "cmdiad_gt_mask_prep": [P, I, I, I, P, P, I, P, P],
 }
 SIZE_QUERIES = {
     "cmdiad_gemm_streamk_workspace_bytes": [],

@@ -21,7 +21,13 @@ multiple_features.py:815-825 / 942-945; this package's drop-in writes the same):
   Batch composition and order are the ones the reference's DataLoader would produce under the same global torch seed
   (RandomSampler draws its permutation seed from the global generator; ``drop_last`` as given), so a run is
   reproducible against the reference sample for sample.
+
+Sample path (second half of this file; docs/sample_prep.md): the reference's ``TrainDataset`` / ``TrainValidationDataset`` /
+``TestDataset`` / ``get_data_loader`` over an MVTec 3D-AD directory with a third ``img_process_method``, ``'hip'`` -- files decoded on
+reader threads, every transform after that in csrc/sample_prep.hip (``SamplePrep``) -- and ``MVTec3DClass``, the real-data class
+source of ``evaluate.evaluate_classes``.
 """
+import math
 import os
 import queue
 import threading
@@ -327,3 +333,527 @@ class FeatureRing:
             for s in range(self.depth):
                 free.put(s)
             th.join(timeout=5)
+
+
+# =========================================================================================== MVTec 3D-AD / Eyecandies samples
+# The reference's sample path (dataset.py:12-244, 364-381) and its device form (docs/sample_prep.md).  img_process_method:
+#   'cpu_v1'  PIL + torch on the host: the reference's torchvision composition written out (Image.resize(BICUBIC) -> ToTensor ->
+#             Normalize; Image.resize(NEAREST) -> ToTensor for the mask) -- the default everywhere, and the yardstick of the device path
+#   'cpu_v2'  the reference's torchvision.transforms.v2 spelling of the same pipeline; here an alias of 'cpu_v1'
+#   'hip'     decoding on reader threads, everything after it in csrc/sample_prep.hip (SamplePrep); the samples are device tensors
+IMG_PROCESS_METHODS = ("cpu_v1", "cpu_v2", "hip")
+IMAGENET_MEAN = [0.485, 0.456, 0.406]
+IMAGENET_STD = [0.229, 0.224, 0.225]
+DEPTH_SIZE = 224          # dataset.py:109 resizes the depth map without a size: always 224
+
+
+def eyecandies_classes():
+    return ['CandyCane', 'ChocolateCookie', 'ChocolatePraline', 'Confetto', 'GummyBear', 'HazelnutTruffle', 'LicoriceSandwich',
+            'Lollipop', 'Marshmallow', 'PeppermintCandy']
+
+
+def mvtec3d_classes():
+    return ["bagel", "cable_gland", "carrot", "cookie", "dowel", "foam", "peach", "potato", "rope", "tire"]
+
+
+def _check_method(img_process_method):
+    if img_process_method not in IMG_PROCESS_METHODS:
+        raise ValueError(f"img_process_method must be one of 'cpu_v1', 'cpu_v2', 'hip', got {img_process_method!r}")
+
+
+# ------------------------------------------------------------------------------------------------ host tables
+def _bicubic_filter(x):
+    """Pillow's bicubic_filter (a = -0.5), the operations in its order, float64."""
+    import numpy as np
+    a = -0.5
+    x = np.abs(x)
+    near = ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    far = (((x - 5) * x + 8) * x - 4) * a
+    return np.where(x < 1.0, near, np.where(x < 2.0, far, 0.0))
+
+
+def bicubic_tables(n_in, n_out):
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for one axis of Image.resize(BICUBIC) on 8-bit channels ->
+    (coef [n_out, ksize] int32 with 22 fractional bits, bounds [n_out, 2] int32 = (first source index, taps)).  float64, every
+    operation in Pillow's order (the weights of a window are summed left to right); docs/sample_prep.md."""
+    import numpy as np
+    scale = n_in / n_out
+    filterscale = max(scale, 1.0)
+    support = 2.0 * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    ss = 1.0 / filterscale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)                 # (int): truncation
+    xmax = np.minimum((center + support + 0.5).astype(np.int64), n_in) - xmin
+    tap = np.arange(ksize, dtype=np.int64)[None, :]
+    w = _bicubic_filter(((tap + xmin[:, None]) - center[:, None] + 0.5) * ss)
+    w = np.where(tap < xmax[:, None], w, 0.0)
+    ww = np.cumsum(w, axis=1)[:, -1:]                                               # sequential sum, as the C loop (adding 0.0 is exact)
+    w = np.where(ww != 0.0, w / np.where(ww != 0.0, ww, 1.0), w)
+    q = w * float(1 << 22)
+    coef = np.where(w < 0, -0.5 + q, 0.5 + q).astype(np.int64).astype(np.int32)     # half away from zero, then (int)
+    return coef, np.stack([xmin, xmax], 1).astype(np.int32)
+
+
+def pillow_nearest_index(n_in, n_out):
+    """Source index of every output position under Pillow's Image.resize(NEAREST) (ImagingScaleAffine): the coordinate starts at
+    half a step and is ADVANCED by additions in float64, then truncated -- not torch's floor(dst * scale) in float32."""
+    import numpy as np
+    step = float(n_in) / n_out
+    xo = 0.0 + step * 0.5
+    out = np.empty(n_out, dtype=np.int32)
+    for x in range(n_out):
+        out[x] = min(int(xo), n_in - 1)
+        xo += step
+    return out
+
+
+def torch_nearest_index(n_in, n_out):
+    """torch's mode='nearest' rule (utils.mvtec3d_util._nearest_index) as an int32 table."""
+    from .utils.mvtec3d_util import _nearest_index
+    return _nearest_index(n_in, n_out).astype("int32")
+
+
+def normalize_table(mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """[3,256] float32: ToTensor + Normalize of every uint8 value, computed by torch with torchvision's operations in their order
+    (to float32, / 255, - mean, / std) -- the device path looks its floats up here, so it equals the host path by construction."""
+    v = torch.arange(256, dtype=torch.uint8).to(torch.float32).div(255).expand(3, 256).clone()
+    m = torch.as_tensor(mean, dtype=torch.float32).view(3, 1)
+    s = torch.as_tensor(std, dtype=torch.float32).view(3, 1)
+    return v.sub_(m).div_(s)
+
+
+# ------------------------------------------------------------------------------------------------ the two host stages, written out
+def host_rgb_transform(img, rgb_size):
+    """PIL RGB image -> float32 [3,S,S]: transforms.Resize((S,S), BICUBIC) + ToTensor + Normalize (dataset.py:62-65) without torchvision."""
+    import numpy as np
+    from PIL import Image
+    img = img.resize((rgb_size, rgb_size), Image.BICUBIC)
+    t = torch.from_numpy(np.array(img, dtype=np.uint8)).permute(2, 0, 1).contiguous().to(torch.float32).div(255)
+    m = torch.as_tensor(IMAGENET_MEAN, dtype=torch.float32).view(3, 1, 1)
+    s = torch.as_tensor(IMAGENET_STD, dtype=torch.float32).view(3, 1, 1)
+    return t.sub_(m).div_(s)
+
+
+def host_gt_transform(gt, gt_size):
+    """PIL 'L' image -> float32 [1,g,g] in {0, 1}: Resize((g,g), NEAREST) + ToTensor, then > 0.5 (dataset.py:168-171, 239-241)."""
+    import numpy as np
+    from PIL import Image
+    gt = gt.resize((gt_size, gt_size), Image.NEAREST)
+    t = torch.from_numpy(np.array(gt, dtype=np.uint8))[None].to(torch.float32).div(255)
+    return torch.where(t > 0.5, 1., .0)
+
+
+def host_cloud_transform(organized_pc, xyz_size):
+    """[H,W,3] array -> (resized cloud [3,xs,xs] float32, depth map three times [3,224,224]); dataset.py:108-111."""
+    import numpy as np
+    from .utils import mvtec3d_util as mu
+    depth3 = np.repeat(mu.organized_pc_to_depth_map(organized_pc)[:, :, np.newaxis], 3, axis=2)
+    resized_depth = mu.resize_organized_pc(depth3)
+    resized_pc = mu.resize_organized_pc(organized_pc, target_height=xyz_size, target_width=xyz_size)
+    return resized_pc.clone().detach().float(), resized_depth
+
+
+# ------------------------------------------------------------------------------------------------ device path
+class DeviceSample(tuple):
+    """(img, resized_organized_pc, resized_depth_map_3channel) on the device, as the reference's sample tuple, carrying the number of
+    valid points of the cloud: ``n_valid_dev`` ([1] int32 on the device) and ``n_valid`` (int; its copy to pinned host memory was
+    queued when the sample was prepared -- the first read waits for that copy, nothing else)."""
+
+    def __new__(cls, items, count):
+        self = super().__new__(cls, items)
+        self._count = count
+        return self
+
+    @property
+    def n_valid_dev(self):
+        return self._count.dev()
+
+    @property
+    def n_valid(self):
+        return self._count.host()
+
+    def batched(self):
+        """The same sample as a DataLoader with batch_size=1 hands it out: every tensor with a leading 1."""
+        return DeviceSample(tuple(t.unsqueeze(0) for t in self), self._count)
+
+
+class _Count:
+    def __init__(self, dev, host, event, i):
+        self._dev, self._host, self._event, self._i, self._value = dev, host, event, i, None
+
+    def dev(self):
+        return self._dev[self._i:self._i + 1]
+
+    def host(self):
+        if self._value is None:
+            self._event.synchronize()
+            self._value = int(self._host[self._i])
+        return self._value
+
+
+class SamplePrep:
+    """Decoded arrays -> the tensors of the reference's ``__getitem__`` on the device (csrc/sample_prep.hip; docs/sample_prep.md).
+
+    ``prepare(rgb_u8 [H,W,3], pc_f32 [H,W,3], gt_u8 [H,W] | None)`` -> ``(DeviceSample(img [3,S,S], cloud [3,xs,xs], depth [3,224,224]),
+    gt [1,g,g] | None)``; ``prepare_batch`` takes lists and returns a list of such pairs.  Samples of equal shapes share their launches;
+    every sample's bytes are the ones a call of its own gives (the arithmetic is per pixel and integer).  Inputs go up through
+    pinned memory on the shared copy stream; the kernels run on the current stream.  Tables are computed once per (n_in, n_out)
+    and kept on the device."""
+
+    def __init__(self, rgb_size=224, xyz_size=224, gt_size=224, device="cuda"):
+        self.rgb_size, self.xyz_size, self.gt_size = int(rgb_size), int(xyz_size), int(gt_size)
+        dev = torch.device(device)
+        if dev.type != "cuda" or not torch.cuda.is_available():
+            from . import _native as nat
+            raise nat.NativeError("SamplePrep needs a GPU: img_process_method='hip' has no CPU path (use 'cpu_v1' on the host)")
+        self.device = dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+        self._tables = {}
+        self._copy_stream = _shared_stream(self.device, "dataset.copy")
+
+    def _table(self, kind, n_in, n_out):
+        key = (kind, n_in, n_out)
+        t = self._tables.get(key)
+        if t is None:
+            if kind == "bicubic":
+                t = tuple(torch.from_numpy(a).to(self.device) for a in bicubic_tables(n_in, n_out))
+            elif kind == "norm":
+                t = normalize_table().to(self.device)
+            else:
+                fn = pillow_nearest_index if kind == "pillow" else torch_nearest_index
+                t = torch.from_numpy(fn(n_in, n_out)).to(self.device)
+            self._tables[key] = t
+        return t
+
+    def _upload(self, arrays, dtype, what):
+        """list of equal-shaped numpy arrays -> one device tensor [n, ...], through pinned memory on the copy stream."""
+        import numpy as np
+        first = np.asarray(arrays[0])
+        host = torch.empty((len(arrays), *first.shape), dtype=dtype, pin_memory=True)
+        view = host.numpy()
+        for i, a in enumerate(arrays):
+            a = np.asarray(a)
+            if a.dtype != view.dtype or a.shape != first.shape:
+                raise TypeError(f"SamplePrep: {what} must be {view.dtype} arrays of one shape per group, got {a.dtype} {a.shape}")
+            view[i] = a
+        cur = torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(self._copy_stream):
+            dev = host.to(self.device, non_blocking=True)
+        cur.wait_stream(self._copy_stream)
+        dev.record_stream(cur)
+        return dev
+
+    def prepare(self, rgb_u8, pc_f32, gt_u8=None):
+        return self.prepare_batch([rgb_u8], [pc_f32], [gt_u8])[0]
+
+    def prepare_batch(self, rgbs, pcs, gts=None):
+        import numpy as np
+        from . import ops
+        n = len(rgbs)
+        gts = list(gts) if gts is not None else [None] * n
+        if not (len(pcs) == len(gts) == n):
+            raise ValueError("SamplePrep.prepare_batch: the lists differ in length")
+        for r, p, g in zip(rgbs, pcs, gts):
+            if np.ndim(r) != 3 or np.shape(r)[2] != 3 or np.ndim(p) != 3 or np.shape(p)[2] != 3 or (g is not None and np.ndim(g) != 2):
+                raise ValueError(f"SamplePrep: rgb [H,W,3], cloud [H,W,3], gt [H,W] expected, got {np.shape(r)}, {np.shape(p)}, "
+                                 f"{None if g is None else np.shape(g)}")
+        imgs, clouds, depths, counts, masks = [None] * n, [None] * n, [None] * n, [None] * n, [None] * n
+        with torch.cuda.device(self.device):
+            norm = self._table("norm", 256, 3)
+            S = self.rgb_size
+            for (H, W), idx in _group_by_shape(rgbs, range(n)).items():
+                src = self._upload([rgbs[i] for i in idx], torch.uint8, "rgb")
+                htab = self._table("bicubic", W, S) if W != S else None
+                vtab = self._table("bicubic", H, S) if H != S else None
+                _, out = ops.resize_bicubic_u8(src, S, S, htab, vtab, norm)
+                for j, i in enumerate(idx):
+                    imgs[i] = out[j]
+            for (H, W), idx in _group_by_shape(pcs, range(n)).items():
+                src = self._upload([pcs[i] for i in idx], torch.float32, "the point cloud")
+                cloud, depth, count = ops.organized_pc_prep(
+                    src, (self._table("torch", H, self.xyz_size), self._table("torch", W, self.xyz_size)),
+                    (self._table("torch", H, DEPTH_SIZE), self._table("torch", W, DEPTH_SIZE)))
+                host = torch.empty(len(idx), dtype=torch.int32, pin_memory=True)
+                host.copy_(count, non_blocking=True)
+                event = torch.cuda.Event()
+                event.record()
+                for j, i in enumerate(idx):
+                    clouds[i], depths[i], counts[i] = cloud[j], depth[j], _Count(count, host, event, j)
+            with_gt = [i for i in range(n) if gts[i] is not None]
+            for (H, W), idx in _group_by_shape(gts, with_gt).items():
+                src = self._upload([gts[i] for i in idx], torch.uint8, "gt")
+                out = ops.gt_mask_prep(src, (self._table("pillow", H, self.gt_size), self._table("pillow", W, self.gt_size)))
+                for j, i in enumerate(idx):
+                    masks[i] = out[j]
+        return [(DeviceSample((imgs[i], clouds[i], depths[i]), counts[i]), masks[i]) for i in range(n)]
+
+
+def _group_by_shape(arrays, indices):
+    import numpy as np
+    groups = {}
+    for i in indices:
+        groups.setdefault(tuple(np.shape(arrays[i])[:2]), []).append(i)
+    return groups
+
+
+# ------------------------------------------------------------------------------------------------ the reference's dataset classes
+def _sorted_glob(*parts):
+    pattern = parts[-1]
+    paths = list(Path(*parts[:-1]).glob(pattern))
+    paths.sort()
+    return paths
+
+
+def _read_rgb(path):
+    from PIL import Image
+    return Image.open(path).convert('RGB')
+
+
+def _read_cloud(path):
+    from .utils import mvtec3d_util as mu
+    return mu.read_tiff_organized_pc(path)     # (looked up at call time: needs `tifffile`, and says so)
+
+
+class BaseAnomalyDetectionDataset(Dataset):
+    """dataset.py:45-70.  `decoded(idx)` returns what the files hold (the part that stays on the host whatever the method);
+    `__getitem__` the reference's item: with 'cpu_v1' / 'cpu_v2' host tensors, with 'hip' device tensors (one SamplePrep call per
+    item; `get_data_loader` batches the calls)."""
+
+    def __init__(self, split, class_name, rgb_size, xyz_size, gt_size, dataset_path, img_process_method):
+        _check_method(img_process_method)
+        self.IMAGENET_MEAN, self.IMAGENET_STD = list(IMAGENET_MEAN), list(IMAGENET_STD)
+        self.cls, self.rgb_size, self.xyz_size, self.gt_size = class_name, rgb_size, xyz_size, gt_size
+        if split == 'train_validation':
+            self.img_path = str(Path(dataset_path, self.cls, 'train'))
+            self.img_path2 = str(Path(dataset_path, self.cls, 'validation'))
+        else:
+            self.img_path = str(Path(dataset_path, self.cls, split))
+        self.img_process_method = img_process_method
+        self._prep = None
+
+    def sample_prep(self):
+        if self._prep is None:
+            self._prep = SamplePrep(self.rgb_size, self.xyz_size, self.gt_size)
+        return self._prep
+
+    def __len__(self):
+        return len(self.img_paths)
+
+    def decoded(self, idx):
+        """(rgb uint8 [H,W,3], cloud [H,W,3], gt uint8 [H,W] or None) of item idx: the decoded files, nothing else."""
+        import numpy as np
+        rgb_path, tiff_path = self.img_paths[idx]
+        gt = getattr(self, "gt_paths", None)
+        gt = gt[idx] if gt is not None else 0
+        if gt != 0:
+            from PIL import Image
+            gt = np.array(Image.open(gt).convert('L'), dtype=np.uint8)
+        return np.array(_read_rgb(rgb_path), dtype=np.uint8), _read_cloud(tiff_path), (None if isinstance(gt, int) else gt)
+
+    def _sample(self, idx):
+        rgb_path, tiff_path = self.img_paths[idx]
+        if self.img_process_method == 'hip':
+            rgb, pc, _ = self.decoded(idx)
+            return self.sample_prep().prepare(rgb, pc)[0]
+        img = host_rgb_transform(_read_rgb(rgb_path), self.rgb_size)
+        resized_pc, resized_depth = host_cloud_transform(_read_cloud(tiff_path), self.xyz_size)
+        return img, resized_pc, resized_depth
+
+    def _good_pairs(self, *roots):
+        rgb_paths, tiff_paths = [], []
+        for root in roots:
+            rgb_paths += list(Path(root, 'good', 'rgb').glob("*.png"))
+            tiff_paths += list(Path(root, 'good', 'xyz').glob("*.tiff"))
+        rgb_paths.sort()
+        tiff_paths.sort()
+        return list(zip(rgb_paths, tiff_paths))
+
+
+class TrainDataset(BaseAnomalyDetectionDataset):
+    """dataset.py:73-113: good/rgb/*.png zipped with good/xyz/*.tiff, both sorted; label 0."""
+
+    def __init__(self, class_name, rgb_size, xyz_size, gt_size, dataset_path, img_process_method):
+        super().__init__(split="train", class_name=class_name, rgb_size=rgb_size, xyz_size=xyz_size, gt_size=gt_size,
+                         dataset_path=dataset_path, img_process_method=img_process_method)
+        self.img_paths, self.labels = self.load_dataset()  # self.labels => good : 0, anomaly : 1
+
+    def load_dataset(self):
+        pairs = self._good_pairs(self.img_path)
+        return pairs, [0] * len(pairs)
+
+    def __getitem__(self, idx):
+        return self._sample(idx), self.labels[idx]
+
+
+class TrainValidationDataset(TrainDataset):
+    """dataset.py:116-160: the good samples of train/ and validation/ together, sorted as one list."""
+
+    def __init__(self, class_name, rgb_size, xyz_size, gt_size, dataset_path, img_process_method):
+        BaseAnomalyDetectionDataset.__init__(self, split="train_validation", class_name=class_name, rgb_size=rgb_size, xyz_size=xyz_size,
+                                             gt_size=gt_size, dataset_path=dataset_path, img_process_method=img_process_method)
+        self.img_paths, self.labels = self.load_dataset()
+
+    def load_dataset(self):
+        pairs = self._good_pairs(self.img_path, self.img_path2)
+        return pairs, [0] * len(pairs)
+
+
+class TestDataset(BaseAnomalyDetectionDataset):
+    """dataset.py:163-244.  The defect directories are visited in SORTED order: the reference walks os.listdir(), whose order is
+    unspecified; sorted is one of the orders it can produce (and the one that makes a run reproducible across file systems)."""
+    __test__ = False      # (not a pytest class)
+
+    def __init__(self, class_name, rgb_size, xyz_size, gt_size, dataset_path, img_process_method):
+        super().__init__(split="test", class_name=class_name, rgb_size=rgb_size, xyz_size=xyz_size, gt_size=gt_size,
+                         dataset_path=dataset_path, img_process_method=img_process_method)
+        self.img_paths, self.gt_paths, self.labels = self.load_dataset()  # self.labels => good : 0, anomaly : 1
+
+    def load_dataset(self):
+        img_tot_paths, gt_tot_paths, tot_labels = [], [], []
+        for defect_type in sorted(os.listdir(self.img_path)):
+            rgb_paths = _sorted_glob(self.img_path, defect_type, 'rgb', "*.png")
+            tiff_paths = _sorted_glob(self.img_path, defect_type, 'xyz', "*.tiff")
+            sample_paths = list(zip(rgb_paths, tiff_paths))
+            img_tot_paths.extend(sample_paths)
+            if defect_type == 'good':
+                gt_tot_paths.extend([0] * len(sample_paths))
+                tot_labels.extend([0] * len(sample_paths))
+            else:
+                gt_tot_paths.extend(_sorted_glob(self.img_path, defect_type, 'gt', "*.png"))
+                tot_labels.extend([1] * len(sample_paths))
+        assert len(img_tot_paths) == len(gt_tot_paths), "Something wrong with test and ground truth pair!"
+        return img_tot_paths, gt_tot_paths, tot_labels
+
+    def __getitem__(self, idx):
+        gt, label = self.gt_paths[idx], self.labels[idx]
+        rgb_path = str(self.img_paths[idx][0])
+        if self.img_process_method == 'hip':
+            rgb, pc, gt_u8 = self.decoded(idx)
+            sample, gt = self.sample_prep().prepare(rgb, pc, gt_u8)
+            if gt is None:
+                gt = torch.zeros([1, DEPTH_SIZE, DEPTH_SIZE], device=sample[0].device)
+            return sample, gt[:1], label, rgb_path
+        sample = self._sample(idx)
+        if gt == 0:
+            gt = torch.zeros([1, sample[2].size()[-2], sample[2].size()[-2]])
+        else:
+            from PIL import Image
+            gt = host_gt_transform(Image.open(gt).convert('L'), self.gt_size)
+        return sample, gt[:1], label, rgb_path     # only need 1 dimension gt instead of 3
+
+
+class DeviceSampleLoader:
+    """What ``DataLoader(dataset, batch_size=1, shuffle=False, num_workers=6, prefetch_factor=6, pin_memory=True)`` (dataset.py:377)
+    is for img_process_method='hip': the same items in the same order -- ``((img, cloud, depth), label)`` or ``((img, cloud, depth), gt,
+    label, [rgb_path])``, every tensor with the leading 1 of a batch of one -- with the sample tensors ON THE DEVICE (a DeviceSample:
+    the valid-point count rides along).  ``readers`` host threads decode the PNG / tiff files of the next samples; this thread hands
+    ``batch`` decoded samples at a time to SamplePrep.  Threads, not worker processes: a child process that has not initialised the
+    GPU must not be handed device state.  The mask is yielded on the HOST (one pinned copy per batch): its only consumers are the
+    metric lists."""
+
+    def __init__(self, dataset, readers=6, batch=16, prep=None):
+        self.dataset, self.readers, self.batch = dataset, max(1, int(readers)), max(1, int(batch))
+        self.prep = prep if prep is not None else dataset.sample_prep()
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def __iter__(self):
+        import concurrent.futures as cf
+        ds, n = self.dataset, len(self.dataset)
+        is_test = hasattr(ds, "gt_paths")
+        ahead = max(2 * self.readers, self.batch)
+        with cf.ThreadPoolExecutor(self.readers) as pool:
+            reads = {i: pool.submit(ds.decoded, i) for i in range(min(ahead, n))}
+            nxt = len(reads)
+            for lo in range(0, n, self.batch):
+                idx = list(range(lo, min(lo + self.batch, n)))
+                dec = []
+                for i in idx:
+                    dec.append(reads.pop(i).result())
+                    if nxt < n:
+                        reads[nxt] = pool.submit(ds.decoded, nxt)
+                        nxt += 1
+                out = self.prep.prepare_batch([d[0] for d in dec], [d[1] for d in dec], [d[2] for d in dec])
+                masks = None
+                if is_test:
+                    masks = self._masks_to_host([m for _, m in out])
+                for j, i in enumerate(idx):
+                    sample = out[j][0].batched()
+                    label = torch.tensor([ds.labels[i]])
+                    if is_test:
+                        yield sample, masks[j], label, [str(ds.img_paths[i][0])]
+                    else:
+                        yield sample, label
+
+    def _masks_to_host(self, masks):
+        have = [m for m in masks if m is not None]
+        host = None
+        if have:
+            host = torch.empty((len(have), *have[0].shape), dtype=torch.float32, pin_memory=True)
+            host.copy_(torch.stack(have), non_blocking=True)
+            torch.cuda.current_stream(have[0].device).synchronize()
+        out, k = [], 0
+        for m in masks:
+            if m is None:
+                out.append(torch.zeros([1, 1, DEPTH_SIZE, DEPTH_SIZE]))
+            else:
+                out.append(host[k][None].clone())
+                k += 1
+        return out
+
+
+def get_data_loader(split, class_name, rgb_size, xyz_size, gt_size, args):
+    """dataset.py:364-381.  args.dataset_path, args.img_process_method (default 'cpu_v1'); args.num_workers (default 6: the reference's
+    worker processes for the host methods, the reader THREADS of 'hip')."""
+    classes = {'train': TrainDataset, 'train_validation': TrainValidationDataset, 'test': TestDataset}
+    if split not in classes:
+        raise ValueError
+    method = getattr(args, "img_process_method", "cpu_v1")
+    dataset = classes[split](class_name=class_name, rgb_size=rgb_size, xyz_size=xyz_size, gt_size=gt_size,
+                             dataset_path=args.dataset_path, img_process_method=method)
+    workers = int(getattr(args, "num_workers", 6))
+    if method == 'hip':
+        return DeviceSampleLoader(dataset, readers=workers)
+    from torch.utils.data import DataLoader
+    return DataLoader(dataset=dataset, batch_size=1, shuffle=False, num_workers=workers, drop_last=False,
+                      prefetch_factor=6 if workers > 0 else None, pin_memory=torch.cuda.is_available())
+
+
+class MVTec3DClass:
+    """One class directory of MVTec 3D-AD (or of an Eyecandies tree preprocessed by the reference's script: the same layout) as the
+    data object of evaluate.ClassRun / evaluate_classes: ``name``, ``n_train``, ``n_test``, ``train()`` yielding ``(sample, label)`` and
+    ``test()`` yielding ``(sample, mask, label, rgb_path)`` -- the reference's two loaders (cmdiad_runner.py:36-42, 77-78), with
+    ``args.img_process_method`` choosing the host or the device path and ``args.train_with_validation`` the train split."""
+
+    def __init__(self, dataset_path, class_name, args):
+        import types
+        self.name = class_name
+        self.args = types.SimpleNamespace(**{**vars(args), "dataset_path": dataset_path})
+        a = self.args
+        self._sizes = dict(rgb_size=getattr(a, "rgb_size", 224), xyz_size=getattr(a, "xyz_size", 224), gt_size=getattr(a, "gt_size", 224))
+        self._train_split = "train_validation" if getattr(a, "train_with_validation", False) else "train"
+        self.n_train = len(self._loader(self._train_split).dataset)
+        self.n_test = len(self._loader("test").dataset)
+
+    def _loader(self, split):
+        return get_data_loader(split, class_name=self.name, args=self.args, **self._sizes)
+
+    def train(self):
+        return iter(self._loader(self._train_split))
+
+    def test(self):
+        return iter(self._loader("test"))
+
+
+def dataset_classes(args):
+    """{class name: MVTec3DClass} for evaluate_classes: the classes of args.dataset_type ('mvtec3d' default, 'eyecandies') that have
+    a directory under args.dataset_path, in the reference's order (main.py:10-16)."""
+    kind = getattr(args, "dataset_type", "mvtec3d")
+    if kind not in ("mvtec3d", "eyecandies"):
+        raise ValueError(f"dataset_type must be 'mvtec3d' or 'eyecandies', got {kind!r}")
+    names = eyecandies_classes() if kind == "eyecandies" else mvtec3d_classes()
+    found = {c: MVTec3DClass(args.dataset_path, c, args) for c in names if os.path.isdir(Path(args.dataset_path, c))}
+    if not found:
+        raise FileNotFoundError(f"no {kind} class directory under {args.dataset_path!r}")
+    return found

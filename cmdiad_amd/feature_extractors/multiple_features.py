@@ -245,13 +245,25 @@ class _MethodBase(Features):
                 host.copy_(torch.cat([t.cpu() for t in tensors]))
             return host, host.to(dev, non_blocking=True)
 
-        rgb = staged([s[self._image_slot] for s in samples])[1] if want_rgb else None
+        # samples prepared on the device (dataset.SamplePrep, img_process_method='hip'): the tensors are where the extraction reads
+        # them and each carries its number of valid points -- no staging, no copy to the host, no count on the host
+        resident = all(hasattr(s, "n_valid_dev") and all(t.is_cuda and t.dtype == torch.float32 for t in s[:3]) for s in samples)
+        if resident:
+            self.__dict__["device_sample_batches"] = self.__dict__.get("device_sample_batches", 0) + 1
+            gather = lambda tensors: torch.cat([t.to(dev) for t in tensors])   # noqa: E731  (.to: no-op on the extraction's device)
+        else:
+            gather = lambda tensors: staged(tensors)[1]                       # noqa: E731
+        rgb = gather([s[self._image_slot] for s in samples]) if want_rgb else None
         if not want_xyz:
             with torch.no_grad():
                 return self._engine.extract(rgb, want_xyz=False)
-        pcs, pcs_dev = staged([s[1] for s in samples])
-        flat = pcs.numpy().reshape(len(samples), 3, -1)   # numpy: no 150 k-element op through torch's CPU thread pool
-        counts = np.count_nonzero(np.all(flat != 0, axis=1), axis=1)
+        if resident:
+            pcs_dev = gather([s[1] for s in samples])
+            counts = np.array([s.n_valid for s in samples])
+        else:
+            pcs, pcs_dev = staged([s[1] for s in samples])
+            flat = pcs.numpy().reshape(len(samples), 3, -1)   # numpy: no 150 k-element op through torch's CPU thread pool
+            counts = np.count_nonzero(np.all(flat != 0, axis=1), axis=1)
         if counts.min() < self.args.group_size:
             raise ValueError(f"point cloud has {int(counts.min())} valid points; the {self.args.group_size}-nearest-neighbour "
                              f"grouping (models/models.py:88-113) needs at least {self.args.group_size}")

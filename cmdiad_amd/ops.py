@@ -944,3 +944,79 @@ def label_histogram(labels, bins):
         return hist
     _call("cmdiad_label_histogram", _p(labels), labels.numel(), _p(hist), int(bins), _stream())
     return hist
+
+
+# ------------------------------------------------------------------------------------ sample preparation (docs/sample_prep.md)
+def resize_bicubic_u8(src, out_h, out_w, htab, vtab, norm=None, want_u8=False, want_f32=True):
+    """src [B,H,W,3] uint8 -> (uint8 [B,out_h,out_w,3] or None, float32 [B,3,out_h,out_w] or None): Pillow's Image.resize(BICUBIC)
+    bit for bit, then ToTensor + Normalize through norm [3,256] f32.  htab / vtab = (coef [n_out,ksize] int32, bounds [n_out,2]
+    int32) of cmdiad_amd.dataset.bicubic_tables on the device; None for a side that does not change.  dataset.py:62-65."""
+    _chk(src, torch.uint8, "resize_bicubic_u8.src"); _chk(norm, torch.float32, "resize_bicubic_u8.norm")
+    if src.dim() != 4 or src.shape[3] != 3:
+        raise ValueError(f"resize_bicubic_u8: src must be [B,H,W,3], got {tuple(src.shape)}")
+    B, H, W, _ = src.shape
+    tabs = []
+    for name, tab, n_in, n_out in (("htab", htab, W, out_w), ("vtab", vtab, H, out_h)):
+        if n_in == n_out:
+            tabs += [None, None, 0]
+            continue
+        if tab is None:
+            raise ValueError(f"resize_bicubic_u8: {name} is needed for {n_in} -> {n_out}")
+        coef, bounds = tab
+        _chk(coef, torch.int32, f"resize_bicubic_u8.{name}.coef"); _chk(bounds, torch.int32, f"resize_bicubic_u8.{name}.bounds")
+        if coef.dim() != 2 or coef.shape[0] != n_out or tuple(bounds.shape) != (n_out, 2):
+            raise ValueError(f"resize_bicubic_u8: {name} is {tuple(coef.shape)} / {tuple(bounds.shape)}, {n_out} rows needed")
+        tabs += [coef, bounds, coef.shape[1]]
+    if want_f32 and norm is None:
+        raise ValueError("resize_bicubic_u8: the float output needs the normalise table")
+    if norm is not None and tuple(norm.shape) != (3, 256):
+        raise ValueError(f"resize_bicubic_u8: norm must be [3,256], got {tuple(norm.shape)}")
+    dev = src.device
+    tmp = torch.empty((B, H, out_w, 3), dtype=torch.uint8, device=dev) if W != out_w and H != out_h else None
+    out_u8 = torch.empty((B, out_h, out_w, 3), dtype=torch.uint8, device=dev) if want_u8 else None
+    out_f32 = torch.empty((B, 3, out_h, out_w), dtype=torch.float32, device=dev) if want_f32 else None
+    _call("cmdiad_resize_bicubic_u8", _p(src), B, H, W, int(out_h), int(out_w), _p(tabs[0]), _p(tabs[1]), tabs[2], _p(tabs[3]),
+          _p(tabs[4]), tabs[5], _p(tmp), _p(norm), _p(out_u8), _p(out_f32), _stream())
+    return out_u8, out_f32
+
+
+def _index_pair(tab, H, W, name):
+    rows, cols = tab
+    _chk(rows, torch.int32, name + ".rows"); _chk(cols, torch.int32, name + ".cols")
+    if rows.dim() != 1 or rows.shape != cols.shape:
+        raise ValueError(f"{name}: rows / cols must be two [S] tables, got {tuple(rows.shape)} / {tuple(cols.shape)}")
+    return rows, cols, rows.shape[0]
+
+
+def organized_pc_prep(pc, xyz_tab, depth_tab=None):
+    """pc [B,H,W,3] f32 -> (cloud [B,3,xs,xs], depth [B,3,ds,ds] or None, count [B] int32): the nearest-resized cloud, its z channel
+    three times, and the number of resized pixels with three non-zero coordinates.  xyz_tab / depth_tab = (rows [S], cols [S]) int32
+    on the device (cmdiad_amd.dataset.torch_nearest_index).  dataset.py:106-111."""
+    _chk(pc, torch.float32, "organized_pc_prep.pc")
+    if pc.dim() != 4 or pc.shape[3] != 3:
+        raise ValueError(f"organized_pc_prep: pc must be [B,H,W,3], got {tuple(pc.shape)}")
+    B, H, W, _ = pc.shape
+    rows, cols, xs = _index_pair(xyz_tab, H, W, "organized_pc_prep.xyz_tab")
+    drows = dcols = depth = None
+    ds = 0
+    if depth_tab is not None:
+        drows, dcols, ds = _index_pair(depth_tab, H, W, "organized_pc_prep.depth_tab")
+        depth = torch.empty((B, 3, ds, ds), dtype=torch.float32, device=pc.device)
+    cloud = torch.empty((B, 3, xs, xs), dtype=torch.float32, device=pc.device)
+    count = torch.empty((B,), dtype=torch.int32, device=pc.device)
+    _call("cmdiad_organized_pc_prep", _p(pc), B, H, W, _p(rows), _p(cols), xs, _p(drows), _p(dcols), ds, _p(cloud), _p(depth),
+          _p(count), _stream())
+    return cloud, depth, count
+
+
+def gt_mask_prep(gt, tab):
+    """gt [B,H,W] uint8 -> [B,1,gs,gs] f32 in {0, 1}: Pillow's NEAREST resize through tab = (rows [gs], cols [gs]) int32 on the device
+    (cmdiad_amd.dataset.pillow_nearest_index), / 255, > 0.5.  dataset.py:168-171, 239-241."""
+    _chk(gt, torch.uint8, "gt_mask_prep.gt")
+    if gt.dim() != 3:
+        raise ValueError(f"gt_mask_prep: gt must be [B,H,W], got {tuple(gt.shape)}")
+    B, H, W = gt.shape
+    rows, cols, gs = _index_pair(tab, H, W, "gt_mask_prep.tab")
+    out = torch.empty((B, 1, gs, gs), dtype=torch.float32, device=gt.device)
+    _call("cmdiad_gt_mask_prep", _p(gt), B, H, W, _p(rows), _p(cols), gs, _p(out), _stream())
+    return out

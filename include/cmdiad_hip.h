@@ -667,6 +667,32 @@ int cmdiad_dbscan(const float* points, int N, double eps, int min_points, int32_
 /* hist[b] = number of labels equal to b - 1, b in [0, bins): bin 0 counts the noise label -1.  hist [bins] int32 (device). */
 int cmdiad_label_histogram(const int32_t* labels, int N, int32_t* hist, int bins, cmdiad_stream_t stream);
 
+/* ---- sample preparation (dataset.py:62-65, 103-113, 168-171, 225-244: PIL + torchvision + numpy per sample on DataLoader workers;
+ * contract: docs/sample_prep.md; additions are backwards compatible, the ABI stays 6).  All index and coefficient tables are device
+ * arrays the caller computes on the host (cmdiad_amd/dataset.py); the kernels clamp every table entry to the source image. ---- */
+
+/* Image.resize((out_w, out_h), BICUBIC) of B equal-sized images src [B,H,W,3] u8, bit for bit Pillow's 8-bit arithmetic: horizontal
+ * pass into the 8-bit intermediate tmp [B,H,out_w,3], then the vertical pass; a pass whose side does not change is skipped (its
+ * tables may be NULL; tmp may be NULL unless both sides change).  hcoef [out_w,hksize] / vcoef [out_h,vksize] int32: coefficients
+ * with 22 fractional bits; hbounds [out_w,2] / vbounds [out_h,2] int32: (first source index, number of taps <= ksize).
+ * out_u8 [B,out_h,out_w,3] (NULL allowed) and out_f32 [B,3,out_h,out_w] = norm[c*256 + value] (NULL allowed; norm [3,256] f32 is
+ * ToTensor + Normalize as a table); at least one of the two. */
+int cmdiad_resize_bicubic_u8(const uint8_t* src, int B, int H, int W, int out_h, int out_w, const int32_t* hcoef,
+                             const int32_t* hbounds, int hksize, const int32_t* vcoef, const int32_t* vbounds, int vksize,
+                             uint8_t* tmp, const float* norm, uint8_t* out_u8, float* out_f32, cmdiad_stream_t stream);
+
+/* Organised cloud pc [B,H,W,3] f32 -> cloud_out [B,3,xyz_size,xyz_size] = pc[xyz_rows[y], xyz_cols[x]] (resize_organized_pc,
+ * utils/mvtec3d_util.py:14-22), depth_out [B,3,depth_size,depth_size] = the z channel at (depth_rows[y], depth_cols[x]) three times
+ * (dataset.py:108-109; NULL: not wanted), count_out [B] int32 = resized pixels whose three coordinates are all non-zero. */
+int cmdiad_organized_pc_prep(const float* pc, int B, int H, int W, const int32_t* xyz_rows, const int32_t* xyz_cols, int xyz_size,
+                             const int32_t* depth_rows, const int32_t* depth_cols, int depth_size, float* cloud_out,
+                             float* depth_out, int32_t* count_out, cmdiad_stream_t stream);
+
+/* Ground-truth mask gt [B,H,W] u8 -> out [B,1,gt_size,gt_size] f32 = 1.0 where gt[rows[y], cols[x]] / 255 > 0.5, else 0.0
+ * (dataset.py:168-171, 239-241; rows / cols: Pillow's NEAREST rule). */
+int cmdiad_gt_mask_prep(const uint8_t* gt, int B, int H, int W, const int32_t* rows, const int32_t* cols, int gt_size, float* out,
+                        cmdiad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
