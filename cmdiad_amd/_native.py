@@ -130,6 +130,10 @@ SIGNATURES = {
     "cmdiad_resize_bicubic_u8": [P, I, I, I, I, I, P, P, I, P, P, I, P, P, P, P, P],
     "cmdiad_organized_pc_prep": [P, I, I, I, P, P, I, P, P, I, P, P, P, P],
     "cmdiad_gt_mask_prep": [P, I, I, I, P, P, I, P, P],
+    "cmdiad_organized_pc_prep_f64": [P, I, I, I, P, P, I, P, P, I, P, P, P, P],
+    "cmdiad_eyecandies_cloud": [P, P, I, I, I, P, P, P, P],
+    "cmdiad_eyecandies_unproject": [P, P, I, I, I, P, P, P],
+    "cmdiad_eyecandies_background": [P, I, P, P, P],
 }
 SIZE_QUERIES = {
     "cmdiad_gemm_streamk_workspace_bytes": [],

@@ -11,7 +11,7 @@
 //   intermediate rows (800 -> 224: 72 rows of 672 bytes for r = 16, 47 KiB, so 3 workgroups per CU) and recomputes the 2 * support
 //   halo rows of every tile (+25 % of the horizontal pass), to save 0.5 MB of write + read per sample that stay in the 4 MiB L2 of
 //   the XCD anyway -- against 1.9 MB of image and 7.7 MB of point cloud that have to come from HBM whatever the kernel does.
-// cmdiad_organized_pc_prep: nearest-resized cloud [B,3,xs,xs] (rows / columns from host tables: torch's mode='nearest' rule), the
+// cmdiad_organized_pc_prep[_f64]: nearest-resized cloud [B,3,xs,xs] (rows / columns from host tables: torch's mode='nearest' rule), the
 //   z channel three times [B,3,ds,ds], and the number of resized pixels with three non-zero coordinates (wave ballot + one vector
 //   atomic per wave).
 // cmdiad_gt_mask_prep: Pillow NEAREST through host tables, then (v / 255 > 0.5) == (v >= 128) -> 1.0 / 0.0.
@@ -83,7 +83,9 @@ __global__ __launch_bounds__(256) void normalize_u8_kernel(const uint8_t* __rest
 
 __device__ __forceinline__ int clamp_index(int v, int n) { return min(max(v, 0), n - 1); }
 
-__global__ __launch_bounds__(256) void cloud_resize_kernel(const float* __restrict__ pc, int H, int W, const int32_t* __restrict__ rows,
+// T = float or double (cmdiad_organized_pc_prep_f64): a double is converted at the gather, round to nearest, as torch's .float()
+template <class T>
+__global__ __launch_bounds__(256) void cloud_resize_kernel(const T* __restrict__ pc, int H, int W, const int32_t* __restrict__ rows,
                                                            const int32_t* __restrict__ cols, int S, float* __restrict__ out,
                                                            int32_t* __restrict__ count)
 {
@@ -91,8 +93,8 @@ __global__ __launch_bounds__(256) void cloud_resize_kernel(const float* __restri
     bool valid = false;
     if (i < S * S) {
         const int y = i / S, x = i - y * S;
-        const float* p = pc + (((size_t)b * H + clamp_index(rows[y], H)) * W + clamp_index(cols[x], W)) * 3;
-        const float px = p[0], py = p[1], pz = p[2];
+        const T* p = pc + (((size_t)b * H + clamp_index(rows[y], H)) * W + clamp_index(cols[x], W)) * 3;
+        const float px = (float)p[0], py = (float)p[1], pz = (float)p[2];
         float* o = out + (size_t)b * 3 * S * S + i;
         o[0] = px, o[(size_t)S * S] = py, o[2 * (size_t)S * S] = pz;
         valid = px != 0.0f && py != 0.0f && pz != 0.0f;   // numpy's all(p != 0): a NaN coordinate counts, -0.0 does not
@@ -101,13 +103,14 @@ __global__ __launch_bounds__(256) void cloud_resize_kernel(const float* __restri
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(&count[b], __popcll(m));
 }
 
-__global__ __launch_bounds__(256) void depth3_resize_kernel(const float* __restrict__ pc, int H, int W, const int32_t* __restrict__ rows,
+template <class T>
+__global__ __launch_bounds__(256) void depth3_resize_kernel(const T* __restrict__ pc, int H, int W, const int32_t* __restrict__ rows,
                                                             const int32_t* __restrict__ cols, int S, float* __restrict__ out)
 {
     const int i = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
     if (i >= S * S) return;
     const int y = i / S, x = i - y * S;
-    const float z = pc[(((size_t)b * H + clamp_index(rows[y], H)) * W + clamp_index(cols[x], W)) * 3 + 2];
+    const float z = (float)pc[(((size_t)b * H + clamp_index(rows[y], H)) * W + clamp_index(cols[x], W)) * 3 + 2];
     float* o = out + (size_t)b * 3 * S * S + i;
     o[0] = z, o[(size_t)S * S] = z, o[2 * (size_t)S * S] = z;
 }
@@ -160,29 +163,50 @@ extern "C" int cmdiad_resize_bicubic_u8(const uint8_t* src, int B, int H, int W,
     return CMDIAD_OK;
 }
 
-extern "C" int cmdiad_organized_pc_prep(const float* pc, int B, int H, int W, const int32_t* xyz_rows, const int32_t* xyz_cols,
-                                        int xyz_size, const int32_t* depth_rows, const int32_t* depth_cols, int depth_size,
-                                        float* cloud_out, float* depth_out, int32_t* count_out, cmdiad_stream_t stream)
+namespace {
+
+template <class T>
+int organized_pc_prep(const char* who, const T* pc, int B, int H, int W, const int32_t* xyz_rows, const int32_t* xyz_cols, int xyz_size,
+                      const int32_t* depth_rows, const int32_t* depth_cols, int depth_size, float* cloud_out, float* depth_out,
+                      int32_t* count_out, cmdiad_stream_t stream)
 {
     CMDIAD_REQUIRE(pc && xyz_rows && xyz_cols && cloud_out && count_out && (!depth_out || (depth_rows && depth_cols)), CMDIAD_ERR_ARG,
-                   "cmdiad_organized_pc_prep: null pointer");
+                   "%s: null pointer", who);
     CMDIAD_REQUIRE(B >= 1 && B <= 65535 && side_ok(H) && side_ok(W) && side_ok(xyz_size) && (!depth_out || side_ok(depth_size)),
-                   CMDIAD_ERR_ARG, "cmdiad_organized_pc_prep: bad sizes B=%d (1..65535) H=%d W=%d xyz_size=%d depth_size=%d (1..%d)", B, H,
-                   W, xyz_size, depth_size, kMaxSide);
+                   CMDIAD_ERR_ARG, "%s: bad sizes B=%d (1..65535) H=%d W=%d xyz_size=%d depth_size=%d (1..%d)", who, B, H, W, xyz_size,
+                   depth_size, kMaxSide);
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(count_out, 0, (size_t)B * sizeof(int32_t), s) != hipSuccess) {
-        cmdiad_set_error("cmdiad_organized_pc_prep: hipMemsetAsync failed");
+        cmdiad_set_error("%s: hipMemsetAsync failed", who);
         return CMDIAD_ERR_LAUNCH;
     }
-    hipLaunchKernelGGL(cloud_resize_kernel, pixel_grid(xyz_size * xyz_size, B), dim3(256), 0, s, pc, H, W, xyz_rows, xyz_cols, xyz_size,
-                       cloud_out, count_out);
+    hipLaunchKernelGGL(cloud_resize_kernel<T>, pixel_grid(xyz_size * xyz_size, B), dim3(256), 0, s, pc, H, W, xyz_rows, xyz_cols,
+                       xyz_size, cloud_out, count_out);
     CMDIAD_CHECK_LAUNCH();
     if (depth_out) {
-        hipLaunchKernelGGL(depth3_resize_kernel, pixel_grid(depth_size * depth_size, B), dim3(256), 0, s, pc, H, W, depth_rows,
+        hipLaunchKernelGGL(depth3_resize_kernel<T>, pixel_grid(depth_size * depth_size, B), dim3(256), 0, s, pc, H, W, depth_rows,
                            depth_cols, depth_size, depth_out);
         CMDIAD_CHECK_LAUNCH();
     }
     return CMDIAD_OK;
+}
+
+}  // namespace
+
+extern "C" int cmdiad_organized_pc_prep(const float* pc, int B, int H, int W, const int32_t* xyz_rows, const int32_t* xyz_cols,
+                                        int xyz_size, const int32_t* depth_rows, const int32_t* depth_cols, int depth_size,
+                                        float* cloud_out, float* depth_out, int32_t* count_out, cmdiad_stream_t stream)
+{
+    return organized_pc_prep("cmdiad_organized_pc_prep", pc, B, H, W, xyz_rows, xyz_cols, xyz_size, depth_rows, depth_cols, depth_size,
+                             cloud_out, depth_out, count_out, stream);
+}
+
+extern "C" int cmdiad_organized_pc_prep_f64(const double* pc, int B, int H, int W, const int32_t* xyz_rows, const int32_t* xyz_cols,
+                                            int xyz_size, const int32_t* depth_rows, const int32_t* depth_cols, int depth_size,
+                                            float* cloud_out, float* depth_out, int32_t* count_out, cmdiad_stream_t stream)
+{
+    return organized_pc_prep("cmdiad_organized_pc_prep_f64", pc, B, H, W, xyz_rows, xyz_cols, xyz_size, depth_rows, depth_cols,
+                             depth_size, cloud_out, depth_out, count_out, stream);
 }
 
 extern "C" int cmdiad_gt_mask_prep(const uint8_t* gt, int B, int H, int W, const int32_t* rows, const int32_t* cols, int gt_size,

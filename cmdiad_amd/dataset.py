@@ -25,7 +25,8 @@ multiple_features.py:815-825 / 942-945; this package's drop-in writes the same):
 Sample path (second half of this file; docs/sample_prep.md): the reference's ``TrainDataset`` / ``TrainValidationDataset`` /
 ``TestDataset`` / ``get_data_loader`` over an MVTec 3D-AD directory with a third ``img_process_method``, ``'hip'`` -- files decoded on
 reader threads, every transform after that in csrc/sample_prep.hip (``SamplePrep``) -- and ``MVTec3DClass``, the real-data class
-source of ``evaluate.evaluate_classes``.
+source of ``evaluate.evaluate_classes``; ``EyecandiesRawClass`` is the same over the raw Eyecandies download (csrc/eyecandies.hip,
+docs/eyecandies.md).
 """
 import math
 import os
@@ -495,9 +496,10 @@ class _Count:
 class SamplePrep:
     """Decoded arrays -> the tensors of the reference's ``__getitem__`` on the device (csrc/sample_prep.hip; docs/sample_prep.md).
 
-    ``prepare(rgb_u8 [H,W,3], pc_f32 [H,W,3], gt_u8 [H,W] | None)`` -> ``(DeviceSample(img [3,S,S], cloud [3,xs,xs], depth [3,224,224]),
+    ``prepare(rgb_u8 [H,W,3], pc [H,W,3] float32 or float64, gt_u8 [H,W] | None)`` -> ``(DeviceSample(img [3,S,S], cloud [3,xs,xs], depth [3,224,224]),
     gt [1,g,g] | None)``; ``prepare_batch`` takes lists and returns a list of such pairs.  Samples of equal shapes share their launches;
-    every sample's bytes are the ones a call of its own gives (the arithmetic is per pixel and integer).  Inputs go up through
+    every sample's bytes are the ones a call of its own gives (the arithmetic is per pixel and integer).  Clouds are grouped by dtype
+    as well: a float64 cloud (an Eyecandies tiff of the reference's script) is converted to float32 at the gather, as ``.float()``.  Inputs go up through
     pinned memory on the shared copy stream; the kernels run on the current stream.  Tables are computed once per (n_in, n_out)
     and kept on the device."""
 
@@ -557,42 +559,70 @@ class SamplePrep:
             if np.ndim(r) != 3 or np.shape(r)[2] != 3 or np.ndim(p) != 3 or np.shape(p)[2] != 3 or (g is not None and np.ndim(g) != 2):
                 raise ValueError(f"SamplePrep: rgb [H,W,3], cloud [H,W,3], gt [H,W] expected, got {np.shape(r)}, {np.shape(p)}, "
                                  f"{None if g is None else np.shape(g)}")
-        imgs, clouds, depths, counts, masks = [None] * n, [None] * n, [None] * n, [None] * n, [None] * n
+        with torch.cuda.device(self.device):
+            imgs = self.prepare_images(rgbs)
+            clouds, depths, counts = [None] * n, [None] * n, [None] * n
+            for (_, dtype), idx in _group_by_shape(pcs, range(n), with_dtype=True).items():
+                if dtype not in ("float32", "float64"):
+                    raise TypeError(f"SamplePrep: the point cloud must be float32 (MVTec 3D-AD) or float64 (Eyecandies) arrays, got {dtype}")
+                src = self._upload([pcs[i] for i in idx], getattr(torch, dtype), "the point cloud")
+                out = self.prepare_device_clouds(src)
+                for j, i in enumerate(idx):
+                    clouds[i], depths[i], counts[i] = out[j]
+            masks = self.prepare_masks(gts)
+        return [(DeviceSample((imgs[i], clouds[i], depths[i]), counts[i]), masks[i]) for i in range(n)]
+
+    def prepare_images(self, rgbs):
+        """list of uint8 [H,W,3] arrays -> list of float32 [3,S,S] device tensors (resize + ToTensor + Normalize)."""
+        from . import ops
+        imgs = [None] * len(rgbs)
         with torch.cuda.device(self.device):
             norm = self._table("norm", 256, 3)
             S = self.rgb_size
-            for (H, W), idx in _group_by_shape(rgbs, range(n)).items():
+            for (H, W), idx in _group_by_shape(rgbs, range(len(rgbs))).items():
                 src = self._upload([rgbs[i] for i in idx], torch.uint8, "rgb")
                 htab = self._table("bicubic", W, S) if W != S else None
                 vtab = self._table("bicubic", H, S) if H != S else None
                 _, out = ops.resize_bicubic_u8(src, S, S, htab, vtab, norm)
                 for j, i in enumerate(idx):
                     imgs[i] = out[j]
-            for (H, W), idx in _group_by_shape(pcs, range(n)).items():
-                src = self._upload([pcs[i] for i in idx], torch.float32, "the point cloud")
-                cloud, depth, count = ops.organized_pc_prep(
-                    src, (self._table("torch", H, self.xyz_size), self._table("torch", W, self.xyz_size)),
-                    (self._table("torch", H, DEPTH_SIZE), self._table("torch", W, DEPTH_SIZE)))
-                host = torch.empty(len(idx), dtype=torch.int32, pin_memory=True)
-                host.copy_(count, non_blocking=True)
-                event = torch.cuda.Event()
-                event.record()
-                for j, i in enumerate(idx):
-                    clouds[i], depths[i], counts[i] = cloud[j], depth[j], _Count(count, host, event, j)
-            with_gt = [i for i in range(n) if gts[i] is not None]
+        return imgs
+
+    def prepare_device_clouds(self, src):
+        """src [B,H,W,3] float32 or float64 ON THE DEVICE -> list of (cloud [3,xs,xs], depth [3,224,224], _Count) per sample, on the
+        current stream; the counts' copy to pinned host memory is queued behind the kernels."""
+        from . import ops
+        B, H, W, _ = src.shape
+        with torch.cuda.device(self.device):
+            cloud, depth, count = ops.organized_pc_prep(
+                src, (self._table("torch", H, self.xyz_size), self._table("torch", W, self.xyz_size)),
+                (self._table("torch", H, DEPTH_SIZE), self._table("torch", W, DEPTH_SIZE)))
+            host = torch.empty(B, dtype=torch.int32, pin_memory=True)
+            host.copy_(count, non_blocking=True)
+            event = torch.cuda.Event()
+            event.record()
+        return [(cloud[j], depth[j], _Count(count, host, event, j)) for j in range(B)]
+
+    def prepare_masks(self, gts):
+        """list of uint8 [H,W] arrays or None -> list of float32 [1,g,g] device tensors or None."""
+        from . import ops
+        masks = [None] * len(gts)
+        with torch.cuda.device(self.device):
+            with_gt = [i for i in range(len(gts)) if gts[i] is not None]
             for (H, W), idx in _group_by_shape(gts, with_gt).items():
                 src = self._upload([gts[i] for i in idx], torch.uint8, "gt")
                 out = ops.gt_mask_prep(src, (self._table("pillow", H, self.gt_size), self._table("pillow", W, self.gt_size)))
                 for j, i in enumerate(idx):
                     masks[i] = out[j]
-        return [(DeviceSample((imgs[i], clouds[i], depths[i]), counts[i]), masks[i]) for i in range(n)]
+        return masks
 
 
-def _group_by_shape(arrays, indices):
+def _group_by_shape(arrays, indices, with_dtype=False):
     import numpy as np
     groups = {}
     for i in indices:
-        groups.setdefault(tuple(np.shape(arrays[i])[:2]), []).append(i)
+        key = tuple(np.shape(arrays[i])[:2])
+        groups.setdefault((key, str(np.asarray(arrays[i]).dtype)) if with_dtype else key, []).append(i)
     return groups
 
 
@@ -787,20 +817,25 @@ class DeviceSampleLoader:
                         yield sample, label
 
     def _masks_to_host(self, masks):
-        have = [m for m in masks if m is not None]
-        host = None
-        if have:
-            host = torch.empty((len(have), *have[0].shape), dtype=torch.float32, pin_memory=True)
-            host.copy_(torch.stack(have), non_blocking=True)
-            torch.cuda.current_stream(have[0].device).synchronize()
-        out, k = [], 0
-        for m in masks:
-            if m is None:
-                out.append(torch.zeros([1, 1, DEPTH_SIZE, DEPTH_SIZE]))
-            else:
-                out.append(host[k][None].clone())
-                k += 1
-        return out
+        return _masks_to_host(masks)
+
+
+def _masks_to_host(masks):
+    """device masks [1,g,g] (None: a good sample) -> host masks [1,1,g,g], through one pinned copy."""
+    have = [m for m in masks if m is not None]
+    host = None
+    if have:
+        host = torch.empty((len(have), *have[0].shape), dtype=torch.float32, pin_memory=True)
+        host.copy_(torch.stack(have), non_blocking=True)
+        torch.cuda.current_stream(have[0].device).synchronize()
+    out, k = [], 0
+    for m in masks:
+        if m is None:
+            out.append(torch.zeros([1, 1, DEPTH_SIZE, DEPTH_SIZE]))
+        else:
+            out.append(host[k][None].clone())
+            k += 1
+    return out
 
 
 def get_data_loader(split, class_name, rgb_size, xyz_size, gt_size, args):
@@ -846,14 +881,121 @@ class MVTec3DClass:
         return iter(self._loader("test"))
 
 
+class EyecandiesRawClass:
+    """One class directory of the RAW Eyecandies download (``<class>/train/data/{i:03d}_*``, ``<class>/test_public/data/{i:02d}_*``) as the
+    data object of evaluate.ClassRun / evaluate_classes, with MVTec3DClass's protocol.  It yields what MVTec3DClass with
+    img_process_method='hip' yields over the tree the reference's utils/preprocessing_eyecandies.py would have written from this
+    directory, without that tree: reader threads decode the 16-bit depth PNG, the yaml, the pose and the images; every batch is one
+    ``eyecandies_cloud`` -> ``organized_pc_prep`` chain on the current stream, and the float64 cloud never leaves the device
+    (docs/eyecandies.md).  Test order: the `bad` samples in index order, then the `good` ones (TestDataset's sorted directories);
+    label 1 / 0; a good sample's mask is zeros; ``rgb_path`` is the raw ``*_image_4.png``.  There is no host path."""
+
+    def __init__(self, dataset_path, class_name, args):
+        from .utils import preprocessing_eyecandies as pe
+        method = getattr(args, "img_process_method", "cpu_v1")
+        _check_method(method)
+        if method != 'hip':
+            raise ValueError(f"EyecandiesRawClass: the raw Eyecandies download is prepared on the device only, there is no host path: "
+                             f"img_process_method must be 'hip', got {method!r} (or run utils/preprocessing_eyecandies.py first and "
+                             f"point dataset_path at its tree)")
+        self.name, self.args = class_name, args
+        self.rgb_size, self.xyz_size, self.gt_size = (getattr(args, k, 224) for k in ("rgb_size", "xyz_size", "gt_size"))
+        self.readers, self.batch = max(1, int(getattr(args, "num_workers", 6))), 16
+        self.focal_length = pe.FOCAL_LENGTH
+        self._train_dir = str(Path(dataset_path, class_name, "train", "data"))
+        self._test_dir = str(Path(dataset_path, class_name, "test_public", "data"))
+        self.n_train = pe.raw_samples(self._train_dir, 3)
+        self.n_test = pe.raw_samples(self._test_dir, 2)
+        self._train_files = [pe.sample_files(self._train_dir, i, 3) for i in range(self.n_train)]
+        test_files = [pe.sample_files(self._test_dir, i, 2) for i in range(self.n_test)]
+        import numpy as np
+        is_bad = [bool(np.any(pe.read_mask(f["mask"]))) for f in test_files]
+        order = [i for i in range(self.n_test) if is_bad[i]] + [i for i in range(self.n_test) if not is_bad[i]]
+        self.test_indices = order                                  # raw index of every test item
+        self.test_labels = [1 if is_bad[i] else 0 for i in order]
+        self._test_files = [test_files[i] for i in order]
+        self._prep = None
+
+    def sample_prep(self):
+        if self._prep is None:
+            self._prep = SamplePrep(self.rgb_size, self.xyz_size, self.gt_size)
+        return self._prep
+
+    def _decode(self, files, label):
+        import numpy as np
+        from .utils import preprocessing_eyecandies as pe
+        gt = None
+        if label:
+            from PIL import Image
+            gt = np.array(Image.open(files["mask"]).convert('RGB').convert('L'), dtype=np.uint8)
+        return np.array(_read_rgb(files["rgb"]), dtype=np.uint8), pe.read_scan(files["depth"], files["info"], files["pose"]), gt
+
+    def _prepare(self, dec):
+        """decoded samples -> [(DeviceSample, mask or None)]: per shape one upload of the codes and one kernel chain."""
+        import numpy as np
+        from .utils import preprocessing_eyecandies as pe
+        prep, n = self.sample_prep(), len(dec)
+        imgs = prep.prepare_images([d[0] for d in dec])
+        masks = prep.prepare_masks([d[2] for d in dec])
+        clouds = [None] * n
+        groups = {}
+        for i, d in enumerate(dec):
+            groups.setdefault(tuple(np.shape(d[1][0])), []).append(i)
+        with torch.cuda.device(prep.device):
+            for idx in groups.values():
+                scans = [dec[i][1] for i in idx]
+                cloud, _ = pe.cloud_on_device([s[0] for s in scans], [s[1] for s in scans], [s[2] for s in scans],
+                                              [s[3] for s in scans], self.focal_length, prep.device, want_removed=False)
+                for i, out in zip(idx, prep.prepare_device_clouds(cloud)):
+                    clouds[i] = out
+        return [(DeviceSample((imgs[i], clouds[i][0], clouds[i][1]), clouds[i][2]), masks[i]) for i in range(n)]
+
+    def _iterate(self, files, labels, is_test):
+        import concurrent.futures as cf
+        n = len(files)
+        ahead = max(2 * self.readers, self.batch)
+        with cf.ThreadPoolExecutor(self.readers) as pool:
+            reads = {i: pool.submit(self._decode, files[i], labels[i]) for i in range(min(ahead, n))}
+            nxt = len(reads)
+            for lo in range(0, n, self.batch):
+                idx = list(range(lo, min(lo + self.batch, n)))
+                dec = []
+                for i in idx:
+                    dec.append(reads.pop(i).result())
+                    if nxt < n:
+                        reads[nxt] = pool.submit(self._decode, files[nxt], labels[nxt])
+                        nxt += 1
+                out = self._prepare(dec)
+                masks = _masks_to_host([m for _, m in out]) if is_test else None
+                for j, i in enumerate(idx):
+                    sample = out[j][0].batched()
+                    label = torch.tensor([labels[i]])
+                    if is_test:
+                        yield sample, masks[j], label, [files[i]["rgb"]]
+                    else:
+                        yield sample, label
+
+    def train(self):
+        return self._iterate(self._train_files, [0] * self.n_train, False)
+
+    def test(self):
+        return self._iterate(self._test_files, self.test_labels, True)
+
+
 def dataset_classes(args):
-    """{class name: MVTec3DClass} for evaluate_classes: the classes of args.dataset_type ('mvtec3d' default, 'eyecandies') that have
-    a directory under args.dataset_path, in the reference's order (main.py:10-16)."""
+    """{class name: data object} for evaluate_classes: the classes of args.dataset_type ('mvtec3d' default, 'eyecandies') that have a
+    directory under args.dataset_path, in the reference's order (main.py:10-16).  An Eyecandies class directory with ``train/data`` is
+    the raw download (EyecandiesRawClass); any other is a tree in MVTec 3D-AD's layout (MVTec3DClass)."""
     kind = getattr(args, "dataset_type", "mvtec3d")
     if kind not in ("mvtec3d", "eyecandies"):
         raise ValueError(f"dataset_type must be 'mvtec3d' or 'eyecandies', got {kind!r}")
     names = eyecandies_classes() if kind == "eyecandies" else mvtec3d_classes()
-    found = {c: MVTec3DClass(args.dataset_path, c, args) for c in names if os.path.isdir(Path(args.dataset_path, c))}
+
+    def source(c):
+        raw = kind == "eyecandies" and os.path.isdir(Path(args.dataset_path, c, "train", "data"))
+        return (EyecandiesRawClass if raw else MVTec3DClass)(args.dataset_path, c, args)
+
+    found = {c: source(c) for c in names if os.path.isdir(Path(args.dataset_path, c))}
     if not found:
         raise FileNotFoundError(f"no {kind} class directory under {args.dataset_path!r}")
     return found

@@ -989,10 +989,13 @@ def _index_pair(tab, H, W, name):
 
 
 def organized_pc_prep(pc, xyz_tab, depth_tab=None):
-    """pc [B,H,W,3] f32 -> (cloud [B,3,xs,xs], depth [B,3,ds,ds] or None, count [B] int32): the nearest-resized cloud, its z channel
-    three times, and the number of resized pixels with three non-zero coordinates.  xyz_tab / depth_tab = (rows [S], cols [S]) int32
+    """pc [B,H,W,3] f32 or f64 -> (cloud [B,3,xs,xs], depth [B,3,ds,ds] or None, count [B] int32), all float32: the nearest-resized
+    cloud, its z channel three times, and the number of resized pixels with three non-zero coordinates.  A float64 cloud (Eyecandies)
+    is converted at the gather, round to nearest, as the reference's .float().  xyz_tab / depth_tab = (rows [S], cols [S]) int32
     on the device (cmdiad_amd.dataset.torch_nearest_index).  dataset.py:106-111."""
-    _chk(pc, torch.float32, "organized_pc_prep.pc")
+    if pc.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"organized_pc_prep.pc: expected torch.float32 or torch.float64, got {pc.dtype}")
+    _chk(pc, pc.dtype, "organized_pc_prep.pc")
     if pc.dim() != 4 or pc.shape[3] != 3:
         raise ValueError(f"organized_pc_prep: pc must be [B,H,W,3], got {tuple(pc.shape)}")
     B, H, W, _ = pc.shape
@@ -1004,7 +1007,7 @@ def organized_pc_prep(pc, xyz_tab, depth_tab=None):
         depth = torch.empty((B, 3, ds, ds), dtype=torch.float32, device=pc.device)
     cloud = torch.empty((B, 3, xs, xs), dtype=torch.float32, device=pc.device)
     count = torch.empty((B,), dtype=torch.int32, device=pc.device)
-    _call("cmdiad_organized_pc_prep", _p(pc), B, H, W, _p(rows), _p(cols), xs, _p(drows), _p(dcols), ds, _p(cloud), _p(depth),
+    _call("cmdiad_organized_pc_prep_f64" if pc.dtype == torch.float64 else "cmdiad_organized_pc_prep", _p(pc), B, H, W, _p(rows), _p(cols), xs, _p(drows), _p(dcols), ds, _p(cloud), _p(depth),
           _p(count), _stream())
     return cloud, depth, count
 
@@ -1020,3 +1023,66 @@ def gt_mask_prep(gt, tab):
     out = torch.empty((B, 1, gs, gs), dtype=torch.float32, device=gt.device)
     _call("cmdiad_gt_mask_prep", _p(gt), B, H, W, _p(rows), _p(cols), gs, _p(out), _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------ Eyecandies (docs/eyecandies.md)
+EYECANDIES_PARAM_BYTES = 136      # cmdiad_eyecandies_params: float32 range, float32 mind, float64 inv(P)[16]
+
+
+def eyecandies_params(mind, maxd, inv_p):
+    """One scan's parameter block on the HOST: uint8 [136] = float32(maxd - mind) (subtracted in double first), float32(mind), and
+    inv_p [4,4] float64 (numpy.linalg.inv(K4 @ pose)), as cmdiad_eyecandies_params lays them out."""
+    import numpy as np
+    inv_p = np.asarray(inv_p, dtype=np.float64)
+    if inv_p.shape != (4, 4):
+        raise ValueError(f"eyecandies_params: inv_p must be [4,4], got {inv_p.shape}")
+    blk = np.empty(EYECANDIES_PARAM_BYTES, dtype=np.uint8)
+    blk[0:8].view(np.float32)[:] = (np.float32(float(maxd) - float(mind)), np.float32(float(mind)))
+    blk[8:].view(np.float64)[:] = inv_p.reshape(16)
+    return torch.from_numpy(blk)
+
+
+def _chk_eyecandies(depth_u16, params, name):
+    _chk(depth_u16, torch.uint16, name + ".depth_u16"); _chk(params, torch.uint8, name + ".params")
+    if depth_u16.dim() != 3:
+        raise ValueError(f"{name}: depth_u16 must be [B,H,W], got {tuple(depth_u16.shape)}")
+    B, H, W = depth_u16.shape
+    if tuple(params.shape) != (B, EYECANDIES_PARAM_BYTES):
+        raise ValueError(f"{name}: params must be [{B},{EYECANDIES_PARAM_BYTES}] uint8 (eyecandies_params per scan), got {tuple(params.shape)}")
+    return B, H, W
+
+
+def eyecandies_cloud(depth_u16, params, want_removed=True, want_depth=False):
+    """depth_u16 [B,H,W] uint16 (the PNG codes), params [B,136] uint8 (eyecandies_params) -> (cloud [B,H,W,3] f64, removed [B,H,W] u8
+    or None, depth [B,H,W] f32 or None): the reference's depth_to_pointcloud + remove_point_cloud_background in one launch; a removed
+    point is the reference's collapsed point, not zero.  utils/preprocessing_eyecandies.py:16-89."""
+    B, H, W = _chk_eyecandies(depth_u16, params, "eyecandies_cloud")
+    dev = depth_u16.device
+    cloud = torch.empty((B, H, W, 3), dtype=torch.float64, device=dev)
+    removed = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if want_removed else None
+    depth = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_depth else None
+    _call("cmdiad_eyecandies_cloud", _p(depth_u16), _p(params), B, H, W, _p(cloud), _p(removed), _p(depth), _stream())
+    return cloud, removed, depth
+
+
+def eyecandies_unproject(depth_u16, params, want_points=True, want_depth=False):
+    """The first stage alone -> (points [B,H*W,3] f64 or None, depth [B,H,W] f32 or None): depth_to_pointcloud / load_and_convert_depth
+    (utils/preprocessing_eyecandies.py:16-59)."""
+    B, H, W = _chk_eyecandies(depth_u16, params, "eyecandies_unproject")
+    dev = depth_u16.device
+    points = torch.empty((B, H * W, 3), dtype=torch.float64, device=dev) if want_points else None
+    depth = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_depth else None
+    _call("cmdiad_eyecandies_unproject", _p(depth_u16), _p(params), B, H, W, _p(points), _p(depth), _stream())
+    return points, depth
+
+
+def eyecandies_background(points):
+    """points [n,3] f64 -> (cloud [n,3] f64, removed [n] u8): remove_point_cloud_background (utils/preprocessing_eyecandies.py:62-89)."""
+    _chk(points, torch.float64, "eyecandies_background.points")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"eyecandies_background: points must be [n,3], got {tuple(points.shape)}")
+    n = points.shape[0]
+    cloud = torch.empty_like(points)
+    removed = torch.empty((n,), dtype=torch.uint8, device=points.device)
+    _call("cmdiad_eyecandies_background", _p(points), n, _p(cloud), _p(removed), _stream())
+    return cloud, removed

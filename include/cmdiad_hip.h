@@ -693,6 +693,41 @@ int cmdiad_organized_pc_prep(const float* pc, int B, int H, int W, const int32_t
 int cmdiad_gt_mask_prep(const uint8_t* gt, int B, int H, int W, const int32_t* rows, const int32_t* cols, int gt_size, float* out,
                         cmdiad_stream_t stream);
 
+/* cmdiad_organized_pc_prep for a float64 cloud pc [B,H,W,3] (the Eyecandies tiffs of the reference's script): every gathered value
+ * is converted to float32, round to nearest, as the reference's .float(); the valid-point rule is evaluated on the converted
+ * values, as the float32 entry point evaluates it. */
+int cmdiad_organized_pc_prep_f64(const double* pc, int B, int H, int W, const int32_t* xyz_rows, const int32_t* xyz_cols, int xyz_size,
+                                 const int32_t* depth_rows, const int32_t* depth_cols, int depth_size, float* cloud_out,
+                                 float* depth_out, int32_t* count_out, cmdiad_stream_t stream);
+
+/* ---- Eyecandies: depth map -> organised cloud (utils/preprocessing_eyecandies.py:16-89; contract and operation order:
+ * docs/eyecandies.md; additions are backwards compatible, the ABI stays 6) ---- */
+
+/* One scan's parameters (device memory, 136 bytes): range = float32(maxd - mind) and mind = float32(mind) of *_info_depth.yaml,
+ * inv_p = numpy.linalg.inv(K4 @ pose), row-major, computed on the host by the reference's own two numpy calls. */
+typedef struct {
+    float range;
+    float mind;
+    double inv_p[16];
+} cmdiad_eyecandies_params;
+
+/* depth_u16 [B,H,W] (the 16-bit PNG codes) -> cloud_out [B,H,W,3] f64 = remove_point_cloud_background(depth_to_pointcloud(...)) in
+ * the reference's final layout and scale; removed_out [B,H,W] u8 = 1 where the background rule fired (NULL: not wanted);
+ * depth_out [B,H,W] f32 = load_and_convert_depth (NULL: not wanted).  A removed point is the collapsed point of the reference, not
+ * zero.  One launch, no synchronisation.  B in 1..65535, sides in 1..16384, H * W >= 513 (the anchors are the points at flat indices
+ * 256 and H * W - 256). */
+int cmdiad_eyecandies_cloud(const uint16_t* depth_u16, const cmdiad_eyecandies_params* params, int B, int H, int W,
+                            double* cloud_out, uint8_t* removed_out, float* depth_out, cmdiad_stream_t stream);
+
+/* The first stage alone: points_out [B,H*W,3] f64 = depth_to_pointcloud (NULL allowed), depth_out [B,H,W] f32 (NULL allowed); at
+ * least one of the two. */
+int cmdiad_eyecandies_unproject(const uint16_t* depth_u16, const cmdiad_eyecandies_params* params, int B, int H, int W,
+                                double* points_out, float* depth_out, cmdiad_stream_t stream);
+
+/* The second stage alone on any cloud: points [n,3] f64 -> cloud_out [n,3] f64 = remove_point_cloud_background(points),
+ * removed_out [n] u8 (NULL allowed).  513 <= n <= 2^28. */
+int cmdiad_eyecandies_background(const double* points, int n, double* cloud_out, uint8_t* removed_out, cmdiad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
