@@ -5,9 +5,10 @@ calls it with B = 32.  Results per sample do not depend on B (tests/test_gpu_eng
 
 Nothing here touches the CPU oracle; every stage is a HIP kernel from libcmdiad_hip.so.
 """
-import ctypes
 import math
 import os
+import types
+from contextlib import nullcontext
 
 import torch
 
@@ -81,12 +82,28 @@ def shard_range(n, rank, world):
 KEY_EMPTY = ops.KEY_EMPTY
 
 
-class _Null:
-    def __enter__(self):
-        return self
+def dedup_enabled():
+    """CMDIAD_DEDUP=0 searches every query row; the default removes the repeated background rows first (csrc/dedup.hip, keys identical)."""
+    return os.environ.get("CMDIAD_DEDUP", "1") != "0"
 
-    def __exit__(self, *a):
-        return False
+
+def search_library(q16, q_sq, bank, keys, plan=None, keys_compact=None, timer=None):
+    """Search ONE library (bank.bf16: this rank's row shard, global rows via bank.row_offset) with this device's 16-bit queries
+    -> `keys` ([n] or [2, n] int64, every entry overwritten).  `timer` (a context manager) brackets the distance GEMM alone.
+    Without `plan`: keys = KEY_EMPTY, then every row of q16 is searched.  With `plan` (ops.DedupPlan, or anything with its q16 /
+    q_sq / count / slot; q16 and q_sq are then not read): the plan's live rows are searched into `keys_compact` (the caller's
+    buffer, shaped as `keys`; allocated when absent) and every original row takes its key through plan.slot."""
+    timer = timer if timer is not None else nullcontext()
+    if plan is None:
+        keys.fill_(KEY_EMPTY)
+        with timer:
+            ops.l2_min_keys(q16, q_sq, bank.bf16, bank.sqnorm, keys, bank.row_offset)
+        return keys
+    kc = keys_compact if keys_compact is not None else torch.empty_like(keys)
+    kc.fill_(KEY_EMPTY)
+    with timer:
+        ops.l2_min_keys_counted(plan.q16, plan.q_sq, plan.count, bank.bf16, bank.sqnorm, kc, bank.row_offset)
+    return ops.keys_expand(kc, plan.slot, keys)
 
 
 def merge_shard_keys(keys, group=None):
@@ -142,7 +159,7 @@ class _HipSearch:
 
     @staticmethod
     def search(q16, q_sq, bank, keys):
-        return ops.l2_min_keys(q16, q_sq, bank.bf16, bank.sqnorm, keys, bank.row_offset)
+        return search_library(q16, q_sq, bank, keys)
 
     @staticmethod
     def search_segments(q_all, s_all, counts, cap, bank, keys_all):
@@ -243,7 +260,7 @@ class ShardedSearch:
         cap = self.cap
         shape = (2, self.world * cap) if self.runner else (self.world * cap,)
         self.keys_all = torch.full(shape, KEY_EMPTY, dtype=torch.int64, device=self.q_all.device)
-        with (timer if timer is not None else _Null()):
+        with (timer if timer is not None else nullcontext()):
             self.impl.search_segments(self.q_all, self.s_all, self.counts_dev, cap, self.bank, self.keys_all)
         return self
 
@@ -277,25 +294,62 @@ def score_patches(patch32, bank, dims, gt_size=224, group=None):
     per-shard distance GEMM, integer-MIN all-reduces of the packed keys (best plane, then runner-up plane); the exact fp32
     decision between the two candidates and the re-weighting use the replicated fp32 library, so no further collectives are needed."""
     B, Q, D = patch32.shape
-    dev = patch32.device
-    flat = patch32.reshape(B * Q, D)
-    q16, _, qsq = ops.normalize_cast(flat)
-    if group is not None and os.environ.get("CMDIAD_DEDUP", "1") != "0":
+    q16, _, qsq = ops.normalize_cast(patch32.reshape(B * Q, D))
+    dedup = dedup_enabled()
+    if group is not None and dedup:
         keys, _ = sharded_min_keys(q16, qsq, bank, group)      # compact locally, gather the live rows only
         return score_patches_from_keys(patch32, keys, bank, dims, gt_size, group)
     q_all, s_all = gather_queries(q16, qsq, group)
-    keys = ops.new_keys(q_all.shape[0], dev, runner=True)
-    if os.environ.get("CMDIAD_DEDUP", "1") != "0":
-        # the rows of the patches without a foreground pixel repeat one vector: searched once (csrc/dedup.hip), keys identical
-        plan = ops.rows_dedup_plan(q_all, s_all)
-        kc = ops.l2_min_keys_counted(plan.q16, plan.q_sq, plan.count, bank.bf16, bank.sqnorm, keys, bank.row_offset)
-        keys = ops.keys_expand(kc, plan.slot, torch.empty_like(kc))
-    else:
-        ops.l2_min_keys(q_all, s_all, bank.bf16, bank.sqnorm, keys, bank.row_offset)
+    # the rows of the patches without a foreground pixel repeat one vector: searched once (csrc/dedup.hip), keys identical
+    keys = search_library(q_all, s_all, bank, torch.empty((2, q_all.shape[0]), dtype=torch.int64, device=patch32.device),
+                          ops.rows_dedup_plan(q_all, s_all) if dedup else None)
     keys = merge_shard_keys(keys, group)
     if group is not None:
         keys = keys[..., bank.rank * B * Q:(bank.rank + 1) * B * Q].contiguous()
     return score_patches_from_keys(patch32, keys, bank, dims, gt_size, group)
+
+
+def _no_answer(n, dev):
+    """(min_val [n] = 0, min_idx [n] = -1): what a query keeps when its key names no row (KEY_EMPTY) -- the re-score writes the others."""
+    return torch.zeros((n,), dtype=torch.float32, device=dev), torch.full((n,), -1, dtype=torch.int64, device=dev)
+
+
+def _tail_head(patch32, keys, bank, window=None, rescored=None):
+    """First half of a library's scoring tail: exact fp32 re-score of the keys (unless the caller made its own `rescored` = (min_val,
+    min_idx)), then ops.score_head over the library rows bank.f32 holds, `window` = (row_offset, rows); default: all.  -> the state
+    `_tail_knn` / `_tail_finish` take.  Every scoring path (single library, pair, sharded fp32 rows) goes through here, so where the
+    reference has no answer the outputs are DEFINED by one zero prefill, never by what the allocator left behind
+    (tests/test_gpu_score_tail.py pins it):
+      * a query whose key is KEY_EMPTY (only possible when EVERY shard of the search was empty): min_val 0, min_idx -1;
+      * an image whose winning patch has min_idx -1 (all of its keys empty): s_idx 0, s_star 0, m_star = the zero vector, s = 0;
+      * a library of fewer than 3 rows (the reference's topk(k=3) raises, features.py:254): the missing neighbours' top3 entries
+        stay KEY_EMPTY and their knn_d entries 0 (`_tail_knn`), i.e. each contributes exp(0) = 1 to the re-weighting sum.
+    A rank that holds a window of the rows writes only what it owns: the zeros elsewhere make the sum over the ranks exact."""
+    B, Q, D = patch32.shape
+    flat = patch32.reshape(B * Q, D)
+    if rescored is None:
+        rescored = _no_answer(B * Q, patch32.device)
+        ops.l2_rescore(flat, bank.f32, keys, *rescored, 0)
+    t = types.SimpleNamespace(bank=bank, window=window or (0, bank.rows), min_val=rescored[0], min_idx=rescored[1], shape=(B, Q, D))
+    t.m_star = torch.zeros((B, D), dtype=torch.float32, device=patch32.device)
+    t.s_star, t.s_idx, t.m_test = ops.score_head(t.min_val, t.min_idx, flat.view(B, Q, D), bank.f32, t.m_star, *t.window)
+    return t
+
+
+def _tail_knn(t, top3):
+    """knn_d [B, 2], zero-prefilled: m_test's distance to the 2nd and 3rd row of top3, where the window holds it (a shard: sum over the ranks)."""
+    return ops.score_tail(t.s_star, t.m_test, top3, t.bank.f32, torch.zeros((t.shape[0], 2), dtype=torch.float32, device=top3.device), *t.window)
+
+
+def _tail_finish(t, top3, dims, gt_size, knn_d=None):
+    """Second half: knn_d (unless the caller passes the summed one), the re-weighted score, the bilinear map -> the result dict."""
+    B, Q, D = t.shape
+    if knn_d is None:
+        knn_d = _tail_knn(t, top3)
+    s = ops.score_final(t.s_star, knn_d, D)
+    s_map = ops.bilinear_up(t.min_val.view(B, dims[0], dims[1]), gt_size)
+    return dict(min_val=t.min_val.view(B, Q), min_idx=t.min_idx.view(B, Q), s_idx=t.s_idx, s_star=t.s_star, s=s,
+                s_map_pre=s_map, top3=top3, knn_d=knn_d)
 
 
 def _sharded_score_steps(patch32, keys, bank, dims, gt_size):
@@ -304,7 +358,8 @@ def _sharded_score_steps(patch32, keys, bank, dims, gt_size):
     keys -- a rank contributes the parts of the rows it owns to sums over the ranks.  A generator: every `yield (kind, tensor)` is one collective over the ranks and receives its
     result -- "sum": element-wise sum (exactly one rank, the owner of the row in question, contributes a non-zero value, so the sum
     is exact); "gather": [W, *shape] of every rank's tensor.  Driven by real collectives (`_drive_collectives`) or, on one device,
-    by a lock-step loop over W generators (tests/test_gpu_fakeworld.py).
+    by a lock-step loop over W generators (tests/test_gpu_fakeworld.py).  The pieces of the tail are the single-library path's, called
+    with this rank's window of the rows; only the re-score is its own:
       1. exact fp32 distance to the winning row (keys [2, .]: to the best and the runner-up): by the rank that owns it -> sum [B*Q] / [2, B*Q] f32
       2. s* = max over a sample's patches; m_star = the winning row of that patch: sent by its owner       -> sum   [B, D] f32
       3. re-weighting scan of the LOCAL rows: three smallest (distance, global row) keys per probe         -> gather [W, B, 3] keys,
@@ -321,30 +376,22 @@ def _sharded_score_steps(patch32, keys, bank, dims, gt_size):
         if nloc:
             ops.l2_rescore_pair_d2(flat, bank.f32, keys, d2_pair, off)
         d2_pair = yield ("sum", d2_pair)
-        min_val = torch.zeros((B * Q,), dtype=torch.float32, device=dev)
-        min_idx = torch.full((B * Q,), -1, dtype=torch.int64, device=dev)
-        ops.l2_choose(keys, d2_pair, min_val, min_idx)
+        min_val, min_idx = ops.l2_choose(keys, d2_pair, *_no_answer(B * Q, dev))
     else:
-        min_val = torch.zeros((B * Q,), dtype=torch.float32, device=dev)
-        scratch_idx = torch.full((B * Q,), -1, dtype=torch.int64, device=dev)
+        min_val, scratch_idx = _no_answer(B * Q, dev)
         ops.l2_rescore(flat, bank.f32, keys, min_val, scratch_idx, off) if nloc else None
         min_val = yield ("sum", min_val)
         min_idx = torch.where(keys == KEY_EMPTY, torch.full_like(keys, -1), keys & 0xFFFFFFFF)       # global rows, known everywhere
-    m_star = torch.zeros((B, D), dtype=torch.float32, device=dev)
-    s_star, s_idx, m_test = ops.score_head(min_val, min_idx, flat.view(B, Q, D), bank.f32, m_star, off, nloc)
-    m_star = yield ("sum", m_star)
+    t = _tail_head(patch32, keys, bank, (off, nloc), (min_val, min_idx))
+    m_star = yield ("sum", t.m_star)
     if nloc:
         top3_local = ops.reweight_scan(m_star, bank.f32, bank.blk16, row_offset=off)
     else:
         top3_local = torch.full((B, 3), KEY_EMPTY, dtype=torch.int64, device=dev)
     everyone = yield ("gather", top3_local)                                                      # [W, B, 3]
     top3 = everyone.permute(1, 0, 2).reshape(B, -1).sort(1).values[:, :3].contiguous()           # keys are non-negative int64
-    knn_d = ops.score_tail(s_star, m_test, top3, bank.f32, torch.zeros((B, 2), dtype=torch.float32, device=dev), off, nloc)
-    knn_d = yield ("sum", knn_d)
-    s = ops.score_final(s_star, knn_d, D)
-    s_map = ops.bilinear_up(min_val.view(B, dims[0], dims[1]), gt_size)
-    return dict(min_val=min_val.view(B, Q), min_idx=min_idx.view(B, Q), s_idx=s_idx, s_star=s_star, s=s,
-                s_map_pre=s_map, top3=top3, knn_d=knn_d)
+    knn_d = yield ("sum", _tail_knn(t, top3))
+    return _tail_finish(t, top3, dims, gt_size, knn_d)
 
 
 def _drive_collectives(gen, group):
@@ -369,34 +416,14 @@ def _drive_collectives(gen, group):
 
 def score_patches_from_keys(patch32, keys, bank, dims, gt_size=224, group=None):
     """Everything after the (merged) nearest-neighbour keys: exact re-score, s*, re-weighting, score map.  `group` is needed only
-    when the library's fp32 rows are sharded as well (Bank(replicate_f32=False)).
-
-    Where the reference has no answer, the outputs are DEFINED by a zero prefill -- the same on the sharded path, the unsharded path
-    and the pair path, never whatever the allocator left behind (tests/test_gpu_score_tail.py pins it):
-      * a query whose key is KEY_EMPTY: min_val 0, min_idx -1;
-      * an image whose winning patch has min_idx -1 (all of its keys empty): s_idx 0, s_star 0, m_star = the zero vector, s = 0;
-      * a library of fewer than 3 rows (the reference's topk(k=3) raises, features.py:254): the missing neighbours' top3 entries
-        stay KEY_EMPTY and their knn_d entries 0, i.e. each contributes exp(0) = 1 to the re-weighting sum."""
+    when the library's fp32 rows are sharded as well (Bank(replicate_f32=False)).  Where the reference has no answer the outputs are
+    defined by the zero prefill of `_tail_head`."""
     if getattr(bank, "f32_sharded", False):
         if group is None:
             raise ValueError("score_patches_from_keys: the library's fp32 rows are sharded -- the process group is needed")
         return _drive_collectives(_sharded_score_steps(patch32, keys, bank, dims, gt_size), group)
-    B, Q, D = patch32.shape
-    dev = patch32.device
-    flat = patch32.reshape(B * Q, D)
-    # a key that names no row of the library (only possible when EVERY shard was empty) leaves (0, -1) behind, not garbage
-    min_val = torch.zeros((B * Q,), dtype=torch.float32, device=dev)
-    min_idx = torch.full((B * Q,), -1, dtype=torch.int64, device=dev)
-    ops.l2_rescore(flat, bank.f32, keys, min_val, min_idx, 0)
-    # zero prefill, as the sharded path: m_star of an image whose winning key is empty, knn_d of a library of fewer than 3 rows
-    m_star = torch.zeros((B, D), dtype=torch.float32, device=dev)
-    s_star, s_idx, m_test = ops.score_head(min_val, min_idx, flat.view(B, Q, D), bank.f32, m_star, 0, bank.rows)
-    top3 = ops.reweight_scan(m_star, bank.f32, bank.blk16)
-    knn_d = ops.score_tail(s_star, m_test, top3, bank.f32, torch.zeros((B, 2), dtype=torch.float32, device=dev), 0, bank.rows)
-    s = ops.score_final(s_star, knn_d, D)
-    s_map = ops.bilinear_up(min_val.view(B, dims[0], dims[1]), gt_size)
-    return dict(min_val=min_val.view(B, Q), min_idx=min_idx.view(B, Q), s_idx=s_idx, s_star=s_star, s=s,
-                s_map_pre=s_map, top3=top3, knn_d=knn_d)
+    t = _tail_head(patch32, keys, bank)
+    return _tail_finish(t, ops.reweight_scan(t.m_star, bank.f32, bank.blk16), dims, gt_size)
 
 
 def score_patches_from_keys_pair(patch_a, keys_a, bank_a, dims_a, patch_b, keys_b, bank_b, dims_b, gt_size=224, group=None):
@@ -410,26 +437,9 @@ def score_patches_from_keys_pair(patch_a, keys_a, bank_a, dims_a, patch_b, keys_
             or patch_b.shape[2] != D or bank_a.rows == 0 or bank_b.rows == 0 or os.environ.get("CMDIAD_SCAN_PAIR", "1") == "0"):
         return (score_patches_from_keys(patch_a, keys_a, bank_a, dims_a, gt_size, group),
                 score_patches_from_keys(patch_b, keys_b, bank_b, dims_b, gt_size, group))
-    dev = patch_a.device
-    heads = []
-    for patch32, keys, bank in ((patch_a, keys_a, bank_a), (patch_b, keys_b, bank_b)):
-        Q = patch32.shape[1]
-        flat = patch32.reshape(B * Q, D)
-        min_val = torch.zeros((B * Q,), dtype=torch.float32, device=dev)
-        min_idx = torch.full((B * Q,), -1, dtype=torch.int64, device=dev)
-        ops.l2_rescore(flat, bank.f32, keys, min_val, min_idx, 0)
-        m_star = torch.zeros((B, D), dtype=torch.float32, device=dev)         # zero prefill: see score_patches_from_keys
-        s_star, s_idx, m_test = ops.score_head(min_val, min_idx, flat.view(B, Q, D), bank.f32, m_star, 0, bank.rows)
-        heads.append((min_val, min_idx, s_star, s_idx, m_test, m_star, Q))
-    tops = ops.reweight_scan_pair(heads[0][5], bank_a.f32, bank_a.blk16, heads[1][5], bank_b.f32, bank_b.blk16)
-    out = []
-    for (min_val, min_idx, s_star, s_idx, m_test, m_star, Q), top3, bank, dims in zip(heads, tops, (bank_a, bank_b), (dims_a, dims_b)):
-        knn_d = ops.score_tail(s_star, m_test, top3, bank.f32, torch.zeros((B, 2), dtype=torch.float32, device=dev), 0, bank.rows)
-        s = ops.score_final(s_star, knn_d, D)
-        s_map = ops.bilinear_up(min_val.view(B, dims[0], dims[1]), gt_size)
-        out.append(dict(min_val=min_val.view(B, Q), min_idx=min_idx.view(B, Q), s_idx=s_idx, s_star=s_star, s=s,
-                        s_map_pre=s_map, top3=top3, knn_d=knn_d))
-    return out[0], out[1]
+    ta, tb = _tail_head(patch_a, keys_a, bank_a), _tail_head(patch_b, keys_b, bank_b)
+    top_a, top_b = ops.reweight_scan_pair(ta.m_star, bank_a.f32, bank_a.blk16, tb.m_star, bank_b.f32, bank_b.blk16)
+    return _tail_finish(ta, top_a, dims_a, gt_size), _tail_finish(tb, top_b, dims_b, gt_size)
 
 
 class Extraction:
@@ -470,7 +480,7 @@ class Engine:
             ex.rgb_tokens = self.vit.forward_tokens(rgb) if want_rgb else None
             return ex
         cur = torch.cuda.current_stream()
-        ctx = torch.cuda.stream(side_stream) if side_stream is not None else _Null()
+        ctx = torch.cuda.stream(side_stream) if side_stream is not None else nullcontext()
         if side_stream is not None:
             side_stream.wait_stream(cur)
 

@@ -69,7 +69,7 @@ class DistHandle:
         bank = eng.Bank(self.lib.to(dev).float())
         q = self.patch.to(dev).float().contiguous()
         q16, _, qsq = ops.normalize_cast(q)
-        keys = ops.l2_min_keys(q16, qsq, bank.bf16, bank.sqnorm, ops.new_keys(q.shape[0], q.device, runner=True))
+        keys = eng.search_library(q16, qsq, bank, torch.empty((2, q.shape[0]), dtype=torch.int64, device=q.device))
         return ops.l2_rescore(q, bank.f32, keys)      # best and runner-up measured in fp32: torch.min's answer on near-ties too
 
 

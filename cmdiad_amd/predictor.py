@@ -53,14 +53,6 @@ class _SharedPlan:
         self.q16, self.q_sq, self.count, self.slot = q16, q_sq, count, slot
 
 
-class _NoTimer:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
 class Ticket:
     """One submitted batch: wait() -> (image scores [B] f64, pixel maps [B, gt, gt] f64) as numpy arrays.
     `flag` / `redo` (row-sharded search only): a pinned int32 that the step set to non-zero when some rank's live query rows did
@@ -137,7 +129,7 @@ class BatchPredictor:
         self.sets = None
         self.static = {}
         # exact removal of the repeated background rows in front of the xyz search (csrc/dedup.hip); CMDIAD_DEDUP=0 searches every row
-        self.dedup = os.environ.get("CMDIAD_DEDUP", "1") != "0"
+        self.dedup = eng.dedup_enabled()
         # row-sharded search: rows of every rank that travel per step -- "auto" (sticky cap, no host read in steady state) | "exact"
         self.shard_cap = os.environ.get("CMDIAD_SHARD_CAP", "auto")
         if self.shard_cap.strip().isdigit():
@@ -211,10 +203,7 @@ class BatchPredictor:
             rq = rq.view(B, Q, D)
             early["rgb"] = (rq, q16, qsq)
             if self.group is None:
-                bank = self.bank_second
-                k = ops.new_keys(B * Q, rq.device, runner=True)
-                ops.l2_min_keys(q16, qsq, bank.bf16, bank.sqnorm, k, bank.row_offset)
-                early["rgb_keys"] = k
+                early["rgb_keys"] = eng.search_library(q16, qsq, self.bank_second, torch.empty((2, B * Q), dtype=torch.int64, device=rq.device))
 
         def xyz_branch(ex):
             # the tail of the point-cloud branch, on ITS stream: patch pooling, 16-bit queries and the row de-duplication plan need
@@ -265,33 +254,34 @@ class BatchPredictor:
             plan = qs.get(f"{name}_plan") if self.dedup else None    # made in stage 1 already (unsharded library)
             q_all, s_all = (None, None) if plan is not None else eng.gather_queries(q16, qsq, self.group)
             n_rows = B * Q if q_all is None else q_all.shape[0]
-            k = self.static.get(f"keys_{name}_{buf}")       # [2, rows]: best + runner-up (ops.new_keys(runner=True))
-            if k is None or k.shape[1] != n_rows:
-                k = self.static[f"keys_{name}_{buf}"] = torch.empty((2, n_rows), dtype=torch.int64, device=q.device)
+            k = self._static_keys(f"keys_{name}_{buf}", n_rows)       # [2, rows]: best + runner-up
+            kc = None
             if self.dedup:
                 # patches without a foreground pixel are one and the same row (and so are their hallucinated features in the MTFI
                 # workload): searched once, the key copied to all
                 if plan is None:
                     plan = self.static[f"plan_{name}_{buf}"] = ops.rows_dedup_plan(q_all, s_all, self.static.get(f"plan_{name}_{buf}"))
-                kc = self.static.get(f"keysc_{name}_{buf}")
-                if kc is None or kc.shape[1] != n_rows:
-                    kc = self.static[f"keysc_{name}_{buf}"] = torch.empty((2, n_rows), dtype=torch.int64, device=q.device)
-                kc.fill_(eng.KEY_EMPTY)
-                with self.timers.get(name, _NoTimer()):
-                    ops.l2_min_keys_counted(plan.q16, plan.q_sq, plan.count, bank.bf16, bank.sqnorm, kc, bank.row_offset)
-                ops.keys_expand(kc, plan.slot, k)
-                live = plan.count
-            else:
-                k.fill_(eng.KEY_EMPTY)
-                with self.timers.get(name, _NoTimer()):
-                    ops.l2_min_keys(q_all, s_all, bank.bf16, bank.sqnorm, k, bank.row_offset)
-                live = q_all.shape[0]
+                kc = self._static_keys(f"keysc_{name}_{buf}", n_rows)
+            eng.search_library(q_all, s_all, bank, k, plan, kc, self.timers.get(name))
             if name == "xyz":
-                self.live_rows += live
+                self.live_rows += plan.count if plan is not None else n_rows
                 self.xyz_searches += 1
             k = eng.merge_shard_keys(k, self.group)
             keys[name] = k[..., bank.rank * B * Q:(bank.rank + 1) * B * Q] if self.group is not None else k
         return keys
+
+    def _static_keys(self, name, n_rows):
+        """A [2, n_rows] key buffer that lives as long as the predictor (the captured stage 2 reads the sets' keys in place)."""
+        k = self.static.get(name)
+        if k is None or k.shape[1] != n_rows:
+            k = self.static[name] = torch.empty((2, n_rows), dtype=torch.int64, device=self.dev)
+        return k
+
+    def _search_into(self, st, which):
+        """The step's library searches for a buffer set; keys that were not written in place are copied into the set's static buffers."""
+        for n, k in self.search(st["qs"], which).items():
+            if k.data_ptr() != st["k"][n].data_ptr():
+                st["k"][n].copy_(k)
 
     # ---- stage 2: exact re-score, re-weighting, bilinear maps, 8-bit blur (a14), lambda weights + one-class SVMs (a19)
     def stage2(self, qs, keys):
@@ -439,17 +429,11 @@ class BatchPredictor:
             # `roofline.launch_ms`.  CMDIAD_SEARCH_POST=0 keeps the searches on the main stream.
             search_on_post = os.environ.get("CMDIAD_SEARCH_POST", "1") == "1"
             if not search_on_post:
-                keys = self.search(st["qs"], which)
-                for n, k in keys.items():
-                    if k.data_ptr() != st["k"][n].data_ptr():
-                        st["k"][n].copy_(k)
+                self._search_into(st, which)
             self.post.wait_stream(cur)
             with torch.cuda.stream(self.post):
                 if search_on_post:
-                    keys = self.search(st["qs"], which)
-                    for n, k in keys.items():
-                        if k.data_ptr() != st["k"][n].data_ptr():
-                            st["k"][n].copy_(k)
+                    self._search_into(st, which)
                 if st["g2"] is not None:
                     st["g2"].replay()
                 else:
@@ -471,12 +455,8 @@ class BatchPredictor:
                     inp["staged"] = stage
             st["done"] = ev
             return self._ticket(host_s, host_m, ev, flag, rgb, pcs)
-        inp = self.inputs[0]
         self.step_no += 1
-        self._load_inputs(inp, rgb, pcs)
-        qs = self.stage1(inp)
-        inp["free"] = torch.cuda.Event()
-        inp["free"].record()
+        qs = self._eager_stage1(rgb, pcs)
         s_dev, maps_dev = self.stage2(qs, self.search(qs, 0))
         host_s.copy_(s_dev, non_blocking=True)
         host_m.copy_(maps_dev, non_blocking=True)
@@ -484,6 +464,16 @@ class BatchPredictor:
         ev = torch.cuda.Event()
         ev.record()
         return self._ticket(host_s, host_m, ev, flag, rgb, pcs)
+
+    def _eager_stage1(self, rgb, pcs):
+        """The eager step up to its queries (submit without graphs, _redo): the batch into set 0's input buffers, stage 1, and the
+        event after which those buffers may be overwritten."""
+        inp = self.inputs[0]
+        self._load_inputs(inp, rgb, pcs)
+        qs = self.stage1(inp)
+        inp["free"] = torch.cuda.Event()
+        inp["free"].record()
+        return qs
 
     def _flag_to_host(self):
         """Row-sharded search: OR of this step's overflow flags -> the pinned flag of the step's ring slot (asynchronous)."""
@@ -513,11 +503,7 @@ class BatchPredictor:
                     v.regrow()
 
         grow({k.split("_")[1] for k, v in searches.items() if v.overflow is None or v.overflowed()})
-        inp = self.inputs[0]
-        self._load_inputs(inp, rgb, pcs)
-        qs = self.stage1(inp)
-        inp["free"] = torch.cuda.Event()
-        inp["free"].record()
+        qs = self._eager_stage1(rgb, pcs)
         for _ in range(3):
             keys = self.search(qs, 0)
             self.step_flags = []

@@ -528,3 +528,69 @@ def test_engine_image_without_any_candidate():
     for x in (ra, rb):
         for k in ("min_val", "min_idx", "s_idx", "s_star", "s", "top3", "knn_d"):
             assert torch.equal(x[k], r[k]), k
+
+
+# ------------------------------------------------------------------------------------ engine level: ordinary sizes, searched keys
+ALL_KEYS = ("min_val", "min_idx", "s_idx", "s_star", "s", "s_map_pre", "top3", "knn_d")
+
+
+def _searched_library(Nb, Q, **bank_kw):
+    """A seeded Gaussian library with B = 3 images of Q patches (no ties), its Bank, and the two-plane keys of a REAL search."""
+    rows, patch = _engine_inputs(Nb, B=3, Q=Q)
+    tp = _dev(patch)
+    bank = eng.Bank(_dev(rows), **bank_kw)
+    bank.blk16
+    q16, _, qsq = ops.normalize_cast(tp.reshape(-1, tp.shape[2]))
+    keys = ops.l2_min_keys(q16, qsq, bank.bf16, bank.sqnorm, ops.new_keys(q16.shape[0], DEV, runner=True), bank.row_offset)
+    return tp, keys, bank
+
+
+@pytest.mark.parametrize("scan_pair", ["1", "0"])
+def test_engine_pair_of_two_different_libraries(scan_pair, monkeypatch):
+    """The two halves of score_patches_from_keys_pair differ in EVERYTHING -- library (300 and 40 rows), patches ([3, 4, 128] and
+    [3, 9, 128]), dims, keys -- so a bank, a `dims` or a `top3` that crossed from one half to the other cannot go unnoticed: each half
+    is, bit for bit and in every key of the result, what the single-library call returns.  CMDIAD_SCAN_PAIR=0: the fallback."""
+    pa, ka, bank_a = _searched_library(300, 4)
+    pb, kb, bank_b = _searched_library(40, 9)
+    D = pa.shape[2]
+    launched = []
+    pair_scan = ops.reweight_scan_pair
+    monkeypatch.setattr(ops, "reweight_scan_pair", lambda *a, **k: launched.append(1) or pair_scan(*a, **k))
+    monkeypatch.setenv("CMDIAD_SCAN_PAIR", scan_pair)
+    _poison_allocator(D)
+    want_a = eng.score_patches_from_keys(pa, ka, bank_a, (2, 2), gt_size=8)
+    _poison_allocator(D)
+    want_b = eng.score_patches_from_keys(pb, kb, bank_b, (3, 3), gt_size=8)
+    _poison_allocator(D)
+    ra, rb = eng.score_patches_from_keys_pair(pa, ka, bank_a, (2, 2), pb, kb, bank_b, (3, 3), gt_size=8)
+    assert len(launched) == int(scan_pair)          # the pair scan really ran / really did not
+    for got, want, half in ((ra, want_a, "a"), (rb, want_b, "b")):
+        assert sorted(got) == sorted(want) == sorted(ALL_KEYS)
+        for k in ALL_KEYS:
+            assert got[k].shape == want[k].shape and torch.equal(got[k], want[k]), (half, k)
+    assert ra["s_map_pre"].shape == rb["s_map_pre"].shape == (3, 8, 8) and not torch.equal(ra["s_map_pre"], rb["s_map_pre"])
+
+
+def test_engine_sharded_tail_at_an_ordinary_size():
+    """The tail of a library whose fp32 rows are sharded (one rank that owns all 300 of them), driven in lock-step without a process
+    group, on searched keys: every key of the result, the score map included, is bit for bit the single-library result."""
+    tp, keys, bank = _searched_library(300, 4)
+    D = tp.shape[2]
+    _poison_allocator(D)
+    want = eng.score_patches_from_keys(tp, keys, bank, (2, 2), gt_size=8)
+    _, keys_s, sharded = _searched_library(300, 4, replicate_f32=False)
+    assert sharded.f32_sharded and torch.equal(keys_s, keys)
+    _poison_allocator(D)
+    gen = eng._sharded_score_steps(tp, keys_s, sharded, (2, 2), 8)
+    kinds = []
+    try:
+        kind, t = next(gen)
+        while True:
+            kinds.append(kind)
+            kind, t = gen.send(t if kind == "sum" else t.unsqueeze(0))
+    except StopIteration as done:
+        got = done.value
+    assert kinds == ["sum", "sum", "gather", "sum"]
+    assert sorted(got) == sorted(want) == sorted(ALL_KEYS)
+    for k in ALL_KEYS:
+        assert torch.equal(got[k], want[k]), k
