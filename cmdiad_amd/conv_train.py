@@ -18,15 +18,10 @@ import os
 
 import torch
 
-from . import _native as nat
 from . import ops
-from .train import SPLIT_K, _reduce_slabs
+from .train import _dw, _ln_grads, _sum_slabs, step_loss, update_running_stats
 
 EPS = 1e-5   # nn.BatchNorm2d default (hallucination_network.py:81)
-
-
-def _call(name, *args):
-    nat.check(getattr(nat.lib(), name)(*args), name)
 
 
 def _conv_w(w):
@@ -48,24 +43,27 @@ def _split_for(rows, n1, n2):
     return int(max(1, min(max(1, target // tiles), rows // 128, 64)))
 
 
-def _wgrad(dz, x, B, H, W):
-    """dz [M,N] bf16, x [M,C] bf16 (M = B*H*W, NHWC rows) -> dW [N,C,3,3] f32."""
+def _wgrad(dz, x, B, H, W, want_bias=False):
+    """dz [M,N] bf16, x [M,C] bf16 (M = B*H*W, NHWC rows) -> dW [N,C,3,3] f32; want_bias: (dW, db [N] f32), the bias gradient being
+    the column sums of dz, from the tiles the centre tap's product stages anyway."""
     N, C = dz.shape[1], x.shape[1]
     dzp, g, rows = ops.pad_nhwc(dz.view(B, H, W, N))
     xp, gx, _ = ops.pad_nhwc(x.view(B, H, W, C))
     P = dzp[g:g + rows]
     split = _split_for(rows, N, C)
     taps = torch.empty((9, N, C), dtype=torch.float32, device=dz.device)
-    for ky in range(3):
-        for kx in range(3):
-            off = (ky - 1) * (W + 2) + (kx - 1)
-            Q = xp[gx + off:gx + off + rows]
+    db = torch.empty((N,), dtype=torch.float32, device=dz.device) if want_bias else None
+    for t in range(9):
+        off = (t // 3 - 1) * (W + 2) + (t % 3 - 1)
+        Q = xp[gx + off:gx + off + rows]
+        if want_bias and t == 4:
+            out, cs = ops.gemm_tn(P, Q, split_k=split, want_colsum=True)
+            _sum_slabs(cs, split, N, db)
+        else:
             out = ops.gemm_tn(P, Q, split_k=split)
-            if split == 1:
-                taps[ky * 3 + kx].copy_(out)
-            else:
-                _reduce_slabs(out, split, N * C, taps[ky * 3 + kx])
-    return taps.permute(1, 2, 0).reshape(N, C, 3, 3).contiguous()
+        _sum_slabs(out, split, N * C, taps[t])
+    dw = taps.permute(1, 2, 0).reshape(N, C, 3, 3).contiguous()
+    return (dw, db) if want_bias else dw
 
 
 def forward_backward(x, target, params, sigmoid, batch, need_grad=True):
@@ -74,7 +72,6 @@ def forward_backward(x, target, params, sigmoid, batch, need_grad=True):
     B, T, C = x.shape
     H = W = int(round(T ** 0.5))
     assert H * W == T
-    dev = x.device
     M = B * T
     ws = [params[0], params[3], params[6], params[9]]
     bns = [(params[1], params[2]), (params[4], params[5]), (params[7], params[8])]
@@ -90,13 +87,8 @@ def forward_backward(x, target, params, sigmoid, batch, need_grad=True):
     Nout = ws[3].shape[0]
     y, _ = ops.conv2d_nhwc(xs[3].view(B, H, W, -1), _conv_w(ws[3]), Nout, want_f32=True, want_bf16=False)
     y = y.view(M, Nout)
-    row_loss = torch.empty((M,), dtype=torch.float32, device=dev)
-    dz = torch.empty((M, Nout), dtype=torch.bfloat16, device=dev) if need_grad else None
-    mode = 0 + (512 if sigmoid else 256)   # l2 rows, CMDIAD_LOSS_OUT_SIGMOID / CMDIAD_LOSS_OUT_NONE
-    _call("cmdiad_loss_head", ops._p(y), ops._p(target.reshape(M, Nout).contiguous()), M, Nout, mode, 1.0 / batch, ops._p(row_loss),
-          ops._p(dz), None, ops._stream())
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    _call("cmdiad_sum_vector", ops._p(row_loss), M, 1.0 / batch, ops._p(loss), ops._stream())
+    loss, dz = ops.loss_and_grad(y, target.reshape(M, Nout).contiguous(), ops.LOSS_L2, batch, need_grad,
+                                 out_act=ops.LOSS_OUT_SIGMOID if sigmoid else ops.LOSS_OUT_NONE)
     if not need_grad:
         return loss, None, stats
     grads = [None] * 10
@@ -111,36 +103,13 @@ def forward_backward(x, target, params, sigmoid, batch, need_grad=True):
     return loss, tuple(grads), stats
 
 
-class _TowerLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, target, sigmoid, batch, need_grad, tower, *params):
-        loss, grads, stats = forward_backward(x, target, tuple(p.detach() for p in params), sigmoid, batch, need_grad)
-        M = x.shape[0] * x.shape[1]
-        bn_layers = [m for m in tower if isinstance(m, torch.nn.BatchNorm2d)]
-        with torch.no_grad():   # what nn.BatchNorm2d does in train(): momentum 0.1, UNBIASED variance into the running buffer
-            for bn, (mean64, var64) in zip(bn_layers, stats):
-                if bn.track_running_stats and bn.running_mean is not None:
-                    mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked + 1)
-                    bn.running_mean.mul_(1 - mom).add_(mean64.to(bn.running_mean.dtype), alpha=mom)
-                    bn.running_var.mul_(1 - mom).add_((var64 * (M / (M - 1))).to(bn.running_var.dtype), alpha=mom)
-                    bn.num_batches_tracked += 1
-        ctx.grads, ctx.n_params = grads, len(params)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        if ctx.grads is None:
-            return (None,) * (6 + ctx.n_params)
-        return (None,) * 6 + tuple(gr * g for gr in ctx.grads)
-
-
 def _check_bn(bns):
     """The hand-written BatchNorm forward / backward is the affine batch-statistics form with eps = EPS (nn.BatchNorm2d's default,
     what every BatchNorm of the reference's heads is constructed with): anything else must not be trained silently differently."""
     for bn in bns:
         if not bn.affine or abs(float(bn.eps) - EPS) > 1e-12:
             raise NotImplementedError(f"hand-written BatchNorm training path: affine BatchNorm2d with eps = {EPS} only (got eps = {bn.eps}, "
-                                      f"affine = {bn.affine}); use the module's torch layers (CMDIAD_HRNET_TRAIN=torch / CMDIAD_CONV_TRAIN=torch)")
+                                      f"affine = {bn.affine})")
 
 
 def tower_params(tower):
@@ -160,8 +129,15 @@ def tower_loss(tower, x, target, sigmoid):
     params = tower_params(tower)
     dev = params[0].device
     x, target = x.to(dev).float().contiguous(), target.to(dev).float().contiguous()
-    need = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-    return _TowerLoss.apply(x, target, bool(sigmoid), x.shape[0], need, tower, *params)
+    B, T = x.shape[:2]
+    bns = [m for m in tower if isinstance(m, torch.nn.BatchNorm2d)]
+
+    def step(ps, need_grad):
+        loss, grads, stats = forward_backward(x, target, ps, bool(sigmoid), B, need_grad)
+        for bn, (mean64, var64) in zip(bns, stats):
+            update_running_stats(bn, mean64, var64, B * T)
+        return loss, grads, None
+    return step_loss(step, params)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -171,44 +147,11 @@ def tower_loss(tower, x, target, sigmoid):
 # 3 -> 4 for outputs / 64 where the tensor is a convolution operand), as in runtime.PackedFtoIConv: padded weights and biases are
 # zero, so padded activations and their gradients stay zero.
 # ------------------------------------------------------------------------------------------------------------------------
-def _pad_w(w, n_pad, c_pad):
-    N, C = w.shape[:2]
-    out = torch.zeros((n_pad, c_pad, 3, 3), dtype=torch.float32, device=w.device)
-    out[:N, :C] = w
+def _pad0(t, *lead):
+    """fp32 copy of t with its leading dimensions zero-padded to `lead`."""
+    out = torch.zeros(lead + tuple(t.shape[len(lead):]), dtype=torch.float32, device=t.device)
+    out[tuple(slice(0, n) for n in t.shape[:len(lead)])] = t
     return out
-
-
-def _pad_v(b, n_pad):
-    out = torch.zeros((n_pad,), dtype=torch.float32, device=b.device)
-    out[:b.shape[0]] = b
-    return out
-
-
-def _wgrad_bias(dz, x, B, H, W):
-    """As _wgrad, plus the bias gradient (column sums of dz, from the tiles the centre tap's product stages anyway)."""
-    N, C = dz.shape[1], x.shape[1]
-    dzp, g, rows = ops.pad_nhwc(dz.view(B, H, W, N))
-    xp, gx, _ = ops.pad_nhwc(x.view(B, H, W, C))
-    P = dzp[g:g + rows]
-    split = _split_for(rows, N, C)
-    taps = torch.empty((9, N, C), dtype=torch.float32, device=dz.device)
-    db = torch.empty((N,), dtype=torch.float32, device=dz.device)
-    for t in range(9):
-        off = (t // 3 - 1) * (W + 2) + (t % 3 - 1)
-        Q = xp[gx + off:gx + off + rows]
-        if t == 4:
-            out, cs = ops.gemm_tn(P, Q, split_k=split, want_colsum=True)
-            if split == 1:
-                db.copy_(cs)
-            else:
-                _reduce_slabs(cs, split, N, db)
-        else:
-            out = ops.gemm_tn(P, Q, split_k=split)
-        if split == 1:
-            taps[t].copy_(out)
-        else:
-            _reduce_slabs(out, split, N * C, taps[t])
-    return taps.permute(1, 2, 0).reshape(N, C, 3, 3).contiguous(), db
 
 
 def ftoi_forward_backward(feature, img, params, batch, need_grad=True):
@@ -221,55 +164,35 @@ def ftoi_forward_backward(feature, img, params, batch, need_grad=True):
     dev = feature.device
     n1, n2, n3, n4 = w1.shape[0], w2.shape[0], w3.shape[0], w4.shape[0]             # 384, 96, 32, 3
     p2, p3, p4 = (n2 + 63) // 64 * 64, (n3 + 63) // 64 * 64, (n4 + 3) // 4 * 4      # 128, 64, 4
-    W1, W2 = w1, _pad_w(w2, p2, n1)
-    W3, W4 = _pad_w(w3, p3, p2), _pad_w(w4, p4, p3)
+    W1, W2 = w1, _pad0(w2, p2, n1)
+    W3, W4 = _pad0(w3, p3, p2), _pad0(w4, p4, p3)
     x0 = ops.cast_bf16(feature.reshape(B * T, C).contiguous()).view(B, h, h, C)
     h1, _ = ops.conv2d_nhwc(x0, _conv_w(W1), n1, bias=b1.contiguous(), want_f32=True, want_bf16=False)               # [B,56,56,384] f32
     u = ops.upsample_bicubic(h1, n1, H, H)                                                                           # [B,224,224,384] bf16
-    _, h2 = ops.conv2d_nhwc(u, _conv_w(W2), p2, bias=_pad_v(b2, p2), act=ops.ACT_RELU)                               # [.,128] bf16
-    _, h3 = ops.conv2d_nhwc(h2, _conv_w(W3), p3, bias=_pad_v(b3, p3), act=ops.ACT_RELU)                              # [.,64]
-    out, _ = ops.conv2d_nhwc(h3, _conv_w(W4), p4, bias=_pad_v(b4, p4), want_f32=True, want_bf16=False)               # [.,4] f32
+    _, h2 = ops.conv2d_nhwc(u, _conv_w(W2), p2, bias=_pad0(b2, p2), act=ops.ACT_RELU)                                # [.,128] bf16
+    _, h3 = ops.conv2d_nhwc(h2, _conv_w(W3), p3, bias=_pad0(b3, p3), act=ops.ACT_RELU)                               # [.,64]
+    out, _ = ops.conv2d_nhwc(h3, _conv_w(W4), p4, bias=_pad0(b4, p4), want_f32=True, want_bf16=False)                # [.,4] f32
     M = B * H * H
     target = torch.zeros((B, H, H, p4), dtype=torch.float32, device=dev)
     target[..., :n4] = img.permute(0, 2, 3, 1)
-    row_loss = torch.empty((M,), dtype=torch.float32, device=dev)
-    dout = torch.empty((M, p4), dtype=torch.bfloat16, device=dev) if need_grad else None
-    _call("cmdiad_loss_head", ops._p(out), ops._p(target), M, p4, 0 + 256, 1.0 / batch, ops._p(row_loss), ops._p(dout), None, ops._stream())
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    _call("cmdiad_sum_vector", ops._p(row_loss), M, 1.0 / batch, ops._p(loss), ops._stream())
+    loss, dout = ops.loss_and_grad(out.view(M, p4), target.view(M, p4), ops.LOSS_L2, batch, need_grad)
     if not need_grad:
         return loss, None
     # conv4: the output gradient as a 64-channel operand (4 live), weight gradient, data gradient, ReLU of conv3
     d4 = torch.zeros((M, 64), dtype=torch.bfloat16, device=dev)
     d4[:, :p4] = dout
-    gw4, gb4 = _wgrad_bias(d4, h3.view(M, p3), B, H, H)
-    W4d = torch.zeros((64, p3, 3, 3), dtype=torch.float32, device=dev)
-    W4d[:p4] = W4
-    dh3, _ = ops.conv2d_nhwc(d4.view(B, H, H, 64), _conv_w_dgrad(W4d), p3, want_f32=True, want_bf16=False)
+    gw4, gb4 = _wgrad(d4, h3.view(M, p3), B, H, H, want_bias=True)
+    dh3, _ = ops.conv2d_nhwc(d4.view(B, H, H, 64), _conv_w_dgrad(_pad0(W4, 64)), p3, want_f32=True, want_bf16=False)
     dz3 = ops.relu_bwd(dh3.view(M, p3), h3.view(M, p3))
-    gw3, gb3 = _wgrad_bias(dz3, h2.view(M, p2), B, H, H)
+    gw3, gb3 = _wgrad(dz3, h2.view(M, p2), B, H, H, want_bias=True)
     dh2, _ = ops.conv2d_nhwc(dz3.view(B, H, H, p3), _conv_w_dgrad(W3), p2, want_f32=True, want_bf16=False)
     dz2 = ops.relu_bwd(dh2.view(M, p2), h2.view(M, p2))
-    gw2, gb2 = _wgrad_bias(dz2, u.view(M, n1), B, H, H)
+    gw2, gb2 = _wgrad(dz2, u.view(M, n1), B, H, H, want_bias=True)
     du, _ = ops.conv2d_nhwc(dz2.view(B, H, H, p2), _conv_w_dgrad(W2), n1, want_f32=True, want_bf16=False)
     dh1 = ops.upsample_bicubic_bwd(du.view(B, H, H, n1), h, h)                                                       # [B,56,56,384] f32
-    gw1, gb1 = _wgrad_bias(ops.cast_bf16(dh1.view(B * T, n1)), x0.view(B * T, C), B, h, h)
+    gw1, gb1 = _wgrad(ops.cast_bf16(dh1.view(B * T, n1)), x0.view(B * T, C), B, h, h, want_bias=True)
     return loss, (gw1, gb1, gw2[:n2].contiguous(), gb2[:n2].contiguous(), gw3[:n3, :n2].contiguous(), gb3[:n3].contiguous(),
                   gw4[:n4, :n3].contiguous(), gb4[:n4].contiguous())
-
-
-class _FtoILoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, feature, img, batch, need_grad, *params):
-        loss, grads = ftoi_forward_backward(feature, img, tuple(p.detach() for p in params), batch, need_grad)
-        ctx.grads, ctx.n_params = grads, len(params)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        if ctx.grads is None:
-            return (None,) * (4 + ctx.n_params)
-        return (None,) * 4 + tuple(gr * g for gr in ctx.grads)
 
 
 def ftoi_conv_loss(module, feature, img):
@@ -278,8 +201,7 @@ def ftoi_conv_loss(module, feature, img):
     params = tuple(p for i in range(1, 5) for p in (getattr(module, f"conv{i}").weight, getattr(module, f"conv{i}").bias))
     dev = params[0].device
     feature, img = feature.to(dev).float().contiguous(), img.to(dev).float().contiguous()
-    need = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-    return _FtoILoss.apply(feature, img, feature.shape[0], need, *params)
+    return step_loss(lambda ps, need_grad: ftoi_forward_backward(feature, img, ps, feature.shape[0], need_grad) + (None,), params)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -290,7 +212,6 @@ def ftoi_conv_loss(module, feature, img):
 def ftoi_mlp_forward_backward(x, img, params, batch, need_grad=True):
     """x [B,3136,768] f32, img [B,out_dim,224,224] f32, params = (ln_w, ln_b, w1, b1, w2, b2, w3, b3, w4, b4).
     -> (loss 0-dim, grads in the order of params | None)."""
-    from .train import CHUNKS, _dw
     ln_w, ln_b, w1, b1, w2, b2, w3, b3, w4, b4 = params
     B, T, D = x.shape
     h = int(round(T ** 0.5))
@@ -299,8 +220,7 @@ def ftoi_mlp_forward_backward(x, img, params, batch, need_grad=True):
     M = B * T
     n3, n4 = w3.shape[0], w4.shape[0]                          # 96, out_dim
     p3, p4 = (n3 + 63) // 64 * 64, 4
-    W3 = torch.zeros((p3, w3.shape[1]), dtype=torch.float32, device=dev); W3[:n3] = w3
-    W4 = torch.zeros((64, p3), dtype=torch.float32, device=dev); W4[:n4, :n3] = w4          # 64 rows: its transpose is a GEMM operand
+    W3, W4 = _pad0(w3, p3), _pad0(w4, 64, p3)                  # W4 to 64 rows: its transpose is a GEMM operand
     w1h, w2h, w3h, w4h = ops.cast_bf16(w1.contiguous()), ops.cast_bf16(w2.contiguous()), ops.cast_bf16(W3), ops.cast_bf16(W4)
     x2 = x.reshape(M, D).contiguous()
     mean = torch.empty((M,), dtype=torch.float32, device=dev)
@@ -311,52 +231,30 @@ def ftoi_mlp_forward_backward(x, img, params, batch, need_grad=True):
     z3 = torch.empty((M, p3), dtype=torch.bfloat16, device=dev)
     _, a1 = ops.gemm(h0, w1h, bias=b1, act=ops.ACT_GELU, out_pre_bf16=z1)
     _, a2 = ops.gemm(a1, w2h, bias=b2, act=ops.ACT_GELU, out_pre_bf16=z2)
-    _, a3 = ops.gemm(a2, w3h, bias=_pad_v(b3, p3), act=ops.ACT_GELU, out_pre_bf16=z3)
-    out, _ = ops.gemm(a3, w4h[:p4].contiguous(), bias=_pad_v(b4, p4), want_f32=True, want_bf16=False)              # [M,4] f32
+    _, a3 = ops.gemm(a2, w3h, bias=_pad0(b3, p3), act=ops.ACT_GELU, out_pre_bf16=z3)
+    out, _ = ops.gemm(a3, w4h[:p4].contiguous(), bias=_pad0(b4, p4), want_f32=True, want_bf16=False)               # [M,4] f32
     up = ops.upsample_bicubic(out.view(B, h, h, p4), p4, H, H, nchw=True)                                           # [B,4,H,H] f32
     Mu = B * H * H
     pred = up.permute(0, 2, 3, 1).contiguous()                                                                      # NHWC rows
     target = torch.zeros((B, H, H, p4), dtype=torch.float32, device=dev)
     target[..., :n4] = img.permute(0, 2, 3, 1)
-    row_loss = torch.empty((Mu,), dtype=torch.float32, device=dev)
-    dup = torch.empty((Mu, p4), dtype=torch.bfloat16, device=dev) if need_grad else None
-    _call("cmdiad_loss_head", ops._p(pred), ops._p(target), Mu, p4, 0 + 256, 1.0 / batch, ops._p(row_loss), ops._p(dup), None, ops._stream())
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    _call("cmdiad_sum_vector", ops._p(row_loss), Mu, 1.0 / batch, ops._p(loss), ops._stream())
+    loss, dup = ops.loss_and_grad(pred.view(Mu, p4), target.view(Mu, p4), ops.LOSS_L2, batch, need_grad)
     if not need_grad:
         return loss, None
     dout = ops.upsample_bicubic_bwd(dup.float().view(B, H, H, p4), h, h)                                            # [B,56,56,4] f32
     dz4 = torch.zeros((M, 64), dtype=torch.bfloat16, device=dev)
     dz4[:, :p4] = dout.view(M, p4).to(torch.bfloat16)
-    g_w4, g_b4 = _dw(dz4, a3, (64, p3))
+    g_w4, g_b4 = _dw(dz4, a3)
     _, dz3 = ops.gemm(dz4, ops.transpose_bf16(w4h), dact_of=z3)          # [M,128] = (dz4 W4) * GELU'(z3)
-    g_w3, g_b3 = _dw(dz3, a2, (p3, w3.shape[1]))
+    g_w3, g_b3 = _dw(dz3, a2)
     _, dz2 = ops.gemm(dz3, ops.transpose_bf16(w3h), dact_of=z2)
-    g_w2, g_b2 = _dw(dz2, a1, tuple(w2.shape))
+    g_w2, g_b2 = _dw(dz2, a1)
     _, dz1 = ops.gemm(dz2, ops.transpose_bf16(w2h), dact_of=z1)
-    g_w1, g_b1 = _dw(dz1, h0, tuple(w1.shape))
+    g_w1, g_b1 = _dw(dz1, h0)
     dh0, _ = ops.gemm(dz1, ops.transpose_bf16(w1h), want_f32=True, want_bf16=False)
-    pg = torch.empty((CHUNKS, D), dtype=torch.float32, device=dev)
-    pb = torch.empty((CHUNKS, D), dtype=torch.float32, device=dev)
-    _call("cmdiad_ln_param_grad", ops._p(dh0), ops._p(x2), ops._p(mean), ops._p(rstd), M, D, CHUNKS, ops._p(pg), ops._p(pb), ops._stream())
-    g_lnw = _reduce_slabs(pg, CHUNKS, D, torch.empty((D,), dtype=torch.float32, device=dev))
-    g_lnb = _reduce_slabs(pb, CHUNKS, D, torch.empty((D,), dtype=torch.float32, device=dev))
+    g_lnw, g_lnb = _ln_grads(dh0, x2, mean, rstd)
     return loss, (g_lnw, g_lnb, g_w1, g_b1, g_w2, g_b2, g_w3[:n3].contiguous(), g_b3[:n3].contiguous(),
                   g_w4[:n4, :n3].contiguous(), g_b4[:n4].contiguous())
-
-
-class _FtoIMlpLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, img, batch, need_grad, *params):
-        loss, grads = ftoi_mlp_forward_backward(x, img, tuple(p.detach() for p in params), batch, need_grad)
-        ctx.grads, ctx.n_params = grads, len(params)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        if ctx.grads is None:
-            return (None,) * (4 + ctx.n_params)
-        return (None,) * 4 + tuple(gr * g for gr in ctx.grads)
 
 
 def ftoi_mlp_loss(module, x, img):
@@ -365,8 +263,7 @@ def ftoi_mlp_loss(module, x, img):
     params = (module.rgb_norm.weight, module.rgb_norm.bias) + tuple(p for m in lin for p in (m.weight, m.bias))
     dev = params[0].device
     x, img = x.to(dev).float().contiguous(), img.to(dev).float().contiguous()
-    need = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-    return _FtoIMlpLoss.apply(x, img, x.shape[0], need, *params)
+    return step_loss(lambda ps, need_grad: ftoi_mlp_forward_backward(x, img, ps, x.shape[0], need_grad) + (None,), params)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -383,14 +280,7 @@ def ftoi_mlp_loss(module, x, img):
 def _bn_affine(z, gamma, beta, eps=EPS):
     """Batch statistics of z [M,C] -> ((scale, shift, mean, rstd) f32, (mean, biased variance) f64): cmdiad_col_moments +
     cmdiad_bn_affine (two launches and one memset per BatchNorm)."""
-    M, C = z.shape
-    acc = torch.zeros((2, C), dtype=torch.float64, device=z.device)
-    _call("cmdiad_col_moments", ops._p(z), M, C, z.stride(0), ops._p(acc[0]), ops._p(acc[1]), ops._stream())
-    st64 = torch.empty((2, C), dtype=torch.float64, device=z.device)
-    aff = torch.empty((4, C), dtype=torch.float32, device=z.device)
-    _call("cmdiad_bn_affine", ops._p(acc[0]), ops._p(acc[1]), ops._p(gamma), ops._p(beta), M, float(eps), C, ops._p(st64[0]), ops._p(st64[1]),
-          ops._p(aff[0]), ops._p(aff[1]), ops._p(aff[2]), ops._p(aff[3]), ops._stream())
-    return (aff[0], aff[1], aff[2], aff[3]), (st64[0], st64[1])
+    return ops.bn_affine(ops.col_sums(z), gamma, beta, z.shape[0], eps)
 
 
 def _w1x1(w):
@@ -400,7 +290,6 @@ def _w1x1(w):
 def hrnet_forward_backward(img, feature, P, batch, need_grad=True):
     """img [B,3,224,224] f32, feature [B,3136,768] f32, P: dict name -> fp32 parameter tensor (the state_dict names of the trunk).
     -> (loss, {name: grad} | None, {bn name: (batch mean, biased batch variance)} in float64)."""
-    from .train import _dw
     B = img.shape[0]
     dev = img.device
     stats, saved = {}, {}
@@ -412,13 +301,10 @@ def hrnet_forward_backward(img, feature, P, batch, need_grad=True):
         return wcache[name]
 
     def dw1x1(dz, a, shape):   # weight gradient of a 1x1 convolution without bias: dz^T a over the tokens (split over M, fixed-order sum)
-        split = _split_for(dz.shape[0], shape[0], shape[1])
         if dz.shape[0] % 64:
-            return _dw(dz, a, (shape[0], shape[1]))[0].view(shape)
-        out = ops.gemm_tn(dz, a, split_k=split)
-        if split > 1:
-            out = _reduce_slabs(out, split, shape[0] * shape[1], torch.empty((shape[0], shape[1]), dtype=torch.float32, device=dz.device))
-        return out.view(shape)
+            return _dw(dz, a)[0].view(shape)
+        split = _split_for(dz.shape[0], shape[0], shape[1])
+        return _sum_slabs(ops.gemm_tn(dz, a, split_k=split), split, shape[0] * shape[1]).view(shape)
 
     def bn(name, z, residual=None, relu=True, want_f32=False):
         aff, st = _bn_affine(z, P[name + ".weight"], P[name + ".bias"])
@@ -459,12 +345,7 @@ def hrnet_forward_backward(img, feature, P, batch, need_grad=True):
     Wf = _w1x1(P["final_layer.weight"])
     out, _ = ops.gemm(x16, Wf, bias=P["final_layer.bias"].contiguous(), want_f32=True, want_bf16=False)
     N = out.shape[1]
-    row_loss = torch.empty((M,), dtype=torch.float32, device=dev)
-    dout = torch.empty((M, N), dtype=torch.bfloat16, device=dev) if need_grad else None
-    _call("cmdiad_loss_head", ops._p(out), ops._p(feature.reshape(M, N).contiguous()), M, N, 0 + 256, 1.0 / batch, ops._p(row_loss),
-          ops._p(dout), None, ops._stream())
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    _call("cmdiad_sum_vector", ops._p(row_loss), M, 1.0 / batch, ops._p(loss), ops._stream())
+    loss, dout = ops.loss_and_grad(out, feature.reshape(M, N).contiguous(), ops.LOSS_L2, batch, need_grad)
     if not need_grad:
         return loss, None, stats
     G = {}
@@ -475,7 +356,7 @@ def hrnet_forward_backward(img, feature, P, batch, need_grad=True):
         G[name + ".weight"], G[name + ".bias"] = dg, db
         return dz
 
-    G["final_layer.weight"], G["final_layer.bias"] = _dw(dout, x16, (N, Wf.shape[1]))
+    G["final_layer.weight"], G["final_layer.bias"] = _dw(dout, x16)
     G["final_layer.weight"] = G["final_layer.weight"].view(N, -1, 1, 1)
     dX, _ = ops.gemm(dout, ops.transpose_bf16(Wf), want_f32=True, want_bf16=False)             # [M,512] f32
     for b in reversed(blocks):
@@ -552,37 +433,6 @@ def _hrnet_step(img, feature, P, batch, need_grad):
     return loss.clone(), G, stats, (ent, ent["gen"])     # (the loss outlives the step in most training loops; the gradients do not)
 
 
-class _HRNetLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, img, feature, batch, need_grad, module, names, *params):
-        P = {n: p.detach() for n, p in zip(names, params)}
-        loss, G, stats, ctx.replay = _hrnet_step(img, feature, P, batch, need_grad)
-        M1, M2 = img.shape[0] * ((img.shape[-1] + 1) // 2) ** 2, feature.shape[0] * feature.shape[1]
-        mods = dict(module.named_modules())
-        with torch.no_grad():   # nn.BatchNorm2d in train(): momentum, UNBIASED variance into the running buffer
-            for name, (mean64, var64) in stats.items():
-                bn = mods[name]
-                if bn.track_running_stats and bn.running_mean is not None:
-                    n = M1 if name == "bn1" else M2
-                    mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked + 1)
-                    bn.running_mean.mul_(1 - mom).add_(mean64.to(bn.running_mean.dtype), alpha=mom)
-                    bn.running_var.mul_(1 - mom).add_((var64 * (n / (n - 1))).to(bn.running_var.dtype), alpha=mom)
-                    bn.num_batches_tracked += 1
-        ctx.grads = None if G is None else tuple(G.get(n) for n in names)
-        ctx.n_params = len(params)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        if ctx.grads is None:
-            return (None,) * (6 + ctx.n_params)
-        if ctx.replay is not None and ctx.replay[0].get("gen") != ctx.replay[1]:
-            raise RuntimeError("HRNet training step: backward() of a forward whose gradients have been overwritten -- the hand-written "
-                               "step keeps them in its HIP graph's buffers until the NEXT forward of the same shapes; call backward() "
-                               "first, or set CMDIAD_HRNET_GRAPH=0")
-        return (None,) * 6 + tuple(None if gr is None else gr * g for gr in ctx.grads)
-
-
 def hrnet_loss(module, img, feature):
     """module: models.hrnet.HRNet (c = 512); img [B,3,224,224], feature [B,3136,768] -> its training loss (hrnet.py:290-299),
     differentiable w.r.t. every parameter its forward uses (layer4 is constructed but never run: no gradient, as in the reference)."""
@@ -590,5 +440,19 @@ def hrnet_loss(module, img, feature):
     _check_bn([m for n, m in module.named_modules() if isinstance(m, torch.nn.BatchNorm2d) and not n.startswith("layer4.")])
     dev = params[0].device
     img, feature = img.to(dev).float().contiguous(), feature.to(dev).float().contiguous()
-    need = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-    return _HRNetLoss.apply(img, feature, img.shape[0], need, module, names, *params)
+    B = img.shape[0]
+    M1, M2 = B * ((img.shape[-1] + 1) // 2) ** 2, B * feature.shape[1]     # values per channel behind bn1 / every other BatchNorm
+
+    def step(ps, need_grad):
+        loss, G, stats, replay = _hrnet_step(img, feature, dict(zip(names, ps)), B, need_grad)
+        mods = dict(module.named_modules())
+        for name, (mean64, var64) in stats.items():
+            update_running_stats(mods[name], mean64, var64, M1 if name == "bn1" else M2)
+
+        def check():
+            if replay[0].get("gen") != replay[1]:
+                raise RuntimeError("HRNet training step: backward() of a forward whose gradients have been overwritten -- the hand-written "
+                                   "step keeps them in its HIP graph's buffers until the NEXT forward of the same shapes; call backward() "
+                                   "first, or set CMDIAD_HRNET_GRAPH=0")
+        return loss, None if G is None else tuple(G.get(n) for n in names), check if replay is not None else None
+    return step_loss(step, params)

@@ -15,12 +15,10 @@ The other heads of the reference file -- HallucinationCrossModalityConv (72-143)
 (cmdiad_conv2d_nhwc_bf16) and cmdiad_upsample_bicubic.  TRAINING (``train()`` with gradients enabled:
 hallucination_network_pretrain.py:106-147): all three train on the hand-written paths of cmdiad_amd/conv_train.py (batch-statistics
 BatchNorm, bf16 MFMA convolutions / GEMMs forward, data gradient and weight gradient, bicubic adjoint; exposed to autograd so the
-reference's loop runs unchanged); CMDIAD_CONV_TRAIN=torch selects the modules' own torch layers (fp32, MIOpen / rocBLAS) as the A/B
-reference.  tests/test_gpu_heads.py checks a three-step Adam loss curve of each head against the reference's own (golden G12);
-tests/test_gpu_conv_train.py the hand-written paths against torch autograd.
+reference's loop runs unchanged); the ``nn`` layers are parameter containers.  tests/test_gpu_heads.py checks a three-step Adam loss
+curve of each head against the reference's own (golden G12); tests/test_gpu_conv_train.py the hand-written paths against torch
+autograd through these layers (tests/heads_torch_ref.py).
 """
-import os
-
 import torch
 import torch.nn as nn
 
@@ -63,9 +61,6 @@ class _PackedHead(nn.Module):
     def _autograd(self):
         """True when forward() has to build a graph: train() mode with gradients enabled (the pretraining loop)."""
         return self.training and torch.is_grad_enabled()
-
-    def _device(self):
-        return next(self.parameters()).device
 
     @staticmethod
     def _mean_row_norm(a, b, dim):
@@ -161,19 +156,13 @@ class HallucinationCrossModalityConv(_PackedHead):
 
     def forward(self, xyz_feature, rgb_feature, sigmoid, dist_method):
         """hallucination_network.py:133-147 -> (distance_to_xyz_real, distance_to_rgb_real)."""
-        if self._autograd() and os.environ.get("CMDIAD_CONV_TRAIN", "hip") == "hip":
+        if self._autograd():
             # hand-written forward + backward (cmdiad_amd/conv_train.py): batch-statistics BatchNorm, bf16 MFMA convolutions,
             # exposed to autograd so loss.backward() / Adam of the reference's loop work unchanged
             from .. import conv_train
             assert xyz_feature.shape[1:] == (3136, self.xyz_dim) and rgb_feature.shape[1:] == (3136, self.rgb_dim)
             return (conv_train.tower_loss(self.rgb_conv, rgb_feature, xyz_feature, sigmoid is True),
                     conv_train.tower_loss(self.xyz_conv, xyz_feature, rgb_feature, sigmoid is True))
-        if self._autograd():   # CMDIAD_CONV_TRAIN=torch: the towers' own torch layers (MIOpen) -- the A/B reference of the above
-            dev = self._device()
-            xyz_feature, rgb_feature = xyz_feature.to(dev).float(), rgb_feature.to(dev).float()
-            xyz_h = feature_reshape_back(self.rgb_conv(feature_reshape(rgb_feature)))
-            rgb_h = feature_reshape_back(self.xyz_conv(feature_reshape(xyz_feature)))
-            return self._losses(xyz_h, rgb_h, xyz_feature, rgb_feature, sigmoid)
         with torch.no_grad():
             xyz_h, rgb_h = self.hallucination_generation(xyz_feature, rgb_feature, 'train')
             return self._losses(xyz_h, rgb_h, xyz_feature.to(xyz_h.device), rgb_feature.to(rgb_h.device), sigmoid)
@@ -212,15 +201,10 @@ class HallucinationRGBFeatureToXYZInputMLP(_PackedHead):
     def forward(self, rgb_feature, xyz):
         """hallucination_network.py:174-182."""
         rgb_feature = rgb_feature.reshape(rgb_feature.shape[0], rgb_feature.shape[1], -1)
-        if self._autograd() and os.environ.get("CMDIAD_CONV_TRAIN", "hip") == "hip":   # hand-written forward + backward
+        if self._autograd():   # hand-written forward + backward
             from .. import conv_train
             assert rgb_feature.shape[1:] == (3136, self.rgb_dim) and xyz.shape[2:] == (224, 224)
             return conv_train.ftoi_mlp_loss(self, rgb_feature, xyz)
-        if self._autograd():   # CMDIAD_CONV_TRAIN=torch: the module's own torch layers, the A/B reference of the above
-            dev = self._device()
-            x = self.mlp(self.rgb_norm(rgb_feature.to(dev).float())).transpose(1, 2)
-            h = nn.functional.interpolate(x.reshape(x.shape[0], x.shape[1], 56, 56), size=(224, 224), mode='bicubic')
-            return self._mean_row_norm(h, xyz.to(dev), 1)
         with torch.no_grad():
             h = self.hallucination_generation(rgb_feature)
             return self._mean_row_norm(h, xyz.to(h.device), 1)
@@ -246,18 +230,10 @@ class HallucinationFeatureToInputConv(_PackedHead):
 
     def forward(self, feature, img):
         """hallucination_network.py:211-220."""
-        if self._autograd() and os.environ.get("CMDIAD_CONV_TRAIN", "hip") == "hip":   # hand-written forward + backward
+        if self._autograd():   # hand-written forward + backward
             from .. import conv_train
             assert feature.shape[1:] == (3136, self.dim) and img.shape[1:] == (3, 224, 224)
             return conv_train.ftoi_conv_loss(self, feature, img)
-        if self._autograd():   # CMDIAD_CONV_TRAIN=torch: the module's own torch layers, the A/B reference of the above
-            dev = self._device()
-            f = feature.to(dev).float().transpose(1, 2)
-            h = self.conv1(f.reshape(f.shape[0], f.shape[1], 56, 56))
-            h = nn.functional.interpolate(h, size=(224, 224), mode='bicubic')
-            h = self.conv4(torch.relu(self.conv3(torch.relu(self.conv2(h)))))
-            assert h.shape[1:] == (3, 224, 224) and img.shape[1:] == (3, 224, 224)
-            return self._mean_row_norm(h, img.to(dev), 1)
         with torch.no_grad():
             h = self.hallucination_generation(feature)
             assert h.shape[1:] == (3, 224, 224) and img.shape[1:] == (3, 224, 224)

@@ -8,13 +8,10 @@ StageModule / BasicBlock / transition code of that file is commented out or neve
 SURVEY 8f row f4: same constructor, state_dict keys and method signatures.  Inference (``eval()`` / ``no_grad``): eval-mode
 arithmetic with BatchNorm folded, on cmdiad_conv_stem + cmdiad_conv2d_nhwc_bf16 (cmdiad_amd.runtime.PackedHRNet).  Training
 (``train()`` with gradients: --train_method *InputTo*FeatureHRNET): the hand-written forward + backward of
-cmdiad_amd/conv_train.py from batch 16 up (the reference's default batch is 64; 1.4x the torch layers at batch 32), the module's own
-torch layers on the GPU (fp32, batch-statistics BatchNorm, autograd; MIOpen kernels) below that, where the hand-written path's
-~500 launches per step are not hidden yet; CMDIAD_HRNET_TRAIN=hip / torch forces one.  Both follow golden G12
-(tests/test_gpu_heads.py) and agree with each other (tests/test_gpu_conv_train.py).
+cmdiad_amd/conv_train.py at every batch size (its ~500 launches per step are replayed as one HIP graph from the third step on); the
+``nn`` layers are parameter containers.  It follows golden G12 (tests/test_gpu_heads.py) and agrees with torch autograd through
+these layers (tests/test_gpu_conv_train.py, tests/heads_torch_ref.py).
 """
-import os
-
 import torch
 from torch import nn
 
@@ -38,7 +35,7 @@ class Bottleneck(nn.Module):
         self.stride = stride
 
     def forward(self, x):
-        """hrnet.py:23-43 (training path of HRNet.forward; inference never calls it)."""
+        """hrnet.py:23-43 (the torch reference of the training tests runs it; the package's own paths never do)."""
         out = torch.relu(self.bn1(self.conv1(x)))
         out = torch.relu(self.bn2(self.conv2(out)))
         out = self.bn3(self.conv3(out))
@@ -76,22 +73,11 @@ class HRNet(_PackedHead):
         """hrnet.py:290-299."""
         # hand-written forward + backward (cmdiad_amd/conv_train.py), replayed as one HIP graph from the third step on: 5.6 / 6.2 /
         # 7.2 / 9.1 / 12.9 / 21.3 ms at batch 1 / 2 / 4 / 8 / 16 / 32 against 7.7 / 7.9 / 7.5 / 11.9 / 21.0 / 39.9 ms on the module's
-        # torch layers (MIOpen / rocBLAS; profiles/r4_notes.md section 17).  CMDIAD_HRNET_TRAIN = auto (default: the hand-written
-        # path) | hip | torch (the module's own layers, kept for A/B runs).
-        mode = os.environ.get("CMDIAD_HRNET_TRAIN", "auto")
-        if mode == "auto":
-            mode = "hip"
-        if self._autograd() and mode == "hip":
+        # torch layers (MIOpen / rocBLAS; profiles/r4_notes.md section 17).
+        if self._autograd():
             from .. import conv_train
             assert tuple(img.shape[1:]) == (3, 224, 224) and tuple(feature.shape[1:]) == (3136, self.final_layer.out_channels)
             return conv_train.hrnet_loss(self, img, feature)
-        if self._autograd():   # CMDIAD_HRNET_TRAIN=torch: the module's own torch layers (MIOpen / rocBLAS, autograd)
-            dev = self._device()
-            x = torch.relu(self.bn1(self.conv1(img.to(dev).float())))
-            x = torch.relu(self.bn2(self.conv2(x)))
-            x = self.final_layer(self.layer3(self.layer2(self.layer1(x))))
-            assert tuple(x.shape[1:]) == (768, 56, 56) and tuple(feature.shape[1:]) == (3136, 768)
-            return self._mean_row_norm(feature_reshape_back(x), feature.to(dev), 2)
         with torch.no_grad():
             h = self.hallucination_tokens(img)
             assert tuple(h.shape[1:]) == (3136, 768) and tuple(feature.shape[1:]) == (3136, 768)

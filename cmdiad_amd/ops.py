@@ -11,6 +11,10 @@ import torch
 from . import _native as nat
 
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_RELU_POST = 0, 1, 2, 3
+# cmdiad_loss_head: mode = the row loss + the activation of the network's output (include/cmdiad_hip.h CMDIAD_LOSS_OUT_*; the GELU
+# that closes an MlpBlock is the default, SIGMOID applies to the output AND the target)
+LOSS_L2, LOSS_COS_DIST, LOSS_SMOOTH_L1 = 0, 1, 2
+LOSS_OUT_GELU, LOSS_OUT_NONE, LOSS_OUT_SIGMOID = 0, 256, 512
 # "no candidate yet" key: the largest NON-NEGATIVE int64.  Every real key is (fp32 bits of d2 >= +0) << 32 | row, i.e. has bit 63
 # clear, so this sentinel is >= every real key under the kernels' unsigned atomicMin AND under the signed MIN all-reduce of the
 # row-sharded search (a rank whose shard is empty contributes only sentinels and can never win the reduce).
@@ -412,14 +416,32 @@ def lead_rows(x, pos, lead_x, lead_pos, B, T):
     return x
 
 
-def col_moments(x):
-    """x [rows, C] f32 -> (mean [C], biased variance [C]) in float64 (cmdiad_col_moments)."""
-    _chk(x, torch.float32, "col_moments.x")
+def col_sums(x):
+    """x [rows, C] f32 -> [2, C] float64: the column sums of x and of x^2 (cmdiad_col_moments)."""
+    _chk(x, torch.float32, "col_sums.x")
     rows, C = x.shape
     acc = torch.zeros((2, C), dtype=torch.float64, device=x.device)
     _call("cmdiad_col_moments", _p(x), rows, C, x.stride(0), _p(acc[0]), _p(acc[1]), _stream())
+    return acc
+
+
+def col_moments(x):
+    """x [rows, C] f32 -> (mean [C], biased variance [C]) in float64 (cmdiad_col_moments)."""
+    acc, rows = col_sums(x), x.shape[0]
     mean = acc[0] / rows
     return mean, acc[1] / rows - mean * mean
+
+
+def bn_affine(sums, gamma, beta, rows, eps):
+    """sums [2, C] f64 (col_sums of the rows-row batch), gamma, beta [C] f32 -> ((scale, shift, mean, rstd) f32, (mean, biased
+    variance) f64): the constants of batch-statistics BatchNorm, y = z * scale + shift (cmdiad_bn_affine)."""
+    _chk(sums, torch.float64, "bn_affine.sums"); _chk(gamma, torch.float32, "bn_affine.gamma"); _chk(beta, torch.float32, "bn_affine.beta")
+    C = sums.shape[1]
+    st64 = torch.empty((2, C), dtype=torch.float64, device=sums.device)
+    aff = torch.empty((4, C), dtype=torch.float32, device=sums.device)
+    _call("cmdiad_bn_affine", _p(sums[0]), _p(sums[1]), _p(gamma), _p(beta), rows, float(eps), C, _p(st64[0]), _p(st64[1]),
+          _p(aff[0]), _p(aff[1]), _p(aff[2]), _p(aff[3]), _stream())
+    return (aff[0], aff[1], aff[2], aff[3]), (st64[0], st64[1])
 
 
 def bn_relu_fwd(z, scale, shift, residual=None, relu=True, want_bf16=True, want_f32=False):
@@ -453,6 +475,80 @@ def bn_relu_bwd(dy, z, scale, shift, mean, rstd, chunks=None, masked=True):
     _call("cmdiad_bn_relu_bwd_apply", _p(dy), _p(z), _p(scale), _p(shift), _p(mean), _p(rstd), _p(dbeta), _p(dgamma), mk, M, C, _p(dz),
           _stream())
     return dz, dgamma, dbeta
+
+
+def loss_head(pred, target, mode, out_act, inv_b, want_grad=True, want_y=False):
+    """pred, target [M,D] f32 -> (row_loss [M] f32, dpred [M,D] bf16 | None[, y [M,D] f32]): the LOSS_* row loss of
+    y = LOSS_OUT_*(pred) against target, dpred = inv_b * d sum(row_loss) / d pred (cmdiad_loss_head)."""
+    _chk(pred, torch.float32, "loss_head.pred"); _chk(target, torch.float32, "loss_head.target")
+    M, D = pred.shape
+    if tuple(target.shape) != (M, D):
+        raise ValueError(f"loss_head: pred {tuple(pred.shape)} against target {tuple(target.shape)}")
+    row_loss = torch.empty((M,), dtype=torch.float32, device=pred.device)
+    dpred = torch.empty((M, D), dtype=torch.bfloat16, device=pred.device) if want_grad else None
+    y = torch.empty((M, D), dtype=torch.float32, device=pred.device) if want_y else None
+    _call("cmdiad_loss_head", _p(pred), _p(target), M, D, mode + out_act, inv_b, _p(row_loss), _p(dpred), _p(y), _stream())
+    return (row_loss, dpred, y) if want_y else (row_loss, dpred)
+
+
+def sum_vector(x, scale=1.0):
+    """x [n] f32 -> scale * sum(x) as a 0-dim f32 tensor, in a fixed order (cmdiad_sum_vector)."""
+    _chk(x, torch.float32, "sum_vector.x")
+    out = torch.empty((), dtype=torch.float32, device=x.device)
+    _call("cmdiad_sum_vector", _p(x), x.numel(), scale, _p(out), _stream())
+    return out
+
+
+def loss_and_grad(pred, target, mode, batch, need_grad, out_act=LOSS_OUT_NONE):
+    """The tail of every training head: -> (loss 0-dim f32 = sum of the row losses / batch, dpred [M,D] bf16 = d loss / d pred |
+    None).  loss_head + sum_vector, 1 / batch in both."""
+    row_loss, dpred = loss_head(pred, target, mode, out_act, 1.0 / batch, want_grad=need_grad)
+    return sum_vector(row_loss, 1.0 / batch), dpred
+
+
+def reduce_slabs(slabs, S, n, out, scale=1.0):
+    """out[:n] = scale * (slabs[0] + ... + slabs[S - 1]) in that order: slabs [S, n] f32 (any shape of n values per slab), out f32
+    (cmdiad_reduce_slabs)."""
+    _chk(slabs, torch.float32, "reduce_slabs.slabs"); _chk(out, torch.float32, "reduce_slabs.out")
+    if slabs.numel() < S * n or out.numel() < n:
+        raise ValueError(f"reduce_slabs: {S} slabs of {n} values from {slabs.numel()}, into {out.numel()}")
+    _call("cmdiad_reduce_slabs", _p(slabs), S, n, n, float(scale), _p(out), _stream())
+    return out
+
+
+def colsum_bf16(x, chunks):
+    """x [M,N] bf16 -> [chunks, N] f32: the column sums of each chunk of ceil(M / chunks) rows (cmdiad_colsum_bf16)."""
+    _chk(x, torch.bfloat16, "colsum.x")
+    M, N = x.shape
+    part = torch.empty((chunks, N), dtype=torch.float32, device=x.device)
+    _call("cmdiad_colsum_bf16", _p(x), M, N, chunks, _p(part), _stream())
+    return part
+
+
+def ln_param_grad(dh, x, mean, rstd, chunks):
+    """dh, x [M,C] f32 (x: the LayerNorm's input), mean, rstd [M] f32 (its saved row statistics) -> the partial weight and bias
+    gradients of each chunk of rows, two [chunks, C] f32 (cmdiad_ln_param_grad; reduce_slabs sums them)."""
+    for t, n in ((dh, "dh"), (x, "x"), (mean, "mean"), (rstd, "rstd")):
+        _chk(t, torch.float32, "ln_param_grad." + n)
+    M, C = x.shape
+    if tuple(dh.shape) != (M, C) or mean.numel() != M or rstd.numel() != M:
+        raise ValueError(f"ln_param_grad: dh {tuple(dh.shape)}, x {tuple(x.shape)}, {mean.numel()} / {rstd.numel()} row statistics")
+    pg = torch.empty((chunks, C), dtype=torch.float32, device=x.device)
+    pb = torch.empty((chunks, C), dtype=torch.float32, device=x.device)
+    _call("cmdiad_ln_param_grad", _p(dh), _p(x), _p(mean), _p(rstd), M, C, chunks, _p(pg), _p(pb), _stream())
+    return pg, pb
+
+
+def adam_step(p, grad, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0, p_bf16=None):
+    """torch.optim.Adam's update of p (no weight decay, no amsgrad) on grad * grad_scale, in place in p, m, v (f32, same size);
+    p_bf16: refreshed with the bf16 cast of the new p (cmdiad_adam_step)."""
+    for t, n in ((p, "p"), (grad, "grad"), (m, "m"), (v, "v")):
+        _chk(t, torch.float32, "adam_step." + n)
+    _chk(p_bf16, torch.bfloat16, "adam_step.p_bf16")
+    if not grad.numel() == m.numel() == v.numel() == p.numel():
+        raise ValueError("adam_step: p, grad, m and v must have the same number of elements")
+    _call("cmdiad_adam_step", _p(p), _p(grad), _p(m), _p(v), p.numel(), float(lr), beta1, beta2, eps, step, float(grad_scale),
+          _p(p_bf16), _stream())
 
 
 def relu_bwd(dx, y, want_bf16=True, want_f32=False):

@@ -17,53 +17,36 @@ unchanged.  Forward and backward are computed together by the kernels:
 ``FusedAdam`` is an optional torch.optim.Optimizer with the update of torch.optim.Adam (no weight decay,
 no amsgrad) running in one HIP kernel per parameter.
 """
-import os
-
 import torch
 
-from . import _native as nat
 from . import ops
 
-_MODE = {"l2": 0, "cos_dist": 1, "smooth_l1": 2}
+_MODE = {"l2": ops.LOSS_L2, "cos_dist": ops.LOSS_COS_DIST, "smooth_l1": ops.LOSS_SMOOTH_L1}
 SPLIT_K = 8
 CHUNKS = 64
+_call, _reduce_slabs = ops._call, ops.reduce_slabs   # the binding layer's, under the names this module had of its own
 
 
-def _call(name, *args):
-    nat.check(getattr(nat.lib(), name)(*args), name)
+def _sum_slabs(out, split, n, dst=None):
+    """out: what a split-K product returned -- n f32 values (split == 1) or `split` slabs of them.  -> their fixed-order sum in dst
+    (a single slab is copied there); without dst a single slab is returned as it is and several are summed into a new tensor."""
+    if split == 1:
+        return out if dst is None else dst.copy_(out)
+    if dst is None:
+        dst = torch.empty(out.shape[1:], dtype=torch.float32, device=out.device)
+    return ops.reduce_slabs(out, split, n, dst)
 
 
-def _reduce_slabs(slabs, S, n, out, scale=1.0):
-    _call("cmdiad_reduce_slabs", ops._p(slabs), S, n, n, float(scale), ops._p(out), ops._stream())
-    return out
-
-
-def _dw(dz, a, out_shape):
+def _dw(dz, a):
     """(dW [dout, din], db [dout]) = sums over the M tokens of dz[m, :]^T a[m, :] and of dz[m, :], split-K over M.  Both
     operands stay row-major (cmdiad_gemm_tn_bf16 gathers its MFMA fragments with transposing LDS reads and adds the column
-    sums of dz from the tiles it has staged anyway); CMDIAD_TRAIN_TN=0 selects the earlier form -- transpose both operands,
-    the K-contiguous GEMM, a separate column-sum kernel -- for A/B runs."""
+    sums of dz from the tiles it has staged anyway)."""
     dzp, ap = _pad_rows(dz), _pad_rows(a)
     M = dzp.shape[0]
     split = SPLIT_K if M >= 64 * SPLIT_K * 4 else 1
-    if os.environ.get("CMDIAD_TRAIN_TN", "1") != "0":
-        slabs, cs = ops.gemm_tn(dzp, ap, split_k=split, want_colsum=True)
-        db = cs if split == 1 else _reduce_slabs(cs, split, cs.shape[1], torch.empty((cs.shape[1],), dtype=torch.float32, device=dz.device))
-    else:
-        slabs, _ = ops.gemm(ops.transpose_bf16(dzp), ops.transpose_bf16(ap), want_f32=True, want_bf16=False, split_k=split)
-        db = _db(dz)
-    if split == 1:
-        return slabs, db
-    out = torch.empty(out_shape, dtype=torch.float32, device=dz.device)
-    return _reduce_slabs(slabs, split, out.numel(), out), db
-
-
-def _db(dz):
-    M, N = dz.shape
-    part = torch.empty((CHUNKS, N), dtype=torch.float32, device=dz.device)
-    _call("cmdiad_colsum_bf16", ops._p(dz), M, N, CHUNKS, ops._p(part), ops._stream())
-    out = torch.empty((N,), dtype=torch.float32, device=dz.device)
-    return _reduce_slabs(part, CHUNKS, N, out)
+    slabs, cs = ops.gemm_tn(dzp, ap, split_k=split, want_colsum=True)
+    db = _sum_slabs(cs, split, cs.shape[-1])
+    return _sum_slabs(slabs, split, slabs.shape[-2] * slabs.shape[-1]), db
 
 
 def _pad_rows(t, mult=64):
@@ -82,7 +65,7 @@ def forward_backward(x, target, params, dist_method, batch, need_grad=True):
     ln_w, ln_b = params[:2]
     blocks = [params[2 + 6 * d: 8 + 6 * d] for d in range((len(params) - 2) // 6)]
     assert blocks and len(params) == 2 + 6 * len(blocks)
-    M, D = x.shape
+    M = x.shape[0]
     dev = x.device
     mode = _MODE[dist_method]
     mean = torch.empty((M,), dtype=torch.float32, device=dev)
@@ -108,13 +91,7 @@ def forward_backward(x, target, params, dist_method, batch, need_grad=True):
             _, nxt = ops.gemm(a2, w3h, bias=b3, act=ops.ACT_GELU, out_pre_bf16=z3b)
             saved.append((h, z1, a1, z2, a2, z3b, (w1h, w2h, w3h)))
             h = nxt
-    Dout = blocks[-1][4].shape[0]
-    row_loss = torch.empty((M,), dtype=torch.float32, device=dev)
-    dz3 = torch.empty((M, Dout), dtype=torch.bfloat16, device=dev) if need_grad else None
-    _call("cmdiad_loss_head", ops._p(z3), ops._p(target.contiguous()), M, Dout, mode, 1.0 / batch, ops._p(row_loss),
-          ops._p(dz3), None, ops._stream())
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    _call("cmdiad_sum_vector", ops._p(row_loss), M, 1.0 / batch, ops._p(loss), ops._stream())
+    loss, dz3 = ops.loss_and_grad(z3, target.contiguous(), mode, batch, need_grad, out_act=ops.LOSS_OUT_GELU)
     if not need_grad:
         return loss, None
     # ---- backward, last block first
@@ -122,40 +99,67 @@ def forward_backward(x, target, params, dist_method, batch, need_grad=True):
     dh0 = None
     for d in range(len(blocks) - 1, -1, -1):
         inp, z1, a1, z2, a2, _, (w1h, w2h, w3h) = saved[d]
-        w1, _, w2, _, w3, _ = blocks[d]
         w3t, w2t, w1t = ops.transpose_bf16(w3h), ops.transpose_bf16(w2h), ops.transpose_bf16(w1h)   # [H,Dout], [H,H], [D,H]
         _, dz2 = ops.gemm(dz3, w3t, dact_of=z2)                       # [M,H]  = (dz3 W3) * GELU'(z2)
         _, dz1 = ops.gemm(dz2, w2t, dact_of=z1)                       # [M,H]
-        g_w3, g_b3 = _dw(dz3, a2, w3.shape)
-        g_w2, g_b2 = _dw(dz2, a1, w2.shape)
-        g_w1, g_b1 = _dw(dz1, inp, w1.shape)
+        g_w3, g_b3 = _dw(dz3, a2)
+        g_w2, g_b2 = _dw(dz2, a1)
+        g_w1, g_b1 = _dw(dz1, inp)
         grads[d] = (g_w1, g_b1, g_w2, g_b2, g_w3, g_b3)
         if d > 0:   # into the previous block through its closing GELU: (dz1 W1) * GELU'(z3 of block d-1)
             _, dz3 = ops.gemm(dz1, w1t, dact_of=saved[d - 1][5])
         else:
             dh0, _ = ops.gemm(dz1, w1t, want_f32=True, want_bf16=False)   # [M,D] f32
-    pg = torch.empty((CHUNKS, D), dtype=torch.float32, device=dev)
-    pb = torch.empty((CHUNKS, D), dtype=torch.float32, device=dev)
-    _call("cmdiad_ln_param_grad", ops._p(dh0), ops._p(x), ops._p(mean), ops._p(rstd), M, D, CHUNKS, ops._p(pg), ops._p(pb),
-          ops._stream())
-    g_lnw = _reduce_slabs(pg, CHUNKS, D, torch.empty((D,), dtype=torch.float32, device=dev))
-    g_lnb = _reduce_slabs(pb, CHUNKS, D, torch.empty((D,), dtype=torch.float32, device=dev))
+    g_lnw, g_lnb = _ln_grads(dh0, x, mean, rstd)
     return loss, (g_lnw, g_lnb) + tuple(g for blk in grads for g in blk)
 
 
-class _DirectionLoss(torch.autograd.Function):
+def _ln_grads(dh, x, mean, rstd):
+    """LayerNorm weight and bias gradients [D] from the gradient dh of its output: per-chunk partials, summed in a fixed order."""
+    D = x.shape[1]
+    pg, pb = ops.ln_param_grad(dh, x, mean, rstd, CHUNKS)
+    return (ops.reduce_slabs(pg, CHUNKS, D, torch.empty((D,), dtype=torch.float32, device=x.device)),
+            ops.reduce_slabs(pb, CHUNKS, D, torch.empty((D,), dtype=torch.float32, device=x.device)))
+
+
+class _StepLoss(torch.autograd.Function):
+    """The loss of one hand-written training step as an autograd node over the step's parameters.  The kernels compute forward and
+    backward together, so forward() runs the whole step and keeps the gradients; backward() hands them out times the upstream
+    factor.  Inputs and targets travel in `step`'s closure: none of them is differentiated."""
+
     @staticmethod
-    def forward(ctx, x, target, dist_method, batch, need_grad, *params):
-        loss, grads = forward_backward(x, target, tuple(p.detach() for p in params), dist_method, batch, need_grad)
-        ctx.grads, ctx.n_params = grads, len(params)
+    def forward(ctx, step, need_grad, *params):
+        loss, ctx.grads, ctx.check = step(tuple(p.detach() for p in params), need_grad)
+        ctx.n_params = len(params)
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        grads = ctx.grads
-        if grads is None:
-            return (None,) * (5 + ctx.n_params)
-        return (None, None, None, None, None) + tuple(gr * g for gr in grads)
+        if ctx.grads is None:
+            return (None,) * (2 + ctx.n_params)
+        if ctx.check is not None:
+            ctx.check()
+        return (None, None) + tuple(None if gr is None else gr * g for gr in ctx.grads)
+
+
+def step_loss(step, params):
+    """The front door of every training head: step(detached params, need_grad) -> (loss 0-dim, gradients in the order of params
+    (None: no gradient for that one) | None, check | None) becomes a loss that autograd differentiates w.r.t. params.  need_grad is
+    decided here (grad mode is always off inside Function.forward); check, when given, runs at the start of backward() and raises
+    if the gradients are no longer valid."""
+    need = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+    return _StepLoss.apply(step, need, *params)
+
+
+@torch.no_grad()
+def update_running_stats(bn, mean64, var64, n):
+    """What nn.BatchNorm2d does to its buffers in train(), from the batch's mean and BIASED variance over n values per channel:
+    momentum (None: the cumulative average), the UNBIASED variance into running_var, num_batches_tracked."""
+    if bn.track_running_stats and bn.running_mean is not None:
+        mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked + 1)
+        bn.running_mean.mul_(1 - mom).add_(mean64.to(bn.running_mean.dtype), alpha=mom)
+        bn.running_var.mul_(1 - mom).add_((var64 * (n / (n - 1))).to(bn.running_var.dtype), alpha=mom)
+        bn.num_batches_tracked += 1
 
 
 def direction_params(module, src):
@@ -175,8 +179,7 @@ def direction_loss(module, src, x, target, dist_method="l2"):
     B = x.shape[0]
     x2 = x.to(dev).float().reshape(-1, x.shape[-1])
     t2 = target.to(dev).float().reshape(-1, target.shape[-1])
-    need = torch.is_grad_enabled() and any(p.requires_grad for p in params)  # (always False inside Function.forward)
-    return _DirectionLoss.apply(x2, t2, dist_method, B, need, *params)
+    return step_loss(lambda ps, need_grad: forward_backward(x2, t2, ps, dist_method, B, need_grad) + (None,), params)
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -198,6 +201,5 @@ class FusedAdam(torch.optim.Optimizer):
                     st["m"] = torch.zeros_like(p)
                     st["v"] = torch.zeros_like(p)
                 st["step"] += 1
-                _call("cmdiad_adam_step", ops._p(p), ops._p(p.grad.contiguous()), ops._p(st["m"]), ops._p(st["v"]), p.numel(),
-                      float(group["lr"]), b1, b2, group["eps"], st["step"], 1.0, None, ops._stream())
+                ops.adam_step(p, p.grad.contiguous(), st["m"], st["v"], group["lr"], b1, b2, group["eps"], st["step"])
                 p.view(-1)[:0].zero_()  # the kernel wrote p in place: bump its version so packed caches refresh

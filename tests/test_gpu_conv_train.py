@@ -4,6 +4,9 @@ autograd in float64 on the same bf16-rounded operands: the BatchNorm + ReLU pair
 filter tap, the data gradient, a whole tower (loss, all ten gradients, running statistics).  The three-step Adam curve of the
 REFERENCE's own module is tests/test_gpu_heads.py::test_head_training_follows_the_reference_loss_curve[conv_ftof] (golden G12),
 which runs through this path."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -11,6 +14,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import heads_torch_ref as torch_ref  # noqa: E402
 
 from cmdiad_amd import conv_train, ops  # noqa: E402
 
@@ -65,6 +71,13 @@ def test_weight_and_data_gradient_of_a_3x3_convolution(B, H, W, C, N):
     scale = float(w.grad.abs().mean())
     assert dw.shape == (N, C, 3, 3)
     np.testing.assert_allclose(dw.cpu().numpy(), w.grad.numpy(), rtol=2e-3, atol=2e-3 * scale)
+    # with the bias gradient: the column sums of dz ride on the centre tap's product, dW is what it was (the small shapes pad
+    # their rows with zeros and take split == 1, B = 16 takes split > 1)
+    dw_b, db = conv_train._wgrad(dz_rows, x_rows, B, H, W, want_bias=True)
+    db_ref = dz.sum((0, 2, 3))
+    assert dw_b.shape == (N, C, 3, 3) and db.shape == (N,)
+    np.testing.assert_allclose(dw_b.cpu().numpy(), w.grad.numpy(), rtol=2e-3, atol=2e-3 * scale)
+    np.testing.assert_allclose(db.cpu().numpy(), db_ref.numpy(), rtol=2e-3, atol=2e-3 * float(db_ref.abs().mean()))
     if N % 64 == 0:   # the data gradient is a convolution with N input channels
         dx, _ = ops.conv2d_nhwc(dz_rows.view(B, H, W, N), conv_train._conv_w_dgrad(w.detach().float().to(DEV)), C,
                                 want_f32=True, want_bf16=False)
@@ -136,9 +149,9 @@ def test_tower_loss_and_gradients_vs_torch_autograd(B, side, C, sigmoid):
     assert not l2.requires_grad
 
 
-def test_head_module_routes_training_through_the_hip_path(monkeypatch):
-    """HallucinationCrossModalityConv.forward in train() mode: the hand-written path (default) and the module's own torch layers
-    (CMDIAD_CONV_TRAIN=torch, fp32 operands) give the same two losses, running statistics and -- up to the ReLU masks that bf16
+def test_head_module_routes_training_through_the_hip_path():
+    """HallucinationCrossModalityConv.forward in train() mode: the hand-written path and the module's own torch layers
+    (heads_torch_ref, fp32 operands) give the same two losses, running statistics and -- up to the ReLU masks that bf16
     operands flip (see above: cosine 0.994-0.997 for the deepest layer) -- gradients."""
     from cmdiad_amd.models import hallucination_network as hn
     from oracle import heads
@@ -146,11 +159,10 @@ def test_head_module_routes_training_through_the_hip_path(monkeypatch):
     gen = torch.Generator().manual_seed(9)
     a, b = torch.randn(2, 3136, 768, generator=gen), torch.randn(2, 3136, 768, generator=gen)
     for mode in ("hip", "torch"):
-        monkeypatch.setenv("CMDIAD_CONV_TRAIN", mode)
         m = hn.HallucinationCrossModalityConv(None, 768, 768)
         m.load_state_dict(heads.synth_head_state_dict("conv_ftof", 41))
         m.to(DEV).train()
-        lx, lr = m(a, b, False, "l2")
+        lx, lr = m(a, b, False, "l2") if mode == "hip" else torch_ref.conv_ftof_losses(m, a, b, False)
         (lx + lr).backward()
         res[mode] = (float(lx.detach()), float(lr.detach()), {k: p.grad.clone() for k, p in m.named_parameters()},
                      {k: v.clone() for k, v in m.named_buffers()})
@@ -184,20 +196,19 @@ def test_relu_backward_from_the_saved_output():
     assert torch.equal(got.cpu(), want)
 
 
-def test_feature_to_input_conv_head_trains_on_the_hip_path(monkeypatch):
-    """HallucinationFeatureToInputConv.forward in train() mode: hand-written path (default) against the module's own torch layers
-    (CMDIAD_CONV_TRAIN=torch, fp32): loss 3e-3, gradient cosines (ReLU masks flip under bf16 operands: > 0.99)."""
+def test_feature_to_input_conv_head_trains_on_the_hip_path():
+    """HallucinationFeatureToInputConv.forward in train() mode: hand-written path against the module's own torch layers
+    (heads_torch_ref, fp32): loss 3e-3, gradient cosines (ReLU masks flip under bf16 operands: > 0.99)."""
     from cmdiad_amd.models import hallucination_network as hn
     from oracle import heads
     gen = torch.Generator().manual_seed(12)
     f, img = torch.randn(2, 3136, 768, generator=gen), torch.randn(2, 3, 224, 224, generator=gen)
     res = {}
     for mode in ("hip", "torch"):
-        monkeypatch.setenv("CMDIAD_CONV_TRAIN", mode)
         m = hn.HallucinationFeatureToInputConv(None, 768)
         m.load_state_dict(heads.synth_head_state_dict("ftoi_conv", 41))
         m.to(DEV).train()
-        loss = m(f, img)
+        loss = m(f, img) if mode == "hip" else torch_ref.ftoi_conv_loss(m, f, img)
         assert loss.requires_grad
         loss.backward()
         res[mode] = (float(loss.detach()), {k: p.grad.clone() for k, p in m.named_parameters() if p.grad is not None})
@@ -208,7 +219,7 @@ def test_feature_to_input_conv_head_trains_on_the_hip_path(monkeypatch):
 
 
 @pytest.mark.parametrize("depth_only", [False, True])
-def test_feature_to_input_mlp_head_trains_on_the_hip_path(depth_only, monkeypatch):
+def test_feature_to_input_mlp_head_trains_on_the_hip_path(depth_only):
     """HallucinationRGBFeatureToXYZInputMLP.forward in train() mode (3 output channels, and 1 with --estimate_depth): hand-written
     path against the module's own torch layers (fp32): loss 3e-3, every gradient cosine > 0.995 (GELU is smooth: no mask flips) and
     norm ratio within 6e-3 of 1, which a gradient off by a constant factor fails (measured |ratio - 1| <= 1.8e-3 with 3 channels,
@@ -221,13 +232,12 @@ def test_feature_to_input_mlp_head_trains_on_the_hip_path(depth_only, monkeypatc
     img = torch.randn(2, 1 if depth_only else 3, 224, 224, generator=gen)
     res = {}
     for mode in ("hip", "torch"):
-        monkeypatch.setenv("CMDIAD_CONV_TRAIN", mode)
         torch.manual_seed(5)
         m = hn.HallucinationRGBFeatureToXYZInputMLP(types.SimpleNamespace(estimate_depth=depth_only), 768)
         if not depth_only:
             m.load_state_dict(heads.synth_head_state_dict("ftoi_mlp", 41))
         m.to(DEV).train()
-        loss = m(f, img)
+        loss = m(f, img) if mode == "hip" else torch_ref.ftoi_mlp_loss(m, f, img)
         assert loss.requires_grad
         loss.backward()
         res[mode] = (float(loss.detach()), {k: p.grad.clone() for k, p in m.named_parameters()})
@@ -238,7 +248,7 @@ def test_feature_to_input_mlp_head_trains_on_the_hip_path(depth_only, monkeypatc
         assert res["hip"][1][k].shape == gq.shape and c > 0.995 and abs(ratio - 1) < 6e-3, (k, c, ratio)
 
 
-def test_hrnet_trunk_trains_on_the_hip_path(monkeypatch):
+def test_hrnet_trunk_trains_on_the_hip_path():
     """models.hrnet.HRNet.forward in train() mode (stem, twelve Bottlenecks, final 1x1; 39 batch-statistics BatchNorms): hand-written
     path against the module's own torch layers (fp32): loss 3e-3, running statistics, and the gradient of every parameter the
     forward uses -- cosine > 0.999 at the final layer, > 0.98 in the last Bottleneck, falling with depth as bf16 operands flip
@@ -250,11 +260,10 @@ def test_hrnet_trunk_trains_on_the_hip_path(monkeypatch):
     img, feat = torch.randn(2, 3, 224, 224, generator=gen), torch.randn(2, 3136, 768, generator=gen)
     res = {}
     for mode in ("hip", "torch"):
-        monkeypatch.setenv("CMDIAD_HRNET_TRAIN", mode)      # (auto = hip, see hrnet.py)
         m = HRNet(512, 768, 0.1)
         m.load_state_dict(heads.synth_head_state_dict("hrnet", 41))
         m.to(DEV).train()
-        loss = m(img, feat)
+        loss = m(img, feat) if mode == "hip" else torch_ref.hrnet_loss(m, img, feat)
         assert loss.requires_grad
         loss.backward()
         res[mode] = (float(loss.detach()), {k: (None if p.grad is None else p.grad.clone()) for k, p in m.named_parameters()},
@@ -284,7 +293,6 @@ def test_hrnet_step_replayed_as_a_graph_equals_the_eager_step(monkeypatch):
     from oracle import heads
     gen = torch.Generator().manual_seed(22)
     batches = [(torch.randn(2, 3, 224, 224, generator=gen).to(DEV), torch.randn(2, 3136, 768, generator=gen).to(DEV)) for _ in range(5)]
-    monkeypatch.setenv("CMDIAD_HRNET_TRAIN", "hip")
     out = {}
     for graph in ("1", "0"):
         monkeypatch.setenv("CMDIAD_HRNET_GRAPH", graph)

@@ -20,7 +20,7 @@ too.  Measured on an MI355X, worst over 5 input seeds per batch size (gradients:
   FtoI  B=1   5.0e-3        1.0e-4             1.3e-5     3.9e-6
   FtoI  B=2   4.5e-3        5.0e-5             9.9e-6     3.6e-6
 The bounds (HRNET_BOUNDS, FTOI_BOUNDS: per stage and kind for HRNet, per layer for FtoI) are 2x the worst value of their group
-for relative L2 and cosine, 4x for the norm ratio, the loss and the statistics.  The running statistics that _HRNetLoss.forward
+for relative L2 and cosine, 4x for the norm ratio, the loss and the statistics.  The running statistics that hrnet_loss
 writes are checked separately against nn.BatchNorm2d's update rule applied to the step's own batch statistics."""
 import numpy as np
 import pytest
@@ -138,7 +138,6 @@ def test_hrnet_running_statistics_follow_batchnorm2d(momentum, monkeypatch):
     applied to the batch statistics that hrnet_forward_backward returns for the same inputs.  To rtol 1e-6: the unbiased
     correction alone is 1 + 4e-5 at bn1 (B = 2)."""
     from cmdiad_amd.models.hrnet import HRNet
-    monkeypatch.setenv("CMDIAD_HRNET_TRAIN", "hip")
     monkeypatch.setenv("CMDIAD_HRNET_GRAPH", "0")
     B = 2
     sd = heads.synth_head_state_dict("hrnet", 41)

@@ -90,7 +90,7 @@ def _loss_head(z, t, mode, act, inv_b, want_dz=True, want_y=True):
     dz = torch.empty((M, D), dtype=torch.bfloat16, device=DEV) if want_dz else None
     y = torch.empty((M, D), dtype=torch.float32, device=DEV) if want_y else None
     code = _MODES[mode] | (_ACTS[act] << 8)
-    train._call("cmdiad_loss_head", _p(z), _p(t), M, D, code, float(inv_b), _p(rl), _p(dz), _p(y), _s())
+    ops._call("cmdiad_loss_head", _p(z), _p(t), M, D, code, float(inv_b), _p(rl), _p(dz), _p(y), _s())
     torch.cuda.synchronize()
     assert torch.all(rl[M:] == CANARY), "row_loss written past M"
     return rl[:M], dz, y
@@ -120,6 +120,29 @@ def test_loss_head_against_float64(D):
             _assert_within(dz, g_ref, _bf16_bound(g_ref) + 1e-5 * g_ref.abs().max(), f"{what} dz3")
             rl2, _, _ = _loss_head(zd, td, mode, act, inv_b, want_dz=False, want_y=False)
             assert torch.equal(rl2, rl), f"{what}: row_loss differs without the dz3 / y_out outputs"
+
+
+def test_loss_and_grad_is_loss_head_then_sum_vector():
+    """ops.loss_and_grad is ops.loss_head followed by ops.sum_vector with 1 / batch in both -- the same two launches, so the loss
+    and the gradient are theirs bit for bit, with and without the gradient; and the names of ops are this file's mode numbers."""
+    assert (ops.LOSS_L2, ops.LOSS_COS_DIST, ops.LOSS_SMOOTH_L1) == tuple(_MODES[k] for k in ("l2", "cos_dist", "smooth_l1"))
+    assert (ops.LOSS_OUT_GELU, ops.LOSS_OUT_NONE, ops.LOSS_OUT_SIGMOID) == tuple(_ACTS[k] << 8 for k in ("gelu", "none", "sigmoid"))
+    M, D, batch = 7, 4, 3
+    g = _gen(100 + D)
+    z = (1.5 * torch.randn(M, D, generator=g)).float().to(DEV)
+    t = torch.randn(M, D, generator=g).float().to(DEV)
+    for mode in _MODES.values():
+        for act in _ACTS.values():
+            rl, dz = ops.loss_head(z, t, mode, act << 8, 1.0 / batch)
+            want = ops.sum_vector(rl, 1.0 / batch)
+            assert want.dim() == 0 and dz.dtype == torch.bfloat16 and dz.shape == z.shape
+            for need_grad in (True, False):
+                loss, grad = ops.loss_and_grad(z, t, mode, batch, need_grad, out_act=act << 8)
+                assert loss.shape == want.shape and torch.equal(loss.view(torch.int32), want.view(torch.int32)), (mode, act, need_grad)
+                if need_grad:
+                    assert torch.equal(grad.view(torch.int16), dz.view(torch.int16)), (mode, act)
+                else:
+                    assert grad is None
 
 
 def test_loss_head_edges():
@@ -209,7 +232,7 @@ def _spacing(x):
 
 
 def _adam_call(p, g, m, v, n, lr, step, gscale=1.0, pb=None):
-    train._call("cmdiad_adam_step", _p(p), _p(g), _p(m), _p(v), n, float(lr), _B1, _B2, _EPS, int(step), float(gscale), _p(pb), _s())
+    ops._call("cmdiad_adam_step", _p(p), _p(g), _p(m), _p(v), n, float(lr), _B1, _B2, _EPS, int(step), float(gscale), _p(pb), _s())
 
 
 def _check_adam_step(before, after, g, lr, step, gscale, n, what):
@@ -304,9 +327,9 @@ def test_reduce_slabs():
             slabs[:, n:] = float("nan")                        # the gap between slabs is never read
             sd = slabs.to(DEV)
             out = torch.full((n + 64,), CANARY, device=DEV)
-            train._call("cmdiad_reduce_slabs", _p(sd), S, n, stride, scale, _p(out), _s())
+            ops._call("cmdiad_reduce_slabs", _p(sd), S, n, stride, scale, _p(out), _s())
             out2 = torch.full((n + 64,), CANARY, device=DEV)
-            train._call("cmdiad_reduce_slabs", _p(sd), S, n, stride, scale, _p(out2), _s())
+            ops._call("cmdiad_reduce_slabs", _p(sd), S, n, stride, scale, _p(out2), _s())
             torch.cuda.synchronize()
             assert torch.equal(out, out2), f"reduce_slabs S={S} n={n}: two calls differ"
             assert torch.all(out[n:] == CANARY), f"reduce_slabs S={S} n={n}: written past n"
@@ -321,9 +344,9 @@ def test_sum_vector():
         x = torch.randn(max(n, 1), generator=g).float()[:n].contiguous()
         xd = x.to(DEV) if n else torch.empty(4, device=DEV)
         out = torch.full((2,), CANARY, device=DEV)
-        train._call("cmdiad_sum_vector", _p(xd), n, 0.25, _p(out), _s())
+        ops._call("cmdiad_sum_vector", _p(xd), n, 0.25, _p(out), _s())
         out2 = torch.full((2,), CANARY, device=DEV)
-        train._call("cmdiad_sum_vector", _p(xd), n, 0.25, _p(out2), _s())
+        ops._call("cmdiad_sum_vector", _p(xd), n, 0.25, _p(out2), _s())
         torch.cuda.synchronize()
         assert torch.equal(out, out2) and out[1].item() == CANARY, f"sum_vector n={n}"
         ref = x.double().sum() * 0.25
@@ -338,7 +361,7 @@ def test_colsum_bf16():
         xd = x.to(DEV)
         for chunks in (1, 64, M + 3):
             part = torch.full((chunks, N), float("nan"), device=DEV)
-            train._call("cmdiad_colsum_bf16", _p(xd), M, N, chunks, _p(part), _s())
+            ops._call("cmdiad_colsum_bf16", _p(xd), M, N, chunks, _p(part), _s())
             part = part.cpu()
             rpc = (M + chunks - 1) // chunks
             x64 = x.double()
@@ -373,7 +396,7 @@ def test_ln_param_grad(C):
     for chunks in (64, M + 5):
         pg = torch.full((chunks, C), float("nan"), device=DEV)
         pb = torch.full((chunks, C), float("nan"), device=DEV)
-        train._call("cmdiad_ln_param_grad", _p(dhd), _p(xd), _p(md), _p(rd), M, C, chunks, _p(pg), _p(pb), _s())
+        ops._call("cmdiad_ln_param_grad", _p(dhd), _p(xd), _p(md), _p(rd), M, C, chunks, _p(pg), _p(pb), _s())
         pg_h, pb_h = pg.cpu(), pb.cpu()
         rpc = (M + chunks - 1) // chunks
         for c in range(chunks):
@@ -383,8 +406,8 @@ def test_ln_param_grad(C):
             _assert_within(pb_h[c], terms_b[sl].sum(0), _sum_bound(k, terms_b[sl].abs().sum(0)), f"ln partial_b C={C} chunks={chunks}")
         dg = torch.empty(C, device=DEV)
         db = torch.empty(C, device=DEV)
-        train._reduce_slabs(pg, chunks, C, dg)
-        train._reduce_slabs(pb, chunks, C, db)
+        ops.reduce_slabs(pg, chunks, C, dg)
+        ops.reduce_slabs(pb, chunks, C, db)
         torch.cuda.synchronize()
         kk = rpc // 4 + 3 + chunks // 4 + 3 + 3
         _assert_within(dg, w.grad, _sum_bound(kk, terms_g.abs().sum(0)) + stat_err, f"LayerNorm dgamma C={C} chunks={chunks}")
@@ -434,7 +457,7 @@ def test_bn_affine():
     outs64 = [torch.full((C + 1,), CANARY, dtype=torch.float64, device=DEV) for _ in range(2)]
     outs32 = [torch.full((C + 1,), CANARY, device=DEV) for _ in range(4)]
     ins = [a.to(DEV) for a in (s, sq, gamma, beta)]         # held until the kernel has run: no temporaries behind a raw pointer
-    train._call("cmdiad_bn_affine", *[_p(a) for a in ins], rows, eps, C, *[_p(o) for o in outs64], *[_p(o) for o in outs32], _s())
+    ops._call("cmdiad_bn_affine", *[_p(a) for a in ins], rows, eps, C, *[_p(o) for o in outs64], *[_p(o) for o in outs32], _s())
     torch.cuda.synchronize()
     for o in outs64 + outs32:
         assert o[C].item() == CANARY, "bn_affine wrote past C"
@@ -538,7 +561,7 @@ def test_pad_nhwc_bit_exact():
         # the raw kernel writes the interior only: a pre-filled border stays as it was
         out = torch.full((B, H + 2, W + 2, C), 3.0, dtype=torch.bfloat16, device=DEV)
         xd = x.to(DEV)
-        train._call("cmdiad_pad_nhwc_bf16", _p(xd), B, H, W, C, _p(out), _s())
+        ops._call("cmdiad_pad_nhwc_bf16", _p(xd), B, H, W, C, _p(out), _s())
         torch.cuda.synchronize()
         want = torch.full((B, H + 2, W + 2, C), 3.0, dtype=torch.bfloat16)
         want[:, 1:H + 1, 1:W + 1] = x
@@ -646,7 +669,7 @@ def test_gemm_split_k_slabs(K, split):
     _assert_within(full, prod, bound, "unsplit f32 product")
     _assert_within(slabs.double().sum(0), prod, bound + split * U32 * (A.double().abs() @ W.double().abs().T), f"split_k={split} slab sum")
     out = torch.empty((M * N,), device=DEV)
-    train._reduce_slabs(slabs, split, M * N, out)
+    ops.reduce_slabs(slabs, split, M * N, out)
     torch.cuda.synchronize()
     _assert_within(out.reshape(M, N), _d(full), 2 * bound + (split + 3) * U32 * (A.double().abs() @ W.double().abs().T),
                    f"split_k={split}: reduced slabs vs the unsplit product")
