@@ -134,6 +134,13 @@ SIGNATURES = {
     "cmdiad_eyecandies_cloud": [P, P, I, I, I, P, P, P, P],
     "cmdiad_eyecandies_unproject": [P, P, I, I, I, P, P, P],
     "cmdiad_eyecandies_background": [P, I, P, P, P],
+    "cmdiad_ccl_label": [P, I, I, I, I, P, P, P, P, I, P, P, SZ, P],
+    "cmdiad_f64_to_keys": [P, I, P, P, P],
+    "cmdiad_keys_to_f64": [P, I, P, P],
+    "cmdiad_sort_u64": [P, I, P, SZ, P],
+    "cmdiad_metrics_split": [P, P, P, I, I, P, I, P, P, I, P, P, P],
+    "cmdiad_auc_counts": [P, I, P, I, P, P],
+    "cmdiad_pro_hist": [P, I, P, P, I, I, P, P],
 }
 SIZE_QUERIES = {
     "cmdiad_gemm_streamk_workspace_bytes": [],
@@ -151,6 +158,9 @@ SIZE_QUERIES = {
     "cmdiad_transformer_block_workspace_bytes": [I, I, I],
     "cmdiad_plane_ransac_workspace_bytes": [I],
     "cmdiad_dbscan_workspace_bytes": [I],
+    "cmdiad_ccl_workspace_bytes": [I, I, I],
+    "cmdiad_sort_u64_tile": [],
+    "cmdiad_sort_u64_workspace_bytes": [I],
 }
 
 

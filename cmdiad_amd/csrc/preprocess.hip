@@ -21,6 +21,7 @@
 #include <limits.h>
 
 #include "common.h"
+#include "union_find.h"
 
 namespace {
 
@@ -403,36 +404,7 @@ __global__ __launch_bounds__(256) void dbscan_core_kernel(const SortedPoint* __r
     parent[s] = s;
 }
 
-__device__ __forceinline__ int uf_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// root of x; parents only ever decrease, so every value read is an ancestor of x and the walk ends at a (then) root
-__device__ __forceinline__ int uf_find(int* parent, int x)
-{
-    int p = uf_load(parent + x);
-    while (p != x) {
-        const int gp = uf_load(parent + p);
-        if (gp != p) atomicMin(parent + x, gp);
-        x = p;
-        p = gp;
-    }
-    return x;
-}
-
-// joins the trees of a and b, the larger root under the smaller; returns the common root
-__device__ __forceinline__ int uf_union(int* parent, int a, int b)
-{
-    for (;;) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return a;
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        if (atomicCAS(parent + a, a, b) == a) return b;
-    }
-}
+// uf_load / uf_find / uf_union: union_find.h
 
 __global__ __launch_bounds__(256) void dbscan_union_kernel(const SortedPoint* __restrict__ sp, int N, const GridParams* __restrict__ gp,
                                                            const int* __restrict__ start, double eps2, const int* __restrict__ core,

@@ -351,7 +351,8 @@ class Features(torch.nn.Module):
         raise NotImplementedError
 
     def calculate_metrics(self):
-        """features.py:302-324."""
+        """features.py:302-324.  With CMDIAD_METRICS_DEVICE=1 the three pixel-level values come from cmdiad_amd.metrics (the HIP
+        kernels of csrc/metrics.hip); image_rocauc -- about a hundred values -- stays on scikit-learn either way."""
         from ..utils.au_pro_util import calculate_au_pro
         self.image_preds = np.stack(self.image_preds)
         self.image_labels = np.stack(self.image_labels)
@@ -362,6 +363,11 @@ class Features(torch.nn.Module):
             os.makedirs(f'./visualization/{self.args.experiment_note}', exist_ok=True)
             np.savetxt(f'./visualization/{self.args.experiment_note}/{self.class_name}_raw_results.csv', txt_to_save, delimiter=',', fmt="%s")
         self.image_rocauc = roc_auc_score(self.image_labels, self.image_preds)
+        if os.environ.get("CMDIAD_METRICS_DEVICE", "0") == "1":     # read at call time; docs/metrics.md
+            from .. import metrics
+            m = metrics.pixel_metrics(self.gts, self.predictions)
+            self.pixel_rocauc, self.au_pro, self.au_pro_001 = m["pixel_rocauc"], m["au_pro"], m["au_pro_001"]
+            return
         self.pixel_rocauc = roc_auc_score(self.pixel_labels, self.pixel_preds)
         self.au_pro, _ = calculate_au_pro(self.gts, self.predictions)
         self.au_pro_001, _ = calculate_au_pro(self.gts, self.predictions, 0.01)

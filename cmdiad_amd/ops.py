@@ -1182,3 +1182,125 @@ def eyecandies_background(points):
     removed = torch.empty((n,), dtype=torch.uint8, device=points.device)
     _call("cmdiad_eyecandies_background", _p(points), n, _p(cloud), _p(removed), _stream())
     return cloud, removed
+
+
+# ------------------------------------------------------------------------------------ pixel metrics (docs/metrics.md)
+SORT_TILE = 4096          # keys per block of a radix pass (cmdiad_sort_u64_tile): sizes around its multiples change the passes' shape
+PRO_MAX_THRESHOLDS = 1024  # cmdiad_pro_hist keeps the thresholds in LDS
+# (the u64 keys travel in int64 tensors, bit for bit, as the search keys do: torch indexes and copies int64 everywhere)
+METRICS_MAX_TOTAL = 1 << 30
+
+
+def ccl_label(masks):
+    """masks [n,H,W] float32 or uint8 (foreground = non-zero) -> (labels [n,H,W] i32, n_comp [n] i32, comp_offset [n+1] i32,
+    comp_size [n ceil(H/2) ceil(W/2)] i32 -- zero past comp_offset[n] entries --, nonbinary [1] i32 = values neither 0 nor 1).
+    8-connected, numbered as scipy.ndimage.label(mask, ones((3,3))) numbers them.  No synchronisation."""
+    if masks.dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f"ccl_label.masks: expected torch.float32 or torch.uint8, got {masks.dtype}")
+    _chk(masks, masks.dtype, "ccl_label.masks")
+    if masks.dim() != 3:
+        raise ValueError(f"ccl_label: masks must be [n,H,W], got {tuple(masks.shape)}")
+    n, H, W = masks.shape
+    if H < 1 or W < 1 or H * W > (1 << 24) or n > 65535 or n * H * W > METRICS_MAX_TOTAL:
+        raise ValueError(f"ccl_label: unsupported shape {tuple(masks.shape)} (n <= 65535, H, W >= 1, H*W <= 2^24, n*H*W <= 2^30)")
+    dev = masks.device
+    cap = n * ((H + 1) // 2) * ((W + 1) // 2)
+    labels = torch.empty((n, H, W), dtype=torch.int32, device=dev)
+    n_comp = torch.empty((n,), dtype=torch.int32, device=dev)
+    comp_offset = torch.zeros((n + 1,), dtype=torch.int32, device=dev)
+    comp_size = torch.empty((cap,), dtype=torch.int32, device=dev)
+    nonbinary = torch.zeros((1,), dtype=torch.int32, device=dev)
+    if n == 0:
+        return labels, n_comp, comp_offset, comp_size, nonbinary
+    wsb = nat.lib().cmdiad_ccl_workspace_bytes(n, H, W)
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+    _call("cmdiad_ccl_label", _p(masks), int(masks.dtype == torch.uint8), n, H, W, _p(labels), _p(n_comp), _p(comp_offset),
+          _p(comp_size), cap, _p(nonbinary), _p(ws), wsb, _stream())
+    return labels, n_comp, comp_offset, comp_size, nonbinary
+
+
+def _chk_list(t, dtype, name):
+    _chk(t, dtype, name)
+    if t.dim() != 1 or t.numel() > METRICS_MAX_TOTAL:
+        raise ValueError(f"{name}: must be one-dimensional with at most 2^30 entries, got {tuple(t.shape)}")
+    return t.numel()
+
+
+def f64_to_keys(x):
+    """x [n] f64 -> (keys [n] u64 in the order of the doubles, -0.0 taken as +0.0; nonfinite [1] i32 = NaN / infinite inputs)."""
+    n = _chk_list(x, torch.float64, "f64_to_keys.x")
+    keys = torch.empty((n,), dtype=torch.int64, device=x.device)
+    nonfinite = torch.zeros((1,), dtype=torch.int32, device=x.device)
+    if n:
+        _call("cmdiad_f64_to_keys", _p(x), n, _p(keys), _p(nonfinite), _stream())
+    return keys, nonfinite
+
+
+def keys_to_f64(keys):
+    """The inverse of f64_to_keys: keys [n] u64 -> [n] f64."""
+    n = _chk_list(keys, torch.int64, "keys_to_f64.keys")
+    out = torch.empty((n,), dtype=torch.float64, device=keys.device)
+    if n:
+        _call("cmdiad_keys_to_f64", _p(keys), n, _p(out), _stream())
+    return out
+
+
+def sort_u64_(keys):
+    """keys [n] u64, sorted ascending IN PLACE (LSD radix sort, keys only); returns keys."""
+    n = _chk_list(keys, torch.int64, "sort_u64_.keys")
+    if n:
+        wsb = nat.lib().cmdiad_sort_u64_workspace_bytes(n)
+        ws = torch.empty((wsb,), dtype=torch.uint8, device=keys.device)
+        _call("cmdiad_sort_u64", _p(keys), n, _p(ws), wsb, _stream())
+    return keys
+
+
+def metrics_split(preds, labels, comp_offset, ok_cap, def_cap):
+    """preds [n,H,W] f64 + the labels / comp_offset of ccl_label -> (ok_keys [ok_cap] u64, def_score [def_cap] f64, def_comp [def_cap]
+    i32, counts [2] i64 = true lengths of the two lists, nonfinite [1] i32).  The order inside the lists is not defined."""
+    _chk(preds, torch.float64, "metrics_split.preds"); _chk(labels, torch.int32, "metrics_split.labels")
+    _chk(comp_offset, torch.int32, "metrics_split.comp_offset")
+    if preds.dim() != 3 or preds.shape != labels.shape or comp_offset.numel() != preds.shape[0] + 1:
+        raise ValueError(f"metrics_split: preds {tuple(preds.shape)} and labels {tuple(labels.shape)} must be the same [n,H,W], "
+                         f"comp_offset [n+1] (got {comp_offset.numel()})")
+    n, H, W = preds.shape
+    total = n * H * W
+    if n > 65535 or H * W > (1 << 24) or total > METRICS_MAX_TOTAL or not (0 <= ok_cap <= total and 0 <= def_cap <= total):
+        raise ValueError(f"metrics_split: unsupported sizes {tuple(preds.shape)} ok_cap={ok_cap} def_cap={def_cap}")
+    dev = preds.device
+    ok_keys = torch.empty((ok_cap,), dtype=torch.int64, device=dev)
+    def_score = torch.empty((def_cap,), dtype=torch.float64, device=dev)
+    def_comp = torch.empty((def_cap,), dtype=torch.int32, device=dev)
+    counts = torch.zeros((2,), dtype=torch.int64, device=dev)
+    nonfinite = torch.zeros((1,), dtype=torch.int32, device=dev)
+    if total:
+        _call("cmdiad_metrics_split", _p(preds), _p(labels), _p(comp_offset), n, H * W, _p(ok_keys), ok_cap, _p(def_score),
+              _p(def_comp), def_cap, _p(counts), _p(nonfinite), _stream())
+    return ok_keys, def_score, def_comp, counts, nonfinite
+
+
+def auc_counts(ok_sorted_keys, def_score):
+    """-> S [1] i64 = sum over the defect scores s of #(ok < s) + #(ok <= s); ok_sorted_keys: the SORTED keys of the defect-free scores."""
+    n_ok = _chk_list(ok_sorted_keys, torch.int64, "auc_counts.ok_sorted_keys")
+    n_def = _chk_list(def_score, torch.float64, "auc_counts.def_score")
+    S = torch.zeros((1,), dtype=torch.int64, device=def_score.device)
+    if n_ok and n_def:
+        _call("cmdiad_auc_counts", _p(ok_sorted_keys), n_ok, _p(def_score), n_def, _p(S), _stream())
+    return S
+
+
+def pro_hist(thr, def_score, def_comp, total_comp):
+    """thr [T] f64 ascending (T <= 1024) -> hist [total_comp, T+1] i32: hist[c][b] = defect pixels of component c with exactly b
+    thresholds strictly below their score."""
+    T = _chk_list(thr, torch.float64, "pro_hist.thr")
+    n_def = _chk_list(def_score, torch.float64, "pro_hist.def_score")
+    if _chk_list(def_comp, torch.int32, "pro_hist.def_comp") != n_def:
+        raise ValueError("pro_hist: def_score and def_comp differ in length")
+    if T > PRO_MAX_THRESHOLDS:
+        raise ValueError(f"pro_hist: {T} thresholds, at most {PRO_MAX_THRESHOLDS}")
+    if total_comp < 0 or total_comp * (T + 1) > (1 << 28):
+        raise ValueError(f"pro_hist: a table of {total_comp} components x {T + 1} bins is above 2^28 entries (1 GiB)")
+    hist = torch.zeros((total_comp, T + 1), dtype=torch.int32, device=def_score.device)
+    if n_def and total_comp:
+        _call("cmdiad_pro_hist", _p(thr), T, _p(def_score), _p(def_comp), n_def, total_comp, _p(hist), _stream())
+    return hist

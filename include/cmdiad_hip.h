@@ -728,6 +728,52 @@ int cmdiad_eyecandies_unproject(const uint16_t* depth_u16, const cmdiad_eyecandi
  * removed_out [n] u8 (NULL allowed).  513 <= n <= 2^28. */
 int cmdiad_eyecandies_background(const double* points, int n, double* cloud_out, uint8_t* removed_out, cmdiad_stream_t stream);
 
+/* ---- pixel-level metrics: P-AUROC and AU-PRO (feature_extractors/features.py:302-324, utils/au_pro_util.py; contracts, the key
+ * transform and the edge cases: docs/metrics.md; additions are backwards compatible, the ABI stays 6).  Every result is an integer
+ * or a set whose order is not defined, so nothing depends on the order in which atomics arrive; the float64 arithmetic of the
+ * metrics stays with the caller.  Everywhere: a negative size is rejected, size 0 returns CMDIAD_OK without a launch (the counters
+ * and flag words that are passed are still zeroed), list lengths and n * H * W are at most 2^30. ---- */
+
+/* 8-connected components of n masks [n,H,W], float32 or uint8 (mask_is_u8 = 0 / 1); foreground = value != 0.
+ * labels [n,H,W] int32: 0 = background, 1 .. n_comp[i] = the components of image i numbered in raster order of their first pixel
+ * (the numbering of scipy.ndimage.label with a 3 x 3 structure of ones); n_comp [n]; comp_offset [n + 1] = exclusive sum of n_comp
+ * (comp_offset[n] = all components: the global id of a component is comp_offset[i] + label - 1); comp_size [comp_cap] int32 = pixels
+ * per global id, zero past the last one; comp_cap >= n * ceil(H/2) * ceil(W/2), the most there can be.  nonbinary [1] int32 (NULL:
+ * not wanted) = mask values that are neither 0 nor 1.  n in 0..65535, H, W >= 1, H * W <= 2^24. */
+size_t cmdiad_ccl_workspace_bytes(int n, int H, int W);
+int cmdiad_ccl_label(const void* masks, int mask_is_u8, int n, int H, int W, int32_t* labels, int32_t* n_comp, int32_t* comp_offset,
+                     int32_t* comp_size, int comp_cap, int32_t* nonbinary, void* workspace, size_t workspace_bytes,
+                     cmdiad_stream_t stream);
+
+/* keys[i] = the bits of x[i] with -0.0 taken as +0.0, all flipped for a negative, the sign bit flipped otherwise: the unsigned order
+ * of the keys is the order of the doubles.  nonfinite [1] int32 (NULL: not wanted) = NaN and infinite inputs.  The second is the
+ * inverse map. */
+int cmdiad_f64_to_keys(const double* x, int n, uint64_t* keys, int32_t* nonfinite, cmdiad_stream_t stream);
+int cmdiad_keys_to_f64(const uint64_t* keys, int n, double* out, cmdiad_stream_t stream);
+
+/* keys [n] sorted ascending in place (LSD radix, 8 passes of 8 bits, keys only; the workspace holds the second copy).  The tile
+ * query returns the keys per block of a pass: sizes around its multiples are where the passes change shape. */
+size_t cmdiad_sort_u64_tile(void);
+size_t cmdiad_sort_u64_workspace_bytes(int n);
+int cmdiad_sort_u64(uint64_t* keys, int n, void* workspace, size_t workspace_bytes, cmdiad_stream_t stream);
+
+/* preds [n,HW] f64 and the labels / comp_offset of the labelling -> ok_keys: the keys of the pixels with label 0; (def_score,
+ * def_comp): score and global component id of every other pixel; counts [2] u64 = lengths of the two lists.  The order inside a list
+ * is not defined.  Nothing is written past ok_cap / def_cap entries (counts still has the true lengths).  nonfinite as above. */
+int cmdiad_metrics_split(const double* preds, const int32_t* labels, const int32_t* comp_offset, int n, int HW, uint64_t* ok_keys,
+                         int ok_cap, double* def_score, int32_t* def_comp, int def_cap, uint64_t* counts, int32_t* nonfinite,
+                         cmdiad_stream_t stream);
+
+/* S [1] u64 = sum over the defect scores s of #(ok < s) + #(ok <= s), ok_sorted_keys [n_ok] = the sorted keys of the defect-free
+ * scores (comparing keys is comparing the doubles): P-AUROC = S / (2 n_ok n_def). */
+int cmdiad_auc_counts(const uint64_t* ok_sorted_keys, int n_ok, const double* def_score, int n_def, uint64_t* S,
+                      cmdiad_stream_t stream);
+
+/* hist [total_comp, T + 1] u32 (zeroed by the caller; at most 2^28 entries): hist[def_comp[i]][b] += 1 with b = the number of
+ * thresholds strictly below def_score[i].  thr [T] f64 ascending, T <= 1024.  An id outside 0 .. total_comp - 1 is skipped. */
+int cmdiad_pro_hist(const double* thr, int T, const double* def_score, const int32_t* def_comp, int n_def, int total_comp,
+                    uint32_t* hist, cmdiad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
