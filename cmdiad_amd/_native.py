@@ -127,6 +127,9 @@ SIGNATURES = {
     "cmdiad_plane_mask": [P, P, SZ, I, P, D, P],
     "cmdiad_dbscan": [P, I, D, I, P, P, P, SZ, P],
     "cmdiad_label_histogram": [P, I, P, I, P],
+    "cmdiad_scan_edges": [P, SZ, I, I, P, I, P, P, SZ, P],
+    "cmdiad_scan_compact": [P, SZ, I, I, P, P, I, P, P, SZ, P],
+    "cmdiad_keep_largest_cluster": [P, P, I, P, I, P, P, P, SZ, I, P, P],
     "cmdiad_resize_bicubic_u8": [P, I, I, I, I, I, P, P, I, P, P, I, P, P, P, P, P],
     "cmdiad_organized_pc_prep": [P, I, I, I, P, P, I, P, P, I, P, P, P, P],
     "cmdiad_gt_mask_prep": [P, I, I, I, P, P, I, P, P],
@@ -158,6 +161,8 @@ SIZE_QUERIES = {
     "cmdiad_transformer_block_workspace_bytes": [I, I, I],
     "cmdiad_plane_ransac_workspace_bytes": [I],
     "cmdiad_dbscan_workspace_bytes": [I],
+    "cmdiad_scan_edges_workspace_bytes": [I, I],
+    "cmdiad_scan_compact_workspace_bytes": [I, I],
     "cmdiad_ccl_workspace_bytes": [I, I, I],
     "cmdiad_sort_u64_tile": [],
     "cmdiad_sort_u64_workspace_bytes": [I],

@@ -17,6 +17,12 @@
 //   (a non-core point takes the lowest cluster number among its core neighbours).  Connected components, minima and counts do not
 //   depend on the order in which threads run or in which the sort places the points of one cell, so neither do the labels.
 // cmdiad_label_histogram: hist[label + 1] counts (bin 0 = noise).
+// cmdiad_scan_edges / cmdiad_scan_compact: one stable compaction over a virtual sequence of pixels (the reference's edge strips, or
+//   all pixels in raster order): per-block counts of the valid points (a 64-bit ballot per wave), an exclusive scan of the block
+//   counts (scan_exclusive_kernel), a scatter that ranks a lane by the popcount of the ballot below it.  No atomic decides a
+//   position, so the output order is the sequence order whatever the schedule.
+// cmdiad_keep_largest_cluster: the first maximum of hist[0 .. n_clusters] (one workgroup), then pc / rgb are zeroed at index[i]
+//   wherever labels[i] is not the winner.
 #include <float.h>
 #include <limits.h>
 
@@ -484,6 +490,124 @@ __global__ __launch_bounds__(256) void label_histogram_kernel(const int32_t* __r
     if (b >= 0 && b < bins) atomicAdd(&hist[b], 1);
 }
 
+// ------------------------------------------------------------------------------------------- compaction, largest cluster
+constexpr int kEdge = 10;   // get_edges_of_pc: the first and last 10 rows, the first and last 10 columns
+
+// element k of the virtual sequence -> pixel (r, c).  edges = 0: all pixels in raster order.  edges = 1: rows 0 .. rh - 1, rows
+// max(H - 10, 0) .. H - 1, then for every row the columns 0 .. cw - 1, then for every row the columns max(W - 10, 0) .. W - 1
+// (rh = min(10, H), cw = min(10, W); the corner blocks appear twice).
+__device__ __forceinline__ void seq_pixel(int k, int H, int W, int edges, int& r, int& c)
+{
+    if (!edges) {
+        r = k / W, c = k - r * W;
+        return;
+    }
+    const int rh = min(kEdge, H), cw = min(kEdge, W);
+    const int A = rh * W, B = H * cw;
+    if (k < A) {
+        r = k / W, c = k - r * W;
+    } else if (k < 2 * A) {
+        k -= A;
+        r = k / W, c = k - r * W, r += max(H - kEdge, 0);
+    } else if (k < 2 * A + B) {
+        k -= 2 * A;
+        r = k / cw, c = k - r * cw;
+    } else {
+        k -= 2 * A + B;
+        r = k / cw, c = k - r * cw, c += max(W - kEdge, 0);
+    }
+}
+
+inline long long seq_length(int H, int W, int edges)
+{
+    if (!edges) return (long long)H * W;
+    const long long rh = H < kEdge ? H : kEdge, cw = W < kEdge ? W : kEdge;
+    return 2 * rh * W + 2 * cw * H;
+}
+
+// numpy's all(p != 0): -0.0 is a zero, NaN is not
+__device__ __forceinline__ bool seq_valid(const float* __restrict__ pc, size_t pitch, int k, int L, int H, int W, int edges,
+                                          int& r, int& c)
+{
+    if (k >= L) return false;
+    seq_pixel(k, H, W, edges, r, c);
+    const float* p = pc + (size_t)r * pitch + (size_t)c * 3;
+    return p[0] != 0.0f && p[1] != 0.0f && p[2] != 0.0f;
+}
+
+__global__ __launch_bounds__(256) void compact_count_kernel(const float* __restrict__ pc, size_t pitch, int H, int W, int edges, int L,
+                                                            int* __restrict__ block_count)
+{
+    __shared__ int s_wave[4];
+    int r, c;
+    const bool ok = seq_valid(pc, pitch, blockIdx.x * 256 + threadIdx.x, L, H, W, edges, r, c);
+    const unsigned long long m = __ballot(ok);
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = __popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) block_count[blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+}
+
+// block_start = the exclusive scan of block_count over the n_blocks blocks, block_start[n_blocks] = all valid points
+__global__ __launch_bounds__(256) void compact_scatter_kernel(const float* __restrict__ pc, size_t pitch, int H, int W, int edges, int L,
+                                                              const int* __restrict__ block_start, int n_blocks, int cap,
+                                                              float* __restrict__ points, int32_t* __restrict__ index,
+                                                              int32_t* __restrict__ count)
+{
+    __shared__ int s_wave[4];
+    if (blockIdx.x == 0 && threadIdx.x == 0) *count = block_start[n_blocks];
+    int r = 0, c = 0;
+    const bool ok = seq_valid(pc, pitch, blockIdx.x * 256 + threadIdx.x, L, H, W, edges, r, c);
+    const unsigned long long m = __ballot(ok);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) s_wave[wave] = __popcll(m);
+    __syncthreads();
+    if (!ok) return;
+    int pos = block_start[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) pos += s_wave[w];
+    if (pos >= cap) return;
+    const float* p = pc + (size_t)r * pitch + (size_t)c * 3;
+    float* q = points + (size_t)pos * 3;
+    q[0] = p[0], q[1] = p[1], q[2] = p[2];
+    if (index) index[pos] = r * W + c;
+}
+
+// winner = (the first maximum of hist[0 .. min(n_clusters, bins - 1)]) - 1: np.unique + argmax over the labels that occur
+__global__ __launch_bounds__(256) void cluster_winner_kernel(const int32_t* __restrict__ hist, int bins, const int32_t* __restrict__ n_clusters,
+                                                             int32_t* __restrict__ winner)
+{
+    __shared__ unsigned long long s_key[4];
+    const int last = min(max(*n_clusters, 0), bins - 1);
+    unsigned long long key = 0xFFFFFFFFull;   // (count << 32) | ~bin: the largest count, ties to the lowest bin; (0, bin 0) to start
+    for (int b = threadIdx.x; b <= last; b += 256) {
+        const unsigned long long k = ((unsigned long long)(uint32_t)max(hist[b], 0) << 32) | (unsigned long long)(~(uint32_t)b);
+        key = k > key ? k : key;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const unsigned long long o = shfl_xor_u64(key, m);
+        key = o > key ? o : key;
+    }
+    if ((threadIdx.x & 63) == 0) s_key[threadIdx.x >> 6] = key;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) key = s_key[w] > key ? s_key[w] : key;
+        *winner = (int32_t)(~(uint32_t)key) - 1;
+    }
+}
+
+__global__ __launch_bounds__(256) void cluster_keep_kernel(const int32_t* __restrict__ labels, const int32_t* __restrict__ index, int N,
+                                                           const int32_t* __restrict__ winner, float* __restrict__ pc,
+                                                           uint8_t* __restrict__ rgb, size_t n_pixels, int rgb_bytes)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N || labels[i] == *winner) return;
+    const int32_t at = index[i];
+    if (at < 0 || (size_t)at >= n_pixels) return;
+    float* p = pc + (size_t)at * 3;
+    p[0] = 0.0f, p[1] = 0.0f, p[2] = 0.0f;
+    for (int k = 0; k < rgb_bytes; ++k) rgb[(size_t)at * (size_t)rgb_bytes + k] = 0;
+}
+
 #define CMDIAD_CHECK_HIP(call)                                                                  \
     do {                                                                                        \
         hipError_t e_ = (call);                                                                 \
@@ -610,6 +734,76 @@ extern "C" int cmdiad_label_histogram(const int32_t* labels, int N, int32_t* his
     CMDIAD_CHECK_HIP(hipMemsetAsync(hist, 0, (size_t)bins * 4, (hipStream_t)stream));
     if (N == 0) return CMDIAD_OK;
     hipLaunchKernelGGL(label_histogram_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, labels, N, hist, bins);
+    CMDIAD_CHECK_LAUNCH();
+    return CMDIAD_OK;
+}
+
+// ---- compaction: workspace = the block counts and their scan
+constexpr int kMaxSide = 16384;
+
+static size_t compact_workspace(int H, int W, int edges)
+{
+    if (H < 1 || W < 1 || H > kMaxSide || W > kMaxSide) return 0;
+    return ((size_t)((seq_length(H, W, edges) + 255) / 256) + 1) * sizeof(int);
+}
+
+static int compact_launch(const char* name, const float* pc, size_t pitch, int H, int W, int edges, float* points, int32_t* index, int cap,
+                          int32_t* count, void* workspace, size_t workspace_bytes, hipStream_t s)
+{
+    CMDIAD_REQUIRE(pc && points && count && workspace, CMDIAD_ERR_ARG, "%s: null pointer", name);
+    CMDIAD_REQUIRE(H >= 1 && W >= 1 && H <= kMaxSide && W <= kMaxSide && (long long)H * W <= (1ll << 26) && pitch >= (size_t)W * 3 &&
+                       pitch <= ((size_t)1 << 24) && cap >= 0,
+                   CMDIAD_ERR_ARG, "%s: bad sizes H=%d W=%d (1..%d, H*W <= 2^26) pitch=%zu (>= 3 W floats) cap=%d", name, H, W, kMaxSide,
+                   pitch, cap);
+    CMDIAD_REQUIRE(workspace_bytes >= compact_workspace(H, W, edges), CMDIAD_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", name,
+                   workspace_bytes, compact_workspace(H, W, edges));
+    const int L = (int)seq_length(H, W, edges);
+    const int blocks = (L + 255) / 256;
+    int* block_count = (int*)workspace;
+    hipLaunchKernelGGL(compact_count_kernel, dim3(blocks), dim3(256), 0, s, pc, pitch, H, W, edges, L, block_count);
+    CMDIAD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(scan_exclusive_kernel, dim3(1), dim3(1024), 0, s, (const int*)block_count, block_count, blocks, (const int*)nullptr);
+    CMDIAD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(compact_scatter_kernel, dim3(blocks), dim3(256), 0, s, pc, pitch, H, W, edges, L, (const int*)block_count, blocks, cap,
+                       points, index, count);
+    CMDIAD_CHECK_LAUNCH();
+    return CMDIAD_OK;
+}
+
+extern "C" size_t cmdiad_scan_edges_workspace_bytes(int H, int W) { return compact_workspace(H, W, 1); }
+
+extern "C" int cmdiad_scan_edges(const float* pc, size_t pitch, int H, int W, float* points, int cap, int32_t* count, void* workspace,
+                                 size_t workspace_bytes, cmdiad_stream_t stream)
+{
+    return compact_launch("cmdiad_scan_edges", pc, pitch, H, W, 1, points, nullptr, cap, count, workspace, workspace_bytes,
+                          (hipStream_t)stream);
+}
+
+extern "C" size_t cmdiad_scan_compact_workspace_bytes(int H, int W) { return compact_workspace(H, W, 0); }
+
+extern "C" int cmdiad_scan_compact(const float* pc, size_t pitch, int H, int W, float* points, int32_t* index, int cap, int32_t* count,
+                                   void* workspace, size_t workspace_bytes, cmdiad_stream_t stream)
+{
+    CMDIAD_REQUIRE(index, CMDIAD_ERR_ARG, "cmdiad_scan_compact: null pointer");
+    return compact_launch("cmdiad_scan_compact", pc, pitch, H, W, 0, points, index, cap, count, workspace, workspace_bytes,
+                          (hipStream_t)stream);
+}
+
+extern "C" int cmdiad_keep_largest_cluster(const int32_t* labels, const int32_t* index, int N, const int32_t* hist, int bins,
+                                           const int32_t* n_clusters, float* pc, uint8_t* rgb, size_t n_pixels, int rgb_bytes,
+                                           int32_t* winner_out, cmdiad_stream_t stream)
+{
+    CMDIAD_REQUIRE(labels && index && hist && n_clusters && pc && winner_out && (rgb || rgb_bytes == 0), CMDIAD_ERR_ARG,
+                   "cmdiad_keep_largest_cluster: null pointer");
+    CMDIAD_REQUIRE(N >= 0 && N <= kMaxPoints && bins >= 1 && rgb_bytes >= 0 && rgb_bytes <= 64 && n_pixels <= ((size_t)1 << 31),
+                   CMDIAD_ERR_ARG, "cmdiad_keep_largest_cluster: bad sizes N=%d (0..%d) bins=%d n_pixels=%zu rgb_bytes=%d", N, kMaxPoints,
+                   bins, n_pixels, rgb_bytes);
+    if (N == 0) return CMDIAD_OK;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(cluster_winner_kernel, dim3(1), dim3(256), 0, s, hist, bins, n_clusters, winner_out);
+    CMDIAD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(cluster_keep_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, labels, index, N, (const int32_t*)winner_out, pc,
+                       rgb, n_pixels, rgb_bytes);
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
 }

@@ -26,7 +26,7 @@ Sample path (second half of this file; docs/sample_prep.md): the reference's ``T
 ``TestDataset`` / ``get_data_loader`` over an MVTec 3D-AD directory with a third ``img_process_method``, ``'hip'`` -- files decoded on
 reader threads, every transform after that in csrc/sample_prep.hip (``SamplePrep``) -- and ``MVTec3DClass``, the real-data class
 source of ``evaluate.evaluate_classes``; ``EyecandiesRawClass`` is the same over the raw Eyecandies download (csrc/eyecandies.hip,
-docs/eyecandies.md).
+docs/eyecandies.md), ``MVTec3DRawClass`` over the raw MVTec 3D-AD download (csrc/preprocess.hip, docs/preprocessing.md).
 """
 import math
 import os
@@ -574,19 +574,25 @@ class SamplePrep:
 
     def prepare_images(self, rgbs):
         """list of uint8 [H,W,3] arrays -> list of float32 [3,S,S] device tensors (resize + ToTensor + Normalize)."""
-        from . import ops
         imgs = [None] * len(rgbs)
         with torch.cuda.device(self.device):
-            norm = self._table("norm", 256, 3)
-            S = self.rgb_size
-            for (H, W), idx in _group_by_shape(rgbs, range(len(rgbs))).items():
-                src = self._upload([rgbs[i] for i in idx], torch.uint8, "rgb")
-                htab = self._table("bicubic", W, S) if W != S else None
-                vtab = self._table("bicubic", H, S) if H != S else None
-                _, out = ops.resize_bicubic_u8(src, S, S, htab, vtab, norm)
+            for _, idx in _group_by_shape(rgbs, range(len(rgbs))).items():
+                out = self.prepare_device_images(self._upload([rgbs[i] for i in idx], torch.uint8, "rgb"))
                 for j, i in enumerate(idx):
                     imgs[i] = out[j]
         return imgs
+
+    def prepare_device_images(self, src):
+        """src [B,H,W,3] uint8 ON THE DEVICE -> float32 [B,3,S,S] on the current stream (resize + ToTensor + Normalize)."""
+        from . import ops
+        if src.dim() != 4:
+            raise ValueError(f"SamplePrep: rgb must be [B,H,W,3], got {tuple(src.shape)}")
+        _, H, W, _ = src.shape
+        S = self.rgb_size
+        with torch.cuda.device(self.device):
+            htab = self._table("bicubic", W, S) if W != S else None
+            vtab = self._table("bicubic", H, S) if H != S else None
+            return ops.resize_bicubic_u8(src, S, S, htab, vtab, self._table("norm", 256, 3))[1]
 
     def prepare_device_clouds(self, src):
         """src [B,H,W,3] float32 or float64 ON THE DEVICE -> list of (cloud [3,xs,xs], depth [3,224,224], _Count) per sample, on the
@@ -605,16 +611,23 @@ class SamplePrep:
 
     def prepare_masks(self, gts):
         """list of uint8 [H,W] arrays or None -> list of float32 [1,g,g] device tensors or None."""
-        from . import ops
         masks = [None] * len(gts)
         with torch.cuda.device(self.device):
             with_gt = [i for i in range(len(gts)) if gts[i] is not None]
-            for (H, W), idx in _group_by_shape(gts, with_gt).items():
-                src = self._upload([gts[i] for i in idx], torch.uint8, "gt")
-                out = ops.gt_mask_prep(src, (self._table("pillow", H, self.gt_size), self._table("pillow", W, self.gt_size)))
+            for _, idx in _group_by_shape(gts, with_gt).items():
+                out = self.prepare_device_masks(self._upload([gts[i] for i in idx], torch.uint8, "gt"))
                 for j, i in enumerate(idx):
                     masks[i] = out[j]
         return masks
+
+    def prepare_device_masks(self, src):
+        """src [B,H,W] uint8 ON THE DEVICE -> float32 [B,1,g,g] in {0, 1} on the current stream (Pillow's NEAREST resize, ToTensor, > 0.5)."""
+        from . import ops
+        if src.dim() != 3:
+            raise ValueError(f"SamplePrep: gt must be [B,H,W], got {tuple(src.shape)}")
+        _, H, W = src.shape
+        with torch.cuda.device(self.device):
+            return ops.gt_mask_prep(src, (self._table("pillow", H, self.gt_size), self._table("pillow", W, self.gt_size)))
 
 
 def _group_by_shape(arrays, indices, with_dtype=False):
@@ -982,16 +995,122 @@ class EyecandiesRawClass:
         return self._iterate(self._test_files, self.test_labels, True)
 
 
+class MVTec3DRawClass:
+    """One class directory of the RAW MVTec 3D-AD download -- the tree on which the reference's utils/preprocessing.py has NOT been
+    run -- as the data object of evaluate.ClassRun / evaluate_classes, with MVTec3DClass's protocol.  It yields, sample for sample and
+    bit for bit, what MVTec3DClass with img_process_method='hip' yields over a copy of the tree that utils.preprocessing.
+    preprocess_dataset has cleaned, without writing anything: reader threads decode rgb, tiff and gt as the script decodes them,
+    every batch goes up through pinned memory on the shared copy stream, every scan runs ``preprocess_on_device`` (plane removal,
+    padding, largest DBSCAN cluster; docs/preprocessing.md) and SamplePrep's device entry points.  Files, order, labels and
+    ``rgb_path`` are TrainDataset's / TrainValidationDataset's / TestDataset's; a good test sample's mask is zeros.  There is no host
+    path."""
+
+    def __init__(self, dataset_path, class_name, args):
+        method = getattr(args, "img_process_method", "cpu_v1")
+        _check_method(method)
+        if method != 'hip':
+            raise ValueError(f"MVTec3DRawClass: raw MVTec 3D-AD scans are cleaned on the device only, there is no host path: "
+                             f"img_process_method must be 'hip', got {method!r} (or run utils/preprocessing.py over the tree first and "
+                             f"read it with MVTec3DClass: raw_scans=False)")
+        self.name, self.args = class_name, args
+        self.rgb_size, self.xyz_size, self.gt_size = (getattr(args, k, 224) for k in ("rgb_size", "xyz_size", "gt_size"))
+        self.readers, self.batch = max(1, int(getattr(args, "num_workers", 6))), 16
+        sizes = dict(class_name=class_name, rgb_size=self.rgb_size, xyz_size=self.xyz_size, gt_size=self.gt_size,
+                     dataset_path=dataset_path, img_process_method='hip')
+        self._train = (TrainValidationDataset if getattr(args, "train_with_validation", False) else TrainDataset)(**sizes)
+        self._test = TestDataset(**sizes)
+        self.n_train, self.n_test = len(self._train), len(self._test)
+        self._prep = None
+
+    def sample_prep(self):
+        if self._prep is None:
+            self._prep = SamplePrep(self.rgb_size, self.xyz_size, self.gt_size)
+        return self._prep
+
+    @staticmethod
+    def _decode(paths, gt_path):
+        """(cloud, rgb, gt or None) as utils.preprocessing._read decodes them: the arrays the files hold, unconverted."""
+        import numpy as np
+        from PIL import Image
+        rgb_path, tiff_path = paths
+        pc = np.asarray(_read_cloud(tiff_path))
+        rgb = np.array(Image.open(rgb_path))
+        gt = np.array(Image.open(gt_path)) if gt_path is not None else None
+        if pc.dtype != np.float32 or pc.ndim != 3 or pc.shape[2] != 3:
+            raise TypeError(f"MVTec3DRawClass: {tiff_path}: the point cloud must be a float32 [H,W,3] array, got {pc.dtype} {pc.shape}")
+        if rgb.dtype != np.uint8 or rgb.shape != pc.shape:
+            raise TypeError(f"MVTec3DRawClass: {rgb_path}: rgb must be a uint8 {pc.shape} array, got {rgb.dtype} {rgb.shape}")
+        if gt is not None and (gt.dtype != np.uint8 or gt.shape != pc.shape[:2]):
+            raise TypeError(f"MVTec3DRawClass: {gt_path}: gt must be a uint8 {pc.shape[:2]} array, got {gt.dtype} {gt.shape}")
+        return pc, rgb, gt
+
+    def _prepare(self, dec):
+        """decoded scans -> [(DeviceSample, mask or None)]: one upload per shape, one cleaning chain and one preparation per scan."""
+        from .utils import preprocessing as pp
+        prep, n = self.sample_prep(), len(dec)
+        out = [None] * n
+        with torch.cuda.device(prep.device):
+            for _, idx in _group_by_shape([d[0] for d in dec], range(n)).items():
+                pcs = prep._upload([dec[i][0] for i in idx], torch.float32, "the point cloud")
+                rgbs = prep._upload([dec[i][1] for i in idx], torch.uint8, "rgb")
+                with_gt = [i for i in idx if dec[i][2] is not None]
+                gts = prep._upload([dec[i][2] for i in with_gt], torch.uint8, "gt") if with_gt else None
+                for j, i in enumerate(idx):
+                    gt = gts[with_gt.index(i)] if dec[i][2] is not None else None
+                    pc, rgb, gt = pp.preprocess_on_device(pcs[j], rgbs[j], gt)
+                    img = prep.prepare_device_images(rgb[None])[0]
+                    cloud, depth, count = prep.prepare_device_clouds(pc[None])[0]
+                    mask = prep.prepare_device_masks(gt[None])[0] if gt is not None else None
+                    out[i] = (DeviceSample((img, cloud, depth), count), mask)
+        return out
+
+    def _iterate(self, ds, is_test):
+        import concurrent.futures as cf
+        n = len(ds)
+        gt_of = (lambda i: ds.gt_paths[i] if ds.gt_paths[i] != 0 else None) if is_test else (lambda i: None)
+        ahead = max(2 * self.readers, self.batch)
+        with cf.ThreadPoolExecutor(self.readers) as pool:
+            reads = {i: pool.submit(self._decode, ds.img_paths[i], gt_of(i)) for i in range(min(ahead, n))}
+            nxt = len(reads)
+            for lo in range(0, n, self.batch):
+                idx = list(range(lo, min(lo + self.batch, n)))
+                dec = []
+                for i in idx:
+                    dec.append(reads.pop(i).result())
+                    if nxt < n:
+                        reads[nxt] = pool.submit(self._decode, ds.img_paths[nxt], gt_of(nxt))
+                        nxt += 1
+                out = self._prepare(dec)
+                masks = _masks_to_host([m for _, m in out]) if is_test else None
+                for j, i in enumerate(idx):
+                    sample = out[j][0].batched()
+                    label = torch.tensor([ds.labels[i]])
+                    if is_test:
+                        yield sample, masks[j], label, [str(ds.img_paths[i][0])]
+                    else:
+                        yield sample, label
+
+    def train(self):
+        return self._iterate(self._train, False)
+
+    def test(self):
+        return self._iterate(self._test, True)
+
+
 def dataset_classes(args):
     """{class name: data object} for evaluate_classes: the classes of args.dataset_type ('mvtec3d' default, 'eyecandies') that have a
     directory under args.dataset_path, in the reference's order (main.py:10-16).  An Eyecandies class directory with ``train/data`` is
-    the raw download (EyecandiesRawClass); any other is a tree in MVTec 3D-AD's layout (MVTec3DClass)."""
+    the raw download (EyecandiesRawClass); any other is a tree in MVTec 3D-AD's layout (MVTec3DClass) -- a tree the preprocessing
+    script has cleaned, unless ``args.raw_scans`` says the MVTec 3D-AD tree is the raw download (MVTec3DRawClass: the scans are
+    cleaned on the device as they are read)."""
     kind = getattr(args, "dataset_type", "mvtec3d")
     if kind not in ("mvtec3d", "eyecandies"):
         raise ValueError(f"dataset_type must be 'mvtec3d' or 'eyecandies', got {kind!r}")
     names = eyecandies_classes() if kind == "eyecandies" else mvtec3d_classes()
 
     def source(c):
+        if kind == "mvtec3d" and getattr(args, "raw_scans", False):
+            return MVTec3DRawClass(args.dataset_path, c, args)
         raw = kind == "eyecandies" and os.path.isdir(Path(args.dataset_path, c, "train", "data"))
         return (EyecandiesRawClass if raw else MVTec3DClass)(args.dataset_path, c, args)
 

@@ -38,7 +38,7 @@ def mtfi_args(**kw):
              use_hn=True, fusion_module_path="", ocsvm_nu=0.5, ocsvm_maxiter=1000, xyz_s_lambda=1.0, xyz_smap_lambda=1.0,
              rgb_s_lambda=0.1, rgb_smap_lambda=0.1, fusion_s_lambda=1.0, fusion_smap_lambda=1.0, memory_bank="multiple",
              max_sample=500, train_with_validation=False, save_feature_for_fusion=False, save_seg_results=False,
-             use_depth=False)
+             use_depth=False, raw_scans=False)
     a.update(kw)
     return types.SimpleNamespace(**a)
 

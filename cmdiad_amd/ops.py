@@ -1042,6 +1042,75 @@ def label_histogram(labels, bins):
     return hist
 
 
+def _scan_window(pc, name):
+    """pc [H,W,3] f32 on the device, every row contiguous: a contiguous scan or the window of a larger one -> (H, W, row pitch in floats)."""
+    if not pc.is_cuda:
+        raise nat.NativeError(f"{name}: tensor must live on the GPU (cmdiad_amd has no CPU path)")
+    if pc.dtype != torch.float32:
+        raise TypeError(f"{name}: expected torch.float32, got {pc.dtype}")
+    if pc.dim() != 3 or pc.shape[2] != 3 or pc.shape[0] < 1 or pc.shape[1] < 1:
+        raise ValueError(f"{name}: the scan must be [H,W,3] with H, W >= 1, got {tuple(pc.shape)}")
+    H, W, _ = pc.shape
+    if pc.stride(2) != 1 or pc.stride(1) != 3 or (H > 1 and pc.stride(0) < 3 * W):
+        raise ValueError(f"{name}: every row of the scan must be contiguous, got strides {pc.stride()}")
+    return H, W, (pc.stride(0) if H > 1 else 3 * W)
+
+
+def scan_edges(pc):
+    """pc [H,W,3] f32 (contiguous, or the window of a larger scan) -> (points [L,3] f32, count [1] int32) on the device: the valid
+    points of get_edges_of_pc's sequence (L entries: first / last 10 rows, first / last 10 columns, corners twice) in its order, in
+    points[:count]; the rows past count are not written.  utils/preprocessing.py:20-27."""
+    H, W, pitch = _scan_window(pc, "scan_edges.pc")
+    L = 2 * min(10, H) * W + 2 * min(10, W) * H
+    points = torch.empty((L, 3), dtype=torch.float32, device=pc.device)
+    count = torch.empty(1, dtype=torch.int32, device=pc.device)
+    wsb = nat.lib().cmdiad_scan_edges_workspace_bytes(H, W)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=pc.device)
+    _call("cmdiad_scan_edges", _p(pc), pitch, H, W, _p(points), L, _p(count), _p(ws), wsb, _stream())
+    return points, count
+
+
+def scan_compact(pc):
+    """pc [H,W,3] f32 -> (points [H*W,3] f32, index [H*W] int32, count [1] int32) on the device: the valid points in raster order and
+    their flat pixel indices in [:count] -- np.nonzero(np.all(pc.reshape(-1, 3) != 0, axis=1)); the rows past count are not written."""
+    H, W, pitch = _scan_window(pc, "scan_compact.pc")
+    points = torch.empty((H * W, 3), dtype=torch.float32, device=pc.device)
+    index = torch.empty(H * W, dtype=torch.int32, device=pc.device)
+    count = torch.empty(1, dtype=torch.int32, device=pc.device)
+    wsb = nat.lib().cmdiad_scan_compact_workspace_bytes(H, W)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=pc.device)
+    _call("cmdiad_scan_compact", _p(pc), pitch, H, W, _p(points), _p(index), H * W, _p(count), _p(ws), wsb, _stream())
+    return points, index, count
+
+
+def keep_largest_cluster(labels, index, hist, n_clusters, pc, rgb=None):
+    """In place: pc [...,3] f32 and rgb [..., C] (any dtype, None = xyz only) are zeroed at the pixels index[i] whose labels[i] is not
+    the most frequent label of hist [bins] (bin 0 = noise, which can win; ties to the lowest label) -> winner [1] int32 on the device.
+    labels, index [N] int32; n_clusters [1] int32 on the device.  utils/preprocessing.py:70-90."""
+    _chk(labels, torch.int32, "keep_largest_cluster.labels"); _chk(index, torch.int32, "keep_largest_cluster.index")
+    _chk(hist, torch.int32, "keep_largest_cluster.hist"); _chk(n_clusters, torch.int32, "keep_largest_cluster.n_clusters")
+    _chk(pc, torch.float32, "keep_largest_cluster.pc")
+    N = labels.numel()
+    if index.numel() != N:
+        raise ValueError(f"keep_largest_cluster: {N} labels, {index.numel()} indices")
+    n = pc.numel() // 3
+    rgb_bytes = 0
+    if rgb is not None:
+        if not rgb.is_cuda:
+            raise nat.NativeError("keep_largest_cluster.rgb: tensor must live on the GPU (cmdiad_amd has no CPU path)")
+        if not rgb.is_contiguous():
+            raise ValueError("keep_largest_cluster.rgb: tensor must be contiguous")
+        if n == 0 or (rgb.numel() * rgb.element_size()) % n or rgb.numel() // n * n != rgb.numel():
+            raise ValueError(f"keep_largest_cluster: rgb {tuple(rgb.shape)} does not match pc {tuple(pc.shape)}")
+        rgb_bytes = rgb.numel() * rgb.element_size() // n
+    winner = torch.full((1,), -1, dtype=torch.int32, device=pc.device)
+    if N == 0 or hist.numel() == 0:      # (an empty tensor has no address to pass)
+        return winner
+    _call("cmdiad_keep_largest_cluster", _p(labels), _p(index), N, _p(hist), hist.numel(), _p(n_clusters), _p(pc), _p(rgb), n, rgb_bytes,
+          _p(winner), _stream())
+    return winner
+
+
 # ------------------------------------------------------------------------------------ sample preparation (docs/sample_prep.md)
 def resize_bicubic_u8(src, out_h, out_w, htab, vtab, norm=None, want_u8=False, want_f32=True):
     """src [B,H,W,3] uint8 -> (uint8 [B,out_h,out_w,3] or None, float32 [B,3,out_h,out_w] or None): Pillow's Image.resize(BICUBIC)

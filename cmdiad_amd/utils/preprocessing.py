@@ -8,6 +8,8 @@ cluster_dbscan -- replaced by the HIP kernels of csrc/preprocess.hip: numpy in, 
   roundup_next_100, pad_cropped_pc preprocessing.py:95-113   host
   preprocess_pc                    preprocessing.py:116-143  files in place, same path conventions
   preprocess_arrays                new: preprocess_pc without the file I/O, one scan or a list of scans
+  preprocess_on_device             new: the same on device tensors -- edge set, plane, mask, padding, compaction, DBSCAN and the final
+                                   zeroing without a trip to the host; preprocess_arrays / preprocess_pc are upload + this + download
   python -m cmdiad_amd.utils.preprocessing --dataset_path ...   the reference's __main__ loop; reader and writer threads around
                                    one device stream instead of the --num_process pool
 
@@ -133,12 +135,62 @@ def pad_cropped_pc(cropped_pc, single_channel=False):
     return np.pad(cropped_pc, pad_width=((a, aa), (b, bb), (0, 0)), mode='constant')
 
 
-def _preprocess_one(organized_pc, organized_rgb, organized_gt, seed, dev, name="<array>"):
-    pc, rgb = _remove_plane(organized_pc, organized_rgb, 0.005, seed, dev)
-    pc, rgb = pad_cropped_pc(pc), pad_cropped_pc(rgb)                      # padding happens between the two stages
-    gt = pad_cropped_pc(organized_gt, single_channel=True) if organized_gt is not None else None
-    pc, rgb = _connected_components_cleaning(pc, rgb, name, dev)
-    return pc, rgb, gt
+def _pad_on_device(t, side, top, left):
+    import torch
+    out = torch.zeros((side, side) + tuple(t.shape[2:]), dtype=t.dtype, device=t.device)
+    out[top:top + t.shape[0], left:left + t.shape[1]].copy_(t)
+    return out
+
+
+def preprocess_on_device(pc, rgb, gt=None, seed=0):
+    """preprocess_pc's steps on device tensors, device tensors back: pc [H,W,3] f32 -> [S,S,3], rgb [H,W,C] u8 -> [S,S,C],
+    gt [H,W] u8 or None -> [S,S] or None, S = the larger side rounded up to the next 100; the inputs are not written.  The scan goes
+    straight into its padded buffers (masking before or after the padding gives the same arrays: a padded pixel is zero either way);
+    the edge set is read from the un-padded window.  Everything runs on the current stream; the host reads two integers: the
+    number of valid edge points (fewer than 50: ValueError before any RANSAC launch) and the number of valid points left after
+    plane removal (the DBSCAN workspace; none: the cleaning stage changes nothing).  A scan without any valid point comes back
+    unchanged, padded.  docs/preprocessing.md."""
+    import torch
+    from .. import ops
+    from .. import _native as nat
+    if not (torch.is_tensor(pc) and pc.is_cuda):
+        raise nat.NativeError("preprocess_on_device: the scan must be device tensors (preprocess_arrays takes numpy arrays)")
+    if pc.dtype != torch.float32:
+        raise TypeError(f"preprocess_on_device: the point cloud must be float32 (MVTec 3D-AD tiffs are), got {pc.dtype}")
+    if pc.dim() != 3 or pc.shape[2] != 3 or rgb.dim() != 3 or tuple(rgb.shape[:2]) != tuple(pc.shape[:2]) or \
+            (gt is not None and tuple(gt.shape) != tuple(pc.shape[:2])):
+        raise ValueError(f"preprocess_on_device: pc [H,W,3], rgb [H,W,C], gt [H,W] expected, got {tuple(pc.shape)}, {tuple(rgb.shape)}, "
+                         f"{None if gt is None else tuple(gt.shape)}")
+    H, W = pc.shape[0], pc.shape[1]
+    side = max(roundup_next_100(H), roundup_next_100(W))
+    top, left = (side - H) // 2, (side - W) // 2
+    with torch.cuda.device(pc.device):
+        pc_out, rgb_out = _pad_on_device(pc, side, top, left), _pad_on_device(rgb, side, top, left)
+        gt_out = _pad_on_device(gt, side, top, left) if gt is not None else None
+        edges, n_edges = ops.scan_edges(pc_out[top:top + H, left:left + W])
+        E = int(n_edges.item())
+        if E < 50:
+            if E == 0 and int(ops.scan_compact(pc_out)[2].item()) == 0:
+                return pc_out, rgb_out, gt_out      # a scan without a valid point comes back unchanged, padded
+            raise ValueError(f"get_plane_eq: {E} valid edge points, 50 needed for one RANSAC sample")
+        plane, _ = ops.plane_ransac(edges[:E], n=50, iterations=RANSAC_ITERATIONS, distance_threshold=RANSAC_THRESHOLD, seed=seed)
+        ops.plane_mask(pc_out, rgb_out, plane, 0.005)
+        points, index, n_points = ops.scan_compact(pc_out)
+        N = int(n_points.item())
+        if N:      # (the reference fails on a scan without a valid point; here it comes back unchanged)
+            labels, n_clusters = ops.dbscan(points[:N], DBSCAN_EPS, DBSCAN_MIN_POINTS)
+            hist = ops.label_histogram(labels, N + 1)      # at most one cluster per point
+            ops.keep_largest_cluster(labels, index[:N], hist, n_clusters, pc_out, rgb_out)
+    return pc_out, rgb_out, gt_out
+
+
+def _preprocess_one(organized_pc, organized_rgb, organized_gt, seed, dev):
+    import torch
+    if organized_pc.dtype != np.float32:
+        raise TypeError(f"remove_plane: the point cloud must be float32 (MVTec 3D-AD tiffs are), got {organized_pc.dtype}")
+    up = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) if a is not None else None for a in (organized_pc, organized_rgb, organized_gt)]
+    pc, rgb, gt = preprocess_on_device(*up, seed=seed)
+    return pc.cpu().numpy(), rgb.cpu().numpy(), (gt.cpu().numpy() if gt is not None else None)
 
 
 def preprocess_arrays(organized_pc, organized_rgb, organized_gt=None, seed=0, device=None):
@@ -184,7 +236,7 @@ def _write(tiff_path, pc, rgb, gt):
 def preprocess_pc(tiff_path, device=None):
     dev = _device(device)
     organized_pc, organized_rgb, organized_gt = _read(tiff_path)
-    _write(tiff_path, *_preprocess_one(organized_pc, organized_rgb, organized_gt, _SEED, dev, tiff_path))
+    _write(tiff_path, *_preprocess_one(organized_pc, organized_rgb, organized_gt, _SEED, dev))
 
 
 def preprocess_dataset(root_path, device=None, readers=4, writers=2, progress=None):
@@ -201,7 +253,7 @@ def preprocess_dataset(root_path, device=None, readers=4, writers=2, progress=No
             pc, rgb, gt = reads.pop(i).result()
             if i + ahead < len(paths):
                 reads[i + ahead] = rd.submit(_read, paths[i + ahead])
-            writes.append(wr.submit(_write, path, *_preprocess_one(pc, rgb, gt, _SEED, dev, path)))
+            writes.append(wr.submit(_write, path, *_preprocess_one(pc, rgb, gt, _SEED, dev)))
             while len(writes) > 2 * writers:
                 writes.pop(0).result()
             if progress is not None:

@@ -667,6 +667,30 @@ int cmdiad_dbscan(const float* points, int N, double eps, int min_points, int32_
 /* hist[b] = number of labels equal to b - 1, b in [0, bins): bin 0 counts the noise label -1.  hist [bins] int32 (device). */
 int cmdiad_label_histogram(const int32_t* labels, int N, int32_t* hist, int bins, cmdiad_stream_t stream);
 
+/* The valid points of a scan as a STABLE compaction (valid: all three coordinates != 0 under numpy's rule: -0.0 is a zero, NaN is
+ * not).  pc [H,W,3] f32 with `pitch` floats from one row to the next (>= 3 W: the window of a larger buffer can be read in place).
+ * scan_edges: the sequence is get_edges_of_pc's (utils/preprocessing.py:20-27) -- rows 0 .. min(10,H) - 1 row-major, rows
+ * max(H-10,0) .. H - 1, for every row the columns 0 .. min(10,W) - 1, for every row the columns max(W-10,0) .. W - 1; the corner blocks
+ * appear twice.  scan_compact: all H * W pixels in raster order (np.nonzero(np.all(pc != 0, axis=1))), with index [.] int32 = the flat
+ * pixel r * W + c of every kept point.  points [cap,3] f32; count [1] int32 = all valid points of the sequence, also when cap is
+ * smaller (nothing is written past cap).  The output order is the sequence order: no atomic decides a position.  Sides in 1..16384,
+ * H * W <= 2^26.  workspace: the size query of the same name. */
+size_t cmdiad_scan_edges_workspace_bytes(int H, int W);
+int cmdiad_scan_edges(const float* pc, size_t pitch, int H, int W, float* points, int cap, int32_t* count, void* workspace,
+                      size_t workspace_bytes, cmdiad_stream_t stream);
+size_t cmdiad_scan_compact_workspace_bytes(int H, int W);
+int cmdiad_scan_compact(const float* pc, size_t pitch, int H, int W, float* points, int32_t* index, int cap, int32_t* count,
+                        void* workspace, size_t workspace_bytes, cmdiad_stream_t stream);
+
+/* connected_components_cleaning's decision and zeroing (utils/preprocessing.py:70-90) without the host: winner_out [1] int32 = (the
+ * first maximum of hist[0 .. n_clusters]) - 1 -- bin 0 is the noise label -1, noise can win, ties go to the lowest bin: np.unique +
+ * argmax --, then pc [n_pixels,3] f32 and rgb [n_pixels, rgb_bytes] bytes (NULL with rgb_bytes = 0) are zeroed at index[i] wherever
+ * labels[i] != winner.  labels, index [N] int32; hist [bins] int32 (cmdiad_label_histogram; bins > n_clusters, else the bins that
+ * are there compete); n_clusters [1] int32.  All device memory.  An index outside 0 .. n_pixels - 1 is skipped.  N = 0: nothing. */
+int cmdiad_keep_largest_cluster(const int32_t* labels, const int32_t* index, int N, const int32_t* hist, int bins,
+                                const int32_t* n_clusters, float* pc, uint8_t* rgb, size_t n_pixels, int rgb_bytes, int32_t* winner_out,
+                                cmdiad_stream_t stream);
+
 /* ---- sample preparation (dataset.py:62-65, 103-113, 168-171, 225-244: PIL + torchvision + numpy per sample on DataLoader workers;
  * contract: docs/sample_prep.md; additions are backwards compatible, the ABI stays 6).  All index and coefficient tables are device
  * arrays the caller computes on the host (cmdiad_amd/dataset.py); the kernels clamp every table entry to the source image. ---- */
