@@ -27,6 +27,8 @@ Sample path (second half of this file; docs/sample_prep.md): the reference's ``T
 reader threads, every transform after that in csrc/sample_prep.hip (``SamplePrep``) -- and ``MVTec3DClass``, the real-data class
 source of ``evaluate.evaluate_classes``; ``EyecandiesRawClass`` is the same over the raw Eyecandies download (csrc/eyecandies.hip,
 docs/eyecandies.md), ``MVTec3DRawClass`` over the raw MVTec 3D-AD download (csrc/preprocess.hip, docs/preprocessing.md).
+The three device sources differ in what they decode and how a batch is prepared, nothing else: ``_device_items`` is their one item
+loop (utils.batching.read_ahead decodes ahead, one prepare call per batch, one pinned copy of the masks, batch-of-one items).
 """
 import math
 import os
@@ -36,6 +38,8 @@ from pathlib import Path
 
 import torch
 from torch.utils.data import Dataset
+
+from .utils.batching import in_batches, read_ahead, scatter_by_shape
 
 
 def _shared_stream(device, role):
@@ -160,15 +164,10 @@ class PairRing:
         self._have = torch.zeros(n, dtype=torch.bool)
 
     def __len__(self):
-        n = len(self.ds)
-        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+        return epoch_length(len(self.ds), self.batch_size, self.drop_last)
 
     def batches(self):
-        order = epoch_permutation(len(self.ds), self.shuffle)
-        out = [order[i:i + self.batch_size] for i in range(0, len(order), self.batch_size)]
-        if self.drop_last and out and len(out[-1]) < self.batch_size:
-            out.pop()
-        return out
+        return epoch_batches(len(self.ds), self.batch_size, self.shuffle, self.drop_last)
 
     def _fill(self, idxs):
         todo = [i for i in idxs if not bool(self._have[i])]
@@ -209,6 +208,18 @@ def epoch_permutation(n, shuffle):
     return torch.randperm(n, generator=g).tolist()
 
 
+def epoch_length(n, batch_size, drop_last):
+    """Batches per epoch of n samples: len(DataLoader)."""
+    return n // batch_size if drop_last else (n + batch_size - 1) // batch_size
+
+
+def epoch_batches(n, batch_size, shuffle, drop_last):
+    """One epoch's batches as lists of sample indices: `epoch_permutation` (one call: it consumes the global RNG as the reference's
+    DataLoader does) cut into batch_size pieces, a short last one dropped with drop_last."""
+    order = epoch_permutation(n, shuffle)
+    return [order[i:i + batch_size] for i in range(0, n, batch_size)][:epoch_length(n, batch_size, drop_last)]
+
+
 class FeatureRing:
     """Iterable over one epoch of batches ``(features [b, rows, cols] on the device, labels [b] zeros)``.
 
@@ -236,16 +247,11 @@ class FeatureRing:
             self._cache = torch.empty((len(self.files), *self.sample_shape), dtype=self.dtype, device=self.device)
 
     def __len__(self):
-        n = len(self.files)
-        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+        return epoch_length(len(self.files), self.batch_size, self.drop_last)
 
     def batches(self):
         """The epoch's batches as lists of file indices (consumes the global RNG like the reference's DataLoader)."""
-        order = epoch_permutation(len(self.files), self.shuffle)
-        out = [order[i:i + self.batch_size] for i in range(0, len(order), self.batch_size)]
-        if self.drop_last and out and len(out[-1]) < self.batch_size:
-            out.pop()
-        return out
+        return epoch_batches(len(self.files), self.batch_size, self.shuffle, self.drop_last)
 
     def __iter__(self):
         plan = self.batches()
@@ -559,28 +565,24 @@ class SamplePrep:
             if np.ndim(r) != 3 or np.shape(r)[2] != 3 or np.ndim(p) != 3 or np.shape(p)[2] != 3 or (g is not None and np.ndim(g) != 2):
                 raise ValueError(f"SamplePrep: rgb [H,W,3], cloud [H,W,3], gt [H,W] expected, got {np.shape(r)}, {np.shape(p)}, "
                                  f"{None if g is None else np.shape(g)}")
+
+        def clouds_of(key, idx):
+            dtype = key[1]
+            if dtype not in ("float32", "float64"):
+                raise TypeError(f"SamplePrep: the point cloud must be float32 (MVTec 3D-AD) or float64 (Eyecandies) arrays, got {dtype}")
+            return self.prepare_device_clouds(self._upload([pcs[i] for i in idx], getattr(torch, dtype), "the point cloud"))
+
         with torch.cuda.device(self.device):
             imgs = self.prepare_images(rgbs)
-            clouds, depths, counts = [None] * n, [None] * n, [None] * n
-            for (_, dtype), idx in _group_by_shape(pcs, range(n), with_dtype=True).items():
-                if dtype not in ("float32", "float64"):
-                    raise TypeError(f"SamplePrep: the point cloud must be float32 (MVTec 3D-AD) or float64 (Eyecandies) arrays, got {dtype}")
-                src = self._upload([pcs[i] for i in idx], getattr(torch, dtype), "the point cloud")
-                out = self.prepare_device_clouds(src)
-                for j, i in enumerate(idx):
-                    clouds[i], depths[i], counts[i] = out[j]
+            clouds = scatter_by_shape(pcs, range(n), clouds_of, with_dtype=True)
             masks = self.prepare_masks(gts)
-        return [(DeviceSample((imgs[i], clouds[i], depths[i]), counts[i]), masks[i]) for i in range(n)]
+        return [(DeviceSample((imgs[i], *clouds[i][:2]), clouds[i][2]), masks[i]) for i in range(n)]
 
     def prepare_images(self, rgbs):
         """list of uint8 [H,W,3] arrays -> list of float32 [3,S,S] device tensors (resize + ToTensor + Normalize)."""
-        imgs = [None] * len(rgbs)
         with torch.cuda.device(self.device):
-            for _, idx in _group_by_shape(rgbs, range(len(rgbs))).items():
-                out = self.prepare_device_images(self._upload([rgbs[i] for i in idx], torch.uint8, "rgb"))
-                for j, i in enumerate(idx):
-                    imgs[i] = out[j]
-        return imgs
+            return scatter_by_shape(rgbs, range(len(rgbs)),
+                                    lambda _, idx: self.prepare_device_images(self._upload([rgbs[i] for i in idx], torch.uint8, "rgb")))
 
     def prepare_device_images(self, src):
         """src [B,H,W,3] uint8 ON THE DEVICE -> float32 [B,3,S,S] on the current stream (resize + ToTensor + Normalize)."""
@@ -611,14 +613,9 @@ class SamplePrep:
 
     def prepare_masks(self, gts):
         """list of uint8 [H,W] arrays or None -> list of float32 [1,g,g] device tensors or None."""
-        masks = [None] * len(gts)
         with torch.cuda.device(self.device):
-            with_gt = [i for i in range(len(gts)) if gts[i] is not None]
-            for _, idx in _group_by_shape(gts, with_gt).items():
-                out = self.prepare_device_masks(self._upload([gts[i] for i in idx], torch.uint8, "gt"))
-                for j, i in enumerate(idx):
-                    masks[i] = out[j]
-        return masks
+            return scatter_by_shape(gts, [i for i in range(len(gts)) if gts[i] is not None],
+                                    lambda _, idx: self.prepare_device_masks(self._upload([gts[i] for i in idx], torch.uint8, "gt")))
 
     def prepare_device_masks(self, src):
         """src [B,H,W] uint8 ON THE DEVICE -> float32 [B,1,g,g] in {0, 1} on the current stream (Pillow's NEAREST resize, ToTensor, > 0.5)."""
@@ -630,13 +627,15 @@ class SamplePrep:
             return ops.gt_mask_prep(src, (self._table("pillow", H, self.gt_size), self._table("pillow", W, self.gt_size)))
 
 
-def _group_by_shape(arrays, indices, with_dtype=False):
-    import numpy as np
-    groups = {}
-    for i in indices:
-        key = tuple(np.shape(arrays[i])[:2])
-        groups.setdefault((key, str(np.asarray(arrays[i]).dtype)) if with_dtype else key, []).append(i)
-    return groups
+class _LazySamplePrep:
+    """``sample_prep()``: the SamplePrep of the object's rgb_size / xyz_size / gt_size, built at first use (it needs a GPU; ``_prep`` is
+    None until then)."""
+    _prep = None
+
+    def sample_prep(self):
+        if self._prep is None:
+            self._prep = SamplePrep(self.rgb_size, self.xyz_size, self.gt_size)
+        return self._prep
 
 
 # ------------------------------------------------------------------------------------------------ the reference's dataset classes
@@ -657,7 +656,7 @@ def _read_cloud(path):
     return mu.read_tiff_organized_pc(path)     # (looked up at call time: needs `tifffile`, and says so)
 
 
-class BaseAnomalyDetectionDataset(Dataset):
+class BaseAnomalyDetectionDataset(_LazySamplePrep, Dataset):
     """dataset.py:45-70.  `decoded(idx)` returns what the files hold (the part that stays on the host whatever the method);
     `__getitem__` the reference's item: with 'cpu_v1' / 'cpu_v2' host tensors, with 'hip' device tensors (one SamplePrep call per
     item; `get_data_loader` batches the calls)."""
@@ -672,12 +671,6 @@ class BaseAnomalyDetectionDataset(Dataset):
         else:
             self.img_path = str(Path(dataset_path, self.cls, split))
         self.img_process_method = img_process_method
-        self._prep = None
-
-    def sample_prep(self):
-        if self._prep is None:
-            self._prep = SamplePrep(self.rgb_size, self.xyz_size, self.gt_size)
-        return self._prep
 
     def __len__(self):
         return len(self.img_paths)
@@ -802,35 +795,30 @@ class DeviceSampleLoader:
         return len(self.dataset)
 
     def __iter__(self):
-        import concurrent.futures as cf
-        ds, n = self.dataset, len(self.dataset)
-        is_test = hasattr(ds, "gt_paths")
-        ahead = max(2 * self.readers, self.batch)
-        with cf.ThreadPoolExecutor(self.readers) as pool:
-            reads = {i: pool.submit(ds.decoded, i) for i in range(min(ahead, n))}
-            nxt = len(reads)
-            for lo in range(0, n, self.batch):
-                idx = list(range(lo, min(lo + self.batch, n)))
-                dec = []
-                for i in idx:
-                    dec.append(reads.pop(i).result())
-                    if nxt < n:
-                        reads[nxt] = pool.submit(ds.decoded, nxt)
-                        nxt += 1
-                out = self.prep.prepare_batch([d[0] for d in dec], [d[1] for d in dec], [d[2] for d in dec])
-                masks = None
-                if is_test:
-                    masks = self._masks_to_host([m for _, m in out])
-                for j, i in enumerate(idx):
-                    sample = out[j][0].batched()
-                    label = torch.tensor([ds.labels[i]])
-                    if is_test:
-                        yield sample, masks[j], label, [str(ds.img_paths[i][0])]
-                    else:
-                        yield sample, label
+        ds = self.dataset
+        return _device_items(len(ds), ds.decoded, lambda dec: self.prep.prepare_batch(*zip(*dec)), ds.labels,
+                             [str(p[0]) for p in ds.img_paths] if hasattr(ds, "gt_paths") else None, self.readers, self.batch)
 
-    def _masks_to_host(self, masks):
-        return _masks_to_host(masks)
+
+def _device_items(n, decode, prepare, labels, rgb_paths, readers, batch):
+    """The item stream of every device source, in index order: ``(sample.batched(), label [1])`` or, with ``rgb_paths`` (a test split),
+    ``(sample.batched(), host mask [1,1,g,g], label [1], [rgb_path])``.  ``decode(i)`` runs on ``readers`` threads, up to
+    ``max(2 * readers, batch)`` items ahead; ``prepare(list of decoded) -> [(DeviceSample, mask | None)]`` runs here, once per ``batch``
+    items, and the batch's masks go to the host through one pinned copy.  A decode error surfaces when its batch is gathered: the
+    batches before it have been yielded.  The reader pool belongs to the `read_ahead` generator: when ``prepare`` or the consumer
+    fails, it is shut down by that generator's close as this one is finalised."""
+    lo = 0
+    for dec in in_batches(read_ahead(decode, range(n), readers, max(2 * readers, batch)), batch):
+        out = prepare(dec)
+        masks = _masks_to_host([m for _, m in out]) if rgb_paths is not None else None
+        for j, (sample, _) in enumerate(out):
+            label = torch.tensor([labels[lo + j]])
+            if rgb_paths is not None:
+                yield sample.batched(), masks[j], label, [rgb_paths[lo + j]]
+            else:
+                yield sample.batched(), label
+        lo += len(dec)
+        del dec      # a batch's decoded arrays (150 MB at 800 x 800) go before the next are taken: the readers' allocations reuse them
 
 
 def _masks_to_host(masks):
@@ -894,7 +882,25 @@ class MVTec3DClass:
         return iter(self._loader("test"))
 
 
-class EyecandiesRawClass:
+class _RawClassSource(_LazySamplePrep):
+    """What the two raw-download class sources share: 'hip' or an error, the three sizes of ``args``, ``readers`` (args.num_workers) and
+    ``batch``, the SamplePrep built at first use, and `_device_items` over the subclass's ``_prepare``.  A subclass sets
+    ``_no_host_path``, its whole error text with a ``{method!r}`` field."""
+
+    def __init__(self, class_name, args):
+        method = getattr(args, "img_process_method", "cpu_v1")
+        _check_method(method)
+        if method != 'hip':
+            raise ValueError(self._no_host_path.format(method=method))
+        self.name, self.args = class_name, args
+        self.rgb_size, self.xyz_size, self.gt_size = (getattr(args, k, 224) for k in ("rgb_size", "xyz_size", "gt_size"))
+        self.readers, self.batch = max(1, int(getattr(args, "num_workers", 6))), 16
+
+    def _items(self, n, decode, labels, rgb_paths=None):
+        return _device_items(n, decode, self._prepare, labels, rgb_paths, self.readers, self.batch)
+
+
+class EyecandiesRawClass(_RawClassSource):
     """One class directory of the RAW Eyecandies download (``<class>/train/data/{i:03d}_*``, ``<class>/test_public/data/{i:02d}_*``) as the
     data object of evaluate.ClassRun / evaluate_classes, with MVTec3DClass's protocol.  It yields what MVTec3DClass with
     img_process_method='hip' yields over the tree the reference's utils/preprocessing_eyecandies.py would have written from this
@@ -902,18 +908,13 @@ class EyecandiesRawClass:
     ``eyecandies_cloud`` -> ``organized_pc_prep`` chain on the current stream, and the float64 cloud never leaves the device
     (docs/eyecandies.md).  Test order: the `bad` samples in index order, then the `good` ones (TestDataset's sorted directories);
     label 1 / 0; a good sample's mask is zeros; ``rgb_path`` is the raw ``*_image_4.png``.  There is no host path."""
+    _no_host_path = ("EyecandiesRawClass: the raw Eyecandies download is prepared on the device only, there is no host path: "
+                     "img_process_method must be 'hip', got {method!r} (or run utils/preprocessing_eyecandies.py first and "
+                     "point dataset_path at its tree)")
 
     def __init__(self, dataset_path, class_name, args):
         from .utils import preprocessing_eyecandies as pe
-        method = getattr(args, "img_process_method", "cpu_v1")
-        _check_method(method)
-        if method != 'hip':
-            raise ValueError(f"EyecandiesRawClass: the raw Eyecandies download is prepared on the device only, there is no host path: "
-                             f"img_process_method must be 'hip', got {method!r} (or run utils/preprocessing_eyecandies.py first and "
-                             f"point dataset_path at its tree)")
-        self.name, self.args = class_name, args
-        self.rgb_size, self.xyz_size, self.gt_size = (getattr(args, k, 224) for k in ("rgb_size", "xyz_size", "gt_size"))
-        self.readers, self.batch = max(1, int(getattr(args, "num_workers", 6))), 16
+        super().__init__(class_name, args)
         self.focal_length = pe.FOCAL_LENGTH
         self._train_dir = str(Path(dataset_path, class_name, "train", "data"))
         self._test_dir = str(Path(dataset_path, class_name, "test_public", "data"))
@@ -927,12 +928,6 @@ class EyecandiesRawClass:
         self.test_indices = order                                  # raw index of every test item
         self.test_labels = [1 if is_bad[i] else 0 for i in order]
         self._test_files = [test_files[i] for i in order]
-        self._prep = None
-
-    def sample_prep(self):
-        if self._prep is None:
-            self._prep = SamplePrep(self.rgb_size, self.xyz_size, self.gt_size)
-        return self._prep
 
     def _decode(self, files, label):
         import numpy as np
@@ -945,57 +940,30 @@ class EyecandiesRawClass:
 
     def _prepare(self, dec):
         """decoded samples -> [(DeviceSample, mask or None)]: per shape one upload of the codes and one kernel chain."""
-        import numpy as np
         from .utils import preprocessing_eyecandies as pe
-        prep, n = self.sample_prep(), len(dec)
+        prep = self.sample_prep()
         imgs = prep.prepare_images([d[0] for d in dec])
         masks = prep.prepare_masks([d[2] for d in dec])
-        clouds = [None] * n
-        groups = {}
-        for i, d in enumerate(dec):
-            groups.setdefault(tuple(np.shape(d[1][0])), []).append(i)
-        with torch.cuda.device(prep.device):
-            for idx in groups.values():
-                scans = [dec[i][1] for i in idx]
-                cloud, _ = pe.cloud_on_device([s[0] for s in scans], [s[1] for s in scans], [s[2] for s in scans],
-                                              [s[3] for s in scans], self.focal_length, prep.device, want_removed=False)
-                for i, out in zip(idx, prep.prepare_device_clouds(cloud)):
-                    clouds[i] = out
-        return [(DeviceSample((imgs[i], clouds[i][0], clouds[i][1]), clouds[i][2]), masks[i]) for i in range(n)]
 
-    def _iterate(self, files, labels, is_test):
-        import concurrent.futures as cf
-        n = len(files)
-        ahead = max(2 * self.readers, self.batch)
-        with cf.ThreadPoolExecutor(self.readers) as pool:
-            reads = {i: pool.submit(self._decode, files[i], labels[i]) for i in range(min(ahead, n))}
-            nxt = len(reads)
-            for lo in range(0, n, self.batch):
-                idx = list(range(lo, min(lo + self.batch, n)))
-                dec = []
-                for i in idx:
-                    dec.append(reads.pop(i).result())
-                    if nxt < n:
-                        reads[nxt] = pool.submit(self._decode, files[nxt], labels[nxt])
-                        nxt += 1
-                out = self._prepare(dec)
-                masks = _masks_to_host([m for _, m in out]) if is_test else None
-                for j, i in enumerate(idx):
-                    sample = out[j][0].batched()
-                    label = torch.tensor([labels[i]])
-                    if is_test:
-                        yield sample, masks[j], label, [files[i]["rgb"]]
-                    else:
-                        yield sample, label
+        def clouds_of(_, idx):
+            codes, minds, maxds, poses = zip(*(dec[i][1] for i in idx))
+            cloud, _ = pe.cloud_on_device(codes, minds, maxds, poses, self.focal_length, prep.device, want_removed=False)
+            return prep.prepare_device_clouds(cloud)
+
+        with torch.cuda.device(prep.device):
+            clouds = scatter_by_shape([d[1][0] for d in dec], range(len(dec)), clouds_of)
+        return [(DeviceSample((img, cloud, depth), count), mask) for img, (cloud, depth, count), mask in zip(imgs, clouds, masks)]
 
     def train(self):
-        return self._iterate(self._train_files, [0] * self.n_train, False)
+        files = self._train_files
+        return self._items(self.n_train, lambda i: self._decode(files[i], 0), [0] * self.n_train)
 
     def test(self):
-        return self._iterate(self._test_files, self.test_labels, True)
+        files, labels = self._test_files, self.test_labels
+        return self._items(self.n_test, lambda i: self._decode(files[i], labels[i]), labels, [f["rgb"] for f in files])
 
 
-class MVTec3DRawClass:
+class MVTec3DRawClass(_RawClassSource):
     """One class directory of the RAW MVTec 3D-AD download -- the tree on which the reference's utils/preprocessing.py has NOT been
     run -- as the data object of evaluate.ClassRun / evaluate_classes, with MVTec3DClass's protocol.  It yields, sample for sample and
     bit for bit, what MVTec3DClass with img_process_method='hip' yields over a copy of the tree that utils.preprocessing.
@@ -1004,28 +972,17 @@ class MVTec3DRawClass:
     padding, largest DBSCAN cluster; docs/preprocessing.md) and SamplePrep's device entry points.  Files, order, labels and
     ``rgb_path`` are TrainDataset's / TrainValidationDataset's / TestDataset's; a good test sample's mask is zeros.  There is no host
     path."""
+    _no_host_path = ("MVTec3DRawClass: raw MVTec 3D-AD scans are cleaned on the device only, there is no host path: "
+                     "img_process_method must be 'hip', got {method!r} (or run utils/preprocessing.py over the tree first and "
+                     "read it with MVTec3DClass: raw_scans=False)")
 
     def __init__(self, dataset_path, class_name, args):
-        method = getattr(args, "img_process_method", "cpu_v1")
-        _check_method(method)
-        if method != 'hip':
-            raise ValueError(f"MVTec3DRawClass: raw MVTec 3D-AD scans are cleaned on the device only, there is no host path: "
-                             f"img_process_method must be 'hip', got {method!r} (or run utils/preprocessing.py over the tree first and "
-                             f"read it with MVTec3DClass: raw_scans=False)")
-        self.name, self.args = class_name, args
-        self.rgb_size, self.xyz_size, self.gt_size = (getattr(args, k, 224) for k in ("rgb_size", "xyz_size", "gt_size"))
-        self.readers, self.batch = max(1, int(getattr(args, "num_workers", 6))), 16
+        super().__init__(class_name, args)
         sizes = dict(class_name=class_name, rgb_size=self.rgb_size, xyz_size=self.xyz_size, gt_size=self.gt_size,
                      dataset_path=dataset_path, img_process_method='hip')
         self._train = (TrainValidationDataset if getattr(args, "train_with_validation", False) else TrainDataset)(**sizes)
         self._test = TestDataset(**sizes)
         self.n_train, self.n_test = len(self._train), len(self._test)
-        self._prep = None
-
-    def sample_prep(self):
-        if self._prep is None:
-            self._prep = SamplePrep(self.rgb_size, self.xyz_size, self.gt_size)
-        return self._prep
 
     @staticmethod
     def _decode(paths, gt_path):
@@ -1047,54 +1004,34 @@ class MVTec3DRawClass:
     def _prepare(self, dec):
         """decoded scans -> [(DeviceSample, mask or None)]: one upload per shape, one cleaning chain and one preparation per scan."""
         from .utils import preprocessing as pp
-        prep, n = self.sample_prep(), len(dec)
-        out = [None] * n
-        with torch.cuda.device(prep.device):
-            for _, idx in _group_by_shape([d[0] for d in dec], range(n)).items():
-                pcs = prep._upload([dec[i][0] for i in idx], torch.float32, "the point cloud")
-                rgbs = prep._upload([dec[i][1] for i in idx], torch.uint8, "rgb")
-                with_gt = [i for i in idx if dec[i][2] is not None]
-                gts = prep._upload([dec[i][2] for i in with_gt], torch.uint8, "gt") if with_gt else None
-                for j, i in enumerate(idx):
-                    gt = gts[with_gt.index(i)] if dec[i][2] is not None else None
-                    pc, rgb, gt = pp.preprocess_on_device(pcs[j], rgbs[j], gt)
-                    img = prep.prepare_device_images(rgb[None])[0]
-                    cloud, depth, count = prep.prepare_device_clouds(pc[None])[0]
-                    mask = prep.prepare_device_masks(gt[None])[0] if gt is not None else None
-                    out[i] = (DeviceSample((img, cloud, depth), count), mask)
-        return out
+        prep = self.sample_prep()
 
-    def _iterate(self, ds, is_test):
-        import concurrent.futures as cf
-        n = len(ds)
-        gt_of = (lambda i: ds.gt_paths[i] if ds.gt_paths[i] != 0 else None) if is_test else (lambda i: None)
-        ahead = max(2 * self.readers, self.batch)
-        with cf.ThreadPoolExecutor(self.readers) as pool:
-            reads = {i: pool.submit(self._decode, ds.img_paths[i], gt_of(i)) for i in range(min(ahead, n))}
-            nxt = len(reads)
-            for lo in range(0, n, self.batch):
-                idx = list(range(lo, min(lo + self.batch, n)))
-                dec = []
-                for i in idx:
-                    dec.append(reads.pop(i).result())
-                    if nxt < n:
-                        reads[nxt] = pool.submit(self._decode, ds.img_paths[nxt], gt_of(nxt))
-                        nxt += 1
-                out = self._prepare(dec)
-                masks = _masks_to_host([m for _, m in out]) if is_test else None
-                for j, i in enumerate(idx):
-                    sample = out[j][0].batched()
-                    label = torch.tensor([ds.labels[i]])
-                    if is_test:
-                        yield sample, masks[j], label, [str(ds.img_paths[i][0])]
-                    else:
-                        yield sample, label
+        def scans_of(_, idx):
+            pcs = prep._upload([dec[i][0] for i in idx], torch.float32, "the point cloud")
+            rgbs = prep._upload([dec[i][1] for i in idx], torch.uint8, "rgb")
+            with_gt = [i for i in idx if dec[i][2] is not None]
+            gts = prep._upload([dec[i][2] for i in with_gt], torch.uint8, "gt") if with_gt else None
+            gt_row = {i: k for k, i in enumerate(with_gt)}
+            out = []
+            for j, i in enumerate(idx):
+                pc, rgb, gt = pp.preprocess_on_device(pcs[j], rgbs[j], gts[gt_row[i]] if i in gt_row else None)
+                img = prep.prepare_device_images(rgb[None])[0]
+                cloud, depth, count = prep.prepare_device_clouds(pc[None])[0]
+                mask = prep.prepare_device_masks(gt[None])[0] if gt is not None else None
+                out.append((DeviceSample((img, cloud, depth), count), mask))
+            return out
+
+        with torch.cuda.device(prep.device):
+            return scatter_by_shape([d[0] for d in dec], range(len(dec)), scans_of)
 
     def train(self):
-        return self._iterate(self._train, False)
+        ds = self._train
+        return self._items(len(ds), lambda i: self._decode(ds.img_paths[i], None), ds.labels)
 
     def test(self):
-        return self._iterate(self._test, True)
+        ds = self._test
+        return self._items(len(ds), lambda i: self._decode(ds.img_paths[i], ds.gt_paths[i] if ds.gt_paths[i] != 0 else None), ds.labels,
+                           [str(p[0]) for p in ds.img_paths])
 
 
 def dataset_classes(args):

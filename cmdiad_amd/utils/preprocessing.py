@@ -25,6 +25,8 @@ from pathlib import Path
 import numpy as np
 
 from . import mvtec3d_util as mvt_util
+from . import gpu_device
+from .batching import read_ahead
 
 log = logging.getLogger("cmdiad_amd.preprocessing")
 
@@ -36,13 +38,7 @@ _SEED = 0                     # the surface of the reference has no seed argumen
 
 
 def _device(device=None):
-    import torch
-    from .. import _native as nat
-    if not torch.cuda.is_available():
-        raise nat.NativeError("cmdiad_amd.utils.preprocessing needs a GPU: plane removal and DBSCAN run on the device (no CPU path)")
-    if device is not None:
-        torch.cuda.set_device(int(device))      # the kernels are enqueued on the current device's current stream
-    return torch.device("cuda", torch.cuda.current_device())
+    return gpu_device(device, "cmdiad_amd.utils.preprocessing needs a GPU: plane removal and DBSCAN run on the device (no CPU path)")
 
 
 def get_edges_of_pc(organized_pc):
@@ -245,15 +241,10 @@ def preprocess_dataset(root_path, device=None, readers=4, writers=2, progress=No
     import concurrent.futures as cf
     dev = _device(device)
     paths = sorted(str(p) for p in Path(root_path).rglob('*.tiff'))
-    with cf.ThreadPoolExecutor(readers) as rd, cf.ThreadPoolExecutor(writers) as wr:
-        ahead = max(2 * readers, 2)
-        reads = {i: rd.submit(_read, paths[i]) for i in range(min(ahead, len(paths)))}
+    with cf.ThreadPoolExecutor(writers) as wr:
         writes = []
-        for i, path in enumerate(paths):
-            pc, rgb, gt = reads.pop(i).result()
-            if i + ahead < len(paths):
-                reads[i + ahead] = rd.submit(_read, paths[i + ahead])
-            writes.append(wr.submit(_write, path, *_preprocess_one(pc, rgb, gt, _SEED, dev)))
+        for i, (pc, rgb, gt) in enumerate(read_ahead(_read, paths, readers, max(2 * readers, 2))):
+            writes.append(wr.submit(_write, paths[i], *_preprocess_one(pc, rgb, gt, _SEED, dev)))
             while len(writes) > 2 * writers:
                 writes.pop(0).result()
             if progress is not None:

@@ -21,19 +21,16 @@ from shutil import copyfile
 
 import numpy as np
 
+from . import gpu_device
+from .batching import in_batches, read_ahead, scatter_by_shape
+
 # The same camera has been used for all the images
 FOCAL_LENGTH = 711.11
 
 
 def _device(device=None):
-    import torch
-    from .. import _native as nat
-    if not torch.cuda.is_available():
-        raise nat.NativeError("cmdiad_amd.utils.preprocessing_eyecandies needs a GPU: the depth-to-cloud stages run on the device "
+    return gpu_device(device, "cmdiad_amd.utils.preprocessing_eyecandies needs a GPU: the depth-to-cloud stages run on the device "
                               "(no CPU path)")
-    if device is not None:
-        torch.cuda.set_device(int(device))      # the kernels are enqueued on the current device's current stream
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 # ------------------------------------------------------------------------------------------------ files
@@ -149,17 +146,14 @@ def cloud_arrays(depth_u16, mind, maxd, pose, focal_length=FOCAL_LENGTH, device=
     n = len(depth_u16)
     if not (len(mind) == len(maxd) == len(pose) == n):
         raise ValueError("cloud_arrays: the lists of scans differ in length")
-    groups = {}
-    for i, c in enumerate(depth_u16):
-        groups.setdefault(tuple(np.shape(c)), []).append(i)
-    clouds, masks = [None] * n, [None] * n
-    for idx in groups.values():
+
+    def group(_, idx):
         cloud, removed = cloud_on_device([depth_u16[i] for i in idx], [mind[i] for i in idx], [maxd[i] for i in idx],
                                          [pose[i] for i in idx], focal_length, dev)
-        cloud, removed = cloud.cpu().numpy(), removed.cpu().numpy().astype(bool)
-        for j, i in enumerate(idx):
-            clouds[i], masks[i] = cloud[j], removed[j]
-    return clouds, masks
+        return zip(cloud.cpu().numpy(), removed.cpu().numpy().astype(bool))
+
+    out = scatter_by_shape(depth_u16, range(n), group)
+    return [o[0] for o in out], [o[1] for o in out]
 
 
 # ------------------------------------------------------------------------------------------------ the reference's __main__
@@ -231,29 +225,18 @@ def preprocess_dataset(dataset_path, target_dir, device=None, readers=4, writers
         return read_scan(files["depth"], files["info"], files["pose"]), (read_mask(files["mask"]) if split == "test" else None)
 
     done = 0
-    with cf.ThreadPoolExecutor(readers) as rd, cf.ThreadPoolExecutor(writers) as wr:
-        ahead = max(2 * readers, 2 * batch)
-        reads = {i: rd.submit(read, jobs[i]) for i in range(min(ahead, len(jobs)))}
-        nxt, writes = len(reads), []
-        for lo in range(0, len(jobs), batch):
-            idx = list(range(lo, min(lo + batch, len(jobs))))
-            dec = []
-            for i in idx:
-                dec.append(reads.pop(i).result())
-                if nxt < len(jobs):
-                    reads[nxt] = rd.submit(read, jobs[nxt])
-                    nxt += 1
+    with cf.ThreadPoolExecutor(writers) as wr:
+        writes = []
+        for dec in in_batches(read_ahead(read, jobs, readers, max(2 * readers, 2 * batch)), batch):
             scans = [d[0] for d in dec]
             clouds, _ = cloud_arrays([s[0] for s in scans], [s[1] for s in scans], [s[2] for s in scans], [s[3] for s in scans],
                                      FOCAL_LENGTH, dev.index)
-            for i, d, cloud in zip(idx, dec, clouds):
-                out, split, k, files = jobs[i]
-                mask = d[1]
+            for (out, split, k, files), (_, mask), cloud in zip(jobs[done:done + len(dec)], dec, clouds):
                 sub = "train/good" if split == "train" else ("test/bad" if np.any(mask) else "test/good")
                 writes.append(wr.submit(_write, files, os.path.join(out, sub), k, cloud, mask))
             while len(writes) > 4 * writers:
                 writes.pop(0).result()
-            done += len(idx)
+            done += len(dec)
             if progress is not None:
                 progress(done, len(jobs))
         for w in writes:

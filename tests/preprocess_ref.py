@@ -6,6 +6,10 @@
            graph numbered by their lowest core index, a border point takes the lowest cluster number among its core neighbours
            (what sklearn.cluster.DBSCAN returns: tests/test_preprocess_cpu.py compares the two on every scene)
 """
+import os
+import sys
+import types
+
 import numpy as np
 
 M32 = 0xFFFFFFFF
@@ -305,3 +309,47 @@ def full_size_scene(seed=31, H=800, W=800, pitch=2e-4, eps=0.006):
     remap = {k: i for i, (_, k) in enumerate(firsts)}
     want = np.array([remap.get(int(k), -1) for k in range(-1, len(discs))])[planted + 1]
     return pts, want.astype(np.int32)
+
+
+# ------------------------------------------------------------------------------------------------ a raw MVTec 3D-AD class directory
+def scene_key(kw):
+    return tuple(sorted(kw.items()))
+
+
+RAW_TREE = [("train/good", [dict(seed=7, H=120, W=120), dict(seed=61, H=120, W=120), dict(seed=52, H=150, W=260)], False),
+            ("test/good", [dict(seed=62, H=120, W=120), dict(seed=63, H=120, W=120)], False),
+            ("test/hole", [dict(seed=64, H=120, W=120), dict(seed=65, H=130, W=110)], True)]
+
+
+def fake_tifffile(monkeypatch):
+    """`tifffile` stand-in that reads and writes np.save content under the .tiff name (float32 arrays either way: lossless)."""
+    fake = types.ModuleType("tifffile")
+
+    def imread(path):
+        with open(path, "rb") as fh:
+            return np.load(fh)
+
+    def imwrite(path, a):
+        with open(path, "wb") as fh:
+            np.save(fh, a)
+    fake.imread, fake.imwrite = imread, imwrite
+    monkeypatch.setitem(sys.modules, "tifffile", fake)
+    return fake
+
+
+def write_raw_tree(root, fake):
+    """<root>/bagel/{train/good x 3, test/good x 2, test/hole x 2 with gt} from make_scan, one scan 150 x 260 -> [(stem, scene key)]."""
+    from PIL import Image
+    items = []
+    for sub, scenes, has_gt in RAW_TREE:
+        base = os.path.join(root, "bagel", sub)
+        for d in ("rgb", "xyz") + (("gt",) if has_gt else ()):
+            os.makedirs(os.path.join(base, d))
+        for i, kw in enumerate(scenes):
+            scan = make_scan(**kw)
+            fake.imwrite(os.path.join(base, "xyz", f"{i:03d}.tiff"), scan["pc"])
+            Image.fromarray(scan["rgb"]).save(os.path.join(base, "rgb", f"{i:03d}.png"))
+            if has_gt:
+                Image.fromarray(scan["gt"], "L").save(os.path.join(base, "gt", f"{i:03d}.png"))
+            items.append((f"{sub}/{i:03d}", scene_key(kw), has_gt))
+    return items

@@ -7,7 +7,6 @@ import functools
 import os
 import shutil
 import sys
-import types
 
 import numpy as np
 import pytest
@@ -161,8 +160,7 @@ def _reference(key):
     return scan, pr.preprocess(scan["pc"], scan["rgb"], scan["gt"])
 
 
-def _key(kw):
-    return tuple(sorted(kw.items()))
+_key = pr.scene_key
 
 
 def _on_device(scan, with_gt=True, seed=0):
@@ -234,43 +232,7 @@ def test_preprocess_on_device_degenerate_scans():
 
 
 # ------------------------------------------------------------------------------------------------------------ the raw class
-TREE = [("train/good", [dict(seed=7, H=120, W=120), dict(seed=61, H=120, W=120), dict(seed=52, H=150, W=260)], False),
-        ("test/good", [dict(seed=62, H=120, W=120), dict(seed=63, H=120, W=120)], False),
-        ("test/hole", [dict(seed=64, H=120, W=120), dict(seed=65, H=130, W=110)], True)]
-
-
-def _fake_tifffile(monkeypatch):
-    """`tifffile` stand-in that reads and writes np.save content under the .tiff name (float32 arrays either way: lossless)."""
-    fake = types.ModuleType("tifffile")
-
-    def imread(path):
-        with open(path, "rb") as fh:
-            return np.load(fh)
-
-    def imwrite(path, a):
-        with open(path, "wb") as fh:
-            np.save(fh, a)
-    fake.imread, fake.imwrite = imread, imwrite
-    monkeypatch.setitem(sys.modules, "tifffile", fake)
-    return fake
-
-
-def _write_raw_tree(root, fake):
-    """<root>/bagel/{train/good x 3, test/good x 2, test/hole x 2 with gt} from make_scan, one scan 150 x 260 -> [(stem, scene key)]."""
-    from PIL import Image
-    items = []
-    for sub, scenes, has_gt in TREE:
-        base = os.path.join(root, "bagel", sub)
-        for d in ("rgb", "xyz") + (("gt",) if has_gt else ()):
-            os.makedirs(os.path.join(base, d))
-        for i, kw in enumerate(scenes):
-            scan = pr.make_scan(**kw)
-            fake.imwrite(os.path.join(base, "xyz", f"{i:03d}.tiff"), scan["pc"])
-            Image.fromarray(scan["rgb"]).save(os.path.join(base, "rgb", f"{i:03d}.png"))
-            if has_gt:
-                Image.fromarray(scan["gt"], "L").save(os.path.join(base, "gt", f"{i:03d}.png"))
-            items.append((f"{sub}/{i:03d}", _key(kw), has_gt))
-    return items
+TREE, _fake_tifffile, _write_raw_tree = pr.RAW_TREE, pr.fake_tifffile, pr.write_raw_tree      # (shared with test_gpu_sample_loader.py)
 
 
 def _args(root, **kw):
