@@ -295,7 +295,8 @@ v = gelu_erf4(v);
 }
 
 // Persistent form for the wide transformer products (fc1-like: whole 256-column tiles, bias, bf16 output): one block per CU
-// walks a contiguous range of the (M tile, N tile) list on the two-group pipeline of the distance GEMM (gemm_pp3.h).  The
+// walks a contiguous range of the (M tile, N tile) list, N tile fastest, on the two-group pipeline (run_two_group in gemm_pp3.h,
+// where the schedule, its staging and its counted waits are derived; the distance GEMM of l2min.hip runs the same schedule).  The
 // 128 x 128 shape moves 32 KiB through the L1 -> LDS path per 512 MFMA cycles, which IS that path's 64 B/clk: two co-resident
 // blocks can never exceed half the MFMA rate; 256 x 256 halves the bytes per FLOP, the job walk removes the per-tile
 // fill / drain and the partial last round (a lock-step 256 x 256 persistent kernel without the two-group schedule gained
@@ -409,7 +410,7 @@ __global__ __launch_bounds__(512, 1) void gemm_std_pp3_kernel(GlobalTile A, Glob
         }
         emit(std::false_type{});
         return 0;
-    }, p.group_m, MT);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1079,7 +1080,6 @@ extern "C" int cmdiad_gemm_bf16(const cmdiad_gemm_args* a, cmdiad_stream_t strea
         if (plain3 && want3) {
             constexpr int kLds3 = SPP3::LDS_BYTES + 8 * kPp3Scratch;
             const dim3 grid(persist_blocks(a->M, a->N));
-            p.group_m = 1;
             rc = with_act(a->act, [&](auto act) {
                 constexpr int ACT = decltype(act)::value;
                 if (a->row_scale) return launch_lds<gemm_std_pp3_kernel<ACT, true>>("cmdiad_gemm_bf16", grid, dim3(512), kLds3, s, A, W, p);

@@ -1,23 +1,42 @@
-// Two-group ("ping-pong") 256 x 256 x 64 MFMA pipeline as a PERSISTENT tile loop with a caller-supplied epilogue: the
-// schedule of l2_min_pp3_kernel (l2min.hip, where the phase / staging / counted-wait design is derived and measured) walking
-// a list of (M tile, N tile) jobs instead of one query tile against a range of library tiles.
+// The two-group ("ping-pong") 256 x 256 x 64 MFMA pipeline: THE one implementation of the schedule (run_two_group) that the
+// persistent network GEMMs (gemm.hip: gemm_std_pp3_kernel through run_pp3_jobs) and the stream-K / one-tile residual kernel
+// (gemm_sk.hip) instantiate with a job type and their hooks.  l2_min_pp3_kernel (l2min.hip) runs the same schedule from a
+// hand-kept copy (its norm fetch / park hooks pushed the shared loop past 256 VGPRs: profiles/two_group_loop.md); a change to
+// the schedule is made here and there.
 //
 //   * 8 waves of 128 x 64 in two groups of four (one wave of each group per SIMD) half a phase apart: one group's fragment
 //     reads and LDS-DMA issue sit under the other group's MFMAs.  A K-tile = 4 phases of 16 MFMAs per wave.
-//   * LDS: three W buffers (3 x 32 KiB) + three A half slots (3 x 16 KiB) = 144 KiB.  Waves 0-3 feed the W stream (seven
-//     half-units ahead, counted wait vmcnt(14)), waves 4-7 the A stream (three ahead, vmcnt(6)); the s_waitcnt counters are
-//     never drained inside a stream, and BOTH streams run on across tile boundaries: the next job's first K-tiles are
-//     in flight while the current tile's last MFMAs and its epilogue execute -- no per-tile fill or drain, and with one block
-//     per CU walking jobs [j0, j1) no partial last round.
-//   * epi(acc, mt, nt) runs after a tile's last phase and returns the number of vector-memory operations it is GUARANTEED to
-//     have issued (0 when unsure).  Loads and stores count in vmcnt like the DMA pieces and retire in order, so for the
-//     phases in which the epilogue's operations are younger than the piece a counted wait protects (7 phases for the W
-//     stream, 3 for the A stream) the wait's immediate is raised by that number: vmcnt(14) right after 32 stores would wait
-//     for 20 of them to reach L2 -- with all eight waves of the CU at the next barrier.
-//   * pre(mt, nt) runs in phase 0 of a tile's LAST K-tile: the place to fetch epilogue operands (bias) by inline asm; eight
-//     DMA pieces are issued between that point and the epilogue (or the stream has ended and drained), so the epilogue opens
-//     with s_waitcnt vmcnt(8) instead of a compiler-placed vmcnt(0) that would drain the prefetch queue.
-// Whole 256-column tiles only (N % 256 == 0); ragged M is clamped on the A stream and masked by the epilogue; K >= 192.
+//   * LDS (SPP3): three W buffers (3 x 32 KiB) + three A HALF slots (3 x 16 KiB: a tile's lo rows are read in phase 0 and its
+//     hi rows in phase 2, so halves rotate through three slots) = 144 KiB.
+//   * The two operands are issued by DIFFERENT waves -- waves 0-3 (the earlier group) feed the W stream, waves 4-7 the A
+//     stream -- because s_waitcnt vmcnt retires in order per wave: in one queue the short-lead A pieces would force the
+//     long-lead W pieces out early.  Each stream is a plain sequence of half-units (8 pieces = 4 waves x 2)
+//     [lo h0, lo h1, hi h0, hi h1] per K-tile, one per phase:   W half-unit (P + 10) and A half-unit (P + 5) are issued in
+//     phase P.
+//       W:  lo(T') in phases 4T'-10, -9 (its buffer held K-tile T'-3, whose lo rows were last read in phase 4T'-12: an
+//           earlier-group issuer needs two phases of distance), hi(T') in 4T'-8, -7 (last read 4T'-11); read in 4T', 4T'+1:
+//           every half-unit has >= 7 phases, so vmcnt(14) (the 7 newest half-units) is the counted wait of the W waves;
+//       A:  lo(T') in 4T'-5, -4 (slot of hi(T'-2), last read 4T'-6: a later-group issuer needs one phase), hi(T') in
+//           4T'-3, -2 (slot of lo(T'-1), last read 4T'-4); the earlier group reads half a phase before the issuing group's
+//           wait, so a half-unit issued in phase P is readable from P + 3: vmcnt(6) for the A waves.
+//     The s_waitcnt counters are never drained inside a stream, and BOTH streams run on across job boundaries: the next job's
+//     first K-tiles are in flight while the current job's last MFMAs and its end hook execute -- no per-tile fill or drain.
+//   * Hooks of run_two_group (all called by every wave, on the consumer side's copy of the job):
+//       phase0(job, left)  in phase 0 of every K-tile, `left` K-tiles of the job remaining including this one: the place to
+//                          fetch the job end's operands by inline asm (eight DMA pieces are issued between phase 0 of the
+//                          last K-tile and the job end, or the stream has ended and drained: the end can open with
+//                          s_waitcnt vmcnt(8) instead of a compiler-placed vmcnt(0) that would drain the prefetch queue);
+//       job_end(job)       after the job's last phase; returns true when it is GUARANTEED to have issued EPI_OPS
+//                          vector-memory operations.  Loads and stores count in vmcnt like the DMA pieces and retire in order,
+//                          so for the phases in which those operations are younger than the piece a counted wait protects (7
+//                          phases for the W stream, 3 for the A stream) the wait's immediate is raised by EPI_OPS: vmcnt(14)
+//                          right after 32 stores would wait for 20 of them to reach L2 -- with all eight waves of the CU at
+//                          the next barrier;
+//       job_start(job)     before the first job's first phase (after the prologue's DMA pieces) and after every job_end but
+//                          the last: sets the accumulators.
+//   * A job is a small value type: mt() / nt() its tile, k0() its first k-tile, kc() its k-tile count (>= 1), next() the step
+//     to the block's next job.  The stream side and the consumer side each walk a copy.
+// Whole 256-column tiles only (N % 256 == 0); ragged M is clamped on the A stream and masked by the caller; K >= 192.
 #pragma once
 #include "gemm_core.h"
 
@@ -32,33 +51,6 @@ struct SPP3 {
 
 __device__ __forceinline__ void pp3_barrier() { asm volatile("s_barrier" ::: "memory"); }
 
-// acc[i][j][r]: row m = mt*256 + wr*128 + i*16 + (lane & 15), column n = nt*256 + wc*64 + j*16 + (lane >> 4)*4 + r
-// (swapped orientation: a lane holds four consecutive columns of one row).
-// Job order: M tiles in groups of GM; inside a group the M tile runs fastest, then the N tile (job -> (g, nt, m) with
-// g = job / (rows(g) * NT)); GM = 1 is plain N-fastest.  A block's consecutive jobs then share the W tile (kept hot in
-// L2) while the A tiles change; the blocks of an XCD (consecutive job ranges) work on few M groups at a time.
-struct JobCursor {
-    int g, nt, mi, rows, GM, NT, MT;
-    __device__ __forceinline__ void init(int job, int GM_, int NT_, int MT_)
-    {
-        GM = GM_; NT = NT_; MT = MT_;
-        const int per = GM * NT;             // jobs of a full group
-        g = job / per;
-        rows = min(GM, MT - g * GM);
-        const int rem = job - g * per;       // (the last, short group is only ever entered at its first job or walked into)
-        nt = rem / rows;
-        mi = rem - nt * rows;
-    }
-    __device__ __forceinline__ int mt() const { return g * GM + mi; }
-    __device__ __forceinline__ void next()
-    {
-        if (++mi == rows) {
-            mi = 0;
-            if (++nt == NT) { nt = 0; ++g; rows = min(GM, MT - g * GM); }
-        }
-    }
-};
-
 template <int N>
 __device__ __forceinline__ void pp3_wait_vmcnt()
 {
@@ -66,23 +58,18 @@ __device__ __forceinline__ void pp3_wait_vmcnt()
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// EPI_OPS: the operation count a FULL-tile epilogue returns (compile time: it becomes an s_waitcnt immediate)
-template <bool F16, int EPI_OPS, class Pre, class Epi>
-__device__ __forceinline__ void run_pp3_jobs(const GlobalTile& A, const GlobalTile& W, int j0, int j1, int NT, int KT, char* lds,
-                                             Pre&& pre, Epi&& epi, int GM = 1, int MT = 1 << 30)
+// acc[i][j][r]: row m = mt*256 + wr*128 + i*16 + (lane & 15), column n = nt*256 + wc*64 + j*16 + (lane >> 4)*4 + r
+// (swapped orientation: a lane holds four consecutive columns of one row).
+// T_total: K-tiles of all the block's jobs together.  EPI_OPS is compile time: it becomes an s_waitcnt immediate.
+template <bool F16, int EPI_OPS, class Job, class Phase0, class JobEnd, class JobStart>
+__device__ __forceinline__ void run_two_group(const GlobalTile& A, const GlobalTile& W, const Job& first, int T_total, char* lds,
+                                              f32x4 (&acc)[8][4], Phase0&& phase0, JobEnd&& job_end, JobStart&& job_start)
 {
     using S = SPP3;
     using frag = typename std::conditional<F16, f16x8, bf16x8>::type;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wr = wave >> 2, wc = wave & 3;
-    const int T_total = (j1 - j0) * KT;
     if (T_total <= 0) return;  // block-uniform
-
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // Everything below is instantiated twice, once per stream: a wave only ever executes its own (lean) issue path.
     auto body = [&](auto BANK) {
@@ -91,16 +78,15 @@ __device__ __forceinline__ void run_pp3_jobs(const GlobalTile& A, const GlobalTi
     const int src_chunk = ((lane & 7) ^ (lane >> 3)) * 8;  // element offset of the 16-byte chunk this lane fetches
     const int row_w = bank_wave ? (sw >> 1) * 64 + (sw & 1) * 16 : sw * 16;  // this wave's share of every half-unit
     const size_t ld2 = (size_t)(bank_wave ? W.ld : A.ld) * 2;                  // row pitch in bytes
-    JobCursor sj;                                                              // the stream's current job
-    sj.init(j0, GM, NT, MT);
-    int s_mt = sj.mt();
+    Job sj = first;                                                            // the stream's current job
+    int s_mt = sj.mt(), s_k = sj.k0(), s_left = sj.kc();
     auto tile_ptr = [&]() {
-        return bank_wave ? reinterpret_cast<const char*>(W.base + (size_t)(sj.nt * S::BN + row_w + (lane >> 3)) * W.ld + src_chunk)
-                         : reinterpret_cast<const char*>(A.base + (size_t)(s_mt * S::BM + row_w + (lane >> 3)) * A.ld + src_chunk);
+        return bank_wave ? reinterpret_cast<const char*>(W.base + (size_t)(sj.nt() * S::BN + row_w + (lane >> 3)) * W.ld + s_k * BK + src_chunk)
+                         : reinterpret_cast<const char*>(A.base + (size_t)(s_mt * S::BM + row_w + (lane >> 3)) * A.ld + s_k * BK + src_chunk);
     };
     const char* ptr = tile_ptr();
     bool a_full = s_mt * S::BM + S::BM <= A.rows;
-    int hT = 0, hK = 0;            // stream cursor: K-tile index over the whole job range, k tile inside the job
+    int hT = 0;                    // stream cursor: K-tile index over the whole job range
     int slot_lo = 0, slot_hi = 1;  // W: both = buffer of K-tile hT;  A: half slots of (lo, hi) of K-tile hT
     if (bank_wave) slot_hi = 0;
     auto issue_part = [&](auto PART) {  // -> true when the half-unit was issued
@@ -117,7 +103,7 @@ __device__ __forceinline__ void run_pp3_jobs(const GlobalTile& A, const GlobalTi
             } else {
                 constexpr int rows = hsel * 128 + hi * 64;
                 if (a_full) src = ptr + (size_t)(rows + e * 8) * ld2;
-                else src = reinterpret_cast<const char*>(A.base + (size_t)min(s_mt * S::BM + row_w + rows + e * 8 + (lane >> 3), A.rows - 1) * A.ld + hK * BK + src_chunk);
+                else src = reinterpret_cast<const char*>(A.base + (size_t)min(s_mt * S::BM + row_w + rows + e * 8 + (lane >> 3), A.rows - 1) * A.ld + s_k * BK + src_chunk);
                 dst = lds + S::A_OFF + (hi ? slot_hi : slot_lo) * S::HALF + (row_w + hsel * 64 + e * 8) * 128;
             }
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
@@ -125,10 +111,10 @@ __device__ __forceinline__ void run_pp3_jobs(const GlobalTile& A, const GlobalTi
         }
         if constexpr (part == 3) {  // next K-tile of this stream
             ++hT;
-            if (++hK == KT) {       // next job
-                hK = 0;
+            ++s_k;
+            if (--s_left == 0 && hT < T_total) {   // next job
                 sj.next();
-                s_mt = sj.mt();
+                s_mt = sj.mt(); s_k = sj.k0(); s_left = sj.kc();
                 ptr = tile_ptr();
                 a_full = s_mt * S::BM + S::BM <= A.rows;
             } else ptr += BK * 2;
@@ -142,7 +128,7 @@ __device__ __forceinline__ void run_pp3_jobs(const GlobalTile& A, const GlobalTi
         constexpr int j = decltype(J)::value;
         return bank_wave ? issue_part(std::integral_constant<int, (j + 2) % 4>{}) : issue_part(std::integral_constant<int, (j + 1) % 4>{});
     };
-    int ep_age = 1 << 20;  // phases since an epilogue that issued EPI_OPS operations (wave-uniform)
+    int ep_age = 1 << 20;  // phases since a job end that issued EPI_OPS operations (wave-uniform)
     auto phase_wait = [&](bool issued) {
         constexpr int lead = bank_wave ? 7 : 3, base = bank_wave ? 14 : 6;
         constexpr int raised = base + EPI_OPS > 63 ? 63 : base + EPI_OPS;
@@ -169,9 +155,9 @@ __device__ __forceinline__ void run_pp3_jobs(const GlobalTile& A, const GlobalTi
     auto ldb = [&](int j, int kk) { return *reinterpret_cast<const frag*>(lds + ((b_base + j * 2048) ^ (kk << 6))); };
 
     frag af[4][2], wlo[2][2], whi[2][2];
-    JobCursor cj;
-    cj.init(j0, GM, NT, MT);
-    int kt_c = 0;
+    Job cj = first;        // the consumer's current job
+    int c_left = cj.kc();
+    job_start(cj);
     for (int T = 0; T < T_total; ++T) {
         a_lo = S::A_OFF + ((2 * T) % 3) * S::HALF + a_off;
         a_hi = S::A_OFF + ((2 * T + 1) % 3) * S::HALF + a_off;
@@ -186,7 +172,7 @@ __device__ __forceinline__ void run_pp3_jobs(const GlobalTile& A, const GlobalTi
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) af[i][kk] = lda(i, kk);
-        if (kt_c == KT - 1) pre(cj.mt(), cj.nt);
+        phase0(cj, c_left);
         phase_wait(issue_phase(std::integral_constant<int, 0>{}));
         pp3_barrier();
         __builtin_amdgcn_s_setprio(1);
@@ -241,26 +227,50 @@ __device__ __forceinline__ void run_pp3_jobs(const GlobalTile& A, const GlobalTi
 #pragma unroll
                 for (int j = 0; j < 2; ++j) acc[4 + i][j] = mfma16(wlo[j][kk], af[i][kk], acc[4 + i][j]);
         __builtin_amdgcn_s_setprio(0);
-        if (kt_c == KT - 1) {  // tile finished
+        if (--c_left == 0) {  // job finished
             __builtin_amdgcn_sched_barrier(0);
-            const int ops = epi(acc, cj.mt(), cj.nt);
-            ep_age = ops >= EPI_OPS ? 0 : 1 << 20;
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            ep_age = job_end(cj) ? 0 : 1 << 20;
+            if (T + 1 < T_total) {
+                cj.next();
+                c_left = cj.kc();
+                job_start(cj);
+            }
             __builtin_amdgcn_sched_barrier(0);
         }
         pp3_barrier();
-        if (++kt_c == KT) {
-            kt_c = 0;
-            cj.next();
-        }
     }
     if (wr == 0) pp3_barrier();  // both groups execute the same number of barriers
     };
     if (wave < 4) body(std::true_type{});
     else body(std::false_type{});
+}
+
+// The persistent walk: jobs [j0, j1) of the (M tile, N tile) list, N tile fastest, every job a whole tile of KT k-tiles.
+struct TileJob {
+    int m, n, NT, KT;
+    __device__ __forceinline__ int mt() const { return m; }
+    __device__ __forceinline__ int nt() const { return n; }
+    __device__ __forceinline__ int k0() const { return 0; }
+    __device__ __forceinline__ int kc() const { return KT; }
+    __device__ __forceinline__ void next() { if (++n == NT) { n = 0; ++m; } }
+};
+
+// pre(mt, nt) runs in phase 0 of a tile's LAST K-tile; epi(acc, mt, nt) after its last phase, returning the number of
+// vector-memory operations it is guaranteed to have issued (EPI_OPS for a full tile, 0 when unsure).
+template <bool F16, int EPI_OPS, class Pre, class Epi>
+__device__ __forceinline__ void run_pp3_jobs(const GlobalTile& A, const GlobalTile& W, int j0, int j1, int NT, int KT, char* lds,
+                                             Pre&& pre, Epi&& epi)
+{
+    f32x4 acc[8][4];
+    run_two_group<F16, EPI_OPS>(A, W, TileJob{j0 / NT, j0 % NT, NT, KT}, (j1 - j0) * KT, lds, acc,
+        [&](const TileJob& j, int left) { if (left == 1) pre(j.m, j.n); },
+        [&](const TileJob& j) { return epi(acc, j.m, j.n) >= EPI_OPS; },
+        [&](const TileJob&) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        });
 }
 
 }  // namespace gemm

@@ -4,7 +4,8 @@
 // Why.  The N = 768 products of ViT-B/8 are 99 x 3 = 297 tiles of 256 x 256: on 256 CUs a tile walk is two rounds for 1.16 rounds
 // of work, which is why they ran on the 128 x 128 kernel (1 188 tiles, three rounds for 2.3).  Here the unit of work is a K-STEP:
 // the (tile, k-tile) list -- 297 x 48 = 14 256 steps for fc2 -- is cut into one contiguous range per CU (55.7 steps each), so
-// every CU does the same amount of MFMA work on the two-group 256 x 256 pipeline of gemm_pp3.h / l2min.hip.  A range covers the
+// every CU does the same amount of MFMA work on the two-group 256 x 256 pipeline (run_two_group, gemm_pp3.h: the schedule, its
+// staging and its counted waits live there; this file supplies the job list and the job-end / job-start hooks).  A range covers the
 // END of one tile, whole tiles, and the BEGINNING of another; a tile that two blocks share is finished IN ORDER:
 //   * the block that owns the tile's first k-tiles accumulates from zero and parks its 256 x 256 fp32 accumulators in a
 //     workspace slot (1 KiB per wave store: fully coalesced), then raises the slot's counter;
@@ -20,6 +21,7 @@
 // The partial accumulators and the epilogue's residual rows arrive by inline-asm loads with explicit counted waits: a
 // compiler-visible load inside the K loop gets an s_waitcnt vmcnt(0) in every iteration (tools/isa_lint.py).
 #include "gemm_pp3.h"
+#include "gemm_sk_jobs.h"
 #include "launch.h"
 
 namespace {
@@ -42,22 +44,12 @@ __global__ __launch_bounds__(512, 1) void gemm_sk_kernel(GlobalTile A, GlobalTil
 {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     using S = SPP3;
-    using frag = bf16x8;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wr = wave >> 2, wc = wave & 3;
-    const int NT = p.N / S::BN, MT = (p.M + S::BM - 1) / S::BM, KT = p.K / BK;
-    const long units = (long)MT * NT * KT;
-    const int b = blockIdx.x, nb = gridDim.x;
-    const int u0 = (int)(units * b / nb), u1 = (int)(units * (b + 1) / nb);
-    const int T_total = u1 - u0;
-    if (T_total <= 0) return;
-    // the block's jobs, in execution order (see the header): [tile tB: k 0 .. kBe) | whole tiles tA + 1 .. tB - 1 | [tile tA: k kA .. KT)
-    const int tA = u0 / KT, kA = u0 - tA * KT;
-    const int tB = (u1 - 1) / KT, kBe = (u1 - 1) - tB * KT + 1;
-    const int nj = tB - tA + 1;
-    auto job_tile = [&](int j) __attribute__((always_inline)) { return nj == 1 ? tA : (j == 0 ? tB : (j == nj - 1 ? tA : tA + j)); };
-    auto job_k0 = [&](int j) __attribute__((always_inline)) { return (nj == 1 || j == nj - 1) ? kA : 0; };
-    auto job_kc = [&](int j) __attribute__((always_inline)) { return nj == 1 ? kBe - kA : (j == 0 ? kBe : (j == nj - 1 ? KT - kA : KT)); };
+    const int b = blockIdx.x;
+    // the block's jobs in execution order (gemm_sk_jobs.h): head piece to hand over | whole tiles | tail piece to take over
+    const SkJob first((p.M + S::BM - 1) / S::BM, p.N / S::BN, p.K / BK, b, (int)gridDim.x);
+    if (first.total <= 0) return;
 
     RowStore32 rs;
     rs.init(lds + S::LDS_BYTES + wave * kRowStoreScratch, lane);
@@ -68,11 +60,6 @@ __global__ __launch_bounds__(512, 1) void gemm_sk_kernel(GlobalTile A, GlobalTil
     const float* slot_in = p.partial + (size_t)(b - 1) * kSkSlotFloats;
 
     f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
     // a job that continues a tile: its first accumulators are what the previous block parked (inline asm: header comment)
     auto take_over = [&]() __attribute__((always_inline)) {
         if (lane == 0) {
@@ -161,189 +148,20 @@ __global__ __launch_bounds__(512, 1) void gemm_sk_kernel(GlobalTile A, GlobalTil
         return full;
     };
 
-    // Everything below is instantiated twice, once per stream: a wave only ever executes its own (lean) issue path.
-    auto body = [&](auto BANK) {
-    constexpr bool bank_wave = decltype(BANK)::value;
-    const int sw = wave & 3;
-    const int src_chunk = ((lane & 7) ^ (lane >> 3)) * 8;  // element offset of the 16-byte chunk this lane fetches
-    const int row_w = bank_wave ? (sw >> 1) * 64 + (sw & 1) * 16 : sw * 16;  // this wave's share of every half-unit
-    const size_t ld2 = (size_t)(bank_wave ? W.ld : A.ld) * 2;                  // row pitch in bytes
-    int s_job = 0, s_left = job_kc(0), s_mt = job_tile(0) / NT, s_k = job_k0(0);   // the stream's current job
-    auto tile_ptr = [&]() {
-        const int t = job_tile(s_job);
-        s_mt = t / NT;
-        const int nt = t - s_mt * NT;
-        return bank_wave ? reinterpret_cast<const char*>(W.base + (size_t)(nt * S::BN + row_w + (lane >> 3)) * W.ld + s_k * BK + src_chunk)
-                         : reinterpret_cast<const char*>(A.base + (size_t)(s_mt * S::BM + row_w + (lane >> 3)) * A.ld + s_k * BK + src_chunk);
-    };
-    const char* ptr = tile_ptr();
-    bool a_full = s_mt * S::BM + S::BM <= A.rows;
-    int hT = 0;                    // stream cursor: K-tile index over the whole unit range
-    int slot_lo = 0, slot_hi = 1;  // W: both = buffer of K-tile hT;  A: half slots of (lo, hi) of K-tile hT
-    if (bank_wave) slot_hi = 0;
-    auto issue_part = [&](auto PART) {  // -> true when the half-unit was issued
-        constexpr int part = decltype(PART)::value, hi = part >> 1, hsel = part & 1;
-        if (hT >= T_total) return false;
+    run_two_group<false, kSkEpiOps>(A, W, first, first.total, lds, acc, [](const SkJob&, int) {},
+        [&](const SkJob& j) {   // job finished: park the accumulators for the next block, or the tile's epilogue
+            if (j.hands_over()) { hand_over(); return true; }
+            return epilogue(j.mt(), j.nt());
+        },
+        [&](const SkJob& j) {   // job started: the accumulators the previous block parked, or zeros
+            if (j.takes_over()) take_over();
+            else {
 #pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const char* src;
-            char* dst;
-            if (bank_wave) {
-                constexpr int rows = hsel * 128 + hi * 32;
-                src = ptr + (size_t)(rows + e * 8) * ld2;
-                dst = lds + slot_lo * S::BUF + (row_w + rows + e * 8) * 128;
-            } else {
-                constexpr int rows = hsel * 128 + hi * 64;
-                if (a_full) src = ptr + (size_t)(rows + e * 8) * ld2;
-                else src = reinterpret_cast<const char*>(A.base + (size_t)min(s_mt * S::BM + row_w + rows + e * 8 + (lane >> 3), A.rows - 1) * A.ld + s_k * BK + src_chunk);
-                dst = lds + S::A_OFF + (hi ? slot_hi : slot_lo) * S::HALF + (row_w + hsel * 64 + e * 8) * 128;
+                for (int i = 0; i < 8; ++i)
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) acc[i][jj] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-        }
-        if constexpr (part == 3) {  // next K-tile of this stream
-            ++hT;
-            ++s_k;
-            if (--s_left == 0 && s_job + 1 < nj) {   // next job
-                ++s_job;
-                s_left = job_kc(s_job);
-                s_k = job_k0(s_job);
-                ptr = tile_ptr();
-                a_full = s_mt * S::BM + S::BM <= A.rows;
-            } else ptr += BK * 2;
-            if (bank_wave) { slot_lo = slot_lo == 2 ? 0 : slot_lo + 1; slot_hi = slot_lo; }
-            else { slot_lo = slot_lo == 0 ? 2 : slot_lo - 1; slot_hi = slot_hi == 0 ? 2 : slot_hi - 1; }  // (x + 2) mod 3
-        }
-        return true;
-    };
-    // phase j issues W part (j + 2) % 4 and A part (j + 1) % 4 (W half-unit P + 10, A half-unit P + 5)
-    auto issue_phase = [&](auto J) {
-        constexpr int j = decltype(J)::value;
-        return bank_wave ? issue_part(std::integral_constant<int, (j + 2) % 4>{}) : issue_part(std::integral_constant<int, (j + 1) % 4>{});
-    };
-    int ep_age = 1 << 20;  // phases since a job end that issued kSkEpiOps stores (wave-uniform)
-    auto phase_wait = [&](bool issued) {
-        constexpr int lead = bank_wave ? 7 : 3, base = bank_wave ? 14 : 6;
-        constexpr int raised = base + kSkEpiOps > 63 ? 63 : base + kSkEpiOps;
-        if (!issued) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (ep_age < lead) pp3_wait_vmcnt<raised>();
-        else pp3_wait_vmcnt<base>();
-        ++ep_age;
-    };
-    {
-        using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
-        using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
-        issue_part(I0{}); issue_part(I1{}); issue_part(I2{}); issue_part(I3{}); issue_part(I0{});  // half-units 0..4
-        if (bank_wave) { issue_part(I1{}); issue_part(I2{}); issue_part(I3{}); issue_part(I0{}); issue_part(I1{}); }  // 5..9
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    pp3_barrier();
-    if (wr == 1) pp3_barrier();  // the second group runs one barrier (half a phase) behind the first
-
-    // fragment addresses: row*128 + ((chunk ^ (row & 7)) << 4), chunk = kk*4 + (lane >> 4); kk = 1 flips bit 6
-    const int swz = (((lane >> 4)) ^ (lane & 7)) << 4;
-    const int a_off = (wr * 64 + (lane & 15)) * 128 + swz, b_off = (wc * 64 + (lane & 15)) * 128 + swz;
-    int a_lo = 0, a_hi = 0, b_base = 0;
-    auto lda = [&](int i, int kk) { return *reinterpret_cast<const frag*>(lds + (((i < 4 ? a_lo : a_hi) + (i & 3) * 2048) ^ (kk << 6))); };
-    auto ldb = [&](int j, int kk) { return *reinterpret_cast<const frag*>(lds + ((b_base + j * 2048) ^ (kk << 6))); };
-
-    frag af[4][2], wlo[2][2], whi[2][2];
-    int c_job = 0, c_left = job_kc(0);
-    if (job_k0(0) > 0) take_over();          // (only when the whole range lies inside one tile)
-    for (int T = 0; T < T_total; ++T) {
-        a_lo = S::A_OFF + ((2 * T) % 3) * S::HALF + a_off;
-        a_hi = S::A_OFF + ((2 * T + 1) % 3) * S::HALF + a_off;
-        b_base = (T % 3) * S::BUF + b_off;
-        // ================= phase 0: W lo + A lo
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) wlo[j][kk] = ldb(j, kk);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) af[i][kk] = lda(i, kk);
-        phase_wait(issue_phase(std::integral_constant<int, 0>{}));
-        pp3_barrier();
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = mfma16(wlo[j][kk], af[i][kk], acc[i][j]);
-        __builtin_amdgcn_s_setprio(0);
-        pp3_barrier();
-        // ================= phase 1: W hi
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) whi[j][kk] = ldb(2 + j, kk);
-        phase_wait(issue_phase(std::integral_constant<int, 1>{}));
-        pp3_barrier();
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][2 + j] = mfma16(whi[j][kk], af[i][kk], acc[i][2 + j]);
-        __builtin_amdgcn_s_setprio(0);
-        pp3_barrier();
-        // ================= phase 2: A hi
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) af[i][kk] = lda(4 + i, kk);
-        phase_wait(issue_phase(std::integral_constant<int, 2>{}));
-        pp3_barrier();
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[4 + i][2 + j] = mfma16(whi[j][kk], af[i][kk], acc[4 + i][2 + j]);
-        __builtin_amdgcn_s_setprio(0);
-        pp3_barrier();
-        // ================= phase 3: no reads (W lo is still in registers)
-        phase_wait(issue_phase(std::integral_constant<int, 3>{}));
-        pp3_barrier();
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[4 + i][j] = mfma16(wlo[j][kk], af[i][kk], acc[4 + i][j]);
-        __builtin_amdgcn_s_setprio(0);
-        if (--c_left == 0) {  // job finished
-            __builtin_amdgcn_sched_barrier(0);
-            const int t = job_tile(c_job);
-            bool counted = true;
-            if (job_k0(c_job) + job_kc(c_job) < KT) hand_over();
-            else counted = epilogue(t / NT, t - (t / NT) * NT);
-            ep_age = counted ? 0 : 1 << 20;
-            ++c_job;
-            if (c_job < nj) {
-                c_left = job_kc(c_job);
-                if (job_k0(c_job) > 0) take_over();
-                else {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        pp3_barrier();
-    }
-    if (wr == 0) pp3_barrier();  // both groups execute the same number of barriers
-    };
-    if (wave < 4) body(std::true_type{});
-    else body(std::false_type{});
+        });
 }
 
 }  // namespace

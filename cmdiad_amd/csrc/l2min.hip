@@ -14,7 +14,7 @@
 // test-only build alone (make ab, -DCMDIAD_AB_VARIANTS; CMDIAD_L2_TILE=2); all three return the same keys.  (Rounds 1-4 also kept
 // a 4-wave 128 x 128-per-wave kernel, a two-buffer two-group kernel and a 32-MFMA-per-phase kernel there: measured in
 // profiles/r1_notes.md .. r4_notes.md, removed in round 5 when the running minimum changed its definition.)
-#include "gemm_core.h"
+#include "gemm_pp3.h"
 #include "launch.h"
 
 namespace {
@@ -245,27 +245,17 @@ __global__ __launch_bounds__(S::THREADS, S::WAVES_PER_SIMD) void l2_min_kernel(G
     }
 }
 
-__device__ __forceinline__ void pp_barrier() { asm volatile("s_barrier" ::: "memory"); }
-
 // ------------------------------------------------------------------------------------------------
-// The two-group pipeline with MORE BANK BYTES IN FLIGHT (the ablations above put the remaining time in the latency of the
-// streamed bank tiles against one K-tile of prefetch): three bank buffers (96 KiB) + three query HALF slots (48 KiB: a
-// query tile's lo rows are read in phase 0 and its hi rows in phase 2, so halves rotate through three slots) = 144 KiB.
-// The two operands are issued by DIFFERENT waves -- waves 0-3 (the earlier group) feed the bank stream, waves 4-7 the query
-// stream -- because s_waitcnt vmcnt retires in order per wave: in one queue the short-lead query pieces would force the
-// long-lead bank pieces out early.  Each stream is a plain sequence of half-units (8 pieces) [lo h0, lo h1, hi h0, hi h1] per
-// K-tile, one per phase:   bank half-unit (P + 10) and query half-unit (P + 5) are issued in phase P.
-//   bank:  lo(T') in phases 4T'-10, -9 (its buffer held tile T'-3, whose lo rows were last read in phase 4T'-12: an
-//          earlier-group issuer needs two phases of distance), hi(T') in 4T'-8, -7 (last read 4T'-11); read in 4T', 4T'+1:
-//          every half-unit has >= 7 phases, so vmcnt(14) (the 7 newest half-units) is the counted wait of the bank waves;
-//   query: lo(T') in 4T'-5, -4 (slot of hi(T'-2), last read 4T'-6: a later-group issuer needs one phase), hi(T') in
-//          4T'-3, -2 (slot of lo(T'-1), last read 4T'-4); the earlier group reads half a phase before the issuing group's
-//          wait, so a half-unit issued in phase P is readable from P + 3: vmcnt(6) for the query waves.
+// The two-group 256 x 256 pipeline with three bank buffers and three query half slots: the schedule of run_two_group
+// (gemm_pp3.h, where the phase / staging / counted-wait design is derived: which half-unit is issued in which phase, and why
+// the waits are vmcnt(14) for the bank = W stream and vmcnt(6) for the query = A stream), here as a hand-kept copy of that
+// loop for one query tile against a range of library tiles.  What this copy adds: the stream walks with a running pointer;
+// wave 0 fetches the next library tile's norms in phase 0 and parks them in phase 3 (+ a prologue pair); accumulators start
+// from qh + bh; a tile ends in rowmin_update; no stores at a tile end, so no raised waits; the DIAG stamps.  With those
+// hooks the shared loop spills (profiles/two_group_loop.md) -- a change to the schedule is made in both places.
 // ------------------------------------------------------------------------------------------------
-struct SPingPong3 {
-    static constexpr int BM = 256, BN = 256, THREADS = 512;
-    static constexpr int BUF = 32768, HALF = 16384;
-    static constexpr int A_OFF = 3 * BUF, BN_OFF = A_OFF + 3 * HALF;
+struct SPingPong3 : SPP3 {   // + the [2][256] float bank-norm area
+    static constexpr int BN_OFF = SPP3::LDS_BYTES;
     static constexpr int LDS_BYTES = BN_OFF + 2 * 256 * 4;
 };
 
@@ -409,7 +399,7 @@ __global__ __launch_bounds__(512, 1) void l2_min_pp3_kernel(GlobalTile A, Global
         constexpr int j = decltype(J)::value;
         return bank_wave ? issue_part(std::integral_constant<int, (j + 2) % 4>{}) : issue_part(std::integral_constant<int, (j + 1) % 4>{});
     };
-    // counted wait of a phase: the bank stream keeps 7 half-units in flight, the query stream 3 (see the header comment)
+    // counted wait of a phase: the bank stream keeps 7 half-units in flight, the query stream 3 (derived in gemm_pp3.h)
     auto phase_wait = [&](bool issued) {
         if (!issued) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else if (bank_wave) asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
@@ -429,9 +419,9 @@ __global__ __launch_bounds__(512, 1) void l2_min_pp3_kernel(GlobalTile A, Global
         bh_park(bnv0, nt0, std::integral_constant<int, 0>{});
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    pp_barrier();
+    pp3_barrier();
     acc_start(nt0);
-    if (wr == 1) pp_barrier();  // the second group runs one barrier (half a phase) behind the first
+    if (wr == 1) pp3_barrier();  // the second group runs one barrier (half a phase) behind the first
 
     // ---- fragment addresses: row*128 + ((chunk ^ (row & 7)) << 4), chunk = kk*4 + (lane >> 4); kk = 1 flips bit 6.
     // Query rows of a half slot: wr*64 + i*16 + (lane & 15); bank rows of a buffer: wc*64 + j*16 + (lane & 15).
@@ -463,7 +453,7 @@ __global__ __launch_bounds__(512, 1) void l2_min_pp3_kernel(GlobalTile A, Global
         if (bn_fetch) bh_fetch(bnv, nt_c + 1);
         { const bool is = issue_phase(std::integral_constant<int, 0>{}); stamp(); phase_wait(is); }
         stamp();
-        pp_barrier();
+        pp3_barrier();
         stamp();
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -474,7 +464,7 @@ __global__ __launch_bounds__(512, 1) void l2_min_pp3_kernel(GlobalTile A, Global
                 for (int j = 0; j < 2; ++j) acc[i][j] = mfma16(wlo[j][kk], af[i][kk], acc[i][j]);
         __builtin_amdgcn_s_setprio(0);
         stamp();
-        pp_barrier();
+        pp3_barrier();
         // ================= phase 1: B hi
         stamp();
 #pragma unroll
@@ -483,7 +473,7 @@ __global__ __launch_bounds__(512, 1) void l2_min_pp3_kernel(GlobalTile A, Global
             for (int kk = 0; kk < 2; ++kk) whi[j][kk] = ldb(2 + j, kk);
         { const bool is = issue_phase(std::integral_constant<int, 1>{}); stamp(); phase_wait(is); }
         stamp();
-        pp_barrier();
+        pp3_barrier();
         stamp();
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -494,7 +484,7 @@ __global__ __launch_bounds__(512, 1) void l2_min_pp3_kernel(GlobalTile A, Global
                 for (int j = 0; j < 2; ++j) acc[i][2 + j] = mfma16(whi[j][kk], af[i][kk], acc[i][2 + j]);
         __builtin_amdgcn_s_setprio(0);
         stamp();
-        pp_barrier();
+        pp3_barrier();
         // ================= phase 2: A hi
         stamp();
 #pragma unroll
@@ -503,7 +493,7 @@ __global__ __launch_bounds__(512, 1) void l2_min_pp3_kernel(GlobalTile A, Global
             for (int kk = 0; kk < 2; ++kk) af[i][kk] = lda(4 + i, kk);
         { const bool is = issue_phase(std::integral_constant<int, 2>{}); stamp(); phase_wait(is); }
         stamp();
-        pp_barrier();
+        pp3_barrier();
         stamp();
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -514,13 +504,13 @@ __global__ __launch_bounds__(512, 1) void l2_min_pp3_kernel(GlobalTile A, Global
                 for (int j = 0; j < 2; ++j) acc[4 + i][2 + j] = mfma16(whi[j][kk], af[i][kk], acc[4 + i][2 + j]);
         __builtin_amdgcn_s_setprio(0);
         stamp();
-        pp_barrier();
+        pp3_barrier();
         // ================= phase 3: no reads (B lo is still in registers)
         stamp();
         if (bn_fetch) bh_park(bnv, nt_c + 1, std::integral_constant<int, 6>{});  // 6 DMA pieces were issued after the fetch (phases 0-2)
         { const bool is = issue_phase(std::integral_constant<int, 3>{}); stamp(); phase_wait(is); }
         stamp();
-        pp_barrier();
+        pp3_barrier();
         stamp();
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -536,10 +526,10 @@ __global__ __launch_bounds__(512, 1) void l2_min_pp3_kernel(GlobalTile A, Global
             for (int i = 0; i < 8; ++i) rowmin_update(best[i], acc[i], (unsigned)(nt_c - nt0));
             if (T + 1 < T_total) acc_start(nt_c + 1);
         }
-        pp_barrier();
+        pp3_barrier();
         if (++kt_c == KT) { kt_c = 0; ++nt_c; }
     }
-    if (wr == 0) pp_barrier();  // both groups execute the same number of barriers
+    if (wr == 0) pp3_barrier();  // both groups execute the same number of barriers
 
 #pragma unroll
     for (int i = 0; i < 8; ++i) {

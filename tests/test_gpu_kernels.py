@@ -374,9 +374,11 @@ def test_gemm_persistent_256_tile_matches_128_tile(monkeypatch):
     """cmdiad_gemm_bf16 on the two-group persistent 256 x 256 kernel (gemm_std_pp3_kernel: one block per CU walks a job list;
     production choice for the fc1 products at batch 32) gives bit for bit what the 128 x 128 kernel gives -- same K order,
     same epilogue arithmetic -- on shapes with ragged M, more and fewer jobs than blocks, every epilogue it supports (the
-    calls it does not take -- fp32 / residual outputs -- fall through to the 128 x 128 kernel in both modes)."""
+    calls it does not take -- fp32 / residual outputs -- fall through to the 128 x 128 kernel in both modes).  The last shape
+    is 603 jobs on 201 blocks at the minimum K of three K-tiles, ragged last M tile: three jobs per block, so a whole job
+    lies between two job boundaries of both the stream's and the consumer's copy of the job cursor."""
     g = torch.Generator().manual_seed(77)
-    for M, N, K in ((1000, 512, 192), (70000, 256, 192), (3 * 785, 1536, 768), (40000, 512, 256)):
+    for M, N, K in ((1000, 512, 192), (70000, 256, 192), (3 * 785, 1536, 768), (40000, 512, 256), (51217, 768, 192)):
         A = _bf(torch.randn(M, K, generator=g))
         W = _bf(torch.randn(N, K, generator=g) / K ** 0.5)
         bias, res = torch.randn(N, generator=g), torch.randn(M, N, generator=g)

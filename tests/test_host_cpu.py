@@ -282,6 +282,24 @@ def test_isa_lint_main_loops():
     assert out.stdout.count("main loops clean") == 5      # gemm, gemm_sk, l2min, conv, encoder_tail
 
 
+def test_streamk_job_list_covers_every_unit_once_in_hand_over_order(tmp_path):
+    """tests/sk_jobs_check.cpp on csrc/gemm_sk_jobs.h, the job arithmetic gemm_sk_kernel runs on, compiled for the host with
+    address + undefined sanitizers: for every block of a 256-block launch at the four eligible shapes of
+    test_gemm_streamk_matches_128_tile_bit_for_bit, and of a one-block-per-tile launch, every (tile, k-tile) unit is executed
+    exactly once, a block's jobs come head piece / whole tiles / tail piece, no block takes over and hands over one tile, and
+    a tile has at most two blocks (the later one the earlier one's successor)."""
+    import shutil
+    cxx = next((c for c in (os.environ.get("CXX"), "c++", "g++", "clang++") if c and shutil.which(c)), None)
+    assert cxx, "no host C++ compiler on PATH"
+    exe = str(tmp_path / "sk_jobs_check")
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           os.path.join(REPO, "tests", "sk_jobs_check.cpp"), "-o", exe]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout + out.stderr
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "sk jobs ok" in out.stdout, out.stdout + out.stderr
+
+
 def test_compat_shims_register_the_cuda_wheel_module_paths():
     code = ("import sys; sys.path.insert(0, %r); import cmdiad_amd.compat as c; c.install();"
             "from pointnet2_ops import pointnet2_utils; from knn_cuda import KNN;"

@@ -1,6 +1,6 @@
 #!/bin/bash
 # ONE parametrised runner for a `gpurun` call (replaces the per-call scripts tools/runs/rN_runM.sh of rounds 5-6):
-#   gpurun --timeout 1800 -- 'bash tools/gpu_session.sh r6_7 "pytest:l2_ or normalize" "py:tools/l2_runner_ab.py 3" bench "ab:CMDIAD_SEARCH_DTYPE:bf16 fp16:2"'
+#   bash tools/gpu_session.sh r6_7 "pytest:l2_ or normalize" "py:tools/two_group_ab.py" bench "ab:CMDIAD_SEARCH_DTYPE:bf16 fp16:2"
 # First argument: the output directory under gpurun_out/ (merged back into the dev container); every further argument is a step,
 # run in order, each with its own log file and a line (+ the log's tail) in <out>/rc.log:
 #   suite[:extra pytest args]        python -m pytest tests -m gpu -q --durations=25
