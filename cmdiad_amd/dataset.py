@@ -40,6 +40,7 @@ import torch
 from torch.utils.data import Dataset
 
 from .utils.batching import in_batches, read_ahead, scatter_by_shape
+from .utils.tiff import RawCloud
 
 
 def _shared_stream(device, role):
@@ -499,11 +500,17 @@ class _Count:
         return self._value
 
 
+def _is_raw(cloud):
+    """A utils.tiff.RawCloud (the bytes of an xyz tiff, CMDIAD_TIFF_DEVICE=1) in the place of a decoded cloud array."""
+    return isinstance(cloud, RawCloud)
+
+
 class SamplePrep:
     """Decoded arrays -> the tensors of the reference's ``__getitem__`` on the device (csrc/sample_prep.hip; docs/sample_prep.md).
 
     ``prepare(rgb_u8 [H,W,3], pc [H,W,3] float32 or float64, gt_u8 [H,W] | None)`` -> ``(DeviceSample(img [3,S,S], cloud [3,xs,xs], depth [3,224,224]),
-    gt [1,g,g] | None)``; ``prepare_batch`` takes lists and returns a list of such pairs.  Samples of equal shapes share their launches;
+    gt [1,g,g] | None)``; ``prepare_batch`` takes lists and returns a list of such pairs.  A cloud may also be a utils.tiff.RawCloud -- the
+    undecoded bytes of its tiff (CMDIAD_TIFF_DEVICE=1) -- which is unpacked on the device and gives the same tensors.  Samples of equal shapes share their launches;
     every sample's bytes are the ones a call of its own gives (the arithmetic is per pixel and integer).  Clouds are grouped by dtype
     as well: a float64 cloud (an Eyecandies tiff of the reference's script) is converted to float32 at the gather, as ``.float()``.  Inputs go up through
     pinned memory on the shared copy stream; the kernels run on the current stream.  Tables are computed once per (n_in, n_out)
@@ -551,6 +558,27 @@ class SamplePrep:
         dev.record_stream(cur)
         return dev
 
+    def _upload_clouds(self, clouds, dtype):
+        """list of equal-shaped clouds, decoded arrays or utils.tiff.RawCloud -> one device tensor [n,H,W,3] of dtype: the arrays through
+        `_upload`, the raw files through tiff.unpack_on_device (their bytes go up as they are and are unpacked by cmdiad_tiff_unpack)."""
+        raw = [k for k, c in enumerate(clouds) if _is_raw(c)]
+        if not raw:
+            return self._upload(clouds, dtype, "the point cloud")
+        from .utils import tiff
+        for k in raw:
+            if getattr(torch, clouds[k].dtype.name) != dtype:
+                raise TypeError(f"SamplePrep: the point cloud must be {dtype} in this group, got {clouds[k].dtype} ({clouds[k].path})")
+        dev = tiff.unpack_on_device([clouds[k] for k in raw], self.device)
+        if len(raw) == len(clouds):
+            return dev
+        is_raw = set(raw)
+        host = [k for k in range(len(clouds)) if k not in is_raw]
+        up = self._upload([clouds[k] for k in host], dtype, "the point cloud")
+        out = torch.empty((len(clouds), *dev.shape[1:]), dtype=dtype, device=self.device)
+        for rows, part in ((raw, dev), (host, up)):      # (a pinned index: the copy of a pageable one would synchronise)
+            out.index_copy_(0, torch.tensor(rows, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True), part)
+        return out
+
     def prepare(self, rgb_u8, pc_f32, gt_u8=None):
         return self.prepare_batch([rgb_u8], [pc_f32], [gt_u8])[0]
 
@@ -562,15 +590,16 @@ class SamplePrep:
         if not (len(pcs) == len(gts) == n):
             raise ValueError("SamplePrep.prepare_batch: the lists differ in length")
         for r, p, g in zip(rgbs, pcs, gts):
-            if np.ndim(r) != 3 or np.shape(r)[2] != 3 or np.ndim(p) != 3 or np.shape(p)[2] != 3 or (g is not None and np.ndim(g) != 2):
-                raise ValueError(f"SamplePrep: rgb [H,W,3], cloud [H,W,3], gt [H,W] expected, got {np.shape(r)}, {np.shape(p)}, "
+            ps = p.shape if _is_raw(p) else np.shape(p)
+            if np.ndim(r) != 3 or np.shape(r)[2] != 3 or len(ps) != 3 or ps[2] != 3 or (g is not None and np.ndim(g) != 2):
+                raise ValueError(f"SamplePrep: rgb [H,W,3], cloud [H,W,3], gt [H,W] expected, got {np.shape(r)}, {tuple(ps)}, "
                                  f"{None if g is None else np.shape(g)}")
 
         def clouds_of(key, idx):
             dtype = key[1]
             if dtype not in ("float32", "float64"):
                 raise TypeError(f"SamplePrep: the point cloud must be float32 (MVTec 3D-AD) or float64 (Eyecandies) arrays, got {dtype}")
-            return self.prepare_device_clouds(self._upload([pcs[i] for i in idx], getattr(torch, dtype), "the point cloud"))
+            return self.prepare_device_clouds(self._upload_clouds([pcs[i] for i in idx], getattr(torch, dtype)))
 
         with torch.cuda.device(self.device):
             imgs = self.prepare_images(rgbs)
@@ -651,9 +680,15 @@ def _read_rgb(path):
     return Image.open(path).convert('RGB')
 
 
-def _read_cloud(path):
+def _read_cloud(path, raw_ok=False):
+    """The cloud of an xyz tiff: the decoded array, or -- raw_ok (a 'hip' reader thread) under CMDIAD_TIFF_DEVICE=1 -- the file's bytes
+    as a utils.tiff.RawCloud, unpacked on the device with its batch (docs/tiff.md)."""
+    if raw_ok:
+        from .utils import tiff
+        if tiff.device_decode_enabled():
+            return tiff.read_raw(path)
     from .utils import mvtec3d_util as mu
-    return mu.read_tiff_organized_pc(path)     # (looked up at call time: needs `tifffile`, and says so)
+    return mu.read_tiff_organized_pc(path)     # (looked up at call time: `tifffile` when it is installed, else utils/tiff.py)
 
 
 class BaseAnomalyDetectionDataset(_LazySamplePrep, Dataset):
@@ -684,7 +719,8 @@ class BaseAnomalyDetectionDataset(_LazySamplePrep, Dataset):
         if gt != 0:
             from PIL import Image
             gt = np.array(Image.open(gt).convert('L'), dtype=np.uint8)
-        return np.array(_read_rgb(rgb_path), dtype=np.uint8), _read_cloud(tiff_path), (None if isinstance(gt, int) else gt)
+        cloud = _read_cloud(tiff_path, raw_ok=self.img_process_method == 'hip')
+        return np.array(_read_rgb(rgb_path), dtype=np.uint8), cloud, (None if isinstance(gt, int) else gt)
 
     def _sample(self, idx):
         rgb_path, tiff_path = self.img_paths[idx]
@@ -990,12 +1026,13 @@ class MVTec3DRawClass(_RawClassSource):
         import numpy as np
         from PIL import Image
         rgb_path, tiff_path = paths
-        pc = np.asarray(_read_cloud(tiff_path))
+        pc = _read_cloud(tiff_path, raw_ok=True)
+        pc = pc if _is_raw(pc) else np.asarray(pc)     # (a RawCloud carries the layout's dtype and shape: the checks below read those)
         rgb = np.array(Image.open(rgb_path))
         gt = np.array(Image.open(gt_path)) if gt_path is not None else None
         if pc.dtype != np.float32 or pc.ndim != 3 or pc.shape[2] != 3:
             raise TypeError(f"MVTec3DRawClass: {tiff_path}: the point cloud must be a float32 [H,W,3] array, got {pc.dtype} {pc.shape}")
-        if rgb.dtype != np.uint8 or rgb.shape != pc.shape:
+        if rgb.dtype != np.uint8 or rgb.shape != tuple(pc.shape):
             raise TypeError(f"MVTec3DRawClass: {rgb_path}: rgb must be a uint8 {pc.shape} array, got {rgb.dtype} {rgb.shape}")
         if gt is not None and (gt.dtype != np.uint8 or gt.shape != pc.shape[:2]):
             raise TypeError(f"MVTec3DRawClass: {gt_path}: gt must be a uint8 {pc.shape[:2]} array, got {gt.dtype} {gt.shape}")
@@ -1007,7 +1044,7 @@ class MVTec3DRawClass(_RawClassSource):
         prep = self.sample_prep()
 
         def scans_of(_, idx):
-            pcs = prep._upload([dec[i][0] for i in idx], torch.float32, "the point cloud")
+            pcs = prep._upload_clouds([dec[i][0] for i in idx], torch.float32)
             rgbs = prep._upload([dec[i][1] for i in idx], torch.uint8, "rgb")
             with_gt = [i for i in idx if dec[i][2] is not None]
             gts = prep._upload([dec[i][2] for i in with_gt], torch.uint8, "gt") if with_gt else None

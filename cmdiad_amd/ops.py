@@ -1190,8 +1190,61 @@ def gt_mask_prep(gt, tab):
     return out
 
 
+# ------------------------------------------------------------------------------------ xyz TIFFs (docs/tiff.md)
+TIFF_MAX_ROW_BYTES = 64 * 1024     # the longest predictor-3 chunk row cmdiad_tiff_unpack undoes (utils.tiff undoes longer ones on the host)
+
+
+def tiff_unpack(raw_u8, layouts, chunk_table, table_dev=None, out=None):
+    """raw_u8 [n] uint8 on the device (file bytes with uncompressed chunks; n a multiple of 4), layouts = the utils.tiff.TiffLayout of
+    every image (equal but for their offsets), chunk_table [B, n_chunks] int64 ON THE HOST = every chunk's byte offset into raw_u8
+    -> [B,H,W,C] float32 or float64, the files' samples bit for bit.  The table is checked here, before the launch, against the
+    geometry and raw_u8's length: a chunk that starts before 0 or ends past the buffer is a ValueError and nothing is launched.
+    table_dev: the same table already on the device (else it is uploaded here); out: the result tensor to fill."""
+    import numpy as np
+    _chk(raw_u8, torch.uint8, "tiff_unpack.raw_u8")
+    layouts = list(layouts)
+    if not layouts:
+        raise ValueError("tiff_unpack: no layouts")
+    lay = layouts[0]
+    B, n = len(layouts), lay.n_chunks
+    if any(l.geometry() != lay.geometry() for l in layouts):
+        raise ValueError("tiff_unpack: the layouts of one call must be equal but for their offsets")
+    if lay.compression != 1:
+        raise ValueError(f"tiff_unpack: chunks must be uncompressed (utils.tiff.read_raw inflates them), got compression {lay.compression}")
+    if lay.predictor == 3 and lay.row_bytes > TIFF_MAX_ROW_BYTES:
+        raise ValueError(f"tiff_unpack: a predictor-3 chunk row of {lay.row_bytes} bytes exceeds {TIFF_MAX_ROW_BYTES}: undo it on the host")
+    table = np.ascontiguousarray(chunk_table.numpy() if isinstance(chunk_table, torch.Tensor) else chunk_table, dtype=np.int64)
+    if table.shape != (B, n):
+        raise ValueError(f"tiff_unpack: chunk_table must be [{B},{n}] for this geometry, got {table.shape}")
+    raw_bytes = raw_u8.numel()
+    if raw_u8.dim() != 1 or raw_bytes == 0 or raw_bytes % 4 or raw_u8.data_ptr() % 4:
+        raise ValueError(f"tiff_unpack: raw_u8 must be a dword-aligned 1-D buffer padded to a multiple of 4 bytes, got {tuple(raw_u8.shape)}")
+    need = lay.all_chunk_bytes()
+    bad = np.argwhere((table < 0) | (table + need[None, :] > raw_bytes))
+    if len(bad):
+        b, k = (int(v) for v in bad[0])
+        raise ValueError(f"tiff_unpack: chunk {k} of image {b} at offset {int(table[b, k])} with {int(need[k])} bytes does not lie inside "
+                         f"the {raw_bytes} bytes of raw_u8")
+    dtype = torch.float32 if lay.bytes_per_sample == 4 else torch.float64
+    shape = (B, lay.height, lay.width, lay.channels)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=raw_u8.device)
+    else:
+        _chk(out, dtype, "tiff_unpack.out")
+        if tuple(out.shape) != shape:
+            raise ValueError(f"tiff_unpack: out must be {shape}, got {tuple(out.shape)}")
+    if table_dev is None:
+        table_dev = torch.from_numpy(table).to(raw_u8.device)
+    _chk(table_dev, torch.int64, "tiff_unpack.table_dev")
+    if tuple(table_dev.shape) != (B, n):
+        raise ValueError(f"tiff_unpack: table_dev must be [{B},{n}], got {tuple(table_dev.shape)}")
+    _call("cmdiad_tiff_unpack", _p(raw_u8), raw_bytes, _p(table_dev), B, n, lay.width, lay.height, lay.channels, lay.chunk_w, lay.chunk_h,
+          int(lay.planar), lay.bytes_per_sample, int(lay.big_endian), lay.predictor, _p(out), _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------ Eyecandies (docs/eyecandies.md)
-EYECANDIES_PARAM_BYTES = 136      # cmdiad_eyecandies_params: float32 range, float32 mind, float64 inv(P)[16]
+EYECANDIES_PARAM_BYTES = 136     # cmdiad_eyecandies_params: float32 range, float32 mind, float64 inv(P)[16]
 
 
 def eyecandies_params(mind, maxd, inv_p):

@@ -3,7 +3,7 @@ calls all four at dataset.py:106-110,153-157,228-231): with the drop-in installe
 exist.  Host-side, one sample at a time, before the hot path starts; no GPU work.
 
   organized_pc_to_unorganized_pc   mvtec3d_util.py:5-6    [H,W,3] -> [H*W,3]
-  read_tiff_organized_pc           mvtec3d_util.py:9-11   the MVTec 3D-AD xyz tiff as the array tifffile returns
+  read_tiff_organized_pc           mvtec3d_util.py:9-11   the MVTec 3D-AD xyz tiff as the array tifffile returns (without tifffile: utils/tiff.py)
   resize_organized_pc              mvtec3d_util.py:14-22  nearest-neighbour resize, [3,h,w] tensor or [h,w,3] array
   organized_pc_to_depth_map        mvtec3d_util.py:25-26  the z channel
 """
@@ -18,8 +18,9 @@ def organized_pc_to_unorganized_pc(organized_pc):
 def read_tiff_organized_pc(path):
     try:
         import tifffile
-    except ImportError as exc:   # (the reference imports it at module import; here only the reader needs it)
-        raise ImportError("read_tiff_organized_pc needs the `tifffile` package (MVTec 3D-AD xyz tiffs are 3-channel float32)") from exc
+    except ImportError:          # (the reference imports it at module import; here it is optional: utils/tiff.py reads the dataset's files)
+        from . import tiff
+        return tiff.imread(path)
     return tifffile.imread(path)
 
 

@@ -219,8 +219,8 @@ def _read(tiff_path):
 def _write(tiff_path, pc, rgb, gt):
     try:
         import tifffile as tiff
-    except ImportError as exc:
-        raise ImportError("preprocess_pc needs the `tifffile` package to write the cleaned xyz tiff") from exc
+    except ImportError:          # (optional: utils/tiff.py writes the same array as an uncompressed float TIFF)
+        from . import tiff
     from PIL import Image
     rgb_path, gt_path = _paths(tiff_path)
     tiff.imwrite(tiff_path, pc)

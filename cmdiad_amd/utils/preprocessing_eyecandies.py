@@ -12,7 +12,7 @@ operation order: docs/eyecandies.md.
                                    the reference's __main__ loop (:92-187): the same tree, reader and writer threads around one
                                    device stream
 
-The 16-bit PNG is read with Pillow, the yaml with PyYAML; `tifffile` is needed by the writer only.  dataset.EyecandiesRawClass feeds
+The 16-bit PNG is read with Pillow, the yaml with PyYAML; the writer uses `tifffile` when it is installed, else utils/tiff.py.  dataset.EyecandiesRawClass feeds
 the extractors from the RAW download without this tree.  The device stages need a GPU: there is no CPU path.
 """
 import argparse
@@ -185,11 +185,11 @@ def read_mask(path):
 
 
 def _tifffile():
+    """The module whose imwrite writes the xyz tiffs: `tifffile` when it is installed, else utils/tiff.py."""
     try:
         import tifffile
-    except ImportError as exc:
-        raise ImportError("preprocessing_eyecandies needs the `tifffile` package to write the xyz tiffs "
-                          "(dataset.EyecandiesRawClass reads the raw download without them)") from exc
+    except ImportError:
+        from . import tiff as tifffile
     return tifffile
 
 

@@ -798,6 +798,19 @@ int cmdiad_auc_counts(const uint64_t* ok_sorted_keys, int n_ok, const double* de
 int cmdiad_pro_hist(const double* thr, int T, const double* def_score, const int32_t* def_comp, int n_def, int total_comp,
                     uint32_t* hist, cmdiad_stream_t stream);
 
+/* ---- xyz TIFFs (docs/tiff.md; utils/mvtec3d_util.py:9-11 of the reference reads them with tifffile on the host) ----
+ * raw [raw_bytes] = file bytes with UNCOMPRESSED chunks (dword aligned, raw_bytes a multiple of 4: the upload buffer is padded),
+ * chunk_off [B, n_chunks] (device) = byte offset into raw of every chunk of every image -> out [B,H,W,C] of the files' own float type
+ * (bytes_per_sample 4 | 8), in the device's byte order.  A strip is a tile of full width (chunk_w == W, chunk_h = rows per strip);
+ * chunks are numbered row-major over the image, plane after plane when planar (n_chunks must equal what the geometry gives).
+ * predictor 1: a copy with a byte swap when big_endian; predictor 3: libtiff's floating-point predictor is undone per chunk row
+ * (chunk_w * (planar ? 1 : C) * bytes_per_sample bytes, at most 64 KiB), big_endian is then not looked at.  Offsets need no
+ * alignment.  Any source byte outside [0, raw_bytes) reads as 0: no table makes the kernels read outside raw.  Tile padding and the
+ * missing rows of a short last strip are neither read as samples nor written.  B in 1..65535, sides in 1..16384, C in 1..4. */
+int cmdiad_tiff_unpack(const uint8_t* raw, int64_t raw_bytes, const int64_t* chunk_off, int B, int n_chunks, int W, int H, int C,
+                       int chunk_w, int chunk_h, int planar, int bytes_per_sample, int big_endian, int predictor, void* out,
+                       cmdiad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,14 +3,18 @@
 'cpu_v1' composition (PIL + torch, one sample at a time, as the reference's dataset.py) on the SAME decoded arrays, and end to end
 from files this tool writes itself.
 
-  python tools/bench_sample_prep.py [--batch 32] [--size 800] [--iters 20] [--files 64] [--out profiles/sample_prep.json]
+  python tools/bench_sample_prep.py [--batch 32] [--size 800] [--iters 20] [--files 64] [--drains 1] [--tiff-device]
+                                    [--out profiles/sample_prep.json]
 
   arrays      batch x (size x size x 3 uint8 + size x size x 3 float32), already decoded and in host memory.
               device: HIP events around prepare_batch (pinned staging, host-to-device copy, the four kernels, the count's copy back);
               kernels only: HIP events around the kernels on arrays that are already on the device;
               host: wall clock around the PIL + torch composition on this process's torch threads.
   end to end  PNG + cloud files -> prepared samples, through get_data_loader with 1, 4 and 16 reader threads ('hip') and through the
-              host datasets in line ('cpu_v1').  Bounded by the host's PNG / tiff decode, not by the kernels.
+              host datasets in line ('cpu_v1').  Bounded by the host's PNG / tiff decode, not by the kernels.  The clouds are real
+              TIFFs: written by `tifffile` when it is installed, else by cmdiad_amd.utils.tiff.  --tiff-device sets
+              CMDIAD_TIFF_DEVICE=1 for the 'hip' loaders (the reader threads hand the files' bytes on, cmdiad_tiff_unpack
+              unpacks them; docs/tiff.md); --drains N times N drains per reader count and reports every one.
 There is no pass / fail threshold: the figures go into profiles/sample_prep.md.  Needs a GPU (no fallback)."""
 import argparse
 import json
@@ -54,6 +58,8 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--host-samples", type=int, default=32)
     ap.add_argument("--files", type=int, default=64, help="samples of the end-to-end tree")
+    ap.add_argument("--drains", type=int, default=1, help="timed drains of the end-to-end loader per reader count")
+    ap.add_argument("--tiff-device", action="store_true", help="CMDIAD_TIFF_DEVICE=1 for the end-to-end 'hip' loaders")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -118,28 +124,29 @@ def main():
         try:
             import tifffile
         except ImportError:
-            tifffile = None
-            from cmdiad_amd.utils import mvtec3d_util
-            mvtec3d_util.read_tiff_organized_pc = spr.read_npy_cloud
-        rec["cloud_files"] = "tiff" if tifffile is not None else "npy (tifffile is not installed: the cloud decode is a raw read)"
+            from cmdiad_amd.utils import tiff as tifffile
+        rec["cloud_files"] = "tiff, written by " + tifffile.__name__
+        rec["tiff_device"] = bool(args.tiff_device)
+        if args.tiff_device:
+            os.environ["CMDIAD_TIFF_DEVICE"] = "1"
         for i in range(args.files):
             pc, rgb = spr.scan(i, S)
             Image.fromarray(rgb).save(os.path.join(base, "rgb", f"{i:03d}.png"))
-            path = os.path.join(base, "xyz", f"{i:03d}.tiff")
-            if tifffile is not None:
-                tifffile.imwrite(path, pc)
-            else:
-                with open(path, "wb") as fh:
-                    np.save(fh, pc)
-        e2e = {}
+            tifffile.imwrite(os.path.join(base, "xyz", f"{i:03d}.tiff"), pc)
+        e2e, drains = {}, {}
         for readers in (1, 4, 16):
             a = types.SimpleNamespace(dataset_path=root, img_process_method="hip", num_workers=readers)
-            for timed in (False, True):          # first pass: page cache, tables
+            rates = []
+            for timed in range(1 + max(1, args.drains)):          # first pass: page cache, tables
                 t = time.perf_counter()
                 k = sum(1 for _ in ds.get_data_loader("train", "bagel", 224, 224, 224, a))
                 torch.cuda.synchronize()
-                dt = time.perf_counter() - t
-            e2e[f"hip_readers_{readers}"] = k / dt
+                if timed:
+                    rates.append(k / (time.perf_counter() - t))
+            e2e[f"hip_readers_{readers}"] = sorted(rates)[len(rates) // 2]
+            drains[f"hip_readers_{readers}"] = [round(r, 1) for r in rates]
+        os.environ.pop("CMDIAD_TIFF_DEVICE", None)
+        rec["end_to_end_drains_samples_per_s"] = drains
         host_ds = ds.TrainDataset("bagel", 224, 224, 224, root, "cpu_v1")
         t = time.perf_counter()
         for i in range(min(16, len(host_ds))):

@@ -3,7 +3,7 @@
 scans, the CPU restatement (tests/preprocess_ref.py for the plane, scikit-learn's DBSCAN for the clusters).
 
   python tools/preprocess_bench.py [--scans 3] [--cpu-scans 1] [--out profiles/preprocess.json]
-  python tools/preprocess_bench.py --reps 7 [--compare OLD_PREPROCESSING.py] [--loader] --cpu-scans 0
+  python tools/preprocess_bench.py --reps 7 [--compare OLD_PREPROCESSING.py] [--loader [--readers N] [--tiff-device]] --cpu-scans 0
 
 --reps N (>= 5 for a figure worth writing down): per-scan wall time of preprocess_on_device (device tensors in, synchronise at the
 end) and of preprocess_arrays (numpy in, numpy out), N repetitions over the same scans, reported as min / median / max.  With
@@ -11,7 +11,8 @@ end) and of preprocess_arrays (numpy in, numpy out), N repetitions over the same
 REV:cmdiad_amd/utils/preprocessing.py > FILE`) runs in the same process on the same scans, alternating with this one, and the two
 outputs are compared.  --loader writes a synthetic class (20 train, 10 test scans of 800 x 800) and times draining train() and
 test() of dataset.MVTec3DRawClass over it against MVTec3DClass('hip') over a copy cleaned by preprocess_dataset: the `load` seconds
-of evaluate.ClassRun, i.e. what cleaning in the loader costs.
+of evaluate.ClassRun, i.e. what cleaning in the loader costs.  The scans are real TIFFs (written by `tifffile` when it is installed,
+else by cmdiad_amd.utils.tiff); --tiff-device sets CMDIAD_TIFF_DEVICE=1 for both classes (docs/tiff.md), --readers their reader threads.
 
 Device numbers: milliseconds per scan end to end (numpy in, numpy out) and per stage from the kernel times of torch.profiler --
 plane (hypotheses + refit + mask), grid build (bounding box, keys, scans, scatter), core test, union, labels (flatten, mark,
@@ -84,11 +85,10 @@ def timed_repetitions(mod, scans, reps, other=None):
     return out
 
 
-def loader_seconds(mod, n_train=20, n_test=10, size=800, reps=3):
+def loader_seconds(mod, n_train=20, n_test=10, size=800, reps=3, readers=None, tiff_device=False):
     """Seconds to drain train() + test() (evaluate.ClassRun's `load`): the raw class against MVTec3DClass('hip') over the cleaned copy."""
     import shutil
     import tempfile
-    import types
     import torch
     from PIL import Image
     import preprocess_ref as pr
@@ -96,11 +96,8 @@ def loader_seconds(mod, n_train=20, n_test=10, size=800, reps=3):
     from cmdiad_amd import evaluate as ev
     try:
         import tifffile
-    except ImportError:      # stand-in: np.save content under the .tiff name (float32 either way)
-        tifffile = types.ModuleType("tifffile")
-        tifffile.imread = lambda p: np.load(open(p, "rb"))
-        tifffile.imwrite = lambda p, a: np.save(open(p, "wb"), a)
-        sys.modules["tifffile"] = tifffile
+    except ImportError:      # the project's own codec writes the same float32 TIFFs (and reads them back: utils/mvtec3d_util.py)
+        from cmdiad_amd.utils import tiff as tifffile
     root = tempfile.mkdtemp(prefix="raw_mvtec_")
     try:
         raw, clean = os.path.join(root, "raw"), os.path.join(root, "clean")
@@ -120,10 +117,13 @@ def loader_seconds(mod, n_train=20, n_test=10, size=800, reps=3):
         t0 = time.perf_counter()
         mod.preprocess_dataset(clean)
         rec = {"train": n_train, "test": n_test, "shape": [size, size], "preprocess_dataset_seconds": round(time.perf_counter() - t0, 3),
-               "raw": [], "clean": []}
+               "cloud_files": "tiff, written by " + tifffile.__name__, "tiff_device": bool(tiff_device), "readers": readers, "raw": [], "clean": []}
+        if tiff_device:
+            os.environ["CMDIAD_TIFF_DEVICE"] = "1"
+        more = {} if readers is None else {"num_workers": readers}
         for rep in range(reps + 1):
             for tag, path, kind in (("raw", raw, ds.MVTec3DRawClass), ("clean", clean, ds.MVTec3DClass)):
-                cls = kind(path, "bagel", ev.mtfi_args(dataset_path=path, img_process_method="hip"))
+                cls = kind(path, "bagel", ev.mtfi_args(dataset_path=path, img_process_method="hip", **more))
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 items = list(cls.train()) + list(cls.test())
@@ -134,6 +134,7 @@ def loader_seconds(mod, n_train=20, n_test=10, size=800, reps=3):
         rec["raw_load_seconds"], rec["clean_load_seconds"] = _spread(rec.pop("raw")), _spread(rec.pop("clean"))
         return rec
     finally:
+        os.environ.pop("CMDIAD_TIFF_DEVICE", None)
         shutil.rmtree(root, ignore_errors=True)
 
 
@@ -147,6 +148,8 @@ def main():
     ap.add_argument("--reps", type=int, default=0, help="repetitions of the wall-time comparison (0: skip it)")
     ap.add_argument("--compare", default=None, help="another version of cmdiad_amd/utils/preprocessing.py, timed alternately")
     ap.add_argument("--loader", action="store_true", help="time the raw class's loader against the cleaned tree's")
+    ap.add_argument("--readers", type=int, default=None, help="reader threads of the --loader classes (default: the classes' own)")
+    ap.add_argument("--tiff-device", action="store_true", help="CMDIAD_TIFF_DEVICE=1 for the --loader classes")
     args = ap.parse_args()
     import torch
     import preprocess_ref as pr
@@ -163,7 +166,7 @@ def main():
     if args.reps:
         rec["repetitions"] = timed_repetitions(mod, scans, args.reps, _load_module(args.compare) if args.compare else None)
     if args.loader:
-        rec["loader"] = loader_seconds(mod)
+        rec["loader"] = loader_seconds(mod, readers=args.readers, tiff_device=args.tiff_device)
     from torch.profiler import ProfilerActivity, profile
     with profile(activities=[ProfilerActivity.CUDA]) as prof:
         for s in scans:
