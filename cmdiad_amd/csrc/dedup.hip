@@ -21,6 +21,7 @@
 // Only the search is shared; the exact fp32 re-score and everything after it run per original row.  Rows that repeat in any other way
 // (a second repeated value) are simply searched individually.
 #include "common.h"
+#include "block_scan.h"
 
 namespace {
 
@@ -139,6 +140,7 @@ __global__ __launch_bounds__(256) void verify_rows_kernel(const uint16_t* __rest
 
 // Order-preserving compaction of the rows that are not repeats, 1 024 rows per block.  Every repeat comes AFTER the representative
 // (its first occurrence) and nothing before the representative is dropped, so the representative's slot is its own index.
+// (compact_count_kernel keeps this private form: through block_ballot_rank it measured 3 % slower, profiles/cell_grid.md)
 __device__ __forceinline__ int block_exclusive_keep(bool keep, int* s_wave, int& total)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -182,7 +184,7 @@ __global__ __launch_bounds__(kPlanThreads) void compact_write_kernel(const unsig
     const int q = blockIdx.x * kPlanThreads + threadIdx.x;
     const bool in = q < Q, keep = in && !dup[q];
     int total;
-    const int pos = base + block_exclusive_keep(keep, s_wave, total);
+    const int pos = base + block_ballot_rank<kPlanThreads / 64>(keep, s_wave, total);
     if (keep) {
         slot[q] = pos;
         rows[pos] = q;

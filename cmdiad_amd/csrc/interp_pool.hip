@@ -17,6 +17,7 @@
 // interp3nn is compiled with -ffp-contract=off and follows oracle/cmdiad_oracle.c:orc_interp3nn
 // operation by operation, so idx3 / w3 are bit-exact against the oracle.
 #include "common.h"
+#include "cell_grid.h"
 #include "launch.h"
 
 namespace {
@@ -34,7 +35,7 @@ __global__ __launch_bounds__(1024) void unorganize_kernel(const float* __restric
 {
     constexpr int kAhead = 7;
     __shared__ int s_wave[2][16];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const float* px = pc + (size_t)b * 3 * HW;
     const float* py = px + HW;
     const float* pz = py + HW;
@@ -61,16 +62,8 @@ __global__ __launch_bounds__(1024) void unorganize_kernel(const float* __restric
             const int i = c * 1024 + tid;
             const float x = cx[e], y = cy[e], z = cz[e];
             const bool keep = i < HW && x != 0.0f && y != 0.0f && z != 0.0f;
-            const unsigned long long m = __ballot(keep);
-            if (lane == 0) s_wave[c & 1][wave] = __popcll(m);
-            __syncthreads();
-            int pos = base + __popcll(m & ((1ull << lane) - 1ull)), total = 0;
-#pragma unroll
-            for (int w = 0; w < 16; ++w) {
-                const int n = s_wave[c & 1][w];
-                pos += w < wave ? n : 0;
-                total += n;
-            }
+            int total;
+            const int pos = base + block_ballot_rank<16>(keep, s_wave[c & 1], total);
             base += total;
             if (i < HW) {
                 if (pix2pt) pix2pt[(size_t)b * HW + i] = (keep && pos < Nmax) ? pos : -1;
@@ -154,9 +147,10 @@ __global__ __launch_bounds__(256) void interp3nn_kernel(const float* __restrict_
 
 // ---------------------------------------------------------------------------------------------
 // a7 (selection) as a NEIGHBOURHOOD search (round 6; the counterpart of knn_grid_*_kernel in knn_group.hip): the S centres of a
-// cloud are binned into a 16 x 16 grid on the two axes of their largest extent (interp3nn_bin_kernel, one workgroup per cloud:
-// counting sort, {x, y, z, |c|^2} + original index per centre), and a point looks at the rings of cells around it, innermost
-// first, until its three best are certified -- ~40 distance evaluations per point instead of S = 1 024.
+// cloud are binned into the 16 x 16 cell grid of cell_grid.h (interp3nn_bin_kernel, one workgroup per cloud; the grid, its builder,
+// the ring walk and the workspace layout live there: {x, y, z, |c|^2} + original index per centre), and a point looks at the
+// rings of cells around it, innermost first, until its three best are certified -- ~40 distance evaluations per point instead
+// of S = 1 024.
 // Exactness.  The three "nearest" centres are the three smallest values of the reference's FORMULA d = -2 a.b + |a|^2 + |b|^2 in
 // fp32 (pointnet2_utils.py:19-22), ties to the lowest index; the same operation sequence as interp3nn_kernel gives the same d
 // for a (point, centre) pair whatever the visiting order, so the selection only has to see every centre that can matter:
@@ -167,129 +161,50 @@ __global__ __launch_bounds__(256) void interp3nn_kernel(const float* __restrict_
 // Coordinates so large that E exceeds the centre spacing (the regime where the reference's own selection is rounding noise)
 // simply never certify early and scan everything: slower, still exact.
 // ---------------------------------------------------------------------------------------------
-constexpr int kCGrid = 16, kCCells = kCGrid * kCGrid, kCHdr = 8;
+constexpr int kCGrid = 16;
+using CGrid = cellgrid::CellGrid<kCGrid>;   // user = max |c|^2
+using cellgrid::Interp3nnLayout;
 
-__device__ __forceinline__ int cgrid_coord(float a, float mn, float inv_h)
+__global__ __launch_bounds__(256) void interp3nn_bin_kernel(const float* __restrict__ center, int S, char* __restrict__ ws)
 {
-    return (int)fminf(fmaxf((a - mn) * inv_h, 0.0f), (float)(kCGrid - 1));   // (NaN -> 0; monotone in a)
-}
-__device__ __forceinline__ float cpick3(float x, float y, float z, int axis) { return axis == 0 ? x : (axis == 1 ? y : z); }
-
-// workspace per cloud: float4 sorted[S] | int orig[S] | int cell_start[257] | float hdr[8]
-__device__ __forceinline__ size_t cgrid_stride(int S) { return (size_t)S * 20 + (size_t)(kCCells + 1) * 4 + kCHdr * 4; }
-
-__global__ __launch_bounds__(256) void interp3nn_bin_kernel(const float* __restrict__ center, int S, char* __restrict__ ws, size_t stride)
-{
-    __shared__ int s_cnt[kCCells];
-    __shared__ float s_red[4][7];
-    __shared__ int s_wave[4];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* cb = center + (size_t)b * S * 3;
-    char* w = ws + (size_t)b * stride;
-    float4* sorted = reinterpret_cast<float4*>(w);
-    int* orig = reinterpret_cast<int*>(w + (size_t)S * 16);
-    int* cs = orig + S;
-    float* hd = reinterpret_cast<float*>(cs + kCCells + 1);
-    float mn[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, mx[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-    float cwmax = 0.0f;
-    for (int k = tid; k < S; k += 256) {
-        const float x = cb[k * 3], y = cb[k * 3 + 1], z = cb[k * 3 + 2];
-        mn[0] = fminf(mn[0], x); mx[0] = fmaxf(mx[0], x);
-        mn[1] = fminf(mn[1], y); mx[1] = fmaxf(mx[1], y);
-        mn[2] = fminf(mn[2], z); mx[2] = fmaxf(mx[2], z);
-        cwmax = fmaxf(cwmax, (x * x + y * y) + z * z);
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], m, 64));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], m, 64));
-        }
-        cwmax = fmaxf(cwmax, __shfl_xor(cwmax, m, 64));
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { s_red[wave][a] = mn[a]; s_red[wave][3 + a] = mx[a]; }
-        s_red[wave][6] = cwmax;
-    }
-    s_cnt[tid] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        mn[a] = fminf(fminf(s_red[0][a], s_red[1][a]), fminf(s_red[2][a], s_red[3][a]));
-        mx[a] = fmaxf(fmaxf(s_red[0][3 + a], s_red[1][3 + a]), fmaxf(s_red[2][3 + a], s_red[3][3 + a]));
-    }
-    cwmax = fmaxf(fmaxf(s_red[0][6], s_red[1][6]), fmaxf(s_red[2][6], s_red[3][6]));
-    const float e0 = mx[0] - mn[0], e1 = mx[1] - mn[1], e2 = mx[2] - mn[2];
-    int A, Bx;
-    if (e0 >= e1 && e0 >= e2) { A = 0; Bx = e1 >= e2 ? 1 : 2; }
-    else if (e1 >= e2) { A = 1; Bx = e0 >= e2 ? 0 : 2; }
-    else { A = 2; Bx = e0 >= e1 ? 0 : 1; }
-    if (A > Bx) { const int t = A; A = Bx; Bx = t; }
-    const float ext = fmaxf(cpick3(e0, e1, e2, A), cpick3(e0, e1, e2, Bx));
-    const float h = ext > 0.0f && ext < __builtin_inff() ? ext * (1.0f / kCGrid) : 0.0f;
-    const float inv_h = h > 0.0f ? 1.0f / h : 0.0f;
-    const float mnA = cpick3(mn[0], mn[1], mn[2], A), mnB = cpick3(mn[0], mn[1], mn[2], Bx);
-    for (int k = tid; k < S; k += 256) {
-        const float x = cb[k * 3], y = cb[k * 3 + 1], z = cb[k * 3 + 2];
-        atomicAdd(&s_cnt[cgrid_coord(cpick3(x, y, z, Bx), mnB, inv_h) * kCGrid + cgrid_coord(cpick3(x, y, z, A), mnA, inv_h)], 1);
-    }
-    __syncthreads();
-    const int mine = s_cnt[tid];
-    int incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int base = 0;
-    for (int q = 0; q < wave; ++q) base += s_wave[q];
-    const int start = base + incl - mine;
-    cs[tid] = start;
-    if (tid == 255) cs[kCCells] = start + mine;
-    __syncthreads();          // (every thread has read its count)
-    s_cnt[tid] = start;       // now the cell's write cursor
-    if (tid == 0) { hd[0] = mnA; hd[1] = mnB; hd[2] = inv_h; hd[3] = h; hd[4] = (float)A; hd[5] = (float)Bx; hd[6] = cwmax; hd[7] = 0.0f; }
-    __syncthreads();
-    for (int k = tid; k < S; k += 256) {
-        const float x = cb[k * 3], y = cb[k * 3 + 1], z = cb[k * 3 + 2];
-        const int cell = cgrid_coord(cpick3(x, y, z, Bx), mnB, inv_h) * kCGrid + cgrid_coord(cpick3(x, y, z, A), mnA, inv_h);
-        const int pos = atomicAdd(&s_cnt[cell], 1);
-        sorted[pos] = float4{x, y, z, (x * x + y * y) + z * z};
-        orig[pos] = k;
-    }
+    const Interp3nnLayout L(S);
+    const float* cb = center + (size_t)blockIdx.x * S * 3;
+    char* w = ws + blockIdx.x * L.stride;
+    float4* sorted = reinterpret_cast<float4*>(w + L.elem);
+    int* orig = reinterpret_cast<int*>(w + L.aux);
+    cellgrid::build<kCGrid, 256>(
+        S, [&](int k, float& x, float& y, float& z) { x = cb[k * 3]; y = cb[k * 3 + 1]; z = cb[k * 3 + 2]; },
+        [](float x, float y, float z) { return (x * x + y * y) + z * z; },
+        [&](int k, int pos, float x, float y, float z) { sorted[pos] = float4{x, y, z, (x * x + y * y) + z * z}; orig[pos] = k; },
+        reinterpret_cast<CGrid*>(w), reinterpret_cast<int*>(w + L.cell_start));
 }
 
 __global__ __launch_bounds__(256) void interp3nn_grid_kernel(const float* __restrict__ xyz, const int32_t* __restrict__ n_valid,
-                                                             const char* __restrict__ ws, size_t stride, int N, int S,
-                                                             int32_t* __restrict__ idx3, float* __restrict__ w3)
+                                                             const char* __restrict__ ws, int N, int S, int32_t* __restrict__ idx3,
+                                                             float* __restrict__ w3)
 {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float4* s_c = reinterpret_cast<float4*>(smem);
-    int* s_i = reinterpret_cast<int*>(smem + (size_t)S * 16);
-    int* s_cs = s_i + S;
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // the cloud's slice behind its header, as it lies in the workspace
+    const Interp3nnLayout L(S);
+    const float4* s_c = reinterpret_cast<const float4*>(smem);
+    const int* s_i = reinterpret_cast<const int*>(smem + (L.aux - L.elem));
+    const int* s_cs = reinterpret_cast<const int*>(smem + (L.cell_start - L.elem));
     const int b = blockIdx.y;
     const int n = n_valid ? n_valid[b] : N;
-    const char* w = ws + (size_t)b * stride;
+    const char* w = ws + b * L.stride;
     {
-        const float4* g_c = reinterpret_cast<const float4*>(w);
-        const int* g_i = reinterpret_cast<const int*>(w + (size_t)S * 16);
-        for (int k = threadIdx.x; k < S; k += 256) { s_c[k] = g_c[k]; s_i[k] = g_i[k]; }
-        for (int k = threadIdx.x; k < kCCells + 1; k += 256) s_cs[k] = g_i[S + k];
+        const int* src = reinterpret_cast<const int*>(w + L.elem);
+        int* dst = reinterpret_cast<int*>(smem);
+        for (int k = threadIdx.x; k < (int)(L.lds_bytes() / 4); k += 256) dst[k] = src[k];
     }
-    const float* hd = reinterpret_cast<const float*>(w + (size_t)S * 20 + (size_t)(kCCells + 1) * 4);
-    const float mnA = hd[0], mnB = hd[1], inv_h = hd[2], h = hd[3], cwmax = hd[6];
-    const int A = (int)hd[4], Bx = (int)hd[5];
+    const CGrid grid = *reinterpret_cast<const CGrid*>(w);
+    const float inv_h = grid.inv_h, h = grid.h, cwmax = grid.user;
     __syncthreads();
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float* p = xyz + ((size_t)b * N + i) * 3;
     const float x = p[0], y = p[1], z = p[2];
     const float n1 = (x * x + y * y) + z * z;
-    const int ia = cgrid_coord(cpick3(x, y, z, A), mnA, inv_h), ib = cgrid_coord(cpick3(x, y, z, Bx), mnB, inv_h);
+    const int ia = grid.ia(x, y, z), ib = grid.ib(x, y, z);
     float d0 = __builtin_inff(), d1 = __builtin_inff(), d2 = __builtin_inff();
     int i0 = 0, i1 = 0, i2 = 0;
     // (d, index) lexicographic order: the lowest index among equal distances, whatever the visiting order
@@ -318,17 +233,7 @@ __global__ __launch_bounds__(256) void interp3nn_grid_kernel(const float* __rest
     int m_done = -1, m = h > 0.0f ? 1 : kCGrid;
     for (;;) {
         m = min(m, kCGrid);
-        for (int dj = -m; dj <= m; ++dj) {
-            const int j = ib + dj;
-            if (j < 0 || j >= kCGrid) continue;
-            const int lo = max(ia - m, 0), hi = min(ia + m, kCGrid - 1);
-            if (dj < -m_done || dj > m_done || m_done < 0) {
-                run(s_cs[j * kCGrid + lo], s_cs[j * kCGrid + hi + 1]);
-            } else {
-                if (ia - m_done - 1 >= lo) run(s_cs[j * kCGrid + lo], s_cs[j * kCGrid + ia - m_done]);
-                if (ia + m_done + 1 <= hi) run(s_cs[j * kCGrid + ia + m_done + 1], s_cs[j * kCGrid + hi + 1]);
-            }
-        }
+        cellgrid::ring_rows<kCGrid>(ia, ib, m, m_done, [&](int j, int lo, int hi) { run(s_cs[j * kCGrid + lo], s_cs[j * kCGrid + hi + 1]); });
         m_done = m;
         if (m >= kCGrid) break;
         const float r = ((float)m - 0.01f) * h;
@@ -528,8 +433,7 @@ extern "C" int cmdiad_interp3nn(const float* xyz, const int32_t* n_valid, const 
 // few centres (S < 64) and with CMDIAD_INTERP_GRID=0 (A/B runs, parity tests; read per call).
 extern "C" size_t cmdiad_interp3nn_workspace_bytes(int B, int S)
 {
-    if (B <= 0 || S <= 0) return 0;
-    return (size_t)B * (((size_t)S * 20 + (size_t)(kCCells + 1) * 4 + kCHdr * 4 + 15) / 16 * 16);
+    return B <= 0 || S <= 0 ? 0 : cellgrid::Interp3nnLayout(S).bytes(B);
 }
 
 extern "C" int cmdiad_interp3nn_ws(const float* xyz, const int32_t* n_valid, const float* center, int B, int N, int S,
@@ -540,12 +444,12 @@ extern "C" int cmdiad_interp3nn_ws(const float* xyz, const int32_t* n_valid, con
     CMDIAD_REQUIRE(xyz && center && idx3 && w3, CMDIAD_ERR_ARG, "cmdiad_interp3nn_ws: null pointer");
     CMDIAD_REQUIRE(workspace && workspace_bytes >= cmdiad_interp3nn_workspace_bytes(B, S) && ((uintptr_t)workspace & 15) == 0,
                    CMDIAD_ERR_WORKSPACE, "cmdiad_interp3nn_ws: workspace too small or not 16-byte aligned");
-    const size_t stride = ((size_t)S * 20 + (size_t)(kCCells + 1) * 4 + kCHdr * 4 + 15) / 16 * 16;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(interp3nn_bin_kernel, dim3(B), dim3(256), 0, s, center, S, (char*)workspace, stride);
-    const size_t lds = (size_t)S * 20 + (size_t)(kCCells + 1) * 4;
-    hipLaunchKernelGGL(interp3nn_grid_kernel, dim3((N + 255) / 256, B), dim3(256), lds, s, xyz, n_valid, (const char*)workspace, stride, N,
-                       S, idx3, w3);
+    hipLaunchKernelGGL(interp3nn_bin_kernel, dim3(B), dim3(256), 0, s, center, S, (char*)workspace);
+    // (above 64 KiB of LDS from S = 3226 on)
+    const int rc = launch_lds<interp3nn_grid_kernel>("cmdiad_interp3nn_ws", dim3((N + 255) / 256, B), dim3(256), cellgrid::Interp3nnLayout(S).lds_bytes(),
+                                                     s, xyz, n_valid, (const char*)workspace, N, S, idx3, w3);
+    if (rc != CMDIAD_OK) return rc;
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
 }

@@ -17,6 +17,7 @@
 //     even though organised clouds arrive in raster order;
 //   * the final sort leaves the K winners in ascending order; the epilogue gathers p[idx] - c.
 #include "common.h"
+#include "cell_grid.h"
 #include "launch.h"
 
 namespace {
@@ -307,125 +308,41 @@ __global__ __launch_bounds__(kWaves * 64) void knn_wave_kernel(const float* __re
 // Third formulation (round 6): the same selection on the points of a NEIGHBOURHOOD instead of the whole cloud -- exact.
 // The streaming kernel above evaluates every centre against every point (1 024 x 24 576 per cloud) although the 128 nearest
 // points of a centre are 0.5 % of an MVTec-3D cloud.  Here a cloud is first binned (knn_grid_build_kernel, one workgroup per
-// cloud): the bounding box, the TWO axes of largest extent (a depth-camera cloud is a 2.5-D sheet), a 64 x 64 grid of square
-// cells on them, a counting sort of the points by cell (x, y, z and the ORIGINAL index as 16 bytes; cells row-major, so a run
-// of cells of one grid row is one contiguous run of points).  A wave then owns ONE centre (knn_grid_query_kernel) and scans the
-// square rings of cells around it, innermost first, through the wave-level selection of the streaming kernel (same keys
+// cloud) into the 64 x 64 cell grid of cell_grid.h -- the grid, its builder, the ring walk, the workspace layout and the argument
+// why a scanned square of radius m certifies every distance below ((m - 0.01) h)^2 are there -- with x, y, z and the ORIGINAL
+// index as the 16 bytes of a sorted point.  A wave then owns ONE centre (knn_grid_query_kernel) and scans the square rings of
+// cells around it, innermost first, through the wave-level selection of the streaming kernel (same keys
 // (d2 bits << 32 | original index), same d2 = (dx*dx + dy*dy) + dz*dz single roundings, same sorted-128 state and prune):
-//   * every point NOT in a scanned cell differs from the centre by more than m cells along a grid axis (m = the scanned ring
-//     radius), i.e. lies farther than m * h -- so once the K-th best squared distance is below ((m - 0.01) h)^2 the K best
-//     of the scanned points are the K best of the cloud (0.01 cells of slack against the roundings of the cell index: 64 *
-//     2^-23 = 8e-6 cells);
+//   * once the K-th best squared distance is below ((m - 0.01) h)^2 the K best of the scanned points are the K best of the cloud;
 //   * otherwise the next radius is the one the current K-th best asks for (floor(sqrt(d2_K) / h) + 2), or twice the radius
 //     while fewer than K points have been met; radius 64 is the whole cloud.
 // Typically two rounds (radius 2, then 4): ~500 distance evaluations and 3-4 prunes per centre instead of 24 576 and 9.
 // The selected set and its order are those of the streaming kernel and of the oracle bit for bit: keys are unique, and the
 // final state is the K smallest keys of the cloud whatever the visiting order.
 // ------------------------------------------------------------------------------------------------
-constexpr int kGridSide = 64, kGridCells = kGridSide * kGridSide;
-constexpr int kGridHdr = 8;   // floats per cloud: min on axis A, min on axis B, 1 / h, h, axis A, axis B, n, unused
-
-__device__ __forceinline__ int grid_coord(float a, float mn, float inv_h)
-{
-    return (int)fminf(fmaxf((a - mn) * inv_h, 0.0f), (float)(kGridSide - 1));   // (NaN -> 0; monotone in a)
-}
-
-__device__ __forceinline__ float pick3(float x, float y, float z, int axis) { return axis == 0 ? x : (axis == 1 ? y : z); }
+constexpr int kGridSide = 64;
+using Grid = cellgrid::CellGrid<kGridSide>;
+using cellgrid::KnnGridLayout;
 
 __global__ __launch_bounds__(1024) void knn_grid_build_kernel(const float* __restrict__ xyz, const int32_t* __restrict__ n_valid, int N,
-                                                              float4* __restrict__ sorted, int* __restrict__ cell_start,
-                                                              float* __restrict__ hdr)
+                                                              char* __restrict__ ws)
 {
-    __shared__ int s_cnt[kGridCells];
-    __shared__ float s_red[16][6];
-    __shared__ int s_wave[16];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = n_valid ? min(n_valid[b], N) : N;
+    const KnnGridLayout L(N);
+    const int b = blockIdx.x;
     const float* p = xyz + (size_t)b * N * 3;
-    float mn[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, mx[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-    for (int k = tid; k < n; k += 1024) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float v = p[k * 3 + a];
-            mn[a] = fminf(mn[a], v);
-            mx[a] = fmaxf(mx[a], v);
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], m, 64));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], m, 64));
-        }
-        if (lane == 0) { s_red[wave][a] = mn[a]; s_red[wave][3 + a] = mx[a]; }
-    }
-    for (int c = tid; c < kGridCells; c += 1024) s_cnt[c] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        mn[a] = s_red[0][a]; mx[a] = s_red[0][3 + a];
-        for (int w = 1; w < 16; ++w) { mn[a] = fminf(mn[a], s_red[w][a]); mx[a] = fmaxf(mx[a], s_red[w][3 + a]); }
-    }
-    // the two axes of largest extent (ties: the lower axis); h = the larger extent / 64
-    const float e0 = mx[0] - mn[0], e1 = mx[1] - mn[1], e2 = mx[2] - mn[2];
-    int A, Bx;
-    if (e0 >= e1 && e0 >= e2) { A = 0; Bx = e1 >= e2 ? 1 : 2; }
-    else if (e1 >= e2) { A = 1; Bx = e0 >= e2 ? 0 : 2; }
-    else { A = 2; Bx = e0 >= e1 ? 0 : 1; }
-    if (A > Bx) { const int t = A; A = Bx; Bx = t; }
-    const float ext = fmaxf(pick3(e0, e1, e2, A), pick3(e0, e1, e2, Bx));
-    const float h = ext > 0.0f && ext < __builtin_inff() ? ext * (1.0f / kGridSide) : 0.0f;
-    const float inv_h = h > 0.0f ? 1.0f / h : 0.0f;
-    const float mnA = pick3(mn[0], mn[1], mn[2], A), mnB = pick3(mn[0], mn[1], mn[2], Bx);
-    for (int k = tid; k < n; k += 1024) {
-        const float x = p[k * 3], y = p[k * 3 + 1], z = p[k * 3 + 2];
-        atomicAdd(&s_cnt[grid_coord(pick3(x, y, z, Bx), mnB, inv_h) * kGridSide + grid_coord(pick3(x, y, z, A), mnA, inv_h)], 1);
-    }
-    __syncthreads();
-    // exclusive scan of the 4 096 counts: four cells per thread, wave scan, 16 wave totals
-    int c4[4], sum = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { c4[i] = s_cnt[tid * 4 + i]; sum += c4[i]; }
-    int incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += s_wave[w];
-    int run = base + incl - sum;
-    int* cs = cell_start + (size_t)b * (kGridCells + 1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        cs[tid * 4 + i] = run;
-        s_cnt[tid * 4 + i] = run;     // now the cell's write cursor
-        run += c4[i];
-    }
-    if (tid == 1023) cs[kGridCells] = run;
-    if (tid == 0) {
-        float* hd = hdr + (size_t)b * kGridHdr;
-        hd[0] = mnA; hd[1] = mnB; hd[2] = inv_h; hd[3] = h; hd[4] = (float)A; hd[5] = (float)Bx; hd[6] = (float)n; hd[7] = 0.0f;
-    }
-    __syncthreads();
-    float4* out = sorted + (size_t)b * N;
-    for (int k = tid; k < n; k += 1024) {
-        const float x = p[k * 3], y = p[k * 3 + 1], z = p[k * 3 + 2];
-        const int cell = grid_coord(pick3(x, y, z, Bx), mnB, inv_h) * kGridSide + grid_coord(pick3(x, y, z, A), mnA, inv_h);
-        const int pos = atomicAdd(&s_cnt[cell], 1);
-        out[pos] = float4{x, y, z, __int_as_float(k)};
-    }
+    char* w = ws + b * L.stride;
+    float4* sorted = reinterpret_cast<float4*>(w + L.elem);
+    cellgrid::build<kGridSide, 1024>(
+        n_valid ? min(n_valid[b], N) : N, [&](int k, float& x, float& y, float& z) { x = p[k * 3]; y = p[k * 3 + 1]; z = p[k * 3 + 2]; },
+        [](float, float, float) { return 0.0f; },
+        [&](int k, int pos, float x, float y, float z) { sorted[pos] = float4{x, y, z, __int_as_float(k)}; }, reinterpret_cast<Grid*>(w),
+        reinterpret_cast<int*>(w + L.cell_start));
 }
 
 template <int kWaves>
 __global__ __launch_bounds__(kWaves * 64) void knn_grid_query_kernel(const float* __restrict__ xyz, const int32_t* __restrict__ n_valid,
-                                                                    const float* __restrict__ center, const float4* __restrict__ sorted,
-                                                                    const int* __restrict__ cell_start, const float* __restrict__ hdr,
-                                                                    int N, int G, int K, int64_t* __restrict__ idx_out,
-                                                                    float* __restrict__ neigh_out)
+                                                                    const float* __restrict__ center, const char* __restrict__ ws, int N, int G,
+                                                                    int K, int64_t* __restrict__ idx_out, float* __restrict__ neigh_out)
 {
     constexpr int kTrig = CMDIAD_KNN_TRIG, kCandCap = kTrig + 64;
     __shared__ unsigned long long s_cand[kWaves][kCandCap];
@@ -434,15 +351,15 @@ __global__ __launch_bounds__(kWaves * 64) void knn_grid_query_kernel(const float
     const int g = blockIdx.x * kWaves + wave;
     if (g >= G) return;
     const float* p = xyz + (size_t)b * N * 3;
-    const float4* sp = sorted + (size_t)b * N;
-    const int* cs = cell_start + (size_t)b * (kGridCells + 1);
-    const float* hd = hdr + (size_t)b * kGridHdr;
-    const float mnA = hd[0], mnB = hd[1], inv_h = hd[2], h = hd[3];
-    const int A = (int)hd[4], Bx = (int)hd[5];
+    const KnnGridLayout L(N);
+    const char* w = ws + b * L.stride;
+    const Grid grid = *reinterpret_cast<const Grid*>(w);
+    const float4* sp = reinterpret_cast<const float4*>(w + L.elem);
+    const int* cs = reinterpret_cast<const int*>(w + L.cell_start);
+    const float h = grid.h, inv_h = grid.inv_h;
     const float* cc = center + ((size_t)b * G + g) * 3;
     const float cx = cc[0], cy = cc[1], cz = cc[2];
-    const int ia = __builtin_amdgcn_readfirstlane(grid_coord(pick3(cx, cy, cz, A), mnA, inv_h));
-    const int ib = __builtin_amdgcn_readfirstlane(grid_coord(pick3(cx, cy, cz, Bx), mnB, inv_h));
+    const int ia = __builtin_amdgcn_readfirstlane(grid.ia(cx, cy, cz)), ib = __builtin_amdgcn_readfirstlane(grid.ib(cx, cy, cz));
 
     unsigned long long ta = kInf, tb = kInf, tau = kInf;
     int cnt = 0;
@@ -492,17 +409,7 @@ __global__ __launch_bounds__(kWaves * 64) void knn_grid_query_kernel(const float
     int m = h > 0.0f ? 2 : kGridSide;   // (a degenerate grid -- all points in one cell -- is scanned whole)
     for (;;) {
         m = min(m, kGridSide);
-        for (int dj = -m; dj <= m; ++dj) {
-            const int j = ib + dj;
-            if (j < 0 || j >= kGridSide) continue;
-            const int lo = max(ia - m, 0), hi = min(ia + m, kGridSide - 1);
-            if (dj < -m_done || dj > m_done || m_done < 0) {
-                row_run(j, lo, hi);                       // a row outside the scanned square: all of it
-            } else {                                       // a row that crosses the scanned square: the two ends
-                if (ia - m_done - 1 >= lo) row_run(j, lo, ia - m_done - 1);
-                if (ia + m_done + 1 <= hi) row_run(j, ia + m_done + 1, hi);
-            }
-        }
+        cellgrid::ring_rows<kGridSide>(ia, ib, m, m_done, row_run);
         if (cnt > 0) prune();
         m_done = m;
         if (m >= kGridSide) break;
@@ -573,8 +480,7 @@ extern "C" int cmdiad_knn_group(const float* xyz, const int32_t* n_valid, const 
 // the streaming kernel for small clouds (binning does not pay) and when CMDIAD_KNN_GRID=0 (A/B runs, parity tests; read per call).
 extern "C" size_t cmdiad_knn_workspace_bytes(int B, int N)
 {
-    if (B <= 0 || N <= 0) return 0;
-    return (size_t)B * ((size_t)N * sizeof(float4) + (size_t)(kGridCells + 1) * sizeof(int) + (size_t)kGridHdr * sizeof(float)) + 64;
+    return B <= 0 || N <= 0 ? 0 : cellgrid::KnnGridLayout(N).bytes(B);
 }
 
 extern "C" int cmdiad_knn_group_ws(const float* xyz, const int32_t* n_valid, const float* center, int B, int N, int G, int K,
@@ -585,13 +491,10 @@ extern "C" int cmdiad_knn_group_ws(const float* xyz, const int32_t* n_valid, con
     CMDIAD_REQUIRE(xyz && center, CMDIAD_ERR_ARG, "cmdiad_knn_group_ws: null pointer");
     CMDIAD_REQUIRE(workspace && workspace_bytes >= cmdiad_knn_workspace_bytes(B, N) && ((uintptr_t)workspace & 15) == 0, CMDIAD_ERR_WORKSPACE,
                    "cmdiad_knn_group_ws: workspace too small or not 16-byte aligned");
-    float4* sorted = (float4*)workspace;
-    int* cell_start = (int*)(sorted + (size_t)B * N);
-    float* hdr = (float*)(cell_start + (size_t)B * (kGridCells + 1));
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(knn_grid_build_kernel, dim3(B), dim3(1024), 0, s, xyz, n_valid, N, sorted, cell_start, hdr);
-    hipLaunchKernelGGL((knn_grid_query_kernel<4>), dim3((G + 3) / 4, B), dim3(256), 0, s, xyz, n_valid, center, (const float4*)sorted,
-                       (const int*)cell_start, (const float*)hdr, N, G, K, idx_out, neigh_out);
+    hipLaunchKernelGGL(knn_grid_build_kernel, dim3(B), dim3(1024), 0, s, xyz, n_valid, N, (char*)workspace);
+    hipLaunchKernelGGL((knn_grid_query_kernel<4>), dim3((G + 3) / 4, B), dim3(256), 0, s, xyz, n_valid, center, (const char*)workspace, N, G, K,
+                       idx_out, neigh_out);
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
 }

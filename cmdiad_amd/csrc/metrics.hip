@@ -22,6 +22,7 @@
 // cmdiad_auc_counts: S = sum over defect pixels of #(ok < s) + #(ok <= s): two binary searches per pixel on the sorted keys
 //   (integer order of the keys == order of the doubles), summed in the wave, one 64-bit integer atomic per wave.
 // cmdiad_pro_hist: hist[component][#thresholds strictly below the score], thresholds in LDS, integer atomics aggregated per wave.
+#include "block_scan.h"
 #include "launch.h"
 #include "union_find.h"
 
@@ -58,33 +59,6 @@ __device__ __forceinline__ double key_f64(unsigned long long k) { return __longl
 __device__ __forceinline__ bool f64_nonfinite(double x)
 {
     return ((unsigned long long)__double_as_longlong(x) & 0x7FF0000000000000ull) == 0x7FF0000000000000ull;
-}
-
-// inclusive sum over the lanes of a wave, then the exclusive sum over the 256 threads of a block (sh: 4 ints; every thread calls it)
-__device__ __forceinline__ int wave_incl_scan(int v)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(v, d, 64);
-        if (lane_id() >= d) v += t;
-    }
-    return v;
-}
-__device__ __forceinline__ int block_excl_scan256(int v, int* sh, int* total)
-{
-    const int incl = wave_incl_scan(v), wave = threadIdx.x >> 6;
-    __syncthreads();   // sh may still be read from the previous call
-    if (lane_id() == 63) sh[wave] = incl;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        const int s = sh[w];
-        base += w < wave ? s : 0;
-        tot += s;
-    }
-    *total = tot;
-    return base + incl - v;
 }
 
 // table[idx] += 1 for every active lane; lanes of the wave with the same idx share one atomic.  Every lane of the wave calls it.
@@ -169,7 +143,8 @@ __global__ __launch_bounds__(256) void row_excl_scan_kernel(const int32_t* in, i
         const int i = s + threadIdx.x;
         const int v = i < len ? src[i] : 0;
         int tot;
-        const int e = block_excl_scan256(v, sh, &tot);
+        __syncthreads();   // sh may still be read from the previous chunk
+        const int e = block_excl_scan<4>(v, sh, tot);
         if (i < len) dst[i] = running + e;
         running += tot;
     }
@@ -291,7 +266,7 @@ __global__ __launch_bounds__(256) void sort_scatter_kernel(const unsigned long l
     __syncthreads();
     {   // thread = digit: keys with smaller digits + this digit's keys in earlier blocks + in earlier waves of this block
         int unused;
-        uint32_t g = (uint32_t)block_excl_scan256(totals[threadIdx.x], sh, &unused) + table[(size_t)threadIdx.x * nb + blockIdx.x];
+        uint32_t g = (uint32_t)block_excl_scan<4>(totals[threadIdx.x], sh, unused) + table[(size_t)threadIdx.x * nb + blockIdx.x];
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
             const uint32_t c = cursor[w][threadIdx.x];

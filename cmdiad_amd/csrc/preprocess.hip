@@ -27,6 +27,7 @@
 #include <limits.h>
 
 #include "common.h"
+#include "block_scan.h"
 #include "union_find.h"
 
 namespace {
@@ -334,28 +335,21 @@ __global__ __launch_bounds__(256) void dbscan_key_kernel(const float* __restrict
 // (in == out is fine).  n = *n_dev when n_dev is given.
 __global__ __launch_bounds__(1024) void scan_exclusive_kernel(const int* in, int* out, int n, const int* __restrict__ n_dev)
 {
-    __shared__ int part[1024];
+    __shared__ int sh[16];
     if (n_dev) n = *n_dev;
     const int t = threadIdx.x;
     const int piece = (n + 1023) / 1024;
     const int lo = min(t * piece, n), hi = min(lo + piece, n);
     int s = 0;
     for (int i = lo; i < hi; ++i) s += in[i];
-    part[t] = s;
-    __syncthreads();
-    for (int step = 1; step < 1024; step <<= 1) {   // inclusive Hillis-Steele over the 1024 piece sums
-        const int add = t >= step ? part[t - step] : 0;
-        __syncthreads();
-        part[t] += add;
-        __syncthreads();
-    }
-    int run = t ? part[t - 1] : 0;
+    int total;
+    int run = block_excl_scan<16>(s, sh, total);
     for (int i = lo; i < hi; ++i) {
         const int v = in[i];
         out[i] = run;
         run += v;
     }
-    if (t == 1023) out[n] = part[1023];
+    if (t == 1023) out[n] = total;
 }
 
 __global__ __launch_bounds__(256) void dbscan_scatter_kernel(const float* __restrict__ pts, int N, const int* __restrict__ key,
@@ -539,12 +533,9 @@ __global__ __launch_bounds__(256) void compact_count_kernel(const float* __restr
                                                             int* __restrict__ block_count)
 {
     __shared__ int s_wave[4];
-    int r, c;
-    const bool ok = seq_valid(pc, pitch, blockIdx.x * 256 + threadIdx.x, L, H, W, edges, r, c);
-    const unsigned long long m = __ballot(ok);
-    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = __popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) block_count[blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+    int r, c, total;
+    block_ballot_rank<4>(seq_valid(pc, pitch, blockIdx.x * 256 + threadIdx.x, L, H, W, edges, r, c), s_wave, total);
+    if (threadIdx.x == 0) block_count[blockIdx.x] = total;
 }
 
 // block_start = the exclusive scan of block_count over the n_blocks blocks, block_start[n_blocks] = all valid points
@@ -555,16 +546,10 @@ __global__ __launch_bounds__(256) void compact_scatter_kernel(const float* __res
 {
     __shared__ int s_wave[4];
     if (blockIdx.x == 0 && threadIdx.x == 0) *count = block_start[n_blocks];
-    int r = 0, c = 0;
+    int r = 0, c = 0, total;
     const bool ok = seq_valid(pc, pitch, blockIdx.x * 256 + threadIdx.x, L, H, W, edges, r, c);
-    const unsigned long long m = __ballot(ok);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) s_wave[wave] = __popcll(m);
-    __syncthreads();
-    if (!ok) return;
-    int pos = block_start[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; ++w) pos += s_wave[w];
-    if (pos >= cap) return;
+    const int pos = block_start[blockIdx.x] + block_ballot_rank<4>(ok, s_wave, total);
+    if (!ok || pos >= cap) return;
     const float* p = pc + (size_t)r * pitch + (size_t)c * 3;
     float* q = points + (size_t)pos * 3;
     q[0] = p[0], q[1] = p[1], q[2] = p[2];

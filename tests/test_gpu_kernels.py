@@ -251,6 +251,62 @@ def test_interp3nn_far_from_the_origin_falls_back_to_the_whole_grid(monkeypatch)
     np.testing.assert_array_equal(w3[0].cpu().numpy(), wr)
 
 
+@pytest.mark.parametrize("K", [1, 128])
+def test_knn_neighbourhood_search_at_its_smallest_cloud(K, monkeypatch):
+    """The edges of the kNN grid path (csrc/cell_grid.h builder under knn_grid_build_kernel): N = 2 048, the smallest size that
+    takes the grid, so the 1 024-thread builder has two points per thread at most; clouds of 128 / 129 / 2 047 / 2 048 valid
+    points with garbage behind them (whole waves of the builder idle, K = 128 = every point of the first cloud); G = 5, so the
+    last query block has idle waves.  Grid == streaming == oracle per cloud, indices and neighbourhoods."""
+    N, G, sizes = 2048, 5, (128, 129, 2047, 2048)
+    rs = np.random.RandomState(21)
+    xyz = np.full((len(sizes), N, 3), 1e6, np.float32)                              # garbage beyond n_valid must not be read as points
+    cen = np.zeros((len(sizes), G, 3), np.float32)
+    for i, n in enumerate(sizes):
+        xyz[i, :n] = _dense_cloud(n, 60 + i)
+        cen[i] = xyz[i, rs.randint(0, n, G)]
+    cen[:, 4] += 0.01                                                               # one centre off the surface
+    nv = torch.tensor(sizes, dtype=torch.int32, device=DEV)
+    x, c = torch.from_numpy(xyz).to(DEV), torch.from_numpy(cen).to(DEV)
+    monkeypatch.setenv("CMDIAD_KNN_GRID", "1")
+    idx, nb = ops.knn_group(x, c, K, n_valid=nv)
+    monkeypatch.setenv("CMDIAD_KNN_GRID", "0")
+    idx_s, nb_s = ops.knn_group(x, c, K, n_valid=nv)
+    assert torch.equal(idx, idx_s) and torch.equal(nb, nb_s)
+    for i, n in enumerate(sizes):
+        ir, nr = ok.knn_group(xyz[i:i + 1, :n], cen[i:i + 1], K)
+        np.testing.assert_array_equal(idx[i].cpu().numpy(), ir[0], err_msg=f"cloud of {n} points")
+        np.testing.assert_array_equal(nb[i].cpu().numpy(), nr[0], err_msg=f"cloud of {n} points")
+
+
+@pytest.mark.parametrize("S", [64, 65, 1024, 4096])
+def test_interp3nn_neighbourhood_search_at_the_edges_of_the_centre_count(S, monkeypatch):
+    """The edges of the 3-NN grid path (csrc/cell_grid.h builder under interp3nn_bin_kernel): S = 64, the fewest centres that take
+    the grid (a quarter of the builder's threads own one), 65, the production 1 024 and 4 096, the most the entry accepts -- its
+    83 KB of LDS need the launch attribute raised (launch_lds); N = 257 (a second block with one point), a second cloud with ONE
+    valid point.  Centres are cloud points, two identical (ties by index), one far outlier.  Grid == full == oracle."""
+    N, sizes = 257, (257, 1)
+    rs = np.random.RandomState(22)
+    pts = _dense_cloud(N, 70)
+    cen = pts[rs.randint(0, N, S)].copy()
+    cen[1::2] += (rs.randn(len(cen[1::2]), 3) * 0.003).astype(np.float32)
+    cen[7] = cen[3]                                                                 # identical centres: ties by index
+    cen[11] = pts.max(0) + 5.0                                                      # a far outlier stretches the grid
+    cens = np.stack([cen, cen[::-1].copy()])
+    xyz = np.stack([pts, pts[::-1].copy()])
+    nv = torch.tensor(sizes, dtype=torch.int32, device=DEV)
+    x, c = torch.from_numpy(xyz).to(DEV), torch.from_numpy(cens).to(DEV)
+    monkeypatch.setenv("CMDIAD_INTERP_GRID", "1")
+    idx3, w3 = ops.interp3nn(x, c, n_valid=nv)
+    monkeypatch.setenv("CMDIAD_INTERP_GRID", "0")
+    idx_f, w_f = ops.interp3nn(x, c, n_valid=nv)
+    assert torch.equal(idx3, idx_f) and torch.equal(w3, w_f)
+    feat = np.zeros((S, 4), np.float32)
+    for i, m in enumerate(sizes):
+        _, ir, wr = ok.interp3nn(xyz[i, :m], cens[i], feat)
+        np.testing.assert_array_equal(idx3[i, :m].cpu().numpy(), ir, err_msg=f"cloud {i}")
+        np.testing.assert_array_equal(w3[i, :m].cpu().numpy(), wr, err_msg=f"cloud {i}")
+
+
 def test_knn_group_production_instantiation_ragged():
     """The grid the pipeline runs (knn_wave_kernel<4, 4>: four waves per block, four centres per wave, chosen when
     B * ceil(G / 16) >= 512) on eight ragged clouds, bit for bit against the oracle and identical over repeated launches.  The

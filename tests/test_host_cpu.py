@@ -300,6 +300,26 @@ def test_streamk_job_list_covers_every_unit_once_in_hand_over_order(tmp_path):
     assert out.returncode == 0 and "sk jobs ok" in out.stdout, out.stdout + out.stderr
 
 
+def test_cell_grid_ring_walk_covers_every_cell_once_and_axes_match_the_model(tmp_path):
+    """tests/cell_grid_check.cpp on csrc/cell_grid.h, the grid arithmetic both neighbourhood searches run on (knn_grid_*_kernel,
+    interp3nn_bin / _grid_kernel), compiled for the host with address + undefined sanitizers and without contraction: for grid
+    sides 16 and 64, every query cell and every (scanned radius, next radius) pair a radius policy can produce, ring_rows reports
+    exactly the cells of the clipped Chebyshev square that the earlier rounds have not scanned, each once; the cell coordinate is
+    monotone and clamps below / above / NaN to 0 / SIDE - 1 / 0, the box maximum on the wider axis lies in the last cell;
+    choose_axes reproduces the tie table, gives h = 0 on degenerate boxes and the numpy model's (A, B, h) bit for bit on the
+    seven geometries of tests/test_neighbourhood_model_cpu.py; the workspace layouts are aligned and disjoint."""
+    import shutil
+    cxx = next((c for c in (os.environ.get("CXX"), "c++", "g++", "clang++") if c and shutil.which(c)), None)
+    assert cxx, "no host C++ compiler on PATH"
+    exe = str(tmp_path / "cell_grid_check")
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           "-ffp-contract=off", os.path.join(REPO, "tests", "cell_grid_check.cpp"), "-o", exe]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout + out.stderr
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "cell grid ok" in out.stdout, out.stdout + out.stderr
+
+
 def test_compat_shims_register_the_cuda_wheel_module_paths():
     code = ("import sys; sys.path.insert(0, %r); import cmdiad_amd.compat as c; c.install();"
             "from pointnet2_ops import pointnet2_utils; from knn_cuda import KNN;"
