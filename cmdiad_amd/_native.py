@@ -145,6 +145,7 @@ SIGNATURES = {
     "cmdiad_auc_counts": [P, I, P, I, P, P],
     "cmdiad_pro_hist": [P, I, P, P, I, I, P, P],
     "cmdiad_tiff_unpack": [P, c_int64, P, I, I, I, I, I, I, I, I, I, I, I, P, P],
+    "cmdiad_png_unfilter": [P, c_int64, P, I, I, I, I, I, I, P, P],
 }
 SIZE_QUERIES = {
     "cmdiad_gemm_streamk_workspace_bytes": [],

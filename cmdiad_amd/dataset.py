@@ -40,6 +40,8 @@ import torch
 from torch.utils.data import Dataset
 
 from .utils.batching import in_batches, read_ahead, scatter_by_shape
+from .utils import png
+from .utils.png import RawImage
 from .utils.tiff import RawCloud
 
 
@@ -505,12 +507,24 @@ def _is_raw(cloud):
     return isinstance(cloud, RawCloud)
 
 
+def _is_raw_image(img):
+    """A utils.png.RawImage (the filtered scanlines of a PNG, CMDIAD_PNG_DEVICE=1) in the place of a decoded rgb or gt array."""
+    return isinstance(img, RawImage)
+
+
+def _shape(a):
+    """The shape of a decoded array, or of the array a RawCloud / RawImage stands for."""
+    import numpy as np
+    return tuple(a.shape) if _is_raw(a) or _is_raw_image(a) else np.shape(a)
+
+
 class SamplePrep:
     """Decoded arrays -> the tensors of the reference's ``__getitem__`` on the device (csrc/sample_prep.hip; docs/sample_prep.md).
 
     ``prepare(rgb_u8 [H,W,3], pc [H,W,3] float32 or float64, gt_u8 [H,W] | None)`` -> ``(DeviceSample(img [3,S,S], cloud [3,xs,xs], depth [3,224,224]),
     gt [1,g,g] | None)``; ``prepare_batch`` takes lists and returns a list of such pairs.  A cloud may also be a utils.tiff.RawCloud -- the
-    undecoded bytes of its tiff (CMDIAD_TIFF_DEVICE=1) -- which is unpacked on the device and gives the same tensors.  Samples of equal shapes share their launches;
+    undecoded bytes of its tiff (CMDIAD_TIFF_DEVICE=1) -- which is unpacked on the device and gives the same tensors; an rgb or a gt may be a
+    utils.png.RawImage -- the filtered scanlines of its PNG (CMDIAD_PNG_DEVICE=1) -- whose filters are undone on the device.  Samples of equal shapes share their launches;
     every sample's bytes are the ones a call of its own gives (the arithmetic is per pixel and integer).  Clouds are grouped by dtype
     as well: a float64 cloud (an Eyecandies tiff of the reference's script) is converted to float32 at the gather, as ``.float()``.  Inputs go up through
     pinned memory on the shared copy stream; the kernels run on the current stream.  Tables are computed once per (n_in, n_out)
@@ -558,6 +572,29 @@ class SamplePrep:
         dev.record_stream(cur)
         return dev
 
+    def _merged(self, n, parts, dtype):
+        """parts = ((rows, tensor [len(rows), ...]), ...) covering 0..n-1 -> one tensor [n, ...] with every part at its rows."""
+        out = torch.empty((n, *parts[0][1].shape[1:]), dtype=dtype, device=self.device)
+        for rows, part in parts:      # (a pinned index: the copy of a pageable one would synchronise)
+            out.index_copy_(0, torch.tensor(rows, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True), part)
+        return out
+
+    def _upload_images(self, images, what):
+        """list of equal-shaped uint8 images, decoded arrays or utils.png.RawImage -> one device tensor [n, ...]: the arrays through
+        `_upload`, the raw files through png.decode_on_device (their scanlines go up filtered and cmdiad_png_unfilter undoes them)."""
+        raw = [k for k, a in enumerate(images) if _is_raw_image(a)]
+        if not raw:
+            return self._upload(images, torch.uint8, what)
+        dev = png.decode_on_device([images[k] for k in raw], self.device)
+        if len(raw) == len(images):
+            return dev
+        is_raw = set(raw)
+        host = [k for k in range(len(images)) if k not in is_raw]
+        up = self._upload([images[k] for k in host], torch.uint8, what)
+        if up.shape[1:] != dev.shape[1:]:
+            raise TypeError(f"SamplePrep: {what} must be arrays of one shape per group, got {tuple(up.shape[1:])} beside {tuple(dev.shape[1:])}")
+        return self._merged(len(images), ((raw, dev), (host, up)), torch.uint8)
+
     def _upload_clouds(self, clouds, dtype):
         """list of equal-shaped clouds, decoded arrays or utils.tiff.RawCloud -> one device tensor [n,H,W,3] of dtype: the arrays through
         `_upload`, the raw files through tiff.unpack_on_device (their bytes go up as they are and are unpacked by cmdiad_tiff_unpack)."""
@@ -574,10 +611,7 @@ class SamplePrep:
         is_raw = set(raw)
         host = [k for k in range(len(clouds)) if k not in is_raw]
         up = self._upload([clouds[k] for k in host], dtype, "the point cloud")
-        out = torch.empty((len(clouds), *dev.shape[1:]), dtype=dtype, device=self.device)
-        for rows, part in ((raw, dev), (host, up)):      # (a pinned index: the copy of a pageable one would synchronise)
-            out.index_copy_(0, torch.tensor(rows, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True), part)
-        return out
+        return self._merged(len(clouds), ((raw, dev), (host, up)), dtype)
 
     def prepare(self, rgb_u8, pc_f32, gt_u8=None):
         return self.prepare_batch([rgb_u8], [pc_f32], [gt_u8])[0]
@@ -590,10 +624,9 @@ class SamplePrep:
         if not (len(pcs) == len(gts) == n):
             raise ValueError("SamplePrep.prepare_batch: the lists differ in length")
         for r, p, g in zip(rgbs, pcs, gts):
-            ps = p.shape if _is_raw(p) else np.shape(p)
-            if np.ndim(r) != 3 or np.shape(r)[2] != 3 or len(ps) != 3 or ps[2] != 3 or (g is not None and np.ndim(g) != 2):
-                raise ValueError(f"SamplePrep: rgb [H,W,3], cloud [H,W,3], gt [H,W] expected, got {np.shape(r)}, {tuple(ps)}, "
-                                 f"{None if g is None else np.shape(g)}")
+            rs, ps, gs = _shape(r), _shape(p), (None if g is None else _shape(g))
+            if len(rs) != 3 or rs[2] != 3 or len(ps) != 3 or ps[2] != 3 or (gs is not None and len(gs) != 2):
+                raise ValueError(f"SamplePrep: rgb [H,W,3], cloud [H,W,3], gt [H,W] expected, got {rs}, {tuple(ps)}, {gs}")
 
         def clouds_of(key, idx):
             dtype = key[1]
@@ -608,10 +641,11 @@ class SamplePrep:
         return [(DeviceSample((imgs[i], *clouds[i][:2]), clouds[i][2]), masks[i]) for i in range(n)]
 
     def prepare_images(self, rgbs):
-        """list of uint8 [H,W,3] arrays -> list of float32 [3,S,S] device tensors (resize + ToTensor + Normalize)."""
+        """list of uint8 [H,W,3] arrays (or utils.png.RawImage of target 'rgb') -> list of float32 [3,S,S] device tensors (resize +
+        ToTensor + Normalize)."""
         with torch.cuda.device(self.device):
             return scatter_by_shape(rgbs, range(len(rgbs)),
-                                    lambda _, idx: self.prepare_device_images(self._upload([rgbs[i] for i in idx], torch.uint8, "rgb")))
+                                    lambda _, idx: self.prepare_device_images(self._upload_images([rgbs[i] for i in idx], "rgb")))
 
     def prepare_device_images(self, src):
         """src [B,H,W,3] uint8 ON THE DEVICE -> float32 [B,3,S,S] on the current stream (resize + ToTensor + Normalize)."""
@@ -641,10 +675,10 @@ class SamplePrep:
         return [(cloud[j], depth[j], _Count(count, host, event, j)) for j in range(B)]
 
     def prepare_masks(self, gts):
-        """list of uint8 [H,W] arrays or None -> list of float32 [1,g,g] device tensors or None."""
+        """list of uint8 [H,W] arrays (or utils.png.RawImage of target 'l') or None -> list of float32 [1,g,g] device tensors or None."""
         with torch.cuda.device(self.device):
             return scatter_by_shape(gts, [i for i in range(len(gts)) if gts[i] is not None],
-                                    lambda _, idx: self.prepare_device_masks(self._upload([gts[i] for i in idx], torch.uint8, "gt")))
+                                    lambda _, idx: self.prepare_device_masks(self._upload_images([gts[i] for i in idx], "gt")))
 
     def prepare_device_masks(self, src):
         """src [B,H,W] uint8 ON THE DEVICE -> float32 [B,1,g,g] in {0, 1} on the current stream (Pillow's NEAREST resize, ToTensor, > 0.5)."""
@@ -680,6 +714,15 @@ def _read_rgb(path):
     return Image.open(path).convert('RGB')
 
 
+def _raw_png(path, target, color_types=(0, 2, 4, 6)):
+    """Under CMDIAD_PNG_DEVICE=1 (read here, per file, on a 'hip' reader thread): the utils.png.RawImage of a PNG the device decodes
+    -- its scanlines inflated here, their filters undone on the device with the batch (docs/png.md) -- else None: the caller decodes
+    the file with Pillow as before (switch off, or a file outside the subset: palette, 16-bit, interlaced, ...)."""
+    if not png.device_decode_enabled():
+        return None
+    return png.read_for_device(path, target, color_types)
+
+
 def _read_cloud(path, raw_ok=False):
     """The cloud of an xyz tiff: the decoded array, or -- raw_ok (a 'hip' reader thread) under CMDIAD_TIFF_DEVICE=1 -- the file's bytes
     as a utils.tiff.RawCloud, unpacked on the device with its batch (docs/tiff.md)."""
@@ -711,16 +754,25 @@ class BaseAnomalyDetectionDataset(_LazySamplePrep, Dataset):
         return len(self.img_paths)
 
     def decoded(self, idx):
-        """(rgb uint8 [H,W,3], cloud [H,W,3], gt uint8 [H,W] or None) of item idx: the decoded files, nothing else."""
+        """(rgb uint8 [H,W,3], cloud [H,W,3], gt uint8 [H,W] or None) of item idx: the decoded files, nothing else.  Under 'hip' the
+        cloud may be a RawCloud (CMDIAD_TIFF_DEVICE=1), the rgb and the gt a RawImage (CMDIAD_PNG_DEVICE=1)."""
         import numpy as np
         rgb_path, tiff_path = self.img_paths[idx]
+        hip = self.img_process_method == 'hip'
         gt = getattr(self, "gt_paths", None)
         gt = gt[idx] if gt is not None else 0
         if gt != 0:
-            from PIL import Image
-            gt = np.array(Image.open(gt).convert('L'), dtype=np.uint8)
-        cloud = _read_cloud(tiff_path, raw_ok=self.img_process_method == 'hip')
-        return np.array(_read_rgb(rgb_path), dtype=np.uint8), cloud, (None if isinstance(gt, int) else gt)
+            gt_path, gt = gt, None
+            if hip:
+                gt = _raw_png(gt_path, 'l')
+            if gt is None:
+                from PIL import Image
+                gt = np.array(Image.open(gt_path).convert('L'), dtype=np.uint8)
+        cloud = _read_cloud(tiff_path, raw_ok=hip)
+        rgb = _raw_png(rgb_path, 'rgb') if hip else None
+        if rgb is None:
+            rgb = np.array(_read_rgb(rgb_path), dtype=np.uint8)
+        return rgb, cloud, (None if isinstance(gt, int) else gt)
 
     def _sample(self, idx):
         rgb_path, tiff_path = self.img_paths[idx]
@@ -970,9 +1022,14 @@ class EyecandiesRawClass(_RawClassSource):
         from .utils import preprocessing_eyecandies as pe
         gt = None
         if label:
-            from PIL import Image
-            gt = np.array(Image.open(files["mask"]).convert('RGB').convert('L'), dtype=np.uint8)
-        return np.array(_read_rgb(files["rgb"]), dtype=np.uint8), pe.read_scan(files["depth"], files["info"], files["pose"]), gt
+            gt = _raw_png(files["mask"], 'l')        # (.convert('RGB').convert('L') equals .convert('L') for the types the device decodes)
+            if gt is None:
+                from PIL import Image
+                gt = np.array(Image.open(files["mask"]).convert('RGB').convert('L'), dtype=np.uint8)
+        rgb = _raw_png(files["rgb"], 'rgb')
+        if rgb is None:
+            rgb = np.array(_read_rgb(files["rgb"]), dtype=np.uint8)
+        return rgb, pe.read_scan(files["depth"], files["info"], files["pose"]), gt
 
     def _prepare(self, dec):
         """decoded samples -> [(DeviceSample, mask or None)]: per shape one upload of the codes and one kernel chain."""
@@ -1028,8 +1085,12 @@ class MVTec3DRawClass(_RawClassSource):
         rgb_path, tiff_path = paths
         pc = _read_cloud(tiff_path, raw_ok=True)
         pc = pc if _is_raw(pc) else np.asarray(pc)     # (a RawCloud carries the layout's dtype and shape: the checks below read those)
-        rgb = np.array(Image.open(rgb_path))
-        gt = np.array(Image.open(gt_path)) if gt_path is not None else None
+        rgb = _raw_png(rgb_path, 'raw', color_types=(2,))       # (any other file: Pillow, and the checks below)
+        if rgb is None:
+            rgb = np.array(Image.open(rgb_path))
+        gt = _raw_png(gt_path, 'raw', color_types=(0,)) if gt_path is not None else None
+        if gt is None and gt_path is not None:
+            gt = np.array(Image.open(gt_path))
         if pc.dtype != np.float32 or pc.ndim != 3 or pc.shape[2] != 3:
             raise TypeError(f"MVTec3DRawClass: {tiff_path}: the point cloud must be a float32 [H,W,3] array, got {pc.dtype} {pc.shape}")
         if rgb.dtype != np.uint8 or rgb.shape != tuple(pc.shape):
@@ -1045,9 +1106,9 @@ class MVTec3DRawClass(_RawClassSource):
 
         def scans_of(_, idx):
             pcs = prep._upload_clouds([dec[i][0] for i in idx], torch.float32)
-            rgbs = prep._upload([dec[i][1] for i in idx], torch.uint8, "rgb")
+            rgbs = prep._upload_images([dec[i][1] for i in idx], "rgb")
             with_gt = [i for i in idx if dec[i][2] is not None]
-            gts = prep._upload([dec[i][2] for i in with_gt], torch.uint8, "gt") if with_gt else None
+            gts = prep._upload_images([dec[i][2] for i in with_gt], "gt") if with_gt else None
             gt_row = {i: k for k, i in enumerate(with_gt)}
             out = []
             for j, i in enumerate(idx):

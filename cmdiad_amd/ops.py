@@ -1243,6 +1243,61 @@ def tiff_unpack(raw_u8, layouts, chunk_table, table_dev=None, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------ PNGs (docs/png.md)
+PNG_TARGETS = ("rgb", "l", "raw")     # the index is cmdiad_png_unfilter's target code
+
+
+def png_unfilter(raw_u8, layouts, offsets, target, out=None, offsets_dev=None, waves=0):
+    """raw_u8 [n] uint8 on the device (inflated, still filtered scanlines), layouts = the utils.png.PngLayout of every image (equal
+    width, height and bytes per pixel; 8-bit, colour type 0 / 2 / 4 / 6), offsets [B] int64 ON THE HOST = where every image's
+    scanlines start in raw_u8, target 'rgb' | 'l' | 'raw' -> uint8 [B,H,W,3] | [B,H,W] | [B,H,W,C] ([B,H,W] for one channel), bit
+    for bit what Pillow decodes and converts.  Every image's [offset, offset + H * (1 + row_bytes)) is checked here against the
+    buffer: a bad one is a ValueError and nothing is launched.  offsets_dev: the same table already on the device (else it is
+    uploaded here); out: the result tensor to fill; waves: 0 = chosen from the width, 1 = the one-wave baseline (tools/bench_png.py)."""
+    import numpy as np
+    _chk(raw_u8, torch.uint8, "png_unfilter.raw_u8")
+    layouts = list(layouts)
+    if not layouts:
+        raise ValueError("png_unfilter: no layouts")
+    if target not in PNG_TARGETS:
+        raise ValueError(f"png_unfilter: target must be one of {PNG_TARGETS}, got {target!r}")
+    lay = layouts[0]
+    B = len(layouts)
+    if any(l.geometry() != lay.geometry() for l in layouts):
+        raise ValueError("png_unfilter: the layouts of one call must share width, height and bytes per pixel")
+    if lay.bit_depth != 8 or lay.color_type not in (0, 2, 4, 6) or lay.interlace or lay.row_bytes != lay.width * lay.bpp:
+        raise ValueError(f"png_unfilter: 8-bit non-interlaced files of colour type 0 / 2 / 4 / 6 only, got bit depth {lay.bit_depth}, "
+                         f"colour type {lay.color_type}, interlace {lay.interlace}")
+    table = np.ascontiguousarray(offsets.numpy() if isinstance(offsets, torch.Tensor) else offsets, dtype=np.int64)
+    if table.shape != (B,):
+        raise ValueError(f"png_unfilter: offsets must be [{B}], got {table.shape}")
+    raw_bytes = raw_u8.numel()
+    if raw_u8.dim() != 1 or raw_bytes == 0:
+        raise ValueError(f"png_unfilter: raw_u8 must be a non-empty 1-D buffer, got {tuple(raw_u8.shape)}")
+    need = lay.height * (1 + lay.row_bytes)
+    bad = np.flatnonzero((table < 0) | (table + need > raw_bytes))
+    if len(bad):
+        b = int(bad[0])
+        raise ValueError(f"png_unfilter: image {b} at offset {int(table[b])} with {need} bytes of scanlines does not lie inside the "
+                         f"{raw_bytes} bytes of raw_u8")
+    H, W, C = lay.height, lay.width, lay.channels
+    shape = (B, H, W, 3) if target == "rgb" else (B, H, W) if target == "l" or C == 1 else (B, H, W, C)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=raw_u8.device)
+    else:
+        _chk(out, torch.uint8, "png_unfilter.out")
+        if tuple(out.shape) != shape:
+            raise ValueError(f"png_unfilter: out must be {shape}, got {tuple(out.shape)}")
+    if offsets_dev is None:
+        offsets_dev = torch.from_numpy(table).to(raw_u8.device)
+    _chk(offsets_dev, torch.int64, "png_unfilter.offsets_dev")
+    if tuple(offsets_dev.shape) != (B,):
+        raise ValueError(f"png_unfilter: offsets_dev must be [{B}], got {tuple(offsets_dev.shape)}")
+    _call("cmdiad_png_unfilter", _p(raw_u8), raw_bytes, _p(offsets_dev), B, W, H, lay.bpp, PNG_TARGETS.index(target), int(waves), _p(out),
+          _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------ Eyecandies (docs/eyecandies.md)
 EYECANDIES_PARAM_BYTES = 136     # cmdiad_eyecandies_params: float32 range, float32 mind, float64 inv(P)[16]
 

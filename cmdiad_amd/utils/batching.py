@@ -42,11 +42,12 @@ def in_batches(items, batch):
 def group_by_shape(arrays, indices, with_dtype=False):
     """{(H, W) or ((H, W), dtype name): [indices]} in order of first appearance: the members of a group share an upload and a launch."""
     import numpy as np
+    from .png import RawImage
     from .tiff import RawCloud
     groups = {}
     for i in indices:
         a = arrays[i]
-        a = a if isinstance(a, RawCloud) else np.asarray(a)      # (a RawCloud stands for the array its file holds)
+        a = a if isinstance(a, (RawCloud, RawImage)) else np.asarray(a)      # (a RawCloud / RawImage stands for the array its file holds)
         key = tuple(a.shape[:2])
         groups.setdefault((key, str(a.dtype)) if with_dtype else key, []).append(i)
     return groups

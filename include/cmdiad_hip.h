@@ -811,6 +811,18 @@ int cmdiad_tiff_unpack(const uint8_t* raw, int64_t raw_bytes, const int64_t* chu
                        int chunk_w, int chunk_h, int planar, int bytes_per_sample, int big_endian, int predictor, void* out,
                        cmdiad_stream_t stream);
 
+/* ---- the datasets' PNGs (docs/png.md; the reference decodes them with Pillow on the host, dataset.py:103, 225, 239) ----
+ * raw [raw_bytes] holds, at offsets[b] (device, [B]) for every image b, its INFLATED and still FILTERED scanlines: H rows of
+ * 1 + W * bpp bytes, the filter type (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth; anything above acts as None) in front of each row;
+ * bpp = bytes per pixel = channels of an 8-bit file (1 grey, 2 grey + alpha, 3 rgb, 4 rgb + alpha).  The filters are undone and the
+ * pixels stored converted -> out uint8: target 0 'rgb' [B,H,W,3] (alpha dropped, grey replicated), 1 'l' [B,H,W] (the grey byte, or
+ * (R * 19595 + G * 38470 + B * 7471 + 0x8000) >> 16), 2 'raw' [B,H,W,bpp] (the file's own channels).  One workgroup per image;
+ * waves = 0 lets the width choose its waves (8 up to 897 pixels, 16 up to 1857, else 1), 1 | 8 | 16 force them (8 and 16 within
+ * those widths only).  Offsets need no alignment.  Any source byte outside [0, raw_bytes) reads as 0: no offset makes the kernel
+ * read outside raw.  No allocation, no synchronisation, no scratch.  B in 1..65535, sides in 1..16384 (a row is at most 64 KiB). */
+int cmdiad_png_unfilter(const uint8_t* raw, int64_t raw_bytes, const int64_t* offsets, int B, int W, int H, int bpp, int target,
+                        int waves, uint8_t* out, cmdiad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

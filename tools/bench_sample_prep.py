@@ -3,7 +3,7 @@
 'cpu_v1' composition (PIL + torch, one sample at a time, as the reference's dataset.py) on the SAME decoded arrays, and end to end
 from files this tool writes itself.
 
-  python tools/bench_sample_prep.py [--batch 32] [--size 800] [--iters 20] [--files 64] [--drains 1] [--tiff-device]
+  python tools/bench_sample_prep.py [--batch 32] [--size 800] [--iters 20] [--files 64] [--drains 1] [--tiff-device] [--png-device]
                                     [--out profiles/sample_prep.json]
 
   arrays      batch x (size x size x 3 uint8 + size x size x 3 float32), already decoded and in host memory.
@@ -14,7 +14,9 @@ from files this tool writes itself.
               host datasets in line ('cpu_v1').  Bounded by the host's PNG / tiff decode, not by the kernels.  The clouds are real
               TIFFs: written by `tifffile` when it is installed, else by cmdiad_amd.utils.tiff.  --tiff-device sets
               CMDIAD_TIFF_DEVICE=1 for the 'hip' loaders (the reader threads hand the files' bytes on, cmdiad_tiff_unpack
-              unpacks them; docs/tiff.md); --drains N times N drains per reader count and reports every one.
+              unpacks them; docs/tiff.md); --png-device sets CMDIAD_PNG_DEVICE=1 (the reader threads inflate the PNGs,
+              cmdiad_png_unfilter undoes their row filters; docs/png.md); --drains N times N drains per reader count and reports
+              every one.
 There is no pass / fail threshold: the figures go into profiles/sample_prep.md.  Needs a GPU (no fallback)."""
 import argparse
 import json
@@ -60,6 +62,7 @@ def main():
     ap.add_argument("--files", type=int, default=64, help="samples of the end-to-end tree")
     ap.add_argument("--drains", type=int, default=1, help="timed drains of the end-to-end loader per reader count")
     ap.add_argument("--tiff-device", action="store_true", help="CMDIAD_TIFF_DEVICE=1 for the end-to-end 'hip' loaders")
+    ap.add_argument("--png-device", action="store_true", help="CMDIAD_PNG_DEVICE=1 for the end-to-end 'hip' loaders")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -127,8 +130,11 @@ def main():
             from cmdiad_amd.utils import tiff as tifffile
         rec["cloud_files"] = "tiff, written by " + tifffile.__name__
         rec["tiff_device"] = bool(args.tiff_device)
+        rec["png_device"] = bool(args.png_device)
         if args.tiff_device:
             os.environ["CMDIAD_TIFF_DEVICE"] = "1"
+        if args.png_device:
+            os.environ["CMDIAD_PNG_DEVICE"] = "1"
         for i in range(args.files):
             pc, rgb = spr.scan(i, S)
             Image.fromarray(rgb).save(os.path.join(base, "rgb", f"{i:03d}.png"))
@@ -146,6 +152,7 @@ def main():
             e2e[f"hip_readers_{readers}"] = sorted(rates)[len(rates) // 2]
             drains[f"hip_readers_{readers}"] = [round(r, 1) for r in rates]
         os.environ.pop("CMDIAD_TIFF_DEVICE", None)
+        os.environ.pop("CMDIAD_PNG_DEVICE", None)
         rec["end_to_end_drains_samples_per_s"] = drains
         host_ds = ds.TrainDataset("bagel", 224, 224, 224, root, "cpu_v1")
         t = time.perf_counter()
