@@ -81,6 +81,7 @@ SIGNATURES = {
     "cmdiad_colsum_bf16": [P, I, I, I, P, P],
     "cmdiad_ln_param_grad": [P, P, P, P, I, I, I, P, P, P],
     "cmdiad_adam_step": [P, P, P, P, SZ, F, F, F, F, I, F, P, P],
+    "cmdiad_adam_flat": [P, P, P, P, SZ, F, F, F, F, I, F, P, P],
     "cmdiad_encoder_stage1": [P, P, P, P, I, I, P, P, P, P],
     "cmdiad_gemm_groupmax": [P, P, P, I, I, I, I, P, P, P],
     "cmdiad_l2_min_keys": [P, P, P, P, I, I, I, U32, P, P, I, P],

@@ -163,24 +163,74 @@ __global__ __launch_bounds__(256) void ln_param_grad_kernel(const float* __restr
     }
 }
 
-// torch.optim.Adam (no weight decay, amsgrad off): one thread per element.
+// torch.optim.Adam (no weight decay, amsgrad off) on one element: the arithmetic of both kernels below.  -> the new p; m and v
+// are updated in place.  The flat-arena launch must give the bits of the per-parameter launches, so which products are fused
+// into an FMA is written out here rather than left to the compiler, which contracts b1 * m + (1 - b1) * g on the OTHER product
+// once the loop body is vectorised (tests/test_gpu_dp_train.py holds the two kernels to equal bits).
+__device__ __forceinline__ float adam_update(float p, float g, float& m, float& v, float lr, float b1, float b2, float eps,
+                                             float bc1, float bc2_sqrt, float gscale)
+{
+#pragma clang fp contract(off)
+    const float gi = g * gscale;
+    const float mi = __fmaf_rn(b1, m, (1.0f - b1) * gi);
+    const float vi = __fmaf_rn(b2, v, (1.0f - b2) * gi * gi);
+    m = mi; v = vi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    return __fmaf_rn(-(lr / bc1), mi / denom, p);
+}
+
+// One thread per element.
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, size_t n, float lr, float b1, float b2, float eps,
                                                    float bc1, float bc2_sqrt, float gscale, bf16_t* __restrict__ p_bf16)
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float gi = g[i] * gscale;
-    const float mi = b1 * m[i] + (1.0f - b1) * gi;
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+    float mi = m[i], vi = v[i];
+    const float pi = adam_update(p[i], g[i], mi, vi, lr, b1, b2, eps, bc1, bc2_sqrt, gscale);
     m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    const float pi = p[i] - (lr / bc1) * (mi / denom);
     p[i] = pi;
     if (p_bf16) p_bf16[i] = f2bf(pi);
 }
 
+// The same update over a flat arena of n4 float4 (every parameter of a module, each padded to a multiple of 4 floats) in ONE launch:
+// 16-byte loads and stores, a grid-stride loop over a grid sized by the device, not by n.  A padding lane has g = m = v = 0 and
+// stays where it is (0 - (lr / bc1) * (0 / eps) = 0).
+__global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, size_t n4, float lr, float b1, float b2, float eps,
+                                                        float bc1, float bc2_sqrt, float gscale, bf16_t* __restrict__ p_bf16)
+{
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        float4 pp = reinterpret_cast<const float4*>(p)[i];
+        const float4 gg = reinterpret_cast<const float4*>(g)[i];
+        float4 mm = reinterpret_cast<const float4*>(m)[i], vv = reinterpret_cast<const float4*>(v)[i];
+        pp.x = adam_update(pp.x, gg.x, mm.x, vv.x, lr, b1, b2, eps, bc1, bc2_sqrt, gscale);
+        pp.y = adam_update(pp.y, gg.y, mm.y, vv.y, lr, b1, b2, eps, bc1, bc2_sqrt, gscale);
+        pp.z = adam_update(pp.z, gg.z, mm.z, vv.z, lr, b1, b2, eps, bc1, bc2_sqrt, gscale);
+        pp.w = adam_update(pp.w, gg.w, mm.w, vv.w, lr, b1, b2, eps, bc1, bc2_sqrt, gscale);
+        reinterpret_cast<float4*>(m)[i] = mm;
+        reinterpret_cast<float4*>(v)[i] = vv;
+        reinterpret_cast<float4*>(p)[i] = pp;
+        if (p_bf16) {
+            bf16x4 o;
+            o[0] = f2bf(pp.x); o[1] = f2bf(pp.y); o[2] = f2bf(pp.z); o[3] = f2bf(pp.w);
+            reinterpret_cast<bf16x4*>(p_bf16)[i] = o;
+        }
+    }
+}
+
 unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256); }
+
+// Compute units of the current device (kPersistCUs where the runtime does not say).
+int device_cus()
+{
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+        return kPersistCUs;
+    return cus;
+}
+constexpr int kAdamFlatBlocksPerCU = 8, kAdamFlatMaxBlocks = 2048;
 
 }  // namespace
 
@@ -245,6 +295,26 @@ extern "C" int cmdiad_adam_step(float* p, const float* g, float* m, float* v, si
     const float bc2s = sqrtf(1.0f - powf(beta2, (float)step));
     hipLaunchKernelGGL(adam_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps,
                        bc1, bc2s, grad_scale, (bf16_t*)p_bf16);
+    CMDIAD_CHECK_LAUNCH();
+    return CMDIAD_OK;
+}
+
+extern "C" int cmdiad_adam_flat(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
+                                float eps, int step, float grad_scale, uint16_t* p_bf16, cmdiad_stream_t stream)
+{
+    CMDIAD_REQUIRE(p && g && m && v, CMDIAD_ERR_ARG, "cmdiad_adam_flat: null pointer");
+    CMDIAD_REQUIRE(n % 4 == 0 && step >= 1, CMDIAD_ERR_ARG, "cmdiad_adam_flat: bad args (n %zu must be a multiple of 4, step %d >= 1)", n,
+                   step);
+    CMDIAD_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && ((uintptr_t)p_bf16 & 7) == 0, CMDIAD_ERR_ARG,
+                   "cmdiad_adam_flat: p, g, m and v must be 16-byte aligned (p_bf16: 8)");
+    if (n == 0) return CMDIAD_OK;
+    const float bc1 = 1.0f - powf(beta1, (float)step);
+    const float bc2s = sqrtf(1.0f - powf(beta2, (float)step));
+    const size_t n4 = n / 4, want = (n4 + 255) / 256;
+    size_t cap = (size_t)device_cus() * kAdamFlatBlocksPerCU;
+    if (cap > kAdamFlatMaxBlocks) cap = kAdamFlatMaxBlocks;
+    hipLaunchKernelGGL(adam_flat_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, lr,
+                       beta1, beta2, eps, bc1, bc2s, grad_scale, (bf16_t*)p_bf16);
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
 }

@@ -158,8 +158,10 @@ class PairRing:
     ONCE (the first epoch, `readers` host threads), kept in two device-resident caches, and every later batch is an on-device
     gather -- no DataLoader workers, no per-step H2D.  Works on the host too (device='cpu': tests)."""
 
-    def __init__(self, dataset, batch_size, shuffle=True, drop_last=True, device="cuda", readers=4):
+    def __init__(self, dataset, batch_size, shuffle=True, drop_last=True, device="cuda", readers=4, rank=0, world=1):
+        _check_shard(drop_last, rank, world)
         self.ds, self.batch_size, self.shuffle, self.drop_last = dataset, batch_size, shuffle, drop_last
+        self.rank, self.world = rank, world          # data-parallel: this rank's part of every global batch (epoch_batches)
         self.device, self.readers = torch.device(device), readers
         a, b = (torch.load(p, map_location="cpu") for p in dataset.pair_paths(0))
         n = len(dataset)
@@ -167,10 +169,10 @@ class PairRing:
         self._have = torch.zeros(n, dtype=torch.bool)
 
     def __len__(self):
-        return epoch_length(len(self.ds), self.batch_size, self.drop_last)
+        return epoch_length(len(self.ds), self.world * self.batch_size, self.drop_last)
 
     def batches(self):
-        return epoch_batches(len(self.ds), self.batch_size, self.shuffle, self.drop_last)
+        return epoch_batches(len(self.ds), self.batch_size, self.shuffle, self.drop_last, self.rank, self.world)
 
     def _fill(self, idxs):
         todo = [i for i in idxs if not bool(self._have[i])]
@@ -216,11 +218,24 @@ def epoch_length(n, batch_size, drop_last):
     return n // batch_size if drop_last else (n + batch_size - 1) // batch_size
 
 
-def epoch_batches(n, batch_size, shuffle, drop_last):
+def _check_shard(drop_last, rank, world):
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError(f"rank {rank} of world {world}")
+    if world > 1 and not drop_last:
+        raise ValueError("world > 1 requires drop_last=True: a short last global batch cannot be dealt to the ranks in equal parts")
+
+
+def epoch_batches(n, batch_size, shuffle, drop_last, rank=0, world=1):
     """One epoch's batches as lists of sample indices: `epoch_permutation` (one call: it consumes the global RNG as the reference's
-    DataLoader does) cut into batch_size pieces, a short last one dropped with drop_last."""
+    DataLoader does) cut into batch_size pieces, a short last one dropped with drop_last.
+    world > 1 (data-parallel training, cmdiad_amd/dp_train.py): the same permutation, from the same global-RNG consumption, is cut
+    into GLOBAL batches of world * batch_size and rank r gets items [r * batch_size, (r + 1) * batch_size) of each: the ranks
+    together see what one process at batch world * batch_size sees, in the same order.  Every rank must be seeded alike (the
+    reference's set_seeds(args.seed)); drop_last=True is required."""
+    _check_shard(drop_last, rank, world)
     order = epoch_permutation(n, shuffle)
-    return [order[i:i + batch_size] for i in range(0, n, batch_size)][:epoch_length(n, batch_size, drop_last)]
+    G = world * batch_size
+    return [order[i + rank * batch_size:min(i + G, i + (rank + 1) * batch_size)] for i in range(0, n, G)][:epoch_length(n, G, drop_last)]
 
 
 class FeatureRing:
@@ -231,8 +246,10 @@ class FeatureRing:
     readers = host threads decoding files (torch.load releases the GIL while reading)."""
 
     def __init__(self, root_path, batch_size, shuffle=True, drop_last=True, device="cuda", depth=3, readers=4,
-                 resident=True, resident_limit_bytes=200 << 30):
+                 resident=True, resident_limit_bytes=200 << 30, rank=0, world=1):
         assert depth >= 2
+        _check_shard(drop_last, rank, world)
+        self.rank, self.world = rank, world          # data-parallel: this rank's part of every global batch (epoch_batches)
         self.root = root_path
         self.files = os.listdir(root_path)
         self.batch_size, self.shuffle, self.drop_last = batch_size, shuffle, drop_last
@@ -250,11 +267,11 @@ class FeatureRing:
             self._cache = torch.empty((len(self.files), *self.sample_shape), dtype=self.dtype, device=self.device)
 
     def __len__(self):
-        return epoch_length(len(self.files), self.batch_size, self.drop_last)
+        return epoch_length(len(self.files), self.world * self.batch_size, self.drop_last)
 
     def batches(self):
         """The epoch's batches as lists of file indices (consumes the global RNG like the reference's DataLoader)."""
-        return epoch_batches(len(self.files), self.batch_size, self.shuffle, self.drop_last)
+        return epoch_batches(len(self.files), self.batch_size, self.shuffle, self.drop_last, self.rank, self.world)
 
     def __iter__(self):
         plan = self.batches()

@@ -551,6 +551,18 @@ def adam_step(p, grad, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0, p_bf16
           _p(p_bf16), _stream())
 
 
+def adam_flat(p, grad, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0, p_bf16=None):
+    """adam_step over a flat arena in ONE launch: p, grad, m, v f32 of the same size, a multiple of 4 elements, 16-byte aligned
+    (dp_train.ParamArena's buffers).  Bit-identical to adam_step per parameter on equal inputs (cmdiad_adam_flat)."""
+    for t, n in ((p, "p"), (grad, "grad"), (m, "m"), (v, "v")):
+        _chk(t, torch.float32, "adam_flat." + n)
+    _chk(p_bf16, torch.bfloat16, "adam_flat.p_bf16")
+    if not grad.numel() == m.numel() == v.numel() == p.numel() or (p_bf16 is not None and p_bf16.numel() != p.numel()):
+        raise ValueError("adam_flat: p, grad, m, v (and p_bf16) must have the same number of elements")
+    _call("cmdiad_adam_flat", _p(p), _p(grad), _p(m), _p(v), p.numel(), float(lr), beta1, beta2, eps, int(step), float(grad_scale),
+          _p(p_bf16), _stream())
+
+
 def relu_bwd(dx, y, want_bf16=True, want_f32=False):
     """dx f32, y bf16 (the ReLU output), same shape -> dx where y > 0 else 0, as bf16 (and / or f32) (cmdiad_relu_bwd_bf16)."""
     _chk(dx, torch.float32, "relu_bwd.dx"); _chk(y, torch.bfloat16, "relu_bwd.y")

@@ -634,6 +634,13 @@ int cmdiad_ln_param_grad(const float* dh, const float* x, const float* mean, con
  * optionally refreshes the bf16 GEMM operand copy of the parameter. */
 int cmdiad_adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
                      float eps, int step, float grad_scale, uint16_t* p_bf16, cmdiad_stream_t stream);
+/* The same update over a FLAT ARENA in one launch (additive, the ABI stays 6): p, g, m, v hold every parameter of a module one after
+ * the other, each padded to a multiple of 4 floats (cmdiad_amd/dp_train.py: ParamArena), n % 4 == 0, all four 16-byte aligned
+ * (p_bf16, optional: 8).  Element for element the arithmetic of cmdiad_adam_step: given equal inputs the results are bit-identical
+ * to per-parameter calls.  A padding lane (g = m = v = 0) is left unchanged.  The grid is sized from the device's compute-unit
+ * count (capped), not from n.  Null pointers, n % 4 != 0 and step < 1 are rejected before any launch. */
+int cmdiad_adam_flat(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
+                     float eps, int step, float grad_scale, uint16_t* p_bf16, cmdiad_stream_t stream);
 
 /* Generic fp32 -> bf16 cast (n % 4 == 0) and bf16 2-D transpose out[c][r] = in[r][c]. */
 int cmdiad_cast_bf16(const float* x, size_t n, uint16_t* out, cmdiad_stream_t stream);
