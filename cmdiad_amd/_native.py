@@ -6,7 +6,7 @@ There is NO CPU fallback: if the shared object is missing or a call fails, this 
 import ctypes
 import os
 import subprocess
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("CMDIAD_HIP_LIB") or os.path.join(_HERE, "libcmdiad_hip.so")  # override: A/B runs of two builds
@@ -147,6 +147,7 @@ SIGNATURES = {
     "cmdiad_pro_hist": [P, I, P, P, I, I, P, P],
     "cmdiad_tiff_unpack": [P, c_int64, P, I, I, I, I, I, I, I, I, I, I, I, P, P],
     "cmdiad_png_unfilter": [P, c_int64, P, I, I, I, I, I, I, P, P],
+    "cmdiad_digest64": [P, SZ, c_uint64, P, P],
 }
 SIZE_QUERIES = {
     "cmdiad_gemm_streamk_workspace_bytes": [],

@@ -60,6 +60,25 @@ class Bank:
         self.bf16, self.sqnorm = b16.contiguous(), sq.contiguous()
         self._blk16 = None
 
+    @classmethod
+    def from_file(cls, path, name, rank=0, world=1, replicate_f32=True, verify=True):
+        """The bank of library `name` of a stored fit (cmdiad_amd/fitted.py), bit-identical to Bank(full_rows, rank, world,
+        replicate_f32) -- it IS that constructor, on the rows this rank needs.  replicate_f32=True: the whole library is streamed
+        to the device.  replicate_f32=False: only the rank's shard_range rows are read from disk (a library fitted on one rank
+        layout comes up on any other): the shard is the whole library of a world of one, relabelled with its place.
+        verify: the rows' cmdiad_digest64 on the device against the header (a shard: against its 128-row blocks' digests)."""
+        from . import fitted
+        head = fitted.read_header(path)
+        n = fitted.array_entry(head, name, path)["shape"][0]
+        dev = torch.device("cuda", torch.cuda.current_device())
+        if replicate_f32:
+            return cls(fitted.rows_to_device(path, name, None, dev, verify, head), rank, world, True)
+        lo, hi = shard_range(n, rank, world)
+        bank = cls(fitted.rows_to_device(path, name, (lo, hi), dev, verify, head), 0, 1, False)
+        bank.rank, bank.world, bank.total_rows = rank, world, n
+        bank.row_offset = bank.f32_offset = lo
+        return bank
+
     @property
     def blk16(self):
         """fp32 copy in the MFMA-operand layout of the re-weighting scan (cmdiad_bank_block16), built on first use."""

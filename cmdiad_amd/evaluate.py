@@ -99,7 +99,12 @@ class ClassRun:
     rgb_path) -- the reference's loaders, or synth.SyntheticClass.  ``weights`` (optional): (ViT state_dict, Point-MAE
     state_dict, fusion state_dict | None) loaded into the fresh method object (offline stand-in for the checkpoints).
     ``extractor`` (optional): the frozen backbones (``Features.deep_feature_extractor``) of an earlier class on this rank --
-    every other piece of state (banks, statistics, SVMs, result lists) is the fresh object's."""
+    every other piece of state (banks, statistics, SVMs, result lists) is the fresh object's.
+
+    Stored fits (docs/fitted.md), both read with getattr(args, ..., None) and off when unset: ``args.save_fit_dir`` -- fit_host()
+    ends by writing ``<dir>/<class>.cmdfit``; ``args.load_fit_dir`` -- where that file exists, fit_device() loads it instead of
+    fitting (``data.train()`` is never called, n_train comes from the header) and fit_host() does nothing: the phases are
+    ``["load_fit", "predict", "metrics"]``."""
 
     def __init__(self, args, data, weights=None, method=None, extractor=None):
         from .utils.utils import set_seeds
@@ -117,6 +122,13 @@ class ClassRun:
         self.sec, self.phases = {}, []
         self.multiple = getattr(args, "memory_bank", "multiple") == "multiple"
         self.n_train = self.n_test = 0
+        # stored fits (cmdiad_amd/fitted.py): args.save_fit_dir writes <dir>/<class>.cmdfit after the fit, args.load_fit_dir skips
+        # the fit of a class whose file exists there -- a class loop that was cut short resumes where it stopped
+        self.save_fit_dir, self.load_fit_dir = getattr(args, "save_fit_dir", None), getattr(args, "load_fit_dir", None)
+        self.loaded = False
+
+    def _fit_file(self, directory):
+        return os.path.join(directory, f"{self.data.name}.cmdfit")
 
     def _loop(self, it, call, limit):
         n = flag = 0
@@ -130,6 +142,17 @@ class ClassRun:
 
     def fit_device(self):
         m, data = self.method, self.data
+        if self.load_fit_dir and os.path.exists(self._fit_file(self.load_fit_dir)):
+            t0 = time.perf_counter()
+            self.test_items = list(data.test())             # data.train() is never called
+            self.sec["load"] = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            self.n_train = int(m.load_fit(self._fit_file(self.load_fit_dir)).get("n_train", 0))
+            torch.cuda.synchronize()
+            self.sec["load_fit"] = time.perf_counter() - t0
+            self.phases.append("load_fit")
+            self.loaded = True
+            return self
         # the loaders are drained first (the reference's DataLoader workers prefetch beside the model; a synthetic class generates its
         # samples on this thread): "load" is reported on its own and the phase timings below are the method's
         t0 = time.perf_counter()
@@ -158,15 +181,24 @@ class ClassRun:
         """True when fit_host() touches no GPU state (scikit-learn fits): it may then run on a worker thread."""
         from sklearn.base import BaseEstimator
         m = self.method
+        if self.loaded or self.save_fit_dir:        # nothing to fit / the fit is written from the device afterwards: in line
+            return False
         return self.multiple and all(isinstance(getattr(m, f, None), BaseEstimator) for f in ("detect_fuser", "seg_fuser"))
 
     def fit_host(self):
+        if self.loaded:
+            return self
         if self.multiple:
             t0 = time.perf_counter()
             self.method.run_late_fusion()
             self.sec["late_fusion_fit"] = time.perf_counter() - t0
             self.sec["late_fusion"] = self.sec["late_fusion_bank"] + self.sec["late_fusion_fit"]
             self.phases.append("late_fusion_fit")
+        if self.save_fit_dir:
+            t0 = time.perf_counter()
+            os.makedirs(self.save_fit_dir, exist_ok=True)
+            self.method.save_fit(self._fit_file(self.save_fit_dir))
+            self.sec["save_fit"] = time.perf_counter() - t0
         return self
 
     def predict(self):

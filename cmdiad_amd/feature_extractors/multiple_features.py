@@ -213,7 +213,25 @@ class _MethodBase(Features):
 
     def add_sample_to_mem_bank(self, sample, class_name=None):
         self.class_name = class_name
+        self.__dict__["_fit_samples"] = self.__dict__.get("_fit_samples", 0) + 1     # (recorded in a stored fit's header)
         self._defer("fit", sample)
+
+    # ------------------------------------------------------------------ stored fits (cmdiad_amd/fitted.py, docs/fitted.md)
+    def save_fit(self, path):
+        """Everything predict() reads, in one file: the libraries as this object holds them after run_coreset, the six statistics
+        (cross-wired as stored) and -- memory_bank == 'multiple' -- the two one-class SVMs; with the digests of the
+        backbone and head weights the fit is valid for.  The deferred 'fit' and 'late' micro-batches are run first.
+        RuntimeError naming the phase when run_coreset (or, where needed, run_late_fusion) has not run."""
+        from .. import fitted
+        return fitted.save(self, path)
+
+    def load_fit(self, path, verify=True):
+        """On a freshly built object: afterwards predict() / calculate_metrics() work with no fit call having been made.
+        fitted.FitMismatch naming the first field that differs (the class, a stored args field, the digest of the rgb backbone, the
+        xyz backbone or the head against THIS object's weights on the device); verify: every library's digest is checked on the
+        device against the header (fitted.FitFileError naming the library).  -> the file's header"""
+        from .. import fitted
+        return fitted.load_into(self, path, verify=verify)
 
     def add_sample_to_late_fusion_mem_bank(self, sample):
         self._defer("late", sample)

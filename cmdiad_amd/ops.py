@@ -1493,3 +1493,55 @@ def pro_hist(thr, def_score, def_comp, total_comp):
     if n_def and total_comp:
         _call("cmdiad_pro_hist", _p(thr), T, _p(def_score), _p(def_comp), n_def, total_comp, _p(hist), _stream())
     return hist
+
+
+# ------------------------------------------------------------------------------------ content digest (stored fits)
+def digest64(tensor, seed=0, acc=None):
+    """cmdiad_digest64 of a device tensor's bytes, ADDED into `acc` ([1] int64 on the tensor's device; None: a fresh zero) -> acc.
+    The tensor must be contiguous and a multiple of 4 bytes long (module_digest pads the others); `seed` is taken mod 2^64.
+    Nothing is read back: `digest_value(acc)` is the one device-to-host copy.  (include/cmdiad_hip.h has the definition.)"""
+    if not tensor.is_cuda:
+        raise nat.NativeError("digest64: tensor must live on the GPU (the host restatement is fitted.digest64_host)")
+    if not tensor.is_contiguous():
+        raise ValueError("digest64: tensor must be contiguous")
+    nbytes = tensor.numel() * tensor.element_size()
+    if nbytes % 4:
+        raise ValueError(f"digest64: {nbytes} bytes is not a multiple of 4")
+    if acc is None:
+        acc = torch.zeros((1,), dtype=torch.int64, device=tensor.device)
+    elif not (acc.is_cuda and acc.dtype == torch.int64 and acc.numel() == 1 and acc.device == tensor.device):
+        raise ValueError("digest64: acc must be one int64 on the tensor's device")
+    _call("cmdiad_digest64", _p(tensor), nbytes, int(seed) & 0xFFFFFFFFFFFFFFFF, _p(acc), _stream())
+    return acc
+
+
+def digest_value(acc):
+    """The accumulator of digest64 as a Python int in [0, 2^64) (one device-to-host read)."""
+    return int(acc.item()) & 0xFFFFFFFFFFFFFFFF
+
+
+def tensor_seed(key, tensor):
+    """Seed of a named tensor in module_digest: the first 8 bytes (little-endian) of sha256("<key>|<dtype>|<shape>"), e.g.
+    "blocks.0.attn.qkv.weight|torch.float32|(2304, 768)" -- a renamed, re-typed or re-shaped tensor changes the digest."""
+    import hashlib
+    text = f"{key}|{tensor.dtype}|{tuple(tensor.shape)}"
+    return int.from_bytes(hashlib.sha256(text.encode()).digest()[:8], "little")
+
+
+def module_digest(module, device=None):
+    """Digest of every tensor of `module.state_dict()` (key order), each seeded by tensor_seed, all added into ONE device
+    accumulator: one device-to-host read for the whole module, no copy of the weights.  A tensor whose byte size is no multiple
+    of 4 is hashed from a zero-padded device copy; a tensor that is not on the GPU is copied there first."""
+    sd = module.state_dict()
+    acc = None
+    for key in sorted(sd):
+        t = sd[key].detach()
+        if not t.is_cuda:
+            t = t.to(device or "cuda")
+        raw = t.contiguous().reshape(-1).view(torch.uint8)
+        if raw.numel() % 4:
+            raw = torch.cat([raw, raw.new_zeros(4 - raw.numel() % 4)])
+        if acc is None:
+            acc = torch.zeros((1,), dtype=torch.int64, device=raw.device)
+        digest64(raw, tensor_seed(key, sd[key]), acc)
+    return digest_value(acc) if acc is not None else 0

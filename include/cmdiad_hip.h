@@ -830,6 +830,24 @@ int cmdiad_tiff_unpack(const uint8_t* raw, int64_t raw_bytes, const int64_t* chu
 int cmdiad_png_unfilter(const uint8_t* raw, int64_t raw_bytes, const int64_t* offsets, int B, int W, int H, int bpp, int target,
                         int waves, uint8_t* out, cmdiad_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Content digest (stored fits: cmdiad_amd/fitted.py, docs/fitted.md)
+ * ------------------------------------------------------------------------------------------- */
+
+/* 64-bit digest of a device buffer, ADDED into *acc (one device uint64 that the caller zeroes; several calls may add into the same
+ * one).  With w_i the n = bytes / 4 little-endian 32-bit words of the buffer and h the splitmix64 finaliser
+ *   h(x):  x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;  x *= 0x94D049BB133111EB;  x ^= x >> 31      (mod 2^64)
+ *   digest(buf, seed) = sum_i h( h(seed + i) ^ w_i )   mod 2^64.
+ * The sum is commutative and associative mod 2^64: any reduction order gives the same bits (one 64-bit atomic add per workgroup,
+ * nothing else), and digest(a || b, s) = digest(a, s) + digest(b, s + len(a) / 4), so a buffer can be hashed in pieces.
+ * The digest guards against MISTAKES -- a fit loaded next to another checkpoint, a truncated or damaged file, a wrong row shard --
+ * NOT against adversaries: collisions are easy to construct on purpose.
+ * data needs 4-byte alignment only (16-byte loads with a head and a tail path).  bytes % 4 != 0, a data pointer that is null
+ * (with bytes > 0) or not 4-byte aligned, or a null acc return CMDIAD_ERR_ARG and touch nothing; bytes == 0 is a success that
+ * leaves *acc unchanged.  No workspace, no allocation, no synchronisation.  (New with ABI 6; the version is unchanged, as for
+ * earlier added entry points.) */
+int cmdiad_digest64(const void* data, size_t bytes, uint64_t seed, uint64_t* acc, cmdiad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
