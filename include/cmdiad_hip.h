@@ -198,7 +198,10 @@ int cmdiad_gemm_qkv(const uint16_t* A, const uint16_t* W, const float* bias, con
 
 /* softmax(q k^T) v per (image, head) (models/models.py:153-157), flash-style, bf16 MFMA; q as written by
  * cmdiad_gemm_qkv (pre-scaled by head_dim^-0.5 * log2(e): the kernel evaluates exp2 of the raw q.k).
- * out [B*T, C] bf16 with heads concatenated along C (the `.transpose(1,2).reshape(B,N,C)` of :157). */
+ * out [B*T, C] bf16 with heads concatenated along C (the `.transpose(1,2).reshape(B,N,C)` of :157).
+ * Padding (rows / columns T .. Tp-1 of q, k [B,H,Tp,64] and vt [B,H,64,Tp], Tp = T rounded up to 64): keys at and beyond T
+ * are masked, whatever finite values the k padding holds; q padding rows are computed and discarded; vt padding columns are
+ * multiplied by exact zeros and must therefore be finite (0 x inf is NaN) -- the caller zeroes them once. */
 int cmdiad_attention(const uint16_t* q, const uint16_t* k, const uint16_t* vt, int B, int H, int T,
                      uint16_t* out, cmdiad_stream_t stream);
 

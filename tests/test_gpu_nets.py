@@ -6,6 +6,7 @@ Tolerance model: every GEMM operand is rounded to bf16 (relative 2^-9 per elemen
 layers the feature error is ~ sqrt(L) * 2^-8 of the feature scale.  The assertions therefore bound the
 error relative to the mean absolute feature value: mean |err| <= 1.5 %, max |err| <= 12 %."""
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -16,6 +17,9 @@ pytestmark = pytest.mark.gpu
 from cmdiad_amd import ops, runtime  # noqa: E402
 from oracle import kernels as ok  # noqa: E402
 from oracle import nets  # noqa: E402
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from block_stages import stage_by_stage  # noqa: E402
 
 DEV = "cuda"
 
@@ -229,25 +233,6 @@ def test_pointmae_batch_statistics_bn_vs_reference_golden(golden):
 # unrounded fp32 oracle (4.5e-3 / 3.1e-2).  A tight end-to-end bound therefore does not exist for a 16-bit chain.  What CAN be
 # tight is every kernel of a block on ITS OWN inputs: one rounding point per comparison, so the two sides differ by at most one
 # bf16 step on the few elements that sit on a boundary, and by fp32 accumulation noise (1e-6) elsewhere.
-def _ulp_check(got, ref64, what, max_ulps=1.0, frac_off=2e-3, abs_slack=None):
-    """got: bf16 tensor from the GPU; ref64: float64 values BEFORE rounding.  Every element must be one of the (at most two)
-    bf16 neighbours of the exact value -- |got - exact| <= max_ulps * ulp(exact) + abs_slack -- and all but a fraction `frac_off`
-    must be the NEAREST one (round(exact) == got).  abs_slack (default 1e-5 of the mean magnitude) covers the fp32 evaluation of
-    values that are small by CANCELLATION (a LayerNorm output or a dot product near zero carries the absolute error of its
-    terms, ~1e-7 of THEIR size, which is many bf16 steps of a result of 1e-4)."""
-    got = got.detach().cpu().double()
-    ref64 = ref64.detach().cpu()
-    if abs_slack is None:
-        abs_slack = 1e-5 * float(ref64.abs().mean())
-    nearest = ref64.float().to(torch.bfloat16).double()
-    ulp = torch.exp2(torch.floor(torch.log2(nearest.abs().clamp_min(1e-37))) - 7.0)       # the bf16 step at the exact value
-    err = (got - ref64).abs()
-    assert bool((err <= max_ulps * ulp + abs_slack).all()), (what, float(((err - abs_slack) / ulp).max()))
-    off = float((got != nearest).double().mean())
-    assert off <= frac_off, (what, off)
-    return off
-
-
 @pytest.mark.parametrize("kind", ["vit", "pointmae", "vit-heavy-tailed"])
 def test_transformer_block_stage_by_stage_vs_fp64(kind):
     """models/models.py:126-180 (and timm's block, same algebra) kernel by kernel at full size, B = 2: LayerNorm (+ the
@@ -255,9 +240,8 @@ def test_transformer_block_stage_by_stage_vs_fp64(kind):
     -- each against float64 arithmetic on the GPU's OWN input of that stage (oracle/nets_rounded.py's model of where operands are
     rounded).  bf16 outputs: within one bf16 step of the exact value everywhere, the nearest bf16 for >= 99.8 % of the elements;
     fp32 outputs (the residual stream): 2e-5 of the feature scale.  A wrong bias element, a mis-scaled head or a transposed tile
-    fails by orders of magnitude."""
-    from cmdiad_amd.runtime import _QkvBuffers, _pack_block
-    from oracle.nets_rounded import LOG2E, r16
+    fails by orders of magnitude.  The body is tests/block_stages.py (tests/test_gpu_attention_edges.py runs it on small
+    geometries); _ulp_check and the float64 model of the attention kernel's tile loop are tests/attn_ref.py."""
     heavy = kind.endswith("heavy-tailed")
     kind = kind.split("-")[0]
     if kind == "vit":
@@ -265,7 +249,6 @@ def test_transformer_block_stage_by_stage_vs_fp64(kind):
     else:
         seed, prefix, B, T, C, H, eps, qkv_bias, with_pos = 21, "blocks.blocks.7.", 2, 1024, 384, 6, 1e-5, False, True
     sd = nets.synth_state_dict(kind, seed)
-    blk = _pack_block(sd, prefix, DEV, qkv_bias)          # (no fold: this test pins the separate launches)
     g = torch.Generator().manual_seed(B * T + C)
     x0 = torch.randn(B * T, C, generator=g)
     if heavy:     # a residual stream as a DINO checkpoint has it: three channels at ~100x on every token, one token at ~40x
@@ -275,85 +258,7 @@ def test_transformer_block_stage_by_stage_vs_fp64(kind):
         x0[400] *= 40.0
         x0[T + 400] *= 40.0
     pos = 0.1 * torch.randn(B * T, C, generator=g) if with_pos else None
-    W = lambda k: sd[prefix + k].double()                                  # noqa: E731
-    Wb = lambda k: r16(sd[prefix + k])                                     # noqa: E731  (weights as the kernels hold them)
-    x = x0.to(DEV)
-    M, hd = B * T, 64
-    # ---- LayerNorm 1 (+ pos): x <- x + pos in place, h = bf16(LN(x))
-    h = ops.layernorm(x, blk["ln1_w"], blk["ln1_b"], eps, add=pos.to(DEV) if with_pos else None)
-    x_ref = x0.double() + (pos.double() if with_pos else 0.0)
-    np.testing.assert_allclose(x.cpu().double().numpy(), x_ref.float().double().numpy(), rtol=0, atol=0)      # one fp32 add: exact
-    ln = lambda v, n: torch.nn.functional.layer_norm(v, (C,), W(n + ".weight"), W(n + ".bias"), eps)   # noqa: E731
-    off = [_ulp_check(h, ln(x.cpu().double(), "norm1"), "LayerNorm 1")]
-    # ---- qkv: q = bf16((h.Wq^T + b) * hd^-0.5 * log2 e), k, v = bf16(h.W^T + b), head-split, v transposed
-    q, k, vt = _QkvBuffers().get(B, H, T, DEV)
-    ops.gemm_qkv(h, blk["qkv_w"], blk["qkv_b"], B, T, q, k, vt)
-    qkv = h.cpu().double() @ Wb("attn.qkv.weight").T + (W("attn.qkv.bias") if qkv_bias else 0.0)
-    qkv = qkv.reshape(B, T, 3, H, hd).permute(2, 0, 3, 1, 4)               # [3,B,H,T,64]
-    scale = float(torch.tensor(hd ** -0.5 * LOG2E, dtype=torch.float32))
-    off.append(_ulp_check(q[:, :, :T], qkv[0].float().double() * scale, "q", max_ulps=1.01))   # (the scale multiplies the fp32 value)
-    off.append(_ulp_check(k[:, :, :T], qkv[1], "k"))
-    off.append(_ulp_check(vt[:, :, :, :T].transpose(-1, -2), qkv[2], "v"))
-    assert not bool(q[:, :, T:].any()) and not bool(k[:, :, T:].any()) and not bool(vt[:, :, :, T:].any())   # padding stays zero
-    # ---- attention on the GPU's own q, k, v: keys in tiles of 64, P = bf16(exp2(S - reference)), row sum of the unrounded exp2.
-    # The reference is the first tile's maximum and moves up only when some query of the WAVE (32 consecutive queries) meets a
-    # score more than 8 (log2 units) above its own; then every query of that wave moves to its running maximum (csrc/attention.hip)
-    a = ops.attention(q, k, vt, B, H, T)
-    qd, kd, vd = q[:, :, :T].cpu().double(), k[:, :, :T].cpu().double(), vt[:, :, :, :T].transpose(-1, -2).cpu().double()
-    sc = qd @ kd.transpose(-2, -1)
-    m_run = torch.full((B, H, T), -float("inf"), dtype=torch.float64)
-    l_run = torch.zeros((B, H, T), dtype=torch.float64)
-    o = torch.zeros((B, H, T, hd), dtype=torch.float64)
-    moved, pad32 = 0, (-T) % 32
-    for t0 in range(0, T, 64):
-        st = sc[..., t0:t0 + 64]
-        grow = st.amax(-1) - m_run                                           # [B,H,T]; +inf in the first tile
-        over = torch.nn.functional.pad(grow > 8.0, (0, pad32)).reshape(B, H, -1, 32).any(-1)   # (queries past T are zero rows: never)
-        move = over.repeat_interleave(32, -1)[..., :T] | (t0 == 0)          # the wave-uniform decision, per query
-        moved += int(move.any(-1).sum()) if t0 else 0
-        m_new = torch.where(move, torch.maximum(m_run, st.amax(-1)), m_run)
-        alpha = torch.exp2(m_run - m_new)
-        p = torch.exp2(st - m_new[..., None])
-        l_run = l_run * alpha + p.sum(-1)
-        o = o * alpha[..., None] + r16(p) @ vd[:, :, t0:t0 + 64]
-        m_run = m_new
-    print(f"  [attention model: the reference moved in {moved} of {(T // 64) * B * H} (head, later tile) pairs]")
-    a_ref = (o / l_run[..., None]).transpose(1, 2).reshape(M, C)
-    # A P element whose rounding falls the other way (1 in ~3 000: the fp32 scores carry ~1e-6 of absolute error) moves every output
-    # of its query by one bf16 step of that weight times the value: <= 2^-8 (p_i / l) |v_i|.  Under uniform attention that is 4e-5
-    # of the output scale, with a dominant key (weight 0.1 ... 0.6) up to 1.5e-2 of it -- whole rows then sit one P step away
-    # (tools/attn_diag.py lists them).  The slack is exactly that bound per (query, column): 2^-7 x the query's largest weight x
-    # the column's largest |v| (two such flips).  With THIS model of the P rounding 99.94 % of the outputs are the nearest bf16 of
-    # the float64 value; with P rounded against the final maximum, or not rounded, only 75-79 % are (same tool).
-    peak = (torch.exp2(sc - m_run[..., None]) / l_run[..., None]).amax(-1)                      # [B,H,T]: largest weight of the query
-    slack = 2.0 ** -7 * peak[..., None] * vd.abs().amax(2)[:, :, None, :]                      # [B,H,T,64]
-    slack = slack.transpose(1, 2).reshape(M, C) + 1e-5 * float(a_ref.abs().mean())
-    off.append(_ulp_check(a, a_ref, "attention", max_ulps=1.05, frac_off=5e-3, abs_slack=slack))
-    # ---- proj + residual (fp32, in place)
-    ops.gemm(a, blk["proj_w"], bias=blk["proj_b"], residual=x, out_f32=x, want_bf16=False)
-    x_ref = x_ref.float().double() + (a.cpu().double() @ Wb("attn.proj.weight").T + W("attn.proj.bias"))
-    scale_x = float(x_ref.abs().mean())
-    # fp32 outputs: 2e-5 of the feature scale -- plus, for the heavy-tailed stream, fp32's own relative step on the 100x elements
-    # (a value of 4 000 carries 2.4e-4 of absolute rounding per fp32 operation: 1e-6 of ITS size)
-    assert bool(((x.cpu().double() - x_ref).abs() <= 2e-5 * scale_x + 1e-6 * x_ref.abs()).all())
-    # ---- LayerNorm 2, fc1 + GELU, fc2 + residual
-    h2 = ops.layernorm(x, blk["ln2_w"], blk["ln2_b"], eps)
-    off.append(_ulp_check(h2, ln(x.cpu().double(), "norm2"), "LayerNorm 2"))
-    _, mid = ops.gemm(h2, blk["fc1_w"], bias=blk["fc1_b"], act=ops.ACT_GELU)
-    z = h2.cpu().double() @ Wb("mlp.fc1.weight").T + W("mlp.fc1.bias")
-    # erf-GELU with one transcendental (|error| <= 5.3e-7 ABSOLUTE, csrc/common.h): a visible share of a bf16 step only for the
-    # small outputs, hence the absolute slack and the larger share of not-nearest roundings
-    off.append(_ulp_check(mid, torch.nn.functional.gelu(z), "fc1 + GELU", max_ulps=1.0, frac_off=3e-2, abs_slack=1e-6))
-    x_before = x.cpu().double()
-    ops.gemm(mid, blk["fc2_w"], bias=blk["fc2_b"], residual=x, out_f32=x, want_bf16=False)
-    x_ref2 = x_before + (mid.cpu().double() @ Wb("mlp.fc2.weight").T + W("mlp.fc2.bias"))
-    assert bool(((x.cpu().double() - x_ref2).abs() <= 2e-5 * float(x_ref2.abs().mean()) + 1e-6 * x_ref2.abs()).all())
-    print(f"{kind}: fraction of bf16 outputs that are not the nearest bf16 of the float64 value, per stage: {['%.1e' % v for v in off]}")
-    # the chained production entry point gives the same block output as these separate calls (bit for bit: same kernels)
-    from cmdiad_amd.runtime import transformer_block_unfused
-    xb = x0.to(DEV)
-    transformer_block_unfused(xb, blk, B, T, H, eps, _QkvBuffers(), pos=pos.to(DEV) if with_pos else None)
-    assert torch.equal(xb, x)
+    stage_by_stage(sd, prefix, B, T, C, H, eps, qkv_bias, x0, pos, kind)
 
 
 def _tight(got, ref):

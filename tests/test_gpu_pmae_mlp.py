@@ -77,10 +77,10 @@ def _same(a, b):
     assert len(ta) == len(tb) and all(torch.equal(u, v) for u, v in zip(ta, tb))
 
 
-@pytest.mark.parametrize("B,T", [(32, 1024), (3, 1000), (1, 1024), (2, 200)])
+@pytest.mark.parametrize("B,T", [(32, 1024), (3, 1000), (1, 1024), (2, 200), (1, 1), (1, 65), (3, 43), (1, 127)])
 def test_fused_mlp_block_equals_separate_launches(B, T, monkeypatch):
     """CMDIAD_PMAE_MLP=1: every row count, ragged ones included (M = 3 000, 400: the last 128-row tile is partial, the last
-    waves of it have no live row at all)."""
+    waves of it have no live row at all; M = 1, 65, 127: a single partial tile; M = 129: one row in the second)."""
     _same(_chain(B, T, "1", monkeypatch), _chain(B, T, "ref", monkeypatch))
 
 
