@@ -145,6 +145,8 @@ SIGNATURES = {
     "cmdiad_metrics_split": [P, P, P, I, I, P, I, P, P, I, P, P, P],
     "cmdiad_auc_counts": [P, I, P, I, P, P],
     "cmdiad_pro_hist": [P, I, P, P, I, I, P, P],
+    "cmdiad_threshold_mask": [P, P, I, I, I, I, P, P, P],
+    "cmdiad_region_table": [P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, SZ, P],
     "cmdiad_tiff_unpack": [P, c_int64, P, I, I, I, I, I, I, I, I, I, I, I, P, P],
     "cmdiad_png_unfilter": [P, c_int64, P, I, I, I, I, I, I, P, P],
     "cmdiad_digest64": [P, SZ, c_uint64, P, P],
@@ -170,6 +172,7 @@ SIZE_QUERIES = {
     "cmdiad_ccl_workspace_bytes": [I, I, I],
     "cmdiad_sort_u64_tile": [],
     "cmdiad_sort_u64_workspace_bytes": [I],
+    "cmdiad_region_table_workspace_bytes": [I, I, I],
 }
 
 

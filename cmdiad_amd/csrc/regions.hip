@@ -1,0 +1,397 @@
+// Defect regions of score maps on the device (docs/regions.md): threshold -> mask, cmdiad_ccl_label (metrics.hip, unchanged) ->
+// labels, and here the per-component statistics and the selection of the strongest regions into a fixed-size table.
+// Everything but score_sum is an integer or a stored double picked by integer work, so nothing depends on the order in which
+// threads or atomics arrive: the peak is an integer atomicMax on the order-preserving 64-bit key of the score (the key transform of
+// metrics.hip), its position an atomicMin of the pixel index among the pixels whose key equals it, the box atomicMin / atomicMax,
+// the centroid two exact 64-bit integer sums and one float64 division each.  No float goes through an atomic.  score_sum is
+// computed for the kept regions only, by the selecting workgroup: it walks the region's bounding box in raster order, thread t
+// taking box pixels t, t + 256, ..., then a fixed butterfly inside each wave and ((w0 + w1) + (w2 + w3)) over the four waves --
+// an order that depends on the component's pixels alone, not on the batch, the image's place in it, or the run.
+//
+// cmdiad_threshold_mask: mask = score > thr as a comparison of doubles (a NaN is background and counted), thr read from DEVICE
+//   memory (one value or one per image) so that a captured graph follows a threshold that changes between replays.
+// cmdiad_region_table: two pixel passes (statistics, then the peak's first pixel) over tables of the labelling's own capacity
+//   n ceil(H/2) ceil(W/2) -- every index into them is checked against it -- and one workgroup per image that runs K rounds of
+//   "largest (key(peak), lowest label) strictly after the previous pick" over the components with area >= min_area: the order is
+//   total, so no table of taken components is needed and no rank is counted.  The launch geometry depends on n, H, W alone.
+#include <limits.h>
+
+#include "launch.h"
+
+namespace {
+
+constexpr int kMaxImagePixels = 1 << 24;
+constexpr int kMaxImages = 65535;
+constexpr int kMaxTotal = 1 << 30;
+constexpr int kMaxRegions = 64;
+constexpr unsigned long long kSign = 0x8000000000000000ull;
+
+__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
+
+// float64 bits -> key whose unsigned order is the order of the doubles (-0.0 == +0.0 -> one key); metrics.hip's transform
+__device__ __forceinline__ unsigned long long f64_key(double x)
+{
+    unsigned long long b = (unsigned long long)__double_as_longlong(x);
+    if (b == kSign) b = 0;
+    return (b & kSign) ? ~b : (b | kSign);
+}
+
+// per global component id, each of `cap` entries
+struct RegionTables {
+    unsigned long long* key;    // max of the score keys (0 = below every real key)
+    unsigned long long* sumx;   // exact sums of the columns / rows
+    unsigned long long* sumy;
+    int32_t* x1;
+    int32_t* y1;
+    int32_t* x0;                // the three "min" tables start at 0x7F7F7F7F
+    int32_t* y0;
+    int32_t* pidx;              // first pixel (raster order) whose key equals key[]
+};
+
+struct RegionLayout {
+    size_t stride;   // entries per table, a multiple of 64: every table starts 256-byte aligned
+    size_t zero_bytes, min_off, min_bytes, total;
+};
+inline RegionLayout region_layout(long long cap)
+{
+    RegionLayout L;
+    L.stride = ((size_t)cap + 63) & ~(size_t)63;
+    L.zero_bytes = L.stride * (3 * 8 + 2 * 4);
+    L.min_off = L.zero_bytes;
+    L.min_bytes = L.stride * 3 * 4;
+    L.total = L.min_off + L.min_bytes;
+    return L;
+}
+inline RegionTables region_tables(void* workspace, const RegionLayout& L)
+{
+    char* w = (char*)workspace;
+    RegionTables T;
+    T.key = (unsigned long long*)w;
+    T.sumx = T.key + L.stride;
+    T.sumy = T.sumx + L.stride;
+    T.x1 = (int32_t*)(T.sumy + L.stride);
+    T.y1 = T.x1 + L.stride;
+    T.x0 = (int32_t*)(w + L.min_off);
+    T.y0 = T.x0 + L.stride;
+    T.pidx = T.y0 + L.stride;
+    return T;
+}
+
+inline bool sizes_ok(int n, int H, int W)
+{
+    return n >= 0 && n <= kMaxImages && H >= 1 && W >= 1 && (long long)H * W <= kMaxImagePixels && (long long)n * H * W <= kMaxTotal;
+}
+inline long long most_components(int n, int H, int W) { return (long long)n * ((H + 1) / 2) * ((W + 1) / 2); }
+inline unsigned blocks512(int n) { return (unsigned)((n + 511) / 512); }
+
+// ---------------------------------------------------------------------------------------------------------------- threshold
+// grid (ceil(HW / 512), n): a lane takes pixels 2t and 2t + 1 of its image.  kVec: HW is even and both buffers are aligned, so the
+// pair is one 16-byte load and one 2-byte store.
+template <bool kVec>
+__global__ __launch_bounds__(256) void threshold_mask_kernel(const double* __restrict__ maps, const double* __restrict__ thr,
+                                                             int thr_per_image, int HW, uint8_t* __restrict__ mask,
+                                                             int32_t* __restrict__ nan_count)
+{
+    const int p = (blockIdx.x * 256 + threadIdx.x) * 2;
+    const size_t at = (size_t)blockIdx.y * HW + p;
+    const double t = thr[thr_per_image ? blockIdx.y : 0];
+    int bad = 0;
+    if (kVec) {
+        if (p < HW) {   // p + 1 < HW as well: both are even
+            const double2 s = *reinterpret_cast<const double2*>(maps + at);
+            bad = (s.x != s.x) + (s.y != s.y);
+            const unsigned short m = (unsigned short)((s.x > t ? 1u : 0u) | (s.y > t ? 0x100u : 0u));
+            *reinterpret_cast<unsigned short*>(mask + at) = m;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            if (p + k < HW) {
+                const double s = maps[at + k];
+                bad += s != s;
+                mask[at + k] = s > t ? 1 : 0;
+            }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) bad += __shfl_xor(bad, m, 64);
+    if (nan_count && bad && lane_id() == 0) atomicAdd(nan_count, bad);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- statistics
+// The tables' start values, written by a kernel and not by memset calls: 32 bytes of zero and three 0x7F7F7F7F per slot.
+__global__ __launch_bounds__(256) void region_init_kernel(RegionTables T, int stride)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= stride) return;
+    T.key[i] = 0ull, T.sumx[i] = 0ull, T.sumy[i] = 0ull;
+    T.x1[i] = 0, T.y1[i] = 0;
+    T.x0[i] = 0x7F7F7F7F, T.y0[i] = 0x7F7F7F7F, T.pidx[i] = 0x7F7F7F7F;
+}
+
+template <bool kVec>
+__device__ __forceinline__ void load_pair(const double* __restrict__ maps, const int32_t* __restrict__ labels, size_t at, int p, int HW,
+                                          double s[2], int lab[2])
+{
+    s[0] = s[1] = 0.0;
+    lab[0] = lab[1] = 0;
+    if (kVec) {
+        if (p < HW) {
+            const double2 v = *reinterpret_cast<const double2*>(maps + at);
+            const int2 l = *reinterpret_cast<const int2*>(labels + at);
+            s[0] = v.x, s[1] = v.y, lab[0] = l.x, lab[1] = l.y;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            if (p + k < HW) s[k] = maps[at + k], lab[k] = labels[at + k];
+    }
+}
+
+// One pixel per lane into the tables of component g; every lane of the wave calls it.  When all active lanes of the wave belong to
+// one component (the inside of a blob) the wave reduces first and its leader issues the seven atomics.
+__device__ __forceinline__ void stats_update(const RegionTables& T, int g, bool active, unsigned long long key, int x, int y)
+{
+    const unsigned long long todo = __ballot(active);
+    if (!todo) return;   // wave-uniform
+    const int leader = __ffsll((long long)todo) - 1;
+    const int lg = __shfl(g, leader, 64);
+    if (__ballot(active && g == lg) == todo) {
+        unsigned long long k = active ? key : 0ull;
+        int mnx = active ? x : INT_MAX, mny = active ? y : INT_MAX, mxx = active ? x : -1, mxy = active ? y : -1;
+        unsigned sx = active ? (unsigned)x : 0u, sy = active ? (unsigned)y : 0u;   // 64 values below 2^24 each
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const unsigned long long ok = shfl_xor_u64(k, m);
+            k = ok > k ? ok : k;
+            mnx = min(mnx, __shfl_xor(mnx, m, 64));
+            mny = min(mny, __shfl_xor(mny, m, 64));
+            mxx = max(mxx, __shfl_xor(mxx, m, 64));
+            mxy = max(mxy, __shfl_xor(mxy, m, 64));
+            sx += __shfl_xor(sx, m, 64);
+            sy += __shfl_xor(sy, m, 64);
+        }
+        if (lane_id() == leader) {
+            atomicMax(T.key + lg, k);
+            atomicMin(T.x0 + lg, mnx);
+            atomicMin(T.y0 + lg, mny);
+            atomicMax(T.x1 + lg, mxx);
+            atomicMax(T.y1 + lg, mxy);
+            atomicAdd(T.sumx + lg, (unsigned long long)sx);
+            atomicAdd(T.sumy + lg, (unsigned long long)sy);
+        }
+    } else if (active) {
+        atomicMax(T.key + g, key);
+        atomicMin(T.x0 + g, x);
+        atomicMin(T.y0 + g, y);
+        atomicMax(T.x1 + g, x);
+        atomicMax(T.y1 + g, y);
+        atomicAdd(T.sumx + g, (unsigned long long)x);
+        atomicAdd(T.sumy + g, (unsigned long long)y);
+    }
+}
+
+// grid (ceil(HW / 512), n)
+template <bool kVec>
+__global__ __launch_bounds__(256) void region_stats_kernel(const double* __restrict__ maps, const int32_t* __restrict__ labels,
+                                                           const int32_t* __restrict__ comp_offset, int HW, int W, int cap, RegionTables T)
+{
+    const int p = (blockIdx.x * 256 + threadIdx.x) * 2;
+    const size_t at = (size_t)blockIdx.y * HW + p;
+    double s[2];
+    int lab[2];
+    load_pair<kVec>(maps, labels, at, p, HW, s, lab);
+    const long long off = comp_offset[blockIdx.y];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const long long g = off + lab[k] - 1;
+        const bool active = lab[k] > 0 && g >= 0 && g < cap;
+        const int q = p + k, y = q / W;
+        stats_update(T, (int)g, active, f64_key(s[k]), q - y * W, y);
+    }
+}
+
+// grid (ceil(HW / 512), n), after region_stats_kernel has finished: the first pixel whose key is the component's largest
+template <bool kVec>
+__global__ __launch_bounds__(256) void region_peak_kernel(const double* __restrict__ maps, const int32_t* __restrict__ labels,
+                                                          const int32_t* __restrict__ comp_offset, int HW, int cap, RegionTables T)
+{
+    const int p = (blockIdx.x * 256 + threadIdx.x) * 2;
+    const size_t at = (size_t)blockIdx.y * HW + p;
+    double s[2];
+    int lab[2];
+    load_pair<kVec>(maps, labels, at, p, HW, s, lab);
+    const long long off = comp_offset[blockIdx.y];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const long long g = off + lab[k] - 1;
+        if (lab[k] > 0 && g >= 0 && g < cap && f64_key(s[k]) == T.key[g]) atomicMin(T.pidx + g, p + k);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- selection
+// (key, label) a comes before b: larger peak first, then the lower label
+__device__ __forceinline__ bool comes_before(unsigned long long ka, int la, unsigned long long kb, int lb)
+{
+    return ka > kb || (ka == kb && la < lb);
+}
+
+// grid (n), one workgroup per image
+__global__ __launch_bounds__(256) void region_select_kernel(const double* __restrict__ maps, const int32_t* __restrict__ labels,
+                                                            const int32_t* __restrict__ n_comp, const int32_t* __restrict__ comp_offset,
+                                                            const int32_t* __restrict__ comp_size, int H, int W, int cap, int min_area,
+                                                            int K, RegionTables T, int32_t* __restrict__ count,
+                                                            int32_t* __restrict__ ints, double* __restrict__ vals)
+{
+    __shared__ int sh_count;
+    __shared__ unsigned long long sh_k[4];
+    __shared__ int sh_l[4];
+    __shared__ double sh_d[4];
+    const int img = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
+    const int HW = H * W;
+    const size_t base = (size_t)img * HW;
+    long long off = comp_offset[img];
+    long long nc = n_comp[img];
+    if (off < 0 || off > cap) off = cap;          // a table the labelling did not write: nothing is read outside the capacity
+    if (nc < 0) nc = 0;
+    if (nc > cap - off) nc = cap - off;
+    if (tid == 0) sh_count = 0;
+    __syncthreads();
+    int mine = 0;
+    for (int c = tid; c < nc; c += 256) mine += comp_size[off + c] >= min_area;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) mine += __shfl_xor(mine, m, 64);
+    if (lane_id() == 0 && mine) atomicAdd(&sh_count, mine);
+    __syncthreads();
+    const int total = sh_count;
+    const int nsel = total < K ? total : K;
+    if (tid == 0) count[img] = total;
+    int32_t* my_ints = ints + (size_t)img * K * 8;
+    double* my_vals = vals + (size_t)img * K * 4;
+    for (int i = nsel * 8 + tid; i < K * 8; i += 256) my_ints[i] = 0;
+    for (int i = nsel * 4 + tid; i < K * 4; i += 256) my_vals[i] = 0.0;
+
+    unsigned long long pk = ~0ull;   // the previous pick: above every real key, label 0 below every real label
+    int pl = 0;
+    for (int r = 0; r < nsel; ++r) {
+        unsigned long long bk = 0ull;
+        int bl = INT_MAX;
+        for (int c = tid; c < nc; c += 256) {
+            if (comp_size[off + c] < min_area) continue;
+            const unsigned long long k = T.key[off + c];
+            const int l = c + 1;
+            if (comes_before(pk, pl, k, l) && comes_before(k, l, bk, bl)) bk = k, bl = l;
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const unsigned long long ok = shfl_xor_u64(bk, m);
+            const int ol = __shfl_xor(bl, m, 64);
+            if (comes_before(ok, ol, bk, bl)) bk = ok, bl = ol;
+        }
+        __syncthreads();   // the previous round's readers of sh_k / sh_l / sh_d are done
+        if (lane_id() == 0) sh_k[wave] = bk, sh_l[wave] = bl;
+        __syncthreads();
+        bk = sh_k[0], bl = sh_l[0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w)
+            if (comes_before(sh_k[w], sh_l[w], bk, bl)) bk = sh_k[w], bl = sh_l[w];
+        if (bl == INT_MAX) break;   // block-uniform; cannot happen while r < nsel
+        pk = bk, pl = bl;
+        const long long g = off + bl - 1;
+        // the region's box, clamped to the image: the walk below reads nothing outside it
+        int x0 = T.x0[g], y0 = T.y0[g], x1 = T.x1[g], y1 = T.y1[g];
+        x0 = max(x0, 0), y0 = max(y0, 0), x1 = min(x1, W - 1), y1 = min(y1, H - 1);
+        const int bw = x1 - x0 + 1, bh = y1 - y0 + 1;
+        double sum = 0.0;
+        if (bw > 0 && bh > 0) {
+            const int nb = bw * bh;
+            for (int j = tid; j < nb; j += 256) {
+                const int yy = j / bw;
+                const size_t at = base + (size_t)(y0 + yy) * W + x0 + (j - yy * bw);
+                if (labels[at] == bl) sum += maps[at];
+            }
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m, 64);
+        if (lane_id() == 0) sh_d[wave] = sum;
+        __syncthreads();
+        if (tid == 0) {
+            int pi = T.pidx[g];
+            if (pi < 0 || pi >= HW) pi = 0;
+            const int area = comp_size[g];
+            const int py = pi / W;
+            int32_t* o = my_ints + r * 8;
+            o[0] = bl, o[1] = area, o[2] = x0, o[3] = y0, o[4] = x1, o[5] = y1, o[6] = pi - py * W, o[7] = py;
+            double* v = my_vals + r * 4;
+            v[0] = maps[base + pi];
+            v[1] = (sh_d[0] + sh_d[1]) + (sh_d[2] + sh_d[3]);
+            v[2] = (double)T.sumx[g] / (double)area;
+            v[3] = (double)T.sumy[g] / (double)area;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int cmdiad_threshold_mask(const double* maps, const double* thr, int thr_per_image, int n, int H, int W, uint8_t* mask,
+                                     int32_t* nan_count, cmdiad_stream_t stream)
+{
+    CMDIAD_REQUIRE(sizes_ok(n, H, W) && (thr_per_image == 0 || thr_per_image == 1), CMDIAD_ERR_ARG,
+                   "cmdiad_threshold_mask: bad sizes n=%d (0..%d) H=%d W=%d (>= 1, H*W <= %d, n*H*W <= %d) thr_per_image=%d", n, kMaxImages,
+                   H, W, kMaxImagePixels, kMaxTotal, thr_per_image);
+    hipStream_t s = (hipStream_t)stream;
+    CMDIAD_REQUIRE(n == 0 || (maps && thr && mask), CMDIAD_ERR_ARG, "cmdiad_threshold_mask: null pointer");
+    if (nan_count) {
+        hipError_t e = hipMemsetAsync(nan_count, 0, sizeof(int32_t), s);
+        CMDIAD_REQUIRE(e == hipSuccess, CMDIAD_ERR_LAUNCH, "cmdiad_threshold_mask: hipMemsetAsync: %s", hipGetErrorString(e));
+    }
+    if (n == 0) return CMDIAD_OK;
+    const int HW = H * W;
+    const bool vec = HW % 2 == 0 && ((uintptr_t)maps & 15) == 0 && ((uintptr_t)mask & 1) == 0;
+    const dim3 grid(blocks512(HW), (unsigned)n);
+    if (vec) hipLaunchKernelGGL(threshold_mask_kernel<true>, grid, dim3(256), 0, s, maps, thr, thr_per_image, HW, mask, nan_count);
+    else hipLaunchKernelGGL(threshold_mask_kernel<false>, grid, dim3(256), 0, s, maps, thr, thr_per_image, HW, mask, nan_count);
+    CMDIAD_CHECK_LAUNCH();
+    return CMDIAD_OK;
+}
+
+extern "C" size_t cmdiad_region_table_workspace_bytes(int n, int H, int W)
+{
+    return sizes_ok(n, H, W) && n > 0 ? region_layout(most_components(n, H, W)).total : 0;
+}
+
+extern "C" int cmdiad_region_table(const double* maps, const int32_t* labels, const int32_t* n_comp, const int32_t* comp_offset,
+                                   const int32_t* comp_size, int comp_cap, int n, int H, int W, int min_area, int max_regions,
+                                   int32_t* count, int32_t* ints, double* vals, void* workspace, size_t workspace_bytes,
+                                   cmdiad_stream_t stream)
+{
+    CMDIAD_REQUIRE(sizes_ok(n, H, W) && comp_cap >= 0 && min_area >= 1 && max_regions >= 1 && max_regions <= kMaxRegions, CMDIAD_ERR_ARG,
+                   "cmdiad_region_table: bad sizes n=%d (0..%d) H=%d W=%d (>= 1, H*W <= %d, n*H*W <= %d) comp_cap=%d min_area=%d (>= 1) "
+                   "max_regions=%d (1..%d)", n, kMaxImages, H, W, kMaxImagePixels, kMaxTotal, comp_cap, min_area, max_regions, kMaxRegions);
+    if (n == 0) return CMDIAD_OK;
+    CMDIAD_REQUIRE(maps && labels && n_comp && comp_offset && comp_size && count && ints && vals && workspace, CMDIAD_ERR_ARG,
+                   "cmdiad_region_table: null pointer");
+    const long long most = most_components(n, H, W);
+    CMDIAD_REQUIRE(comp_cap >= most, CMDIAD_ERR_ARG,
+                   "cmdiad_region_table: comp_size holds %d components, %lld are possible (n ceil(H/2) ceil(W/2))", comp_cap, most);
+    const RegionLayout L = region_layout(most);
+    CMDIAD_REQUIRE(workspace_bytes >= L.total, CMDIAD_ERR_WORKSPACE, "cmdiad_region_table: workspace of %zu bytes, %zu needed",
+                   workspace_bytes, L.total);
+    CMDIAD_REQUIRE(((uintptr_t)workspace & 7) == 0, CMDIAD_ERR_ARG, "cmdiad_region_table: the workspace must be 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const RegionTables T = region_tables(workspace, L);
+    const int HW = H * W, cap = (int)most;   // the tables' capacity: ids at or above it are skipped by every kernel
+    hipLaunchKernelGGL(region_init_kernel, dim3((unsigned)((L.stride + 255) / 256)), dim3(256), 0, s, T, (int)L.stride);
+    CMDIAD_CHECK_LAUNCH();
+    const bool vec = HW % 2 == 0 && ((uintptr_t)maps & 15) == 0 && ((uintptr_t)labels & 7) == 0;
+    const dim3 grid(blocks512(HW), (unsigned)n);
+    if (vec) hipLaunchKernelGGL(region_stats_kernel<true>, grid, dim3(256), 0, s, maps, labels, comp_offset, HW, W, cap, T);
+    else hipLaunchKernelGGL(region_stats_kernel<false>, grid, dim3(256), 0, s, maps, labels, comp_offset, HW, W, cap, T);
+    CMDIAD_CHECK_LAUNCH();
+    if (vec) hipLaunchKernelGGL(region_peak_kernel<true>, grid, dim3(256), 0, s, maps, labels, comp_offset, HW, cap, T);
+    else hipLaunchKernelGGL(region_peak_kernel<false>, grid, dim3(256), 0, s, maps, labels, comp_offset, HW, cap, T);
+    CMDIAD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(region_select_kernel, dim3((unsigned)n), dim3(256), 0, s, maps, labels, n_comp, comp_offset, comp_size, H, W, cap,
+                       min_area, max_regions, T, count, ints, vals);
+    CMDIAD_CHECK_LAUNCH();
+    return CMDIAD_OK;
+}

@@ -104,7 +104,16 @@ class ClassRun:
     Stored fits (docs/fitted.md), both read with getattr(args, ..., None) and off when unset: ``args.save_fit_dir`` -- fit_host()
     ends by writing ``<dir>/<class>.cmdfit``; ``args.load_fit_dir`` -- where that file exists, fit_device() loads it instead of
     fitting (``data.train()`` is never called, n_train comes from the header) and fit_host() does nothing: the phases are
-    ``["load_fit", "predict", "metrics"]``."""
+    ``["load_fit", "predict", "metrics"]``.
+
+    Calibrated decisions and defect regions (docs/regions.md), read the same way and off when unset:
+    ``args.calibration_holdout = k`` -- the last k training items are kept out of the fit (ValueError unless more than k remain)
+    and scored after fit_host() through regions.calibrate_method; with save_fit_dir the calibration is written as
+    ``<dir>/<class>.cmdcal`` beside the fit it belongs to, with load_fit_dir an existing ``.cmdcal`` is loaded and checked against
+    the ``.cmdfit`` instead (the class is not fitted, so calibration_holdout plays no part there; where it or regions_dir is set
+    and the ``.cmdcal`` is missing beside a stored fit, fit_device() raises instead of running without regions).  ``args.regions_dir`` -- when the class has a calibration, predict() ends by writing
+    ``<regions_dir>/<class>.regions.json`` (thresholds, then per test image its decision and regions) and result() gains a
+    ``regions`` entry.  ``args.min_area`` / ``args.max_regions``: defaults 1 and 16."""
 
     def __init__(self, args, data, weights=None, method=None, extractor=None):
         from .utils.utils import set_seeds
@@ -126,9 +135,18 @@ class ClassRun:
         # the fit of a class whose file exists there -- a class loop that was cut short resumes where it stopped
         self.save_fit_dir, self.load_fit_dir = getattr(args, "save_fit_dir", None), getattr(args, "load_fit_dir", None)
         self.loaded = False
+        self.holdout = getattr(args, "calibration_holdout", None)
+        self.regions_dir = getattr(args, "regions_dir", None)
+        self.min_area, self.max_regions = getattr(args, "min_area", None) or 1, getattr(args, "max_regions", None) or 16
+        self.calibration = self.held_out = self.regions_summary = None
+        if self.regions_dir and not self.holdout and not self.load_fit_dir:
+            raise ValueError("regions_dir needs a calibration: set calibration_holdout, or load_fit_dir with a .cmdcal beside the fit")
 
     def _fit_file(self, directory):
         return os.path.join(directory, f"{self.data.name}.cmdfit")
+
+    def _cal_file(self, directory):
+        return os.path.join(directory, f"{self.data.name}.cmdcal")
 
     def _loop(self, it, call, limit):
         n = flag = 0
@@ -152,12 +170,24 @@ class ClassRun:
             self.sec["load_fit"] = time.perf_counter() - t0
             self.phases.append("load_fit")
             self.loaded = True
+            if os.path.exists(self._cal_file(self.load_fit_dir)):
+                from . import regions
+                self.calibration = regions.Calibration.load(self._cal_file(self.load_fit_dir), fit=self._fit_file(self.load_fit_dir))
+            elif self.holdout or self.regions_dir:
+                raise ValueError(f"{self._cal_file(self.load_fit_dir)} is missing: the stored fit of class {data.name} is loaded, not "
+                                 "fitted, so calibration_holdout / regions_dir need the calibration saved beside it")
             return self
         # the loaders are drained first (the reference's DataLoader workers prefetch beside the model; a synthetic class generates its
         # samples on this thread): "load" is reported on its own and the phase timings below are the method's
         t0 = time.perf_counter()
         self.train_items = list(data.train())
         self.test_items = list(data.test())
+        if self.holdout:
+            k = int(self.holdout)
+            if k < 1 or len(self.train_items) <= k:
+                raise ValueError(f"calibration_holdout = {k}: the class has {len(self.train_items)} training items, more than "
+                                 f"{max(k, 0)} must remain for the fit")
+            self.train_items, self.held_out = self.train_items[:-k], self.train_items[-k:]
         self.sec["load"] = time.perf_counter() - t0
         t0 = time.perf_counter()
         self.n_train = self._loop(self.train_items, lambda it: m.add_sample_to_mem_bank(it[0], class_name=data.name), self.count)
@@ -181,7 +211,7 @@ class ClassRun:
         """True when fit_host() touches no GPU state (scikit-learn fits): it may then run on a worker thread."""
         from sklearn.base import BaseEstimator
         m = self.method
-        if self.loaded or self.save_fit_dir:        # nothing to fit / the fit is written from the device afterwards: in line
+        if self.loaded or self.save_fit_dir or self.held_out:   # nothing to fit / the fit is written, the held-out items scored, on the device afterwards: in line
             return False
         return self.multiple and all(isinstance(getattr(m, f, None), BaseEstimator) for f in ("detect_fuser", "seg_fuser"))
 
@@ -199,6 +229,14 @@ class ClassRun:
             os.makedirs(self.save_fit_dir, exist_ok=True)
             self.method.save_fit(self._fit_file(self.save_fit_dir))
             self.sec["save_fit"] = time.perf_counter() - t0
+        if self.held_out:
+            from . import regions
+            t0 = time.perf_counter()
+            self.calibration = regions.calibrate_method(self.method, self.held_out)
+            self.held_out = None
+            if self.save_fit_dir:
+                self.calibration.save(self._cal_file(self.save_fit_dir), fit=self._fit_file(self.save_fit_dir))
+            self.sec["calibration"] = time.perf_counter() - t0
         return self
 
     def predict(self):
@@ -216,7 +254,35 @@ class ClassRun:
         self.sec["metrics"] = time.perf_counter() - t0
         self.phases.append("metrics")
         self.test_items = None
+        if self.regions_dir and self.calibration is not None:
+            self._write_regions()
         return self
+
+    def _write_regions(self):
+        """<regions_dir>/<class>.regions.json: the thresholds, then per test image its decision and its regions; the summary of
+        the decisions against the image labels is kept for result().  calculate_metrics has run: the result lists are arrays."""
+        import json
+        from . import regions
+        m, cal = self.method, self.calibration
+        t0 = time.perf_counter()
+        found = regions.find_regions(m.predictions, cal.spec(self.min_area, self.max_regions))
+        scores = np.asarray(m.image_preds, dtype=np.float64).reshape(-1)
+        labels = np.asarray(m.image_labels).reshape(-1) != 0
+        names = np.asarray(m.img_name).reshape(-1)
+        decided = cal.decide(scores)
+        thresholds = dict(pixel_threshold=cal.pixel_threshold, image_threshold=cal.image_threshold, pixel_quantile=cal.pixel_quantile,
+                          image_quantile=cal.image_quantile, n_images=cal.n_images, n_pixels=cal.n_pixels, min_area=self.min_area,
+                          max_regions=self.max_regions)
+        images = [dict(index=i, img_name=str(names[i]), image_score=float(scores[i]), decision=bool(decided[i]), label=int(labels[i]),
+                       n_comp=int(found.n_comp[i]), count=int(found.count[i]), truncated=bool(found.truncated[i]), regions=regs)
+                  for i, regs in enumerate(found.to_list())]
+        os.makedirs(self.regions_dir, exist_ok=True)
+        path = os.path.join(self.regions_dir, f"{self.data.name}.regions.json")
+        with open(path, "w") as f:
+            json.dump(dict(class_name=self.data.name, thresholds=thresholds, images=images), f, indent=1)
+        self.regions_summary = dict(thresholds, file=path, tp=int((decided & labels).sum()), fp=int((decided & ~labels).sum()),
+                                    tn=int((~decided & ~labels).sum()), fn=int((~decided & labels).sum()))
+        self.sec["regions"] = time.perf_counter() - t0
 
     def result(self):
         m = self.method
@@ -225,6 +291,8 @@ class ClassRun:
                    phases=list(self.phases),
                    library_rows={k: int(getattr(m, f"patch_{k}_lib").shape[0]) for k in ("xyz", "rgb", "fusion")
                                  if torch.is_tensor(getattr(m, f"patch_{k}_lib", None))})
+        if self.regions_summary is not None:
+            out["regions"] = dict(self.regions_summary)
         out["_extractor"] = m.deep_feature_extractor
         return out
 

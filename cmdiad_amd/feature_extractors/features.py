@@ -89,6 +89,17 @@ class PixelList:
     def append(self, value):
         self.extend([value])
 
+    def truncate(self, length):
+        """Keep the first `length` values (regions.calibrate_method takes its samples out again); whole chunks are kept as they
+        are, only the chunk the cut falls into is sliced."""
+        kept, n = [], 0
+        for c in self._chunks:
+            if n >= length:
+                break
+            kept.append(c if n + c.shape[0] <= length else c[:length - n])
+            n += kept[-1].shape[0]
+        self._chunks, self._flat = kept, None
+
     def __array__(self, dtype=None, copy=None):
         if self._flat is None:
             self._flat = np.concatenate(self._chunks) if self._chunks else np.zeros((0,))

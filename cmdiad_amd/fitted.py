@@ -102,8 +102,9 @@ def _dtype_name(dt):
     raise FitFileError(f"dtype: {np.dtype(dt)} is not one of {sorted(DTYPES)}")
 
 
-def write_file(path, header, arrays, digests=None, blocks=None):
-    """Write `arrays` ({name: numpy array}) with `header` (a JSON-able dict; "format", "version" and "arrays" are filled in here).
+def write_file(path, header, arrays, digests=None, blocks=None, fmt="cmdfit"):
+    """Write `arrays` ({name: numpy array}) with `header` (a JSON-able dict; "format", "version" and "arrays" are filled in here;
+    fmt: the header's "format", "cmdfit" for a fit -- other files in this container name their own, regions.py's calibration).
     digests / blocks: {name: int} / {name: [int]} already known (computed on the device); the others are computed on the host.
     Atomic: written under a temporary name in the same directory, flushed, then os.replace()d."""
     digests, blocks = digests or {}, blocks or {}
@@ -119,7 +120,7 @@ def write_file(path, header, arrays, digests=None, blocks=None):
             entry.update(block_rows=BLOCK_ROWS, block_digests=[f"{b & _MASK:016x}" for b in bl])
         table.append(entry)
         items.append(a)
-    head = dict(header, format="cmdfit", version=VERSION, arrays=table)
+    head = dict(header, format=fmt, version=VERSION, arrays=table)
     # the offsets depend on the header's length and are part of it: fixed-width placeholders first, then the real values
     for e in table:
         e["offset"] = 10 ** 15

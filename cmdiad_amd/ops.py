@@ -1495,6 +1495,71 @@ def pro_hist(thr, def_score, def_comp, total_comp):
     return hist
 
 
+# ------------------------------------------------------------------------------------ defect regions (docs/regions.md)
+REGION_MAX = 64          # cmdiad_region_table: slots per image
+
+
+def _chk_maps(maps, who):
+    _chk(maps, torch.float64, f"{who}.maps")
+    if maps.dim() != 3:
+        raise ValueError(f"{who}: maps must be [n,H,W], got {tuple(maps.shape)}")
+    n, H, W = maps.shape
+    if H < 1 or W < 1 or H * W > (1 << 24) or n > 65535 or n * H * W > METRICS_MAX_TOTAL:
+        raise ValueError(f"{who}: unsupported shape {tuple(maps.shape)} (n <= 65535, H, W >= 1, H*W <= 2^24, n*H*W <= 2^30)")
+    return n, H, W
+
+
+def threshold_mask(maps, thr, mask=None, nan_count=None):
+    """maps [n,H,W] f64, thr f64 ON THE DEVICE with 1 or n entries -> (mask [n,H,W] u8 = maps > thr, nan_count [1] i32 = NaN scores,
+    which stay background).  -0.0 > +0.0 is false.  The threshold is read by the kernel: rewriting `thr` in place changes what the
+    next launch (or graph replay) computes.  mask / nan_count: buffers to write into.  No synchronisation."""
+    n, H, W = _chk_maps(maps, "threshold_mask")
+    _chk(thr, torch.float64, "threshold_mask.thr")
+    if thr.numel() not in (1, n) or thr.device != maps.device:
+        raise ValueError(f"threshold_mask: thr must hold 1 or n = {n} values on the maps' device, got {tuple(thr.shape)} on {thr.device}")
+    dev = maps.device
+    if mask is None:
+        mask = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
+    if nan_count is None:
+        nan_count = torch.zeros((1,), dtype=torch.int32, device=dev)
+    _chk(mask, torch.uint8, "threshold_mask.mask"); _chk(nan_count, torch.int32, "threshold_mask.nan_count")
+    if mask.shape != maps.shape or nan_count.numel() != 1:
+        raise ValueError("threshold_mask: mask must have the maps' shape and nan_count one entry")
+    if n:
+        _call("cmdiad_threshold_mask", _p(maps), _p(thr), int(thr.numel() == n and n > 1), n, H, W, _p(mask), _p(nan_count), _stream())
+    return mask, nan_count
+
+
+def region_table(maps, labels, n_comp, comp_offset, comp_size, min_area=1, max_regions=16):
+    """maps [n,H,W] f64 + the outputs of ccl_label on their mask -> (count [n] i32 = components with area >= min_area, ints
+    [n,K,8] i32 = label, area, x0, y0, x1, y1, peak_x, peak_y, vals [n,K,4] f64 = peak, score_sum, cx, cy) of the first K =
+    max_regions of them by (peak descending, label ascending); zero behind the last region, count > K = truncated.  No
+    synchronisation, nothing is read back."""
+    min_area, K = int(min_area), int(max_regions)
+    if min_area < 1 or not 1 <= K <= REGION_MAX:
+        raise ValueError(f"region_table: min_area = {min_area} (>= 1), max_regions = {K} (1..{REGION_MAX})")
+    n, H, W = _chk_maps(maps, "region_table")
+    _chk(labels, torch.int32, "region_table.labels"); _chk(n_comp, torch.int32, "region_table.n_comp")
+    _chk(comp_offset, torch.int32, "region_table.comp_offset"); _chk(comp_size, torch.int32, "region_table.comp_size")
+    cap = n * ((H + 1) // 2) * ((W + 1) // 2)
+    if labels.shape != maps.shape or n_comp.numel() != n or comp_offset.numel() != n + 1 or comp_size.numel() < cap:
+        raise ValueError(f"region_table: maps {tuple(maps.shape)} need labels of that shape, n_comp [n], comp_offset [n+1] and comp_size "
+                         f"[>= {cap}]; got {tuple(labels.shape)}, {n_comp.numel()}, {comp_offset.numel()}, {comp_size.numel()}")
+    dev = maps.device
+    for t in (labels, n_comp, comp_offset, comp_size):
+        if t.device != dev:
+            raise ValueError("region_table: every tensor must be on the maps' device")
+    count = torch.zeros((n,), dtype=torch.int32, device=dev)
+    ints = torch.zeros((n, K, 8), dtype=torch.int32, device=dev)
+    vals = torch.zeros((n, K, 4), dtype=torch.float64, device=dev)
+    if n:
+        wsb = nat.lib().cmdiad_region_table_workspace_bytes(n, H, W)
+        ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+        _call("cmdiad_region_table", _p(maps), _p(labels), _p(n_comp), _p(comp_offset), _p(comp_size), comp_size.numel(), n, H, W,
+              min_area, K, _p(count), _p(ints), _p(vals), _p(ws), wsb, _stream())
+    return count, ints, vals
+
+
 # ------------------------------------------------------------------------------------ content digest (stored fits)
 def digest64(tensor, seed=0, acc=None):
     """cmdiad_digest64 of a device tensor's bytes, ADDED into `acc` ([1] int64 on the tensor's device; None: a fresh zero) -> acc.

@@ -54,15 +54,18 @@ class _SharedPlan:
 
 
 class Ticket:
-    """One submitted batch: wait() -> (image scores [B] f64, pixel maps [B, gt, gt] f64) as numpy arrays.
+    """One submitted batch: wait() -> (image scores [B] f64, pixel maps [B, gt, gt] f64) as numpy arrays (the maps are None for a
+    predictor built with return_maps=False).  A predictor built with regions= also gives regions() -> regions.Regions, the
+    strongest defect regions of every map, and -- with an image threshold -- decisions() -> [B] bool, score > threshold.
     `flag` / `redo` (row-sharded search only): a pinned int32 that the step set to non-zero when some rank's live query rows did
     not fit the sticky gather cap (engine.ShardedSearch) -- the step's keys are then incomplete and wait() repeats the batch through
     `redo` (the same decision on every rank: the flag is computed from the all-gathered counts)."""
 
-    def __init__(self, host_s, host_m, event, gt, flag=None, redo=None):
+    def __init__(self, host_s, host_m, event, gt, flag=None, redo=None, host_r=None, image_threshold=None):
         self._s, self._m, self._ev, self._gt = host_s, host_m, event, gt
         self._flag, self._redo = flag, redo
-        self._out = None
+        self._r, self._image_threshold = host_r, image_threshold      # pinned region tables of the slot; the threshold at submit
+        self._out = self._regions = None
 
     @property
     def taken(self):
@@ -74,11 +77,32 @@ class Ticket:
             self._ev.synchronize()
             B = self._s.shape[0]
             if self._flag is not None and int(self._flag.item()) != 0:
-                self._out = self._redo()
+                s, m, self._regions = self._redo()
+                self._out = (s, m)
             else:
-                self._out = (self._s.numpy().reshape(B).copy(), self._m.numpy().reshape(B, self._gt, self._gt).copy())
-            self._s = self._m = self._flag = self._redo = None
+                self._out = (self._s.numpy().reshape(B).copy(),
+                             self._m.numpy().reshape(B, self._gt, self._gt).copy() if self._m is not None else None)
+                if self._r is not None:
+                    self._regions = tuple(t.numpy().copy() for t in self._r)
+            self._s = self._m = self._flag = self._redo = self._r = None
         return self._out
+
+    def regions(self):
+        """regions.Regions of the batch (n_comp, count, ints, vals, truncated).  ValueError when a map held a NaN."""
+        from .regions import Regions
+        self.wait()
+        if self._regions is None:
+            raise RuntimeError("Ticket.regions: the predictor was built without regions=")
+        n_comp, count, ints, vals, nan = self._regions
+        if int(nan.reshape(-1)[0]):
+            raise ValueError(f"Ticket.regions: the maps of this batch contain {int(nan.reshape(-1)[0])} NaN scores")
+        return Regions(n_comp, count, ints, vals)
+
+    def decisions(self):
+        """[B] bool: image score > image threshold (strict), with the threshold the predictor held when the batch was submitted."""
+        if self._image_threshold is None:
+            raise RuntimeError("Ticket.decisions: no image threshold was given (RegionSpec.image_threshold / set_thresholds)")
+        return self.wait()[0] > self._image_threshold
 
 
 class BatchPredictor:
@@ -89,11 +113,15 @@ class BatchPredictor:
     (main.py:114-125).  workload: 'dino_pointmae' (both modalities extracted) or 'mtfi' (Point-MAE extraction +
     `halluc`: runtime.PackedHallucination generating the second modality's features from the xyz patches).
     group: torch.distributed process group -> row-sharded library search (all-gather of the queries, per-shard
-    distance GEMM, one integer-MIN all-reduce of packed keys); None -> every rank searches its own copy."""
+    distance GEMM, one integer-MIN all-reduce of packed keys); None -> every rank searches its own copy.
+    regions: a regions.RegionSpec or regions.Calibration (docs/regions.md) -> the scoring tail ends with threshold, labelling,
+    component statistics and selection on the pixel maps (on the tail's stream, behind the captured stage 2), and every Ticket
+    carries the region tables and, with an image threshold, the decisions; None -> nothing of this exists: no buffer, no
+    launch.  return_maps=False: the maps are neither copied to the host nor returned (wait()[1] is None)."""
 
     def __init__(self, engine, bank_xyz, bank_second, stats, det, seg, lambdas=(1.0, 1.0, 0.1, 0.1), batch=32, n_max=None,
                  workload="dino_pointmae", halluc=None, group=None, use_graph=True, timers=None, ring=3, size=224,
-                 gt_size=224, blur_radius=4.0, rgb_size=None):
+                 gt_size=224, blur_radius=4.0, rgb_size=None, regions=None, return_maps=True):
         if workload not in ("dino_pointmae", "mtfi"):
             raise ValueError(f"unknown workload {workload!r}")
         if workload == "mtfi" and halluc is None:
@@ -119,8 +147,28 @@ class BatchPredictor:
         self.side, self.post, self.copy = (ops.shared_stream(dev, "predictor.side", prio[0]), ops.shared_stream(dev, "predictor.post", prio[1]),
                                            ops.shared_stream(dev, "predictor.copy", copy_prio))
         # host ring: the step's FINAL outputs (image score, pixel map), f64 as sklearn's score_samples returns them
+        self.return_maps = bool(return_maps)
         self.ring = [(torch.empty((batch, 1), dtype=torch.float64, pin_memory=True),
-                      torch.empty((batch, gt_size * gt_size), dtype=torch.float64, pin_memory=True)) for _ in range(ring)]
+                      torch.empty((batch, gt_size * gt_size), dtype=torch.float64, pin_memory=True) if self.return_maps else None)
+                     for _ in range(ring)]
+        # defect regions (docs/regions.md): the pixel threshold lives in a device tensor the threshold kernel reads, so a captured
+        # tail follows set_thresholds without a re-capture; every ring slot gains the pinned tables n_comp, count, ints, vals, NaN flag
+        self.region_spec = self.thr = self.region_ring = self.image_threshold = None
+        # The region tail is NOT part of the captured stage 2: it is launched eagerly on the tail's stream right behind the replay.
+        # Captured, it returned wrong tables in most processes for a reason that was not found (docs/regions.md, "Where the region
+        # tail runs"), so the capture of these kernels is not offered.
+        if regions is not None:
+            from . import regions as rg
+            self.region_spec = rg.as_spec(regions)
+            if not isinstance(self.region_spec.pixel_threshold, float):
+                raise ValueError("BatchPredictor: regions takes ONE pixel threshold (per-image thresholds: regions.find_regions)")
+            K = self.region_spec.max_regions
+            self.thr = torch.full((1,), self.region_spec.pixel_threshold, dtype=torch.float64, device=dev)
+            self.image_threshold = self.region_spec.image_threshold
+            self.region_ring = [(torch.zeros((batch,), dtype=torch.int32, pin_memory=True), torch.zeros((batch,), dtype=torch.int32, pin_memory=True),
+                                 torch.zeros((batch, K, 8), dtype=torch.int32, pin_memory=True),
+                                 torch.zeros((batch, K, 4), dtype=torch.float64, pin_memory=True),
+                                 torch.zeros((1,), dtype=torch.int32, pin_memory=True)) for _ in range(ring)]
         # row-sharded search: one pinned flag per ring slot ("this step's live rows exceeded the gather cap on some rank")
         self.flag_ring = [torch.zeros((1,), dtype=torch.int32, pin_memory=True) for _ in range(ring)] if group is not None else None
         self.slot = 0
@@ -299,9 +347,44 @@ class BatchPredictor:
         img = ops.ocsvm_score_maps(s.view(B, 2, 1).contiguous(), (lam[0], lam[2]), self.det.coef_, self.det.offset_)
         return img, pix
 
+    def _tail(self, qs, keys, regions=True):
+        """stage2 and, with regions, the region tables of its maps -> (img, pix, (n_comp, count, ints, vals, nan) | None)."""
+        img, pix = self.stage2(qs, keys)
+        return img, pix, (self._region_tail(pix) if regions else None)
+
+    def _region_tail(self, pix):
+        if self.region_spec is None:
+            return None
+        from .regions import region_tables_device
+        sp = self.region_spec
+        return region_tables_device(pix.view(pix.shape[0], self.gt, self.gt), self.thr, sp.min_area, sp.max_regions)
+
+    def set_thresholds(self, pixel, image=None):
+        """New thresholds from the next submit on: the pixel threshold is written into the device tensor in place, ordered on the
+        stream the scoring tail runs on (steps already submitted keep theirs; nothing is captured again); the image
+        threshold (None: no decisions) is applied by the tickets of later submits."""
+        if self.region_spec is None:
+            raise RuntimeError("BatchPredictor.set_thresholds: the predictor was built without regions=")
+        pixel = float(pixel)
+        if not math.isfinite(pixel) or (image is not None and not math.isfinite(float(image))):
+            raise ValueError("BatchPredictor.set_thresholds: NaN and infinity are not thresholds")
+        with torch.cuda.stream(self.post if self.use_graph else torch.cuda.current_stream()):
+            self.thr.fill_(pixel)
+        self.image_threshold = None if image is None else float(image)
+
+    def _outputs_to_host(self, out, slot):
+        """The step's results into the pinned ring slot, asynchronously on the current stream."""
+        host_s, host_m = self.ring[slot]
+        host_s.copy_(out[0], non_blocking=True)
+        if host_m is not None:
+            host_m.copy_(out[1], non_blocking=True)
+        if out[2] is not None:
+            for h, d in zip(self.region_ring[slot], out[2]):
+                h.copy_(d, non_blocking=True)
+
     def _capture(self):
         qs = self.stage1(self.inputs[0])  # one eager pass first: module loading / attribute setting must not happen in capture
-        self.stage2(qs, self.search(qs, 0))
+        self._tail(qs, self.search(qs, 0))
         torch.cuda.synchronize()
         # capture_error_mode="thread_local": with a process group alive, RCCL's watchdog THREAD polls the events of earlier
         # collectives (hipEventQuery); under the default "global" mode that call from another thread invalidates this thread's
@@ -319,11 +402,11 @@ class BatchPredictor:
                 k = {n: v.contiguous() for n, v in keys.items()}
                 g2 = None
                 if self.stage2_eager:       # fp32 rows sharded too: the scoring tail holds collectives and runs eagerly
-                    out = self.stage2(qs, k)
+                    out = self._tail(qs, k)
                 else:
                     g2 = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g2, capture_error_mode="thread_local"):
-                        out = self.stage2(qs, k)
+                        out = self._tail(qs, k, regions=False)
                 torch.cuda.synchronize()
                 sets.append(dict(g1=g1, g2=g2, qs=qs, k=k, out=out, done=None))
             self.sets = sets
@@ -400,7 +483,8 @@ class BatchPredictor:
                 inp["pcs"].copy_(pcs)
             torch.cuda.synchronize()
             self._capture()
-        host_s, host_m = self.ring[self.slot]
+        slot = self.slot
+        host_s, host_m = self.ring[slot]
         self.slot = (self.slot + 1) % len(self.ring)
         cur = torch.cuda.current_stream()
         if self.use_graph:
@@ -436,11 +520,10 @@ class BatchPredictor:
                     self._search_into(st, which)
                 if st["g2"] is not None:
                     st["g2"].replay()
+                    st["out"] = (st["out"][0], st["out"][1], self._region_tail(st["out"][1]))
                 else:
-                    st["out"] = self.stage2(st["qs"], st["k"])
-                s_dev, maps_dev = st["out"]
-                host_s.copy_(s_dev, non_blocking=True)
-                host_m.copy_(maps_dev, non_blocking=True)
+                    st["out"] = self._tail(st["qs"], st["k"])
+                self._outputs_to_host(st["out"], slot)
                 flag = self._flag_to_host()
                 ev = torch.cuda.Event()
                 ev.record()
@@ -457,9 +540,7 @@ class BatchPredictor:
             return self._ticket(host_s, host_m, ev, flag, rgb, pcs)
         self.step_no += 1
         qs = self._eager_stage1(rgb, pcs)
-        s_dev, maps_dev = self.stage2(qs, self.search(qs, 0))
-        host_s.copy_(s_dev, non_blocking=True)
-        host_m.copy_(maps_dev, non_blocking=True)
+        self._outputs_to_host(self._tail(qs, self.search(qs, 0)), slot)
         flag = self._flag_to_host()
         ev = torch.cuda.Event()
         ev.record()
@@ -514,13 +595,17 @@ class BatchPredictor:
         else:   # a fixed CMDIAD_SHARD_CAP below the live rows of this batch: nothing to re-read
             raise RuntimeError("BatchPredictor: the repeated batch still overflows the gather cap (CMDIAD_SHARD_CAP too small?); "
                                "its keys would be incomplete")
-        s_dev, maps_dev = self.stage2(qs, keys)
+        s_dev, maps_dev, reg = self._tail(qs, keys)
         B = s_dev.shape[0]
-        return s_dev.cpu().numpy().reshape(B).copy(), maps_dev.cpu().numpy().reshape(B, self.gt, self.gt).copy()
+        return (s_dev.cpu().numpy().reshape(B).copy(),
+                maps_dev.cpu().numpy().reshape(B, self.gt, self.gt).copy() if self.return_maps else None,
+                tuple(t.cpu().numpy() for t in reg) if reg is not None else None)
 
     def _ticket(self, host_s, host_m, ev, flag=None, rgb=None, pcs=None):
-        t = Ticket(host_s, host_m, ev, self.gt, flag, (lambda: self._redo(rgb, pcs)) if flag is not None else None)
-        self.tickets[(self.slot - 1) % len(self.ring)] = t
+        slot = (self.slot - 1) % len(self.ring)
+        t = Ticket(host_s, host_m, ev, self.gt, flag, (lambda: self._redo(rgb, pcs)) if flag is not None else None,
+                   self.region_ring[slot] if self.region_ring is not None else None, self.image_threshold)
+        self.tickets[slot] = t
         return t
 
     def predict_batch(self, rgb, pcs):

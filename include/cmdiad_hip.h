@@ -808,6 +808,35 @@ int cmdiad_auc_counts(const uint64_t* ok_sorted_keys, int n_ok, const double* de
 int cmdiad_pro_hist(const double* thr, int T, const double* def_score, const int32_t* def_comp, int n_def, int total_comp,
                     uint32_t* hist, cmdiad_stream_t stream);
 
+/* ---- defect regions of score maps (docs/regions.md; additions, the ABI stays 6).  Everything but score_sum is an integer or a
+ * stored double found by integer work (integer atomics only; no float goes through an atomic), so it is bit-exact whatever the
+ * order of arrival.  Sizes as for the labelling: n in 0..65535, H, W >= 1, H * W <= 2^24, n * H * W <= 2^30; n == 0 returns
+ * CMDIAD_OK without a launch. ---- */
+
+/* mask [n,H,W] uint8 = maps [n,H,W] f64 > thr, a comparison of doubles (-0.0 > +0.0 is false; a NaN score is background).  thr lives
+ * in DEVICE memory: [1] (thr_per_image = 0) or [n] (thr_per_image = 1), so a captured graph follows a threshold that is rewritten
+ * between replays.  nan_count [1] int32 (NULL: not wanted) = NaN scores; zeroed first, also when n == 0. */
+int cmdiad_threshold_mask(const double* maps, const double* thr, int thr_per_image, int n, int H, int W, uint8_t* mask,
+                          int32_t* nan_count, cmdiad_stream_t stream);
+
+/* The strongest regions of every image.  maps [n,H,W] f64 and the labels / n_comp / comp_offset / comp_size (comp_cap entries,
+ * comp_cap >= n ceil(H/2) ceil(W/2)) of the labelling of their mask.  Among the components of image i with comp_size >= min_area,
+ * count [n] int32 = how many there are, and the first max_regions (1..64) in the order (peak descending, label ascending; -0.0 and
+ * +0.0 are one peak) go to slots 0 .. min(count, max_regions) - 1 of
+ *   ints [n, max_regions, 8] int32: label, area, x0, y0, x1, y1 (inclusive box; x = column, y = row), peak_x, peak_y (the first
+ *     pixel in raster order whose score equals the peak),
+ *   vals [n, max_regions, 4] f64: peak (the stored double at peak_x, peak_y), score_sum, cx, cy (exact integer sums of the columns
+ *     / rows, one f64 division by the area each).
+ * The slots behind them are zero; count[i] > max_regions says the table was truncated.  score_sum is summed over the region's
+ * bounding box in raster order with a fixed lane assignment and a fixed reduction tree: it depends on the component's pixels alone,
+ * not on n, on i or on the run.  The per-component tables live in the workspace (8-byte aligned; the size query returns 0 for sizes
+ * that are refused); every index into them is checked against n ceil(H/2) ceil(W/2).  The launch geometry depends on n, H, W only:
+ * nothing is read back. */
+size_t cmdiad_region_table_workspace_bytes(int n, int H, int W);
+int cmdiad_region_table(const double* maps, const int32_t* labels, const int32_t* n_comp, const int32_t* comp_offset,
+                        const int32_t* comp_size, int comp_cap, int n, int H, int W, int min_area, int max_regions, int32_t* count,
+                        int32_t* ints, double* vals, void* workspace, size_t workspace_bytes, cmdiad_stream_t stream);
+
 /* ---- xyz TIFFs (docs/tiff.md; utils/mvtec3d_util.py:9-11 of the reference reads them with tifffile on the host) ----
  * raw [raw_bytes] = file bytes with UNCOMPRESSED chunks (dword aligned, raw_bytes a multiple of 4: the upload buffer is padded),
  * chunk_off [B, n_chunks] (device) = byte offset into raw of every chunk of every image -> out [B,H,W,C] of the files' own float type
