@@ -13,8 +13,7 @@ def greedy_coreset(z, n_select, coreset_dtype="FP16"):
     n, d = z.shape
     if coreset_dtype == "TF32":      # the fp32 scan (allow_tf32 changes matrix products only: the loop has none)
         out = torch.empty((n_select,), dtype=torch.int64, device=z.device)
-        wsb = nat.lib().cmdiad_coreset_f32_workspace_bytes(n, d, n_select)
-        ws = torch.empty((wsb + 7) // 8, dtype=torch.int64, device=z.device)
+        ws, wsb = ops._workspace("cmdiad_coreset_f32_workspace_bytes", z.device, n, d, n_select)
         nat.check(nat.lib().cmdiad_coreset_greedy_f32(ops._p(z), n, d, n_select, 0, ops._p(out), ops._p(ws), wsb, ops._stream()),
                   "cmdiad_coreset_greedy_f32")
         return out
@@ -22,8 +21,7 @@ def greedy_coreset(z, n_select, coreset_dtype="FP16"):
         z = torch.nn.functional.pad(z, (0, 1))
         d += 1
     out = torch.empty((n_select,), dtype=torch.int64, device=z.device)
-    wsb = nat.lib().cmdiad_coreset_workspace_bytes(n, d, n_select)
-    ws = torch.empty((wsb + 7) // 8, dtype=torch.int64, device=z.device)
+    ws, wsb = ops._workspace("cmdiad_coreset_workspace_bytes", z.device, n, d, n_select)
     nat.check(nat.lib().cmdiad_coreset_greedy(ops._p(z), n, d, n_select, 0, ops._p(out), ops._p(ws), wsb, ops._stream()),
               "cmdiad_coreset_greedy")
     return out
@@ -38,8 +36,7 @@ class _HipRounds:
         if z.shape[1] % 2:
             z = torch.nn.functional.pad(z, (0, 1))
         self.n, self.d = z.shape
-        wsb = nat.lib().cmdiad_coreset_workspace_bytes(self.n, self.d, 1)
-        self.ws = torch.empty((wsb + 7) // 8, dtype=torch.int64, device=z.device)
+        self.ws, wsb = ops._workspace("cmdiad_coreset_workspace_bytes", z.device, self.n, self.d, 1)
         nat.check(nat.lib().cmdiad_coreset_prepare(ops._p(z), self.n, self.d, 0, ops._p(self.ws), wsb, ops._stream()), "cmdiad_coreset_prepare")
 
     def round(self, lo, hi, pivot_key, out_key):

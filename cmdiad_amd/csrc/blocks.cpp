@@ -19,13 +19,21 @@ static bool pmae_mlp_fused_wanted(bool folded, int M, int C, int hidden)
     return M >= 192 * 128;
 }
 
+struct BlockWs {
+    uint16_t *h, *a, *m;   // [M, C]: LayerNorm output, or the raw rows as bf16 (folded) | [M, C]: attention output | [M, hidden]
+    float *part, *rstd;    // LayerNorm fold: chunk partials [C/64][M][2] | 1 / sigma per row (readable up to M rounded up to 256)
+    size_t total;
+};
+static BlockWs block_layout(void* base, int M, int C, int hidden)
+{
+    Carve c(base);
+    return {c.take<uint16_t>((size_t)M * C), c.take<uint16_t>((size_t)M * C), c.take<uint16_t>((size_t)M * hidden),
+            c.take<float>((size_t)(C / 64) * M * 2), c.take<float>(((size_t)M + 255) / 256 * 256), c.total()};
+}
+
 extern "C" size_t cmdiad_transformer_block_workspace_bytes(int M, int C, int hidden)
 {
-    if (M <= 0 || C <= 0 || hidden <= 0) return 0;
-    const size_t rows256 = ((size_t)M + 255) / 256 * 256;
-    return (size_t)M * (size_t)(2 * C + hidden) * sizeof(uint16_t)   // LN output / raw bf16 rows, attention output, MLP hidden (bf16)
-         + (size_t)(C / 64) * M * 2 * sizeof(float)                  // LayerNorm fold: chunk partials [C/64][M][2]
-         + rows256 * sizeof(float);                                  // ... and 1 / sigma per row (readable up to M rounded up to 256)
+    return M <= 0 || C <= 0 || hidden <= 0 ? 0 : block_layout(nullptr, M, C, hidden).total;
 }
 
 // models/models.py:177-180 (Block.forward; timm's ViT block has the same algebra, models.py:48):
@@ -42,19 +50,15 @@ extern "C" int cmdiad_transformer_block_fwd(float* x, const float* pos, const cm
     CMDIAD_REQUIRE(B > 0 && T > 0 && C > 0 && H > 0 && C == H * 64 && hidden > 0, CMDIAD_ERR_ARG,
                    "cmdiad_transformer_block_fwd: need C == 64*H (B=%d T=%d C=%d H=%d hidden=%d)", B, T, C, H, hidden);
     const int M = B * T;
-    CMDIAD_REQUIRE(workspace_bytes >= cmdiad_transformer_block_workspace_bytes(M, C, hidden), CMDIAD_ERR_WORKSPACE,
-                   "cmdiad_transformer_block_fwd: workspace %zu < %zu bytes", workspace_bytes,
-                   cmdiad_transformer_block_workspace_bytes(M, C, hidden));
+    const BlockWs L = block_layout(workspace, M, C, hidden);
+    if (const int rc = workspace_ok("cmdiad_transformer_block_fwd", workspace, workspace_bytes, L.total)) return rc;
+    uint16_t *const h = L.h, *const a = L.a, *const m = L.m;
+    float *const part = L.part, *const rstd = L.rstd;
     const bool folded = w->qkv_wf != nullptr;
     CMDIAD_REQUIRE(folded ? (w->qkv_bf && w->fc1_wf && w->fc1_bf) : (!w->qkv_bf && !w->fc1_wf && !w->fc1_bf), CMDIAD_ERR_ARG,
                    "cmdiad_transformer_block_fwd: the folded weights come as all four or none");
     CMDIAD_REQUIRE((flags & ~(CMDIAD_BLOCK_LN1_READY | CMDIAD_BLOCK_PREP_NEXT)) == 0 && (folded || flags == 0), CMDIAD_ERR_ARG,
                    "cmdiad_transformer_block_fwd: flags %d need the folded weights", flags);
-    uint16_t* h = (uint16_t*)workspace;            // [M, C]: LayerNorm output, or the raw rows as bf16 (folded)
-    uint16_t* a = h + (size_t)M * C;               // [M, C]
-    uint16_t* m = a + (size_t)M * C;               // [M, hidden]
-    float* part = (float*)(m + (size_t)M * hidden);          // [C/64][M][2]
-    float* rstd = part + (size_t)(C / 64) * M * 2;           // [M rounded up to 256]
     int rc;
     if (flags & CMDIAD_BLOCK_LN1_READY) {
         if ((rc = cmdiad_gemm_qkv(h, w->qkv_wf, w->qkv_bf, rstd, B, T, C, q, k, vt, stream))) return rc;

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/cmdiad_hip.h"
+#include "workspace.h"   // host only: Carve, workspace_ok
 
 typedef __bf16 bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;

@@ -262,13 +262,26 @@ __global__ void coreset_decode_kernel(const unsigned long long* __restrict__ bes
 
 }  // namespace
 
-static size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-
-extern "C" size_t cmdiad_coreset_workspace_bytes(int n, int d, int n_select)
+// fp16 selection: the row-major copy (the pivot row is fetched from it) | the transposed rows, n rounded up to 4 | the running
+// minima | the winner keys [n_select] (not used by the sharded prepare / round, which size the workspace with n_select = 1)
+struct CoresetWs { __half *z16, *zT, *min_d; unsigned long long* best; size_t total; };
+static CoresetWs coreset_layout(void* base, int n, int d, int n_select)
 {
     const size_t n4 = ((size_t)n + 3) / 4;
-    return up256((size_t)n * d * 2) + up256(n4 * 4 * (size_t)d * 2) + up256(n4 * 4 * 2) + (size_t)(n_select > 0 ? n_select : 1) * 8;
+    Carve c(base);
+    return {c.take<__half>((size_t)n * d, 256), c.take<__half>(n4 * 4 * (size_t)d, 256), c.take<__half>(n4 * 4, 256),
+            c.take<unsigned long long>(n_select > 0 ? n_select : 1), c.total()};
 }
+// fp32 selection: the pivot row is read from z32 itself
+struct CoresetF32Ws { float *zT, *min_d; unsigned long long* best; size_t total; };
+static CoresetF32Ws coreset_f32_layout(void* base, int n, int d, int n_select)
+{
+    const size_t n4 = ((size_t)n + 3) / 4;
+    Carve c(base);
+    return {c.take<float>(n4 * 4 * (size_t)d, 256), c.take<float>(n4 * 4, 256), c.take<unsigned long long>(n_select > 0 ? n_select : 1), c.total()};
+}
+
+extern "C" size_t cmdiad_coreset_workspace_bytes(int n, int d, int n_select) { return coreset_layout(nullptr, n, d, n_select).total; }
 
 // Row-sharded selection (SURVEY 8e "fit-time sharding"): every rank holds the whole projected library (the pivot row of a round can be
 // any row) but SCANS only its row range; per round one packed-key all_reduce(MAX) of 8 bytes between the ranks (the caller's: RCCL /
@@ -281,14 +294,10 @@ extern "C" int cmdiad_coreset_prepare(const float* z32, int n, int d, int first_
 {
     CMDIAD_REQUIRE(z32 && n > 0 && d > 0 && d % 2 == 0 && d <= 1024 && first_idx >= 0 && first_idx < n, CMDIAD_ERR_ARG,
                    "cmdiad_coreset_prepare: bad args (need d even, d <= 1024)");
-    CMDIAD_REQUIRE(workspace && workspace_bytes >= cmdiad_coreset_workspace_bytes(n, d, 1), CMDIAD_ERR_WORKSPACE,
-                   "cmdiad_coreset_prepare: workspace too small");
-    char* ws = (char*)workspace;
-    const int n4 = (n + 3) / 4;
-    __half* z16 = (__half*)ws;
-    __half* zT = (__half*)(ws + up256((size_t)n * d * 2));
-    __half* min_d = (__half*)((char*)zT + up256((size_t)n4 * 4 * d * 2));
-    hipLaunchKernelGGL(coreset_init_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, z32, n, n4, d, first_idx, z16, zT, min_d);
+    const CoresetWs L = coreset_layout(workspace, n, d, 1);
+    if (const int rc = workspace_ok("cmdiad_coreset_prepare", workspace, workspace_bytes, L.total)) return rc;
+    hipLaunchKernelGGL(coreset_init_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, z32, n, (n + 3) / 4, d, first_idx, L.z16, L.zT,
+                       L.min_d);
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
 }
@@ -300,17 +309,13 @@ extern "C" int cmdiad_coreset_round(void* workspace, int n, int d, int row_lo, i
                    CMDIAD_ERR_ARG, "cmdiad_coreset_round: bad args (0 <= row_lo <= row_hi <= n)");
     if (row_lo == row_hi) return CMDIAD_OK;     // an empty shard proposes nothing: its key stays 0 and loses the MAX (any row_lo)
     CMDIAD_REQUIRE(row_lo % 4 == 0, CMDIAD_ERR_ARG, "cmdiad_coreset_round: row_lo %% 4 == 0 (the scan owns groups of four rows)");
-    char* ws = (char*)workspace;
-    const int n4 = (n + 3) / 4;
-    __half* z16 = (__half*)ws;
-    __half* zT = (__half*)(ws + up256((size_t)n * d * 2));
-    __half* min_d = (__half*)((char*)zT + up256((size_t)n4 * 4 * d * 2));
+    const CoresetWs L = coreset_layout(workspace, n, d, 1);
     const int q0 = row_lo / 4, q1 = (row_hi + 3) / 4;
     // rows of the last group beyond row_hi belong to the next rank (or are padding): the shard boundaries are 4-row aligned except
     // at n itself, where the kernel's `row < n` test applies
     CMDIAD_REQUIRE(row_hi % 4 == 0 || row_hi == n, CMDIAD_ERR_ARG, "cmdiad_coreset_round: row_hi must be a multiple of 4 or n");
-    hipLaunchKernelGGL(coreset_round_kernel<true>, dim3((q1 - q0 + 255) / 256), dim3(256), 0, (hipStream_t)stream, z16, (const uint4*)zT, n, n4,
-                       d / 2, min_d, pivot_key, best_out, first_idx, q0, q1);
+    hipLaunchKernelGGL(coreset_round_kernel<true>, dim3((q1 - q0 + 255) / 256), dim3(256), 0, (hipStream_t)stream, L.z16, (const uint4*)L.zT, n,
+                       (n + 3) / 4, d / 2, L.min_d, pivot_key, best_out, first_idx, q0, q1);
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
 }
@@ -323,11 +328,7 @@ extern "C" int cmdiad_coreset_decode(const unsigned long long* keys, int n_selec
     return CMDIAD_OK;
 }
 
-extern "C" size_t cmdiad_coreset_f32_workspace_bytes(int n, int d, int n_select)
-{
-    const size_t n4 = ((size_t)n + 3) / 4;
-    return up256(n4 * 4 * (size_t)d * 4) + up256(n4 * 4 * 4) + (size_t)(n_select > 0 ? n_select : 1) * 8;
-}
+extern "C" size_t cmdiad_coreset_f32_workspace_bytes(int n, int d, int n_select) { return coreset_f32_layout(nullptr, n, d, n_select).total; }
 
 // coreset_dtype 'TF32': the selection on the fp32 rows (see coreset_round_f32_kernel); the pivot row is read from z32 itself.
 extern "C" int cmdiad_coreset_greedy_f32(const float* z32, int n, int d, int n_select, int first_idx, int64_t* idx_out,
@@ -335,24 +336,20 @@ extern "C" int cmdiad_coreset_greedy_f32(const float* z32, int n, int d, int n_s
 {
     CMDIAD_REQUIRE(z32 && idx_out && n > 0 && d > 0 && n_select > 0 && n_select <= n && d <= 1024, CMDIAD_ERR_ARG,
                    "cmdiad_coreset_greedy_f32: bad args (need d <= 1024)");
-    CMDIAD_REQUIRE(workspace && workspace_bytes >= cmdiad_coreset_f32_workspace_bytes(n, d, n_select), CMDIAD_ERR_WORKSPACE,
-                   "cmdiad_coreset_greedy_f32: workspace too small");
+    const CoresetF32Ws L = coreset_f32_layout(workspace, n, d, n_select);
+    if (const int rc = workspace_ok("cmdiad_coreset_greedy_f32", workspace, workspace_bytes, L.total)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
     const int n4 = (n + 3) / 4;
-    float* zT = (float*)ws;
-    float* min_d = (float*)(ws + up256((size_t)n4 * 4 * d * 4));
-    unsigned long long* best = (unsigned long long*)((char*)min_d + up256((size_t)n4 * 4 * 4));
-    if (hipMemsetAsync(best, 0, (size_t)n_select * 8, s) != hipSuccess) {
+    if (hipMemsetAsync(L.best, 0, (size_t)n_select * 8, s) != hipSuccess) {
         cmdiad_set_error("cmdiad_coreset_greedy_f32: memset failed");
         return CMDIAD_ERR_LAUNCH;
     }
-    hipLaunchKernelGGL(coreset_init_f32_kernel, dim3(2048), dim3(256), 0, s, z32, n, n4, d, first_idx, zT, min_d);
+    hipLaunchKernelGGL(coreset_init_f32_kernel, dim3(2048), dim3(256), 0, s, z32, n, n4, d, first_idx, L.zT, L.min_d);
     const int grid = (n4 + 255) / 256;
     for (int r = 0; r + 1 < n_select; ++r)
-        hipLaunchKernelGGL(coreset_round_f32_kernel, dim3(grid), dim3(256), 0, s, z32, (const float4*)zT, n, n4, d, min_d,
-                           r == 0 ? nullptr : best + (r - 1), best + r, first_idx);
-    hipLaunchKernelGGL(coreset_decode_kernel, dim3((n_select + 255) / 256), dim3(256), 0, s, best, n_select, first_idx, idx_out);
+        hipLaunchKernelGGL(coreset_round_f32_kernel, dim3(grid), dim3(256), 0, s, z32, (const float4*)L.zT, n, n4, d, L.min_d,
+                           r == 0 ? nullptr : L.best + (r - 1), L.best + r, first_idx);
+    hipLaunchKernelGGL(coreset_decode_kernel, dim3((n_select + 255) / 256), dim3(256), 0, s, L.best, n_select, first_idx, idx_out);
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
 }
@@ -362,29 +359,24 @@ extern "C" int cmdiad_coreset_greedy(const float* z32, int n, int d, int n_selec
 {
     CMDIAD_REQUIRE(z32 && idx_out && n > 0 && d > 0 && n_select > 0 && n_select <= n && d % 2 == 0 && d <= 1024, CMDIAD_ERR_ARG,
                    "cmdiad_coreset_greedy: bad args (need d even, d <= 1024)");
-    CMDIAD_REQUIRE(workspace && workspace_bytes >= cmdiad_coreset_workspace_bytes(n, d, n_select), CMDIAD_ERR_WORKSPACE,
-                   "cmdiad_coreset_greedy: workspace too small");
+    const CoresetWs L = coreset_layout(workspace, n, d, n_select);
+    if (const int rc = workspace_ok("cmdiad_coreset_greedy", workspace, workspace_bytes, L.total)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
     const int n4 = (n + 3) / 4;
-    __half* z16 = (__half*)ws;
-    __half* zT = (__half*)(ws + up256((size_t)n * d * 2));
-    __half* min_d = (__half*)((char*)zT + up256((size_t)n4 * 4 * d * 2));
-    unsigned long long* best = (unsigned long long*)((char*)min_d + up256((size_t)n4 * 4 * 2));
-    if (hipMemsetAsync(best, 0, (size_t)n_select * 8, s) != hipSuccess) {
+    if (hipMemsetAsync(L.best, 0, (size_t)n_select * 8, s) != hipSuccess) {
         cmdiad_set_error("cmdiad_coreset_greedy: memset failed");
         return CMDIAD_ERR_LAUNCH;
     }
-    hipLaunchKernelGGL(coreset_init_kernel, dim3(2048), dim3(256), 0, s, z32, n, n4, d, first_idx, z16, zT, min_d);
+    hipLaunchKernelGGL(coreset_init_kernel, dim3(2048), dim3(256), 0, s, z32, n, n4, d, first_idx, L.z16, L.zT, L.min_d);
     const int grid = (n4 + 255) / 256;
     const bool early = !env_is("CMDIAD_CORESET_EARLY", '0');   // =0: every row reads all its dimensions every round (A/B runs)
     for (int r = 0; r + 1 < n_select; ++r) {
-        if (early) hipLaunchKernelGGL(coreset_round_kernel<true>, dim3(grid), dim3(256), 0, s, z16, (const uint4*)zT, n, n4, d / 2, min_d,
-                                      r == 0 ? nullptr : best + (r - 1), best + r, first_idx, 0, n4);
-        else hipLaunchKernelGGL(coreset_round_kernel<false>, dim3(grid), dim3(256), 0, s, z16, (const uint4*)zT, n, n4, d / 2, min_d,
-                                r == 0 ? nullptr : best + (r - 1), best + r, first_idx, 0, n4);
+        if (early) hipLaunchKernelGGL(coreset_round_kernel<true>, dim3(grid), dim3(256), 0, s, L.z16, (const uint4*)L.zT, n, n4, d / 2, L.min_d,
+                                      r == 0 ? nullptr : L.best + (r - 1), L.best + r, first_idx, 0, n4);
+        else hipLaunchKernelGGL(coreset_round_kernel<false>, dim3(grid), dim3(256), 0, s, L.z16, (const uint4*)L.zT, n, n4, d / 2, L.min_d,
+                                r == 0 ? nullptr : L.best + (r - 1), L.best + r, first_idx, 0, n4);
     }
-    hipLaunchKernelGGL(coreset_decode_kernel, dim3((n_select + 255) / 256), dim3(256), 0, s, best, n_select, first_idx,
+    hipLaunchKernelGGL(coreset_decode_kernel, dim3((n_select + 255) / 256), dim3(256), 0, s, L.best, n_select, first_idx,
                        idx_out);
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;

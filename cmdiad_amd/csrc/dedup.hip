@@ -214,7 +214,6 @@ __global__ __launch_bounds__(256) void expand_keys_kernel(const unsigned long lo
 
 }  // namespace
 
-// workspace: tag [Q] u32 | info [4] i32 | dup [Q] u8 (padded to 16) | sums [ceil(Q / 1024)] i32
 __global__ __launch_bounds__(256) void expand_rows_f32_kernel(const float4* __restrict__ src, const int* __restrict__ slot, int Q, int D4,
                                                               float4* __restrict__ out)
 {
@@ -225,11 +224,16 @@ __global__ __launch_bounds__(256) void expand_rows_f32_kernel(const float4* __re
     for (int c = lane; c < D4; c += 64) b[c] = a[c];
 }
 
-extern "C" size_t cmdiad_rows_dedup_workspace_bytes(int Q)
+// workspace: tag [Q] u32 | info [4] i32 | dup [Q] u8 (padded to 16) | sums [ceil(Q / 1024)] i32
+struct DedupWs { unsigned* tag; int* info; unsigned char* dup; int* sums; size_t total; };
+static DedupWs dedup_layout(void* base, int Q)
 {
     const size_t q = (size_t)(Q > 0 ? Q : 0);
-    return q * 4 + 16 + ((q + 15) & ~(size_t)15) + (q + kPlanThreads - 1) / kPlanThreads * 4;
+    Carve c(base);
+    return {c.take<unsigned>(q, 4), c.take<int>(4, 16), c.take<unsigned char>(q, 16), c.take<int>((q + kPlanThreads - 1) / kPlanThreads, 4), c.total()};
 }
+
+extern "C" size_t cmdiad_rows_dedup_workspace_bytes(int Q) { return dedup_layout(nullptr, Q).total; }
 
 extern "C" int cmdiad_rows_dedup_plan(const uint16_t* q, const float* q_sqnorm, int Q, int D, void* workspace, int* slot, int* rows,
                                       int* count, uint16_t* q_compact, float* q_sqnorm_compact, cmdiad_stream_t stream)
@@ -239,18 +243,15 @@ extern "C" int cmdiad_rows_dedup_plan(const uint16_t* q, const float* q_sqnorm, 
     CMDIAD_REQUIRE(Q >= 0 && D > 0 && D % 8 == 0, CMDIAD_ERR_ARG, "cmdiad_rows_dedup_plan: need D%%8==0 (D=%d)", D);
     CMDIAD_REQUIRE(aligned16(q) && aligned16(q_compact), CMDIAD_ERR_ARG, "cmdiad_rows_dedup_plan: 16-byte alignment");
     hipStream_t s = (hipStream_t)stream;
-    unsigned* tag = (unsigned*)workspace;
-    int* info = (int*)(tag + (Q > 0 ? Q : 0));
-    unsigned char* dup = (unsigned char*)(info + 4);
+    const DedupWs L = dedup_layout(workspace, Q);
     const int nb = (Q + kPlanThreads - 1) / kPlanThreads;
-    int* sums = (int*)(dup + (((size_t)(Q > 0 ? Q : 0) + 15) & ~(size_t)15));
-    if (Q > 0) hipLaunchKernelGGL(hash_rows_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, q, Q, D, tag);
-    hipLaunchKernelGGL(pick_rep_kernel, dim3(1), dim3(kPlanThreads), 0, s, tag, Q, info);
-    if (Q > 0) hipLaunchKernelGGL(first_match_kernel, dim3(nb), dim3(kPlanThreads), 0, s, tag, Q, info);
-    if (Q > 0) hipLaunchKernelGGL(verify_rows_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, q, q_sqnorm, tag, info, Q, D, dup);
+    if (Q > 0) hipLaunchKernelGGL(hash_rows_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, q, Q, D, L.tag);
+    hipLaunchKernelGGL(pick_rep_kernel, dim3(1), dim3(kPlanThreads), 0, s, L.tag, Q, L.info);
+    if (Q > 0) hipLaunchKernelGGL(first_match_kernel, dim3(nb), dim3(kPlanThreads), 0, s, L.tag, Q, L.info);
+    if (Q > 0) hipLaunchKernelGGL(verify_rows_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, q, q_sqnorm, L.tag, L.info, Q, D, L.dup);
     if (Q > 0) {
-        hipLaunchKernelGGL(compact_count_kernel, dim3(nb), dim3(kPlanThreads), 0, s, dup, Q, sums);
-        hipLaunchKernelGGL(compact_write_kernel, dim3(nb), dim3(kPlanThreads), 0, s, dup, sums, info, Q, slot, rows, count);
+        hipLaunchKernelGGL(compact_count_kernel, dim3(nb), dim3(kPlanThreads), 0, s, L.dup, Q, L.sums);
+        hipLaunchKernelGGL(compact_write_kernel, dim3(nb), dim3(kPlanThreads), 0, s, L.dup, L.sums, L.info, Q, slot, rows, count);
     } else if (hipMemsetAsync(count, 0, sizeof(int), s) != hipSuccess) {
         cmdiad_set_error("cmdiad_rows_dedup_plan: hipMemsetAsync failed");
         return CMDIAD_ERR_LAUNCH;

@@ -311,11 +311,15 @@ __global__ __launch_bounds__(kThreads) void fps_mem_kernel(const float* __restri
 
 }  // namespace
 
-extern "C" size_t cmdiad_fps_workspace_bytes(int B, int N)
+// running minima of the points beyond the register + LDS tiers of fps_ragged_kernel (indexed by point: B * N floats); below, nothing
+struct FpsWs { float* min_d; size_t total; };
+static FpsWs fps_layout(void* base, int B, int N)
 {
-    // running minima of the points beyond the register + LDS tiers of fps_ragged_kernel (indexed by point: B * N floats)
-    return N > kMaxRegPoints + kMaxLdsPoints ? (size_t)B * (size_t)N * sizeof(float) : 0;
+    Carve c(base);
+    return {c.take<float>(N > kMaxRegPoints + kMaxLdsPoints ? (size_t)B * (size_t)N : 0), c.total()};
 }
+
+extern "C" size_t cmdiad_fps_workspace_bytes(int B, int N) { return fps_layout(nullptr, B, N).total; }
 
 extern "C" int cmdiad_fps(const float* xyz, const int32_t* n_valid, int B, int N, int G, int32_t* idx_out,
                           float* center_out, void* workspace, size_t workspace_bytes, cmdiad_stream_t stream)
@@ -344,11 +348,10 @@ extern "C" int cmdiad_fps(const float* xyz, const int32_t* n_valid, int B, int N
     const bool ragged = ragged_ok && N > 1024 * 16 && (n_valid != nullptr || N > kMaxRegPoints);
     if (ragged) {
         const int lds_cap = N > kMaxRegPoints ? (N - kMaxRegPoints < kMaxLdsPoints ? N - kMaxRegPoints : kMaxLdsPoints) : 0;
-        const size_t need = cmdiad_fps_workspace_bytes(B, N);
-        CMDIAD_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), CMDIAD_ERR_WORKSPACE,
-                       "cmdiad_fps: N=%d needs %zu workspace bytes", N, need);
+        const FpsWs L = fps_layout(workspace, B, N);
+        if (const int rc = workspace_ok("cmdiad_fps", workspace, workspace_bytes, L.total)) return rc;
         if (const int rc = launch_lds<fps_ragged_kernel>("cmdiad_fps", dim3(B), dim3(kRaggedThreads), (size_t)lds_cap * sizeof(float4), s, xyz, n_valid,
-                                                         N, G, lds_cap, need ? (float*)workspace : nullptr, idx_out, center_out))
+                                                         N, G, lds_cap, L.total ? L.min_d : nullptr, idx_out, center_out))
             return rc;
     }
     else if (N <= 1024 * 4) FPS_LAUNCH(1024, 4);
@@ -360,9 +363,10 @@ extern "C" int cmdiad_fps(const float* xyz, const int32_t* n_valid, int B, int N
 #undef FPS_LAUNCH
     else {
 #ifdef CMDIAD_AB_VARIANTS
-        const size_t need = (size_t)B * (size_t)N * sizeof(float);
-        CMDIAD_REQUIRE(workspace && workspace_bytes >= need, CMDIAD_ERR_WORKSPACE, "cmdiad_fps: N=%d needs %zu workspace bytes", N, need);
-        hipLaunchKernelGGL(fps_mem_kernel, dim3(B), dim3(kThreads), 0, s, xyz, n_valid, N, G, (float*)workspace, idx_out, center_out);
+        Carve c(workspace);   // the memory-resident loop keeps every point's running minimum there
+        float* const min_d = c.take<float>((size_t)B * (size_t)N);
+        if (const int rc = workspace_ok("cmdiad_fps", workspace, workspace_bytes, c.total())) return rc;
+        hipLaunchKernelGGL(fps_mem_kernel, dim3(B), dim3(kThreads), 0, s, xyz, n_valid, N, G, min_d, idx_out, center_out);
 #else
         cmdiad_set_error("cmdiad_fps: unreachable dispatch (N=%d)", N);
         return CMDIAD_ERR_ARG;

@@ -182,10 +182,15 @@ int gemm_residual_tiles_launch(const cmdiad_gemm_args* a, hipStream_t stream)
     return CMDIAD_OK;
 }
 
-extern "C" size_t cmdiad_gemm_streamk_workspace_bytes(void)
+// a hand-over slot per block | two counters per block
+struct SkWs { float* partial; unsigned* counters; size_t total; };
+static SkWs sk_layout(void* base)
 {
-    return (size_t)kPersistCUs * kSkSlotFloats * sizeof(float) + (size_t)kPersistCUs * 2 * sizeof(unsigned);
+    Carve c(base);
+    return {c.take<float>((size_t)kPersistCUs * kSkSlotFloats), c.take<unsigned>((size_t)kPersistCUs * 2), c.total()};
 }
+
+extern "C" size_t cmdiad_gemm_streamk_workspace_bytes(void) { return sk_layout(nullptr).total; }
 
 extern "C" int cmdiad_gemm_streamk_eligible(int M, int N, int K)
 {
@@ -208,13 +213,11 @@ extern "C" int cmdiad_gemm_streamk_bf16(const cmdiad_gemm_args* a, void* workspa
     CMDIAD_REQUIRE(a->lda % 8 == 0 && a->ldw % 8 == 0 && aligned16(a->A) && aligned16(a->W) && a->ldo32 % 4 == 0 && a->ldr % 4 == 0 &&
                        aligned16(a->out_f32) && aligned16(a->residual) && aligned16(a->bias) && aligned16(workspace),
                    CMDIAD_ERR_ARG, "cmdiad_gemm_streamk_bf16: 16-byte alignment, lda / ldw %% 8, ldo / ldr %% 4");
-    CMDIAD_REQUIRE(workspace_bytes >= cmdiad_gemm_streamk_workspace_bytes(), CMDIAD_ERR_WORKSPACE,
-                   "cmdiad_gemm_streamk_bf16: workspace %zu < %zu bytes", workspace_bytes, cmdiad_gemm_streamk_workspace_bytes());
+    const SkWs L = sk_layout(workspace);
+    if (const int rc = workspace_ok("cmdiad_gemm_streamk_bf16", workspace, workspace_bytes, L.total)) return rc;
     constexpr int kLds = SPP3::LDS_BYTES + 8 * kRowStoreScratch;
     GlobalTile A{(const bf16_t*)a->A, a->lda, a->M}, W{(const bf16_t*)a->W, a->ldw, a->N};
-    float* partial = (float*)workspace;
-    SkParams p{a->M, a->N, a->K, a->bias, a->residual, a->ldr, a->out_f32, a->ldo32, partial,
-               (unsigned*)(partial + (size_t)kPersistCUs * kSkSlotFloats)};
+    SkParams p{a->M, a->N, a->K, a->bias, a->residual, a->ldr, a->out_f32, a->ldo32, L.partial, L.counters};
     if (const int rc = launch_lds<gemm_sk_kernel>("cmdiad_gemm_streamk_bf16", dim3(kPersistCUs), dim3(512), kLds, (hipStream_t)stream, A, W, p)) return rc;
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;

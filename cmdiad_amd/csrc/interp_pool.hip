@@ -442,8 +442,8 @@ extern "C" int cmdiad_interp3nn_ws(const float* xyz, const int32_t* n_valid, con
     if (env_is("CMDIAD_INTERP_GRID", '0') || S < 64 || S > kMaxCentres || B <= 0 || N <= 0)
         return cmdiad_interp3nn(xyz, n_valid, center, B, N, S, idx3, w3, stream);
     CMDIAD_REQUIRE(xyz && center && idx3 && w3, CMDIAD_ERR_ARG, "cmdiad_interp3nn_ws: null pointer");
-    CMDIAD_REQUIRE(workspace && workspace_bytes >= cmdiad_interp3nn_workspace_bytes(B, S) && ((uintptr_t)workspace & 15) == 0,
-                   CMDIAD_ERR_WORKSPACE, "cmdiad_interp3nn_ws: workspace too small or not 16-byte aligned");
+    if (const int rc = workspace_ok("cmdiad_interp3nn_ws", workspace, workspace_bytes, cmdiad_interp3nn_workspace_bytes(B, S))) return rc;
+    CMDIAD_REQUIRE(aligned16(workspace), CMDIAD_ERR_WORKSPACE, "cmdiad_interp3nn_ws: the workspace must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(interp3nn_bin_kernel, dim3(B), dim3(256), 0, s, center, S, (char*)workspace);
     // (above 64 KiB of LDS from S = 3226 on)

@@ -489,8 +489,8 @@ extern "C" int cmdiad_knn_group_ws(const float* xyz, const int32_t* n_valid, con
     const bool grid = !env_is("CMDIAD_KNN_GRID", '0') && N >= 2048 && G > 0 && B > 0 && K > 0 && K <= 128 && K <= N;
     if (!grid) return cmdiad_knn_group(xyz, n_valid, center, B, N, G, K, idx_out, neigh_out, stream);
     CMDIAD_REQUIRE(xyz && center, CMDIAD_ERR_ARG, "cmdiad_knn_group_ws: null pointer");
-    CMDIAD_REQUIRE(workspace && workspace_bytes >= cmdiad_knn_workspace_bytes(B, N) && ((uintptr_t)workspace & 15) == 0, CMDIAD_ERR_WORKSPACE,
-                   "cmdiad_knn_group_ws: workspace too small or not 16-byte aligned");
+    if (const int rc = workspace_ok("cmdiad_knn_group_ws", workspace, workspace_bytes, cmdiad_knn_workspace_bytes(B, N))) return rc;
+    CMDIAD_REQUIRE(aligned16(workspace), CMDIAD_ERR_WORKSPACE, "cmdiad_knn_group_ws: the workspace must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(knn_grid_build_kernel, dim3(B), dim3(1024), 0, s, xyz, n_valid, N, (char*)workspace);
     hipLaunchKernelGGL((knn_grid_query_kernel<4>), dim3((G + 3) / 4, B), dim3(256), 0, s, xyz, n_valid, center, (const char*)workspace, N, G, K,

@@ -392,39 +392,26 @@ __global__ __launch_bounds__(256) void pro_hist_kernel(const double* __restrict_
     wave_agg_inc(hist, idx, active);
 }
 
-struct CclLayout {
-    int tiles;
-    size_t rank, tile_count, tile_off, total;
-};
-inline CclLayout ccl_layout(int n, int HW)
+// rank [n, HW] | roots per tile [n, tiles] | their exclusive scan per image
+struct CclWs { int tiles; int32_t *rank, *tile_count, *tile_off; size_t total; };
+inline CclWs ccl_layout(void* base, int n, int HW)
 {
-    CclLayout L;
-    L.tiles = (HW + kCclTile - 1) / kCclTile;
-    const size_t per = ((size_t)n * L.tiles * 4 + 255) & ~(size_t)255;
-    L.rank = 0;
-    L.tile_count = ((size_t)n * HW * 4 + 255) & ~(size_t)255;
-    L.tile_off = L.tile_count + per;
-    L.total = L.tile_off + per;
-    return L;
+    const int tiles = (HW + kCclTile - 1) / kCclTile;
+    Carve c(base);
+    return {tiles, c.take<int32_t>((size_t)n * HW, 256), c.take<int32_t>((size_t)n * tiles, 256), c.take<int32_t>((size_t)n * tiles, 256), c.total()};
 }
 inline bool ccl_sizes_ok(int n, int H, int W)
 {
     return n >= 0 && n <= kMaxImages && H >= 1 && W >= 1 && (long long)H * W <= kMaxImagePixels && (long long)n * H * W <= kMaxTotal;
 }
 
-struct SortLayout {
-    int nb;
-    size_t alt, table, totals, total;
-};
-inline SortLayout sort_layout(int n)
+// the second copy of the keys | digit counts [256][nb] | the digit totals (not padded)
+struct SortWs { int nb; unsigned long long* alt; uint32_t* table; int32_t* totals; size_t total; };
+inline SortWs sort_layout(void* base, int n)
 {
-    SortLayout L;
-    L.nb = (n + kSortTile - 1) / kSortTile;
-    L.alt = 0;
-    L.table = ((size_t)n * 8 + 255) & ~(size_t)255;
-    L.totals = L.table + (((size_t)L.nb * 256 * 4 + 255) & ~(size_t)255);
-    L.total = L.totals + 256 * 4;
-    return L;
+    const int nb = (n + kSortTile - 1) / kSortTile;
+    Carve c(base);
+    return {nb, c.take<unsigned long long>(n, 256), c.take<uint32_t>((size_t)nb * 256, 256), c.take<int32_t>(256), c.total()};
 }
 
 inline unsigned blocks256(int n) { return (unsigned)((n + 255) / 256); }
@@ -433,7 +420,7 @@ inline unsigned blocks256(int n) { return (unsigned)((n + 255) / 256); }
 
 extern "C" size_t cmdiad_ccl_workspace_bytes(int n, int H, int W)
 {
-    return ccl_sizes_ok(n, H, W) && n > 0 ? ccl_layout(n, H * W).total : 0;
+    return ccl_sizes_ok(n, H, W) && n > 0 ? ccl_layout(nullptr, n, H * W).total : 0;
 }
 
 extern "C" int cmdiad_ccl_label(const void* masks, int mask_is_u8, int n, int H, int W, int32_t* labels, int32_t* n_comp,
@@ -450,17 +437,12 @@ extern "C" int cmdiad_ccl_label(const void* masks, int mask_is_u8, int n, int H,
     }
     CMDIAD_REQUIRE(masks && labels && n_comp && comp_offset && comp_size && workspace, CMDIAD_ERR_ARG, "cmdiad_ccl_label: null pointer");
     const int HW = H * W;
-    const CclLayout L = ccl_layout(n, HW);
-    CMDIAD_REQUIRE(workspace_bytes >= L.total, CMDIAD_ERR_WORKSPACE, "cmdiad_ccl_label: workspace of %zu bytes, %zu needed",
-                   workspace_bytes, L.total);
+    const CclWs L = ccl_layout(workspace, n, HW);
+    if (const int rc = workspace_ok("cmdiad_ccl_label", workspace, workspace_bytes, L.total)) return rc;
     // the pixels of a 2 x 2 cell touch one another, so a cell meets at most one component: at most ceil(H/2) ceil(W/2) per image
     const long long most = (long long)n * ((H + 1) / 2) * ((W + 1) / 2);
     CMDIAD_REQUIRE(comp_cap >= most, CMDIAD_ERR_ARG, "cmdiad_ccl_label: comp_size holds %d components, %lld are possible (n ceil(H/2) ceil(W/2))",
                    comp_cap, most);
-    char* w = (char*)workspace;
-    int32_t* rank = (int32_t*)(w + L.rank);
-    int32_t* tile_count = (int32_t*)(w + L.tile_count);
-    int32_t* tile_off = (int32_t*)(w + L.tile_off);
     const dim3 px(blocks256(HW), (unsigned)n), tl((unsigned)L.tiles, (unsigned)n);
     CMDIAD_CHECK_HIP(hipMemsetAsync(comp_size, 0, (size_t)comp_cap * 4, s));
     if (nonbinary) CMDIAD_CHECK_HIP(hipMemsetAsync(nonbinary, 0, sizeof(int32_t), s));
@@ -469,15 +451,15 @@ extern "C" int cmdiad_ccl_label(const void* masks, int mask_is_u8, int n, int H,
     CMDIAD_CHECK_LAUNCH();
     hipLaunchKernelGGL(ccl_union_kernel, px, dim3(256), 0, s, labels, HW, W);
     CMDIAD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ccl_count_kernel, tl, dim3(256), 0, s, labels, HW, L.tiles, tile_count);
+    hipLaunchKernelGGL(ccl_count_kernel, tl, dim3(256), 0, s, labels, HW, L.tiles, L.tile_count);
     CMDIAD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(row_excl_scan_kernel, dim3((unsigned)n), dim3(256), 0, s, (const int32_t*)tile_count, tile_off, L.tiles, n_comp);
+    hipLaunchKernelGGL(row_excl_scan_kernel, dim3((unsigned)n), dim3(256), 0, s, (const int32_t*)L.tile_count, L.tile_off, L.tiles, n_comp);
     CMDIAD_CHECK_LAUNCH();
     hipLaunchKernelGGL(row_excl_scan_kernel, dim3(1), dim3(256), 0, s, (const int32_t*)n_comp, comp_offset, n, comp_offset + n);
     CMDIAD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ccl_rank_kernel, tl, dim3(256), 0, s, (const int32_t*)labels, HW, L.tiles, (const int32_t*)tile_off, rank);
+    hipLaunchKernelGGL(ccl_rank_kernel, tl, dim3(256), 0, s, (const int32_t*)labels, HW, L.tiles, (const int32_t*)L.tile_off, L.rank);
     CMDIAD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ccl_relabel_kernel, px, dim3(256), 0, s, labels, HW, (const int32_t*)rank, (const int32_t*)comp_offset, comp_size,
+    hipLaunchKernelGGL(ccl_relabel_kernel, px, dim3(256), 0, s, labels, HW, (const int32_t*)L.rank, (const int32_t*)comp_offset, comp_size,
                        comp_cap);
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
@@ -507,29 +489,25 @@ extern "C" int cmdiad_keys_to_f64(const uint64_t* keys, int n, double* out, cmdi
 
 extern "C" size_t cmdiad_sort_u64_tile(void) { return kSortTile; }
 
-extern "C" size_t cmdiad_sort_u64_workspace_bytes(int n) { return n > 0 && n <= kMaxTotal ? sort_layout(n).total : 0; }
+extern "C" size_t cmdiad_sort_u64_workspace_bytes(int n) { return n > 0 && n <= kMaxTotal ? sort_layout(nullptr, n).total : 0; }
 
 extern "C" int cmdiad_sort_u64(uint64_t* keys, int n, void* workspace, size_t workspace_bytes, cmdiad_stream_t stream)
 {
     CMDIAD_REQUIRE(n >= 0 && n <= kMaxTotal, CMDIAD_ERR_ARG, "cmdiad_sort_u64: bad size n=%d (0..%d)", n, kMaxTotal);
     if (n == 0) return CMDIAD_OK;
     CMDIAD_REQUIRE(keys && workspace, CMDIAD_ERR_ARG, "cmdiad_sort_u64: null pointer");
-    const SortLayout L = sort_layout(n);
-    CMDIAD_REQUIRE(workspace_bytes >= L.total, CMDIAD_ERR_WORKSPACE, "cmdiad_sort_u64: workspace of %zu bytes, %zu needed",
-                   workspace_bytes, L.total);
+    const SortWs L = sort_layout(workspace, n);
+    if (const int rc = workspace_ok("cmdiad_sort_u64", workspace, workspace_bytes, L.total)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    char* w = (char*)workspace;
     unsigned long long* a = (unsigned long long*)keys;
-    unsigned long long* b = (unsigned long long*)(w + L.alt);
-    uint32_t* table = (uint32_t*)(w + L.table);
-    int32_t* totals = (int32_t*)(w + L.totals);
+    unsigned long long* b = L.alt;
     for (int shift = 0; shift < 64; shift += 8) {   // eight passes: the result ends where it started
-        hipLaunchKernelGGL(sort_hist_kernel, dim3((unsigned)L.nb), dim3(256), 0, s, (const unsigned long long*)a, n, shift, L.nb, table);
+        hipLaunchKernelGGL(sort_hist_kernel, dim3((unsigned)L.nb), dim3(256), 0, s, (const unsigned long long*)a, n, shift, L.nb, L.table);
         CMDIAD_CHECK_LAUNCH();
-        hipLaunchKernelGGL(row_excl_scan_kernel, dim3(256), dim3(256), 0, s, (const int32_t*)table, (int32_t*)table, L.nb, totals);
+        hipLaunchKernelGGL(row_excl_scan_kernel, dim3(256), dim3(256), 0, s, (const int32_t*)L.table, (int32_t*)L.table, L.nb, L.totals);
         CMDIAD_CHECK_LAUNCH();
         hipLaunchKernelGGL(sort_scatter_kernel, dim3((unsigned)L.nb), dim3(256), 0, s, (const unsigned long long*)a, b, n, shift, L.nb,
-                           (const uint32_t*)table, (const int32_t*)totals);
+                           (const uint32_t*)L.table, (const int32_t*)L.totals);
         CMDIAD_CHECK_LAUNCH();
         unsigned long long* t = a;
         a = b;

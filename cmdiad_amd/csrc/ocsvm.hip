@@ -182,16 +182,32 @@ __global__ __launch_bounds__(64) void ocsvm_epoch_kernel(const float* __restrict
     }
 }
 
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+// Fisher-Yates targets j, the permutation P, the two epoch orders | the swap keys, unsorted and sorted | the gathered rows | the
+// SGD state | the xorshift table (4 KiB) | hipcub's temporary storage for the sort of the n - 1 keys
+struct OcsvmWs {
+    int *j, *P, *order_a, *order_b;
+    unsigned long long *keys, *keys_sorted;
+    float* xp;
+    SgdState* st;
+    unsigned* pow2;
+    void* sort_tmp;
+    size_t sort_tmp_bytes, total;
+};
+OcsvmWs ocsvm_layout(void* base, int n, int F)
+{
+    Carve c(base);
+    OcsvmWs L{c.take<int>(n, 256), c.take<int>(n, 256), c.take<int>(n, 256), c.take<int>(n, 256), c.take<unsigned long long>(n, 256),
+              c.take<unsigned long long>(n, 256), c.take<float>((size_t)n * F, 256), c.take<SgdState>(1, 256), c.take<unsigned>(1024),
+              nullptr, 0, 0};
+    (void)hipcub::DeviceRadixSort::SortKeys(nullptr, L.sort_tmp_bytes, L.keys, L.keys_sorted, n > 1 ? n - 1 : 1);
+    L.sort_tmp = c.take<char>(L.sort_tmp_bytes, 256);
+    L.total = c.total();
+    return L;
+}
 
 }  // namespace
 
-extern "C" size_t cmdiad_ocsvm_fit_workspace_bytes(int n, int F)
-{
-    size_t sort_tmp = 0;
-    (void)hipcub::DeviceRadixSort::SortKeys(nullptr, sort_tmp, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, n > 1 ? n - 1 : 1);
-    return up256((size_t)n * 4) * 4 + up256((size_t)n * 8) * 2 + up256((size_t)n * F * 4) + up256(sort_tmp) + up256(sizeof(SgdState)) + 4096;
-}
+extern "C" size_t cmdiad_ocsvm_fit_workspace_bytes(int n, int F) { return ocsvm_layout(nullptr, n, F).total; }
 
 // X [n, F] float32 on the device -> coef_out[F] (float, host), *offset_out, *n_iter_out (host).  pow2[32][32]: column b of
 // M^(2^e) for the xorshift32 step M (computed by the caller: cmdiad_amd/ocsvm.py).  Synchronous: the stopping rule is evaluated
@@ -202,31 +218,20 @@ extern "C" int cmdiad_ocsvm_fit(const float* X, int n, int F, double nu, int max
 {
     CMDIAD_REQUIRE(X && pow2_host && coef_out && offset_out && n_iter_out && workspace, CMDIAD_ERR_ARG, "cmdiad_ocsvm_fit: null pointer");
     CMDIAD_REQUIRE(n >= 2 && F >= 1 && F <= 4 && nu > 0.0 && max_iter >= 1, CMDIAD_ERR_ARG, "cmdiad_ocsvm_fit: need n >= 2, 1 <= F <= 4 (n=%d F=%d)", n, F);
-    CMDIAD_REQUIRE(workspace_bytes >= cmdiad_ocsvm_fit_workspace_bytes(n, F), CMDIAD_ERR_WORKSPACE, "cmdiad_ocsvm_fit: workspace too small");
+    const OcsvmWs L = ocsvm_layout(workspace, n, F);
+    if (const int rc = workspace_ok("cmdiad_ocsvm_fit", workspace, workspace_bytes, L.total)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    int* j = (int*)ws; ws += up256((size_t)n * 4);
-    int* P = (int*)ws; ws += up256((size_t)n * 4);
-    int* order_a = (int*)ws; ws += up256((size_t)n * 4);
-    int* order_b = (int*)ws; ws += up256((size_t)n * 4);
-    unsigned long long* keys = (unsigned long long*)ws; ws += up256((size_t)n * 8);
-    unsigned long long* keys_sorted = (unsigned long long*)ws; ws += up256((size_t)n * 8);
-    float* xp = (float*)ws; ws += up256((size_t)n * F * 4);
-    SgdState* st = (SgdState*)ws; ws += up256(sizeof(SgdState));
-    unsigned* pow2 = (unsigned*)ws; ws += 4096;
-    size_t sort_tmp = 0;
-    (void)hipcub::DeviceRadixSort::SortKeys(nullptr, sort_tmp, keys, keys_sorted, n - 1);
-    void* sort_ws = ws;
 
 #define OCSVM_HIP(call) do { if ((call) != hipSuccess) { cmdiad_set_error("cmdiad_ocsvm_fit: %s failed", #call); return CMDIAD_ERR_LAUNCH; } } while (0)
-    OCSVM_HIP(hipMemcpyAsync(pow2, pow2_host, 4096, hipMemcpyHostToDevice, s));
+    OCSVM_HIP(hipMemcpyAsync(L.pow2, pow2_host, 4096, hipMemcpyHostToDevice, s));
     const unsigned sd = seed == 0 ? 1u : seed;   // our_rand_r: "seed shouldn't ever be 0"
     const int nb = (n + 255) / 256;
-    hipLaunchKernelGGL(fy_targets_kernel, dim3((unsigned)(((long long)n + 64 * 256 - 1) / (64 * 256))), dim3(256), 0, s, pow2, sd, n, j);
-    hipLaunchKernelGGL(fy_keys_kernel, dim3(nb), dim3(256), 0, s, j, n, keys);
-    OCSVM_HIP(hipcub::DeviceRadixSort::SortKeys(sort_ws, sort_tmp, keys, keys_sorted, n - 1, 0, 64, s));
-    hipLaunchKernelGGL(fy_chase_kernel, dim3(nb), dim3(256), 0, s, j, keys_sorted, n, P);
-    hipLaunchKernelGGL(iota_kernel, dim3(nb), dim3(256), 0, s, order_a, n);
+    hipLaunchKernelGGL(fy_targets_kernel, dim3((unsigned)(((long long)n + 64 * 256 - 1) / (64 * 256))), dim3(256), 0, s, L.pow2, sd, n, L.j);
+    hipLaunchKernelGGL(fy_keys_kernel, dim3(nb), dim3(256), 0, s, L.j, n, L.keys);
+    size_t sort_tmp_bytes = L.sort_tmp_bytes;
+    OCSVM_HIP(hipcub::DeviceRadixSort::SortKeys(L.sort_tmp, sort_tmp_bytes, L.keys, L.keys_sorted, n - 1, 0, 64, s));
+    hipLaunchKernelGGL(fy_chase_kernel, dim3(nb), dim3(256), 0, s, L.j, L.keys_sorted, n, L.P);
+    hipLaunchKernelGGL(iota_kernel, dim3(nb), dim3(256), 0, s, L.order_a, n);
 
     // SGDOneClassSVM._fit: alpha = nu / 2, coef_ = 0, offset_ = 0 -> intercept = 1, t_ = 1; 'optimal': typw = sqrt(1 / sqrt(alpha)),
     // eta0 = typw / max(1, dloss(1, -typw)) with Hinge.dloss(y = 1, p = -typw) = -1 -> eta0 = typw, optimal_init = 1 / (eta0 alpha)
@@ -238,24 +243,24 @@ extern "C" int cmdiad_ocsvm_fit(const float* X, int n, int F, double nu, int max
     h.intercept = 1.0;
     h.t = 1.0;
     h.wscale = 1.0;
-    OCSVM_HIP(hipMemcpyAsync(st, &h, sizeof(h), hipMemcpyHostToDevice, s));
+    OCSVM_HIP(hipMemcpyAsync(L.st, &h, sizeof(h), hipMemcpyHostToDevice, s));
     double best_loss = INFINITY;
     int no_improve = 0, epoch = 0;
-    int* oin = order_a;
-    int* oout = order_b;
+    int* oin = L.order_a;
+    int* oout = L.order_b;
     for (epoch = 0; epoch < max_iter; ++epoch) {
         switch (F) {
-        case 1: hipLaunchKernelGGL(gather_order_kernel<1>, dim3(nb), dim3(256), 0, s, oin, P, X, n, oout, xp);
-                hipLaunchKernelGGL(ocsvm_epoch_kernel<1>, dim3(1), dim3(64), 0, s, xp, n, alpha, optimal_init, st); break;
-        case 2: hipLaunchKernelGGL(gather_order_kernel<2>, dim3(nb), dim3(256), 0, s, oin, P, X, n, oout, xp);
-                hipLaunchKernelGGL(ocsvm_epoch_kernel<2>, dim3(1), dim3(64), 0, s, xp, n, alpha, optimal_init, st); break;
-        case 3: hipLaunchKernelGGL(gather_order_kernel<3>, dim3(nb), dim3(256), 0, s, oin, P, X, n, oout, xp);
-                hipLaunchKernelGGL(ocsvm_epoch_kernel<3>, dim3(1), dim3(64), 0, s, xp, n, alpha, optimal_init, st); break;
-        default: hipLaunchKernelGGL(gather_order_kernel<4>, dim3(nb), dim3(256), 0, s, oin, P, X, n, oout, xp);
-                 hipLaunchKernelGGL(ocsvm_epoch_kernel<4>, dim3(1), dim3(64), 0, s, xp, n, alpha, optimal_init, st); break;
+        case 1: hipLaunchKernelGGL(gather_order_kernel<1>, dim3(nb), dim3(256), 0, s, oin, L.P, X, n, oout, L.xp);
+                hipLaunchKernelGGL(ocsvm_epoch_kernel<1>, dim3(1), dim3(64), 0, s, L.xp, n, alpha, optimal_init, L.st); break;
+        case 2: hipLaunchKernelGGL(gather_order_kernel<2>, dim3(nb), dim3(256), 0, s, oin, L.P, X, n, oout, L.xp);
+                hipLaunchKernelGGL(ocsvm_epoch_kernel<2>, dim3(1), dim3(64), 0, s, L.xp, n, alpha, optimal_init, L.st); break;
+        case 3: hipLaunchKernelGGL(gather_order_kernel<3>, dim3(nb), dim3(256), 0, s, oin, L.P, X, n, oout, L.xp);
+                hipLaunchKernelGGL(ocsvm_epoch_kernel<3>, dim3(1), dim3(64), 0, s, L.xp, n, alpha, optimal_init, L.st); break;
+        default: hipLaunchKernelGGL(gather_order_kernel<4>, dim3(nb), dim3(256), 0, s, oin, L.P, X, n, oout, L.xp);
+                 hipLaunchKernelGGL(ocsvm_epoch_kernel<4>, dim3(1), dim3(64), 0, s, L.xp, n, alpha, optimal_init, L.st); break;
         }
         int* tmp = oin; oin = oout; oout = tmp;
-        OCSVM_HIP(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, s));
+        OCSVM_HIP(hipMemcpyAsync(&h, L.st, sizeof(h), hipMemcpyDeviceToHost, s));
         OCSVM_HIP(hipStreamSynchronize(s));
         bool finite = std::isfinite(h.intercept);
         for (int f = 0; f < F; ++f) finite = finite && std::isfinite(h.w[f]);

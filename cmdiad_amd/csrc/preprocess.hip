@@ -229,37 +229,29 @@ struct __attribute__((aligned(16))) SortedPoint {
     int i;   // index in the caller's array
 };
 
-struct Layout {
-    size_t params, bbox, start, count, key, spts, core, parent, comp, minorig, rank, total;
-    int maxc;
-};
-
 inline int dbscan_max_cells(int N)
 {
     const long long c = 2ll * (long long)N;
     return (int)(c < 4096 ? 4096 : (c > (1ll << 21) ? (1ll << 21) : c));
 }
 
-inline Layout dbscan_layout(int N)
+struct DbscanWs {
+    int maxc;
+    GridParams* gp;
+    uint32_t* bbox;
+    int *start, *count, *key;
+    SortedPoint* sp;
+    int *core, *parent, *comp, *minorig, *rank;
+    size_t total;
+};
+inline DbscanWs dbscan_layout(void* base, int N)
 {
-    Layout L;
-    L.maxc = dbscan_max_cells(N);
-    size_t o = 0;
-    auto take = [&o](size_t bytes) { const size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
+    const int maxc = dbscan_max_cells(N);
     const size_t n = (size_t)(N > 0 ? N : 1);
-    L.params = take(sizeof(GridParams));
-    L.bbox = take(6 * sizeof(uint32_t));
-    L.start = take(((size_t)L.maxc + 1) * 4);
-    L.count = take((size_t)L.maxc * 4);
-    L.key = take(n * 4);
-    L.spts = take(n * sizeof(SortedPoint));
-    L.core = take(n * 4);
-    L.parent = take(n * 4);
-    L.comp = take(n * 4);
-    L.minorig = take(n * 4);
-    L.rank = take((n + 1) * 4);
-    L.total = o;
-    return L;
+    Carve c(base);   // every piece padded to 256 bytes
+    return {maxc, c.take<GridParams>(1, 256), c.take<uint32_t>(6, 256), c.take<int>((size_t)maxc + 1, 256), c.take<int>(maxc, 256),
+            c.take<int>(n, 256), c.take<SortedPoint>(n, 256), c.take<int>(n, 256), c.take<int>(n, 256), c.take<int>(n, 256),
+            c.take<int>(n, 256), c.take<int>(n + 1, 256), c.total()};
 }
 
 // order-preserving map float -> uint32 (for atomicMin / atomicMax on coordinates)
@@ -604,10 +596,15 @@ __global__ __launch_bounds__(256) void cluster_keep_kernel(const int32_t* __rest
 
 }  // namespace
 
-extern "C" size_t cmdiad_plane_ransac_workspace_bytes(int iterations)
+// the winning hypothesis' key (in 256 bytes of its own) | a plane per hypothesis
+struct RansacWs { unsigned long long* best; double* planes; size_t total; };
+static RansacWs ransac_layout(void* base, int iterations)
 {
-    return iterations > 0 ? 256 + (size_t)iterations * 4 * sizeof(double) : 0;
+    Carve c(base);
+    return {c.take<unsigned long long>(1, 256), c.take<double>((size_t)iterations * 4), c.total()};
 }
+
+extern "C" size_t cmdiad_plane_ransac_workspace_bytes(int iterations) { return iterations > 0 ? ransac_layout(nullptr, iterations).total : 0; }
 
 extern "C" int cmdiad_plane_ransac(const float* points, int E, int n, int iterations, double distance_threshold, uint32_t seed,
                                    double* plane_out, int32_t* info_out, void* workspace, size_t workspace_bytes,
@@ -617,18 +614,15 @@ extern "C" int cmdiad_plane_ransac(const float* points, int E, int n, int iterat
     CMDIAD_REQUIRE(n >= 3 && n <= 64 && E >= n && iterations >= 1 && iterations <= (1 << 20) && distance_threshold > 0.0,
                    CMDIAD_ERR_ARG, "cmdiad_plane_ransac: bad sizes E=%d n=%d (3..64, <= E) iterations=%d threshold=%g", E, n,
                    iterations, distance_threshold);
-    CMDIAD_REQUIRE(workspace_bytes >= cmdiad_plane_ransac_workspace_bytes(iterations), CMDIAD_ERR_WORKSPACE,
-                   "cmdiad_plane_ransac: workspace of %zu bytes, %zu needed", workspace_bytes,
-                   cmdiad_plane_ransac_workspace_bytes(iterations));
+    const RansacWs L = ransac_layout(workspace, iterations);
+    if (const int rc = workspace_ok("cmdiad_plane_ransac", workspace, workspace_bytes, L.total)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    unsigned long long* best = (unsigned long long*)workspace;
-    double* planes = (double*)((char*)workspace + 256);
-    CMDIAD_CHECK_HIP(hipMemsetAsync(best, 0, sizeof(unsigned long long), s));
+    CMDIAD_CHECK_HIP(hipMemsetAsync(L.best, 0, sizeof(unsigned long long), s));
     hipLaunchKernelGGL(plane_hypothesis_kernel, dim3(iterations), dim3(kPlaneThreads), 0, s, points, E, n, seed, distance_threshold,
-                       planes, best);
+                       L.planes, L.best);
     CMDIAD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(plane_refit_kernel, dim3(1), dim3(kPlaneThreads), 0, s, points, E, distance_threshold, (const double*)planes,
-                       (const unsigned long long*)best, plane_out, info_out);
+    hipLaunchKernelGGL(plane_refit_kernel, dim3(1), dim3(kPlaneThreads), 0, s, points, E, distance_threshold, (const double*)L.planes,
+                       (const unsigned long long*)L.best, plane_out, info_out);
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
 }
@@ -646,7 +640,7 @@ extern "C" int cmdiad_plane_mask(float* pc, uint8_t* rgb, size_t n_points, int r
     return CMDIAD_OK;
 }
 
-extern "C" size_t cmdiad_dbscan_workspace_bytes(int N) { return N < 0 ? 0 : dbscan_layout(N).total; }
+extern "C" size_t cmdiad_dbscan_workspace_bytes(int N) { return N < 0 ? 0 : dbscan_layout(nullptr, N).total; }
 
 extern "C" int cmdiad_dbscan(const float* points, int N, double eps, int min_points, int32_t* labels, int32_t* n_clusters,
                              void* workspace, size_t workspace_bytes, cmdiad_stream_t stream)
@@ -654,59 +648,46 @@ extern "C" int cmdiad_dbscan(const float* points, int N, double eps, int min_poi
     CMDIAD_REQUIRE(points && labels && n_clusters && workspace, CMDIAD_ERR_ARG, "cmdiad_dbscan: null pointer");
     CMDIAD_REQUIRE(N >= 0 && N <= kMaxPoints && eps > 0.0 && eps <= 1e30 && min_points >= 1, CMDIAD_ERR_ARG,
                    "cmdiad_dbscan: bad sizes N=%d (0..%d) eps=%g min_points=%d", N, kMaxPoints, eps, min_points);
-    const Layout L = dbscan_layout(N);
-    CMDIAD_REQUIRE(workspace_bytes >= L.total, CMDIAD_ERR_WORKSPACE, "cmdiad_dbscan: workspace of %zu bytes, %zu needed",
-                   workspace_bytes, L.total);
+    const DbscanWs L = dbscan_layout(workspace, N);
+    if (const int rc = workspace_ok("cmdiad_dbscan", workspace, workspace_bytes, L.total)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (N == 0) {
         CMDIAD_CHECK_HIP(hipMemsetAsync(n_clusters, 0, sizeof(int32_t), s));
         return CMDIAD_OK;
     }
-    char* w = (char*)workspace;
-    GridParams* gp = (GridParams*)(w + L.params);
-    uint32_t* bbox = (uint32_t*)(w + L.bbox);
-    int* start = (int*)(w + L.start);
-    int* count = (int*)(w + L.count);
-    int* key = (int*)(w + L.key);
-    SortedPoint* sp = (SortedPoint*)(w + L.spts);
-    int* core = (int*)(w + L.core);
-    int* parent = (int*)(w + L.parent);
-    int* comp = (int*)(w + L.comp);
-    int* minorig = (int*)(w + L.minorig);
-    int* rank = (int*)(w + L.rank);
     const double eps2 = eps * eps;
     const unsigned blocks = (unsigned)((N + 255) / 256);
-    CMDIAD_CHECK_HIP(hipMemsetAsync(bbox, 0xFF, 3 * sizeof(uint32_t), s));
-    CMDIAD_CHECK_HIP(hipMemsetAsync(bbox + 3, 0, 3 * sizeof(uint32_t), s));
-    CMDIAD_CHECK_HIP(hipMemsetAsync(count, 0, (size_t)L.maxc * 4, s));
-    CMDIAD_CHECK_HIP(hipMemsetAsync(minorig, 0x7F, (size_t)N * 4, s));
-    CMDIAD_CHECK_HIP(hipMemsetAsync(rank, 0, ((size_t)N + 1) * 4, s));
-    hipLaunchKernelGGL(dbscan_bbox_kernel, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, s, points, N, bbox);
+    CMDIAD_CHECK_HIP(hipMemsetAsync(L.bbox, 0xFF, 3 * sizeof(uint32_t), s));
+    CMDIAD_CHECK_HIP(hipMemsetAsync(L.bbox + 3, 0, 3 * sizeof(uint32_t), s));
+    CMDIAD_CHECK_HIP(hipMemsetAsync(L.count, 0, (size_t)L.maxc * 4, s));
+    CMDIAD_CHECK_HIP(hipMemsetAsync(L.minorig, 0x7F, (size_t)N * 4, s));
+    CMDIAD_CHECK_HIP(hipMemsetAsync(L.rank, 0, ((size_t)N + 1) * 4, s));
+    hipLaunchKernelGGL(dbscan_bbox_kernel, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, s, points, N, L.bbox);
     CMDIAD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(dbscan_grid_kernel, dim3(1), dim3(64), 0, s, (const uint32_t*)bbox, eps, L.maxc, gp);
+    hipLaunchKernelGGL(dbscan_grid_kernel, dim3(1), dim3(64), 0, s, (const uint32_t*)L.bbox, eps, L.maxc, L.gp);
     CMDIAD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(dbscan_key_kernel, dim3(blocks), dim3(256), 0, s, points, N, (const GridParams*)gp, key, count);
+    hipLaunchKernelGGL(dbscan_key_kernel, dim3(blocks), dim3(256), 0, s, points, N, (const GridParams*)L.gp, L.key, L.count);
     CMDIAD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(scan_exclusive_kernel, dim3(1), dim3(1024), 0, s, (const int*)count, start, 0, (const int*)&gp->ncell);
+    hipLaunchKernelGGL(scan_exclusive_kernel, dim3(1), dim3(1024), 0, s, (const int*)L.count, L.start, 0, (const int*)&L.gp->ncell);
     CMDIAD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(dbscan_scatter_kernel, dim3(blocks), dim3(256), 0, s, points, N, (const int*)key, (const int*)start, count, sp);
+    hipLaunchKernelGGL(dbscan_scatter_kernel, dim3(blocks), dim3(256), 0, s, points, N, (const int*)L.key, (const int*)L.start, L.count, L.sp);
     CMDIAD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(dbscan_core_kernel, dim3(blocks), dim3(256), 0, s, (const SortedPoint*)sp, N, (const GridParams*)gp,
-                       (const int*)start, eps2, min_points, core, parent);
+    hipLaunchKernelGGL(dbscan_core_kernel, dim3(blocks), dim3(256), 0, s, (const SortedPoint*)L.sp, N, (const GridParams*)L.gp,
+                       (const int*)L.start, eps2, min_points, L.core, L.parent);
     CMDIAD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(dbscan_union_kernel, dim3(blocks), dim3(256), 0, s, (const SortedPoint*)sp, N, (const GridParams*)gp,
-                       (const int*)start, eps2, (const int*)core, parent);
+    hipLaunchKernelGGL(dbscan_union_kernel, dim3(blocks), dim3(256), 0, s, (const SortedPoint*)L.sp, N, (const GridParams*)L.gp,
+                       (const int*)L.start, eps2, (const int*)L.core, L.parent);
     CMDIAD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(dbscan_flatten_kernel, dim3(blocks), dim3(256), 0, s, (const SortedPoint*)sp, N, (const int*)core, parent, comp,
-                       minorig);
+    hipLaunchKernelGGL(dbscan_flatten_kernel, dim3(blocks), dim3(256), 0, s, (const SortedPoint*)L.sp, N, (const int*)L.core, L.parent, L.comp,
+                       L.minorig);
     CMDIAD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(dbscan_mark_kernel, dim3(blocks), dim3(256), 0, s, N, (const int*)core, (const int*)comp, (const int*)minorig,
-                       rank);
+    hipLaunchKernelGGL(dbscan_mark_kernel, dim3(blocks), dim3(256), 0, s, N, (const int*)L.core, (const int*)L.comp, (const int*)L.minorig,
+                       L.rank);
     CMDIAD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(scan_exclusive_kernel, dim3(1), dim3(1024), 0, s, (const int*)rank, rank, N, (const int*)nullptr);
+    hipLaunchKernelGGL(scan_exclusive_kernel, dim3(1), dim3(1024), 0, s, (const int*)L.rank, L.rank, N, (const int*)nullptr);
     CMDIAD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(dbscan_label_kernel, dim3(blocks), dim3(256), 0, s, (const SortedPoint*)sp, N, (const GridParams*)gp,
-                       (const int*)start, eps2, (const int*)core, (const int*)comp, (const int*)minorig, (const int*)rank, labels,
+    hipLaunchKernelGGL(dbscan_label_kernel, dim3(blocks), dim3(256), 0, s, (const SortedPoint*)L.sp, N, (const GridParams*)L.gp,
+                       (const int*)L.start, eps2, (const int*)L.core, (const int*)L.comp, (const int*)L.minorig, (const int*)L.rank, labels,
                        n_clusters);
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
@@ -726,10 +707,15 @@ extern "C" int cmdiad_label_histogram(const int32_t* labels, int N, int32_t* his
 // ---- compaction: workspace = the block counts and their scan
 constexpr int kMaxSide = 16384;
 
+struct CompactWs { int* block_count; size_t total; };   // one count per block of 256 elements, and the total
+static CompactWs compact_layout(void* base, int H, int W, int edges)
+{
+    Carve c(base);
+    return {c.take<int>((size_t)((seq_length(H, W, edges) + 255) / 256) + 1), c.total()};
+}
 static size_t compact_workspace(int H, int W, int edges)
 {
-    if (H < 1 || W < 1 || H > kMaxSide || W > kMaxSide) return 0;
-    return ((size_t)((seq_length(H, W, edges) + 255) / 256) + 1) * sizeof(int);
+    return H < 1 || W < 1 || H > kMaxSide || W > kMaxSide ? 0 : compact_layout(nullptr, H, W, edges).total;
 }
 
 static int compact_launch(const char* name, const float* pc, size_t pitch, int H, int W, int edges, float* points, int32_t* index, int cap,
@@ -740,11 +726,11 @@ static int compact_launch(const char* name, const float* pc, size_t pitch, int H
                        pitch <= ((size_t)1 << 24) && cap >= 0,
                    CMDIAD_ERR_ARG, "%s: bad sizes H=%d W=%d (1..%d, H*W <= 2^26) pitch=%zu (>= 3 W floats) cap=%d", name, H, W, kMaxSide,
                    pitch, cap);
-    CMDIAD_REQUIRE(workspace_bytes >= compact_workspace(H, W, edges), CMDIAD_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", name,
-                   workspace_bytes, compact_workspace(H, W, edges));
+    const CompactWs ws = compact_layout(workspace, H, W, edges);
+    if (const int rc = workspace_ok(name, workspace, workspace_bytes, ws.total)) return rc;
+    int* const block_count = ws.block_count;
     const int L = (int)seq_length(H, W, edges);
     const int blocks = (L + 255) / 256;
-    int* block_count = (int*)workspace;
     hipLaunchKernelGGL(compact_count_kernel, dim3(blocks), dim3(256), 0, s, pc, pitch, H, W, edges, L, block_count);
     CMDIAD_CHECK_LAUNCH();
     hipLaunchKernelGGL(scan_exclusive_kernel, dim3(1), dim3(1024), 0, s, (const int*)block_count, block_count, blocks, (const int*)nullptr);

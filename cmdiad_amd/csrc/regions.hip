@@ -48,33 +48,15 @@ struct RegionTables {
     int32_t* pidx;              // first pixel (raster order) whose key equals key[]
 };
 
-struct RegionLayout {
-    size_t stride;   // entries per table, a multiple of 64: every table starts 256-byte aligned
-    size_t zero_bytes, min_off, min_bytes, total;
-};
-inline RegionLayout region_layout(long long cap)
+// the tables of `cap` components; entries per table = cap rounded up to 64, so every table starts 256-byte aligned
+struct RegionWs { size_t stride; RegionTables T; size_t total; };
+inline RegionWs region_layout(void* base, long long cap)
 {
-    RegionLayout L;
-    L.stride = ((size_t)cap + 63) & ~(size_t)63;
-    L.zero_bytes = L.stride * (3 * 8 + 2 * 4);
-    L.min_off = L.zero_bytes;
-    L.min_bytes = L.stride * 3 * 4;
-    L.total = L.min_off + L.min_bytes;
-    return L;
-}
-inline RegionTables region_tables(void* workspace, const RegionLayout& L)
-{
-    char* w = (char*)workspace;
-    RegionTables T;
-    T.key = (unsigned long long*)w;
-    T.sumx = T.key + L.stride;
-    T.sumy = T.sumx + L.stride;
-    T.x1 = (int32_t*)(T.sumy + L.stride);
-    T.y1 = T.x1 + L.stride;
-    T.x0 = (int32_t*)(w + L.min_off);
-    T.y0 = T.x0 + L.stride;
-    T.pidx = T.y0 + L.stride;
-    return T;
+    const size_t stride = ((size_t)cap + 63) & ~(size_t)63;
+    Carve c(base);
+    return {stride, {c.take<unsigned long long>(stride), c.take<unsigned long long>(stride), c.take<unsigned long long>(stride),
+                     c.take<int32_t>(stride), c.take<int32_t>(stride), c.take<int32_t>(stride), c.take<int32_t>(stride), c.take<int32_t>(stride)},
+            c.total()};
 }
 
 inline bool sizes_ok(int n, int H, int W)
@@ -356,7 +338,7 @@ extern "C" int cmdiad_threshold_mask(const double* maps, const double* thr, int 
 
 extern "C" size_t cmdiad_region_table_workspace_bytes(int n, int H, int W)
 {
-    return sizes_ok(n, H, W) && n > 0 ? region_layout(most_components(n, H, W)).total : 0;
+    return sizes_ok(n, H, W) && n > 0 ? region_layout(nullptr, most_components(n, H, W)).total : 0;
 }
 
 extern "C" int cmdiad_region_table(const double* maps, const int32_t* labels, const int32_t* n_comp, const int32_t* comp_offset,
@@ -373,12 +355,11 @@ extern "C" int cmdiad_region_table(const double* maps, const int32_t* labels, co
     const long long most = most_components(n, H, W);
     CMDIAD_REQUIRE(comp_cap >= most, CMDIAD_ERR_ARG,
                    "cmdiad_region_table: comp_size holds %d components, %lld are possible (n ceil(H/2) ceil(W/2))", comp_cap, most);
-    const RegionLayout L = region_layout(most);
-    CMDIAD_REQUIRE(workspace_bytes >= L.total, CMDIAD_ERR_WORKSPACE, "cmdiad_region_table: workspace of %zu bytes, %zu needed",
-                   workspace_bytes, L.total);
+    const RegionWs L = region_layout(workspace, most);
+    if (const int rc = workspace_ok("cmdiad_region_table", workspace, workspace_bytes, L.total)) return rc;
     CMDIAD_REQUIRE(((uintptr_t)workspace & 7) == 0, CMDIAD_ERR_ARG, "cmdiad_region_table: the workspace must be 8-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    const RegionTables T = region_tables(workspace, L);
+    const RegionTables& T = L.T;
     const int HW = H * W, cap = (int)most;   // the tables' capacity: ids at or above it are skipped by every kernel
     hipLaunchKernelGGL(region_init_kernel, dim3((unsigned)((L.stride + 255) / 256)), dim3(256), 0, s, T, (int)L.stride);
     CMDIAD_CHECK_LAUNCH();

@@ -397,10 +397,17 @@ extern "C" int cmdiad_bank_block16(const float* bank, int Nb, int D, float* out,
     return CMDIAD_OK;
 }
 
+// A library's piece of a workspace: kCand approximate candidates per probe and workgroup, for the most workgroups a library of Nb
+// rows gets (scan_blocks) and all kProbes probes, whatever R is.  The pair launch carves two of them, an upper bound (together
+// the libraries get 256 workgroups).
+static unsigned long long* scan_candidates(Carve& c, int Nb) { return c.take<unsigned long long>((size_t)kProbes * scan_blocks(Nb) * kCand); }
+
 extern "C" size_t cmdiad_reweight_workspace_bytes(int R, int Nb)
 {
     (void)R;
-    return (size_t)kProbes * scan_blocks(Nb) * kCand * sizeof(unsigned long long);
+    Carve c(nullptr);
+    scan_candidates(c, Nb);
+    return c.total();
 }
 
 static int scan_launch(ScanPair& pair, int D, hipStream_t s, const char* who)
@@ -424,10 +431,11 @@ extern "C" int cmdiad_reweight_scan(const float* probes, const float* bank, cons
                        aligned16(bank_block16),
                    CMDIAD_ERR_ARG, "cmdiad_reweight_scan: 0<R<=32, D%%128==0, D<=1024, 16-byte alignment (R=%d D=%d)", R, D);
     if (Nb == 0) return CMDIAD_OK;
-    CMDIAD_REQUIRE(workspace && workspace_bytes >= cmdiad_reweight_workspace_bytes(R, Nb), CMDIAD_ERR_WORKSPACE,
-                   "cmdiad_reweight_scan: workspace too small");
+    Carve c(workspace);
+    unsigned long long* const cand = scan_candidates(c, Nb);
+    if (const int rc = workspace_ok("cmdiad_reweight_scan", workspace, workspace_bytes, c.total())) return rc;
     ScanPair pair{};
-    pair.p[0] = ScanProblem{probes, bank_block16, bank, R, Nb, row_offset, (unsigned long long*)workspace, top3, scan_blocks(Nb)};
+    pair.p[0] = ScanProblem{probes, bank_block16, bank, R, Nb, row_offset, cand, top3, scan_blocks(Nb)};
     return scan_launch(pair, D, (hipStream_t)stream, "cmdiad_reweight_scan");
 }
 
@@ -444,7 +452,10 @@ extern "C" int cmdiad_reweight_scan(const float* probes, const float* bank, cons
 // the parity tests (bench-sized libraries, random and duplicated rows: tests/test_gpu_kernels.py, tools/fuzz_gpu.py) have not met a case.
 extern "C" size_t cmdiad_reweight_pair_workspace_bytes(int Nb0, int Nb1)
 {
-    return cmdiad_reweight_workspace_bytes(kProbes, Nb0) + cmdiad_reweight_workspace_bytes(kProbes, Nb1);   // (upper bound: <= 256 workgroups each)
+    Carve c(nullptr);
+    scan_candidates(c, Nb0);
+    scan_candidates(c, Nb1);
+    return c.total();
 }
 
 extern "C" int cmdiad_reweight_scan_pair(const float* probes0, const float* bank0, const float* bank0_block16, int R0, int Nb0,
@@ -458,8 +469,9 @@ extern "C" int cmdiad_reweight_scan_pair(const float* probes0, const float* bank
                        aligned16(probes0) && aligned16(bank0) && aligned16(bank0_block16) && aligned16(probes1) && aligned16(bank1) &&
                        aligned16(bank1_block16),
                    CMDIAD_ERR_ARG, "cmdiad_reweight_scan_pair: 0<R<=32, Nb>0, D%%128==0, D<=1024, 16-byte alignment (R=%d,%d D=%d)", R0, R1, D);
-    CMDIAD_REQUIRE(workspace && workspace_bytes >= cmdiad_reweight_pair_workspace_bytes(Nb0, Nb1), CMDIAD_ERR_WORKSPACE,
-                   "cmdiad_reweight_scan_pair: workspace too small");
+    Carve c(workspace);
+    unsigned long long *const cand0 = scan_candidates(c, Nb0), *const cand1 = scan_candidates(c, Nb1);
+    if (const int rc = workspace_ok("cmdiad_reweight_scan_pair", workspace, workspace_bytes, c.total())) return rc;
     // one workgroup per CU in all, shared in proportion to the rows; never more than a library alone would get, never fewer than one
     const int cap0 = scan_blocks(Nb0), cap1 = scan_blocks(Nb1);
     int b0 = (int)((256.0 * Nb0) / ((double)Nb0 + Nb1) + 0.5);
@@ -468,9 +480,8 @@ extern "C" int cmdiad_reweight_scan_pair(const float* probes0, const float* bank
     b0 = b0 > cap0 ? cap0 : b0;
     b1 = b1 > cap1 ? cap1 : b1;
     ScanPair pair{};
-    unsigned long long* ws = (unsigned long long*)workspace;
-    pair.p[0] = ScanProblem{probes0, bank0_block16, bank0, R0, Nb0, row_offset0, ws, top3_0, b0};
-    pair.p[1] = ScanProblem{probes1, bank1_block16, bank1, R1, Nb1, row_offset1, ws + (size_t)kProbes * cap0 * kCand, top3_1, b1};
+    pair.p[0] = ScanProblem{probes0, bank0_block16, bank0, R0, Nb0, row_offset0, cand0, top3_0, b0};
+    pair.p[1] = ScanProblem{probes1, bank1_block16, bank1, R1, Nb1, row_offset1, cand1, top3_1, b1};
     return scan_launch(pair, D, (hipStream_t)stream, "cmdiad_reweight_scan_pair");
 }
 

@@ -13,7 +13,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _native
+from . import _native, ops
 
 MAX_INT32 = np.iinfo(np.int32).max
 
@@ -87,13 +87,13 @@ class DeviceSGDOneClassSVM:
         X = X.contiguous()
         n, F = X.shape
         L = _native.lib()
-        ws = torch.empty(L.cmdiad_ocsvm_fit_workspace_bytes(n, F), dtype=torch.uint8, device=X.device)
+        ws, wsb = ops._workspace("cmdiad_ocsvm_fit_workspace_bytes", X.device, n, F)
         tab = np.ascontiguousarray(xorshift32_pow2_table())
         coef = np.zeros(F, dtype=np.float32)
         offset, n_iter = ctypes.c_double(0.0), ctypes.c_int(0)
         rc = L.cmdiad_ocsvm_fit(X.data_ptr(), n, F, float(self.nu), int(self.max_iter), float(self.tol if self.tol is not None else -np.inf),
                                 int(self.n_iter_no_change), self._seed(), tab.ctypes.data_as(ctypes.c_void_p), coef.ctypes.data_as(ctypes.c_void_p),
-                                ctypes.byref(offset), ctypes.byref(n_iter), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(X.device).cuda_stream)
+                                ctypes.byref(offset), ctypes.byref(n_iter), ws.data_ptr(), wsb, torch.cuda.current_stream(X.device).cuda_stream)
         _native.check(rc, "cmdiad_ocsvm_fit")
         self.coef_ = coef
         self.offset_ = np.array([offset.value])

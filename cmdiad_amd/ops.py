@@ -71,6 +71,13 @@ def _call(name, *args):
     nat.check(getattr(nat.lib(), name)(*args), name)
 
 
+def _workspace(query_name, device, *args):
+    """(uint8 tensor, nbytes) for the library's size query `query_name`(*args).  The tensor holds at least 16 bytes: the _ws entry
+    points want a non-null pointer when the size is 0."""
+    nbytes = int(getattr(nat.lib(), query_name)(*args))
+    return torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=device), nbytes
+
+
 # ------------------------------------------------------------------------------------ point cloud
 def fps(xyz, G, n_valid=None):
     """xyz [B,N,3] f32 -> (idx [B,G] int32, centers [B,G,3] f32).  models/models.py:70-78."""
@@ -78,8 +85,7 @@ def fps(xyz, G, n_valid=None):
     B, N, _ = xyz.shape
     idx = torch.empty((B, G), dtype=torch.int32, device=xyz.device)
     cen = torch.empty((B, G, 3), dtype=torch.float32, device=xyz.device)
-    wsb = nat.lib().cmdiad_fps_workspace_bytes(B, N)
-    ws = torch.empty(max(wsb, 4) // 4, dtype=torch.float32, device=xyz.device) if wsb else None
+    ws, wsb = _workspace("cmdiad_fps_workspace_bytes", xyz.device, B, N)
     _call("cmdiad_fps", _p(xyz), _p(n_valid), B, N, G, _p(idx), _p(cen), _p(ws), wsb, _stream())
     return idx, cen
 
@@ -91,8 +97,7 @@ def knn_group(xyz, center, K, n_valid=None, want_idx=True):
     G = center.shape[1]
     idx = torch.empty((B, G, K), dtype=torch.int64, device=xyz.device) if want_idx else None
     nb = torch.empty((B, G, K, 3), dtype=torch.float32, device=xyz.device)
-    wsb = nat.lib().cmdiad_knn_workspace_bytes(B, N)     # the binned clouds of the neighbourhood search (clouds >= 2 048 points)
-    ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=xyz.device)
+    ws, wsb = _workspace("cmdiad_knn_workspace_bytes", xyz.device, B, N)     # the binned clouds of the neighbourhood search (clouds >= 2 048 points)
     _call("cmdiad_knn_group_ws", _p(xyz), _p(n_valid), _p(center), B, N, G, K, _p(idx), _p(nb), _p(ws), wsb, _stream())
     return idx, nb
 
@@ -140,8 +145,7 @@ def interp3nn(xyz, center, n_valid=None):
     idx3 = torch.zeros((B, N, 3), dtype=torch.int32, device=xyz.device)
     w3 = torch.zeros((B, N, 3), dtype=torch.float32, device=xyz.device)
     S = center.shape[1]
-    wsb = nat.lib().cmdiad_interp3nn_workspace_bytes(B, S)      # the binned centres of the neighbourhood search (S >= 64)
-    ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=xyz.device)
+    ws, wsb = _workspace("cmdiad_interp3nn_workspace_bytes", xyz.device, B, S)      # the binned centres of the neighbourhood search (S >= 64)
     _call("cmdiad_interp3nn_ws", _p(xyz), _p(n_valid), _p(center), B, N, S, _p(idx3), _p(w3), _p(ws), wsb, _stream())
     return idx3, w3
 
@@ -219,8 +223,8 @@ def gemm_streamk(A, W, bias, residual, out_f32=None):
     key = A.device.index
     ent = _streamk_ws.get(key)
     if ent is None:
-        ent = _streamk_ws[key] = {"ws": torch.zeros((nat.lib().cmdiad_gemm_streamk_workspace_bytes(),), dtype=torch.uint8, device=A.device),
-                                  "done": None, "stream": None}
+        ent = _streamk_ws[key] = {"ws": _workspace("cmdiad_gemm_streamk_workspace_bytes", A.device)[0].zero_(), "done": None,
+                                  "stream": None}
     ws = ent["ws"]
     cur = torch.cuda.current_stream(A.device)
     # Not under stream capture: the cross-stream serialisation is an event recorded OUTSIDE the graph (waiting on it from inside a
@@ -697,7 +701,7 @@ class DedupPlan:
         self.count = torch.zeros((1,), dtype=torch.int32, device=device)
         self.q16 = torch.empty((Q, D), dtype=dtype, device=device)
         self.q_sq = torch.empty((Q,), dtype=torch.float32, device=device)
-        self.work = torch.empty((max(int(nat.lib().cmdiad_rows_dedup_workspace_bytes(Q)), 4),), dtype=torch.uint8, device=device)
+        self.work = _workspace("cmdiad_rows_dedup_workspace_bytes", device, Q)[0]
 
 
 def rows_dedup_plan(q16, q_sq, plan=None):
@@ -855,8 +859,7 @@ def reweight_scan(probes, bank32, blk16=None, top3=None, row_offset=0):
         top3 = torch.full((R, 3), KEY_EMPTY, dtype=torch.int64, device=probes.device)
     for lo in range(0, R, 32):
         r = min(32, R - lo)
-        wsb = nat.lib().cmdiad_reweight_workspace_bytes(r, Nb)
-        ws = torch.empty(max(wsb // 8, 1), dtype=torch.int64, device=probes.device)
+        ws, wsb = _workspace("cmdiad_reweight_workspace_bytes", probes.device, r, Nb)
         _call("cmdiad_reweight_scan", _p(probes[lo:lo + r]), _p(bank32), _p(blk16), r, Nb, D, row_offset, _p(top3[lo:lo + r]),
               _p(ws), wsb, _stream())
     return top3
@@ -874,8 +877,7 @@ def reweight_scan_pair(probes0, bank0, blk0, probes1, bank1, blk1, row_offset0=0
     dev = probes0.device
     top0 = torch.full((R0, 3), KEY_EMPTY, dtype=torch.int64, device=dev)
     top1 = torch.full((R1, 3), KEY_EMPTY, dtype=torch.int64, device=dev)
-    wsb = nat.lib().cmdiad_reweight_pair_workspace_bytes(Nb0, Nb1)
-    ws = torch.empty(max(wsb // 8, 1), dtype=torch.int64, device=dev)
+    ws, wsb = _workspace("cmdiad_reweight_pair_workspace_bytes", dev, Nb0, Nb1)
     _call("cmdiad_reweight_scan_pair", _p(probes0), _p(bank0), _p(blk0), R0, Nb0, row_offset0, _p(top0),
           _p(probes1), _p(bank1), _p(blk1), R1, Nb1, row_offset1, _p(top1), D, _p(ws), wsb, _stream())
     return top0, top1
@@ -1003,8 +1005,7 @@ def plane_ransac(points, n=50, iterations=1000, distance_threshold=0.004, seed=0
         raise ValueError(f"plane_ransac: {E} points, {n} needed for one sample")
     plane = torch.empty(4, dtype=torch.float64, device=points.device)
     info = torch.empty(2, dtype=torch.int32, device=points.device)
-    wsb = nat.lib().cmdiad_plane_ransac_workspace_bytes(int(iterations))
-    ws = torch.empty(wsb, dtype=torch.uint8, device=points.device)
+    ws, wsb = _workspace("cmdiad_plane_ransac_workspace_bytes", points.device, int(iterations))
     _call("cmdiad_plane_ransac", _p(points), E, int(n), int(iterations), float(distance_threshold), int(seed) & 0xFFFFFFFF,
           _p(plane), _p(info), _p(ws), wsb, _stream())
     return plane, info
@@ -1038,8 +1039,7 @@ def dbscan(points, eps=0.006, min_points=30):
     ncl = torch.zeros(1, dtype=torch.int32, device=points.device)
     if N == 0:      # (an empty tensor has no address to pass)
         return labels, ncl
-    wsb = nat.lib().cmdiad_dbscan_workspace_bytes(N)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=points.device)
+    ws, wsb = _workspace("cmdiad_dbscan_workspace_bytes", points.device, N)
     _call("cmdiad_dbscan", _p(points), N, float(eps), int(min_points), _p(labels), _p(ncl), _p(ws), wsb, _stream())
     return labels, ncl
 
@@ -1076,8 +1076,7 @@ def scan_edges(pc):
     L = 2 * min(10, H) * W + 2 * min(10, W) * H
     points = torch.empty((L, 3), dtype=torch.float32, device=pc.device)
     count = torch.empty(1, dtype=torch.int32, device=pc.device)
-    wsb = nat.lib().cmdiad_scan_edges_workspace_bytes(H, W)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=pc.device)
+    ws, wsb = _workspace("cmdiad_scan_edges_workspace_bytes", pc.device, H, W)
     _call("cmdiad_scan_edges", _p(pc), pitch, H, W, _p(points), L, _p(count), _p(ws), wsb, _stream())
     return points, count
 
@@ -1089,8 +1088,7 @@ def scan_compact(pc):
     points = torch.empty((H * W, 3), dtype=torch.float32, device=pc.device)
     index = torch.empty(H * W, dtype=torch.int32, device=pc.device)
     count = torch.empty(1, dtype=torch.int32, device=pc.device)
-    wsb = nat.lib().cmdiad_scan_compact_workspace_bytes(H, W)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=pc.device)
+    ws, wsb = _workspace("cmdiad_scan_compact_workspace_bytes", pc.device, H, W)
     _call("cmdiad_scan_compact", _p(pc), pitch, H, W, _p(points), _p(index), H * W, _p(count), _p(ws), wsb, _stream())
     return points, index, count
 
@@ -1401,8 +1399,7 @@ def ccl_label(masks):
     nonbinary = torch.zeros((1,), dtype=torch.int32, device=dev)
     if n == 0:
         return labels, n_comp, comp_offset, comp_size, nonbinary
-    wsb = nat.lib().cmdiad_ccl_workspace_bytes(n, H, W)
-    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+    ws, wsb = _workspace("cmdiad_ccl_workspace_bytes", dev, n, H, W)
     _call("cmdiad_ccl_label", _p(masks), int(masks.dtype == torch.uint8), n, H, W, _p(labels), _p(n_comp), _p(comp_offset),
           _p(comp_size), cap, _p(nonbinary), _p(ws), wsb, _stream())
     return labels, n_comp, comp_offset, comp_size, nonbinary
@@ -1438,8 +1435,7 @@ def sort_u64_(keys):
     """keys [n] u64, sorted ascending IN PLACE (LSD radix sort, keys only); returns keys."""
     n = _chk_list(keys, torch.int64, "sort_u64_.keys")
     if n:
-        wsb = nat.lib().cmdiad_sort_u64_workspace_bytes(n)
-        ws = torch.empty((wsb,), dtype=torch.uint8, device=keys.device)
+        ws, wsb = _workspace("cmdiad_sort_u64_workspace_bytes", keys.device, n)
         _call("cmdiad_sort_u64", _p(keys), n, _p(ws), wsb, _stream())
     return keys
 
@@ -1553,8 +1549,7 @@ def region_table(maps, labels, n_comp, comp_offset, comp_size, min_area=1, max_r
     ints = torch.zeros((n, K, 8), dtype=torch.int32, device=dev)
     vals = torch.zeros((n, K, 4), dtype=torch.float64, device=dev)
     if n:
-        wsb = nat.lib().cmdiad_region_table_workspace_bytes(n, H, W)
-        ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+        ws, wsb = _workspace("cmdiad_region_table_workspace_bytes", dev, n, H, W)
         _call("cmdiad_region_table", _p(maps), _p(labels), _p(n_comp), _p(comp_offset), _p(comp_size), comp_size.numel(), n, H, W,
               min_area, K, _p(count), _p(ints), _p(vals), _p(ws), wsb, _stream())
     return count, ints, vals

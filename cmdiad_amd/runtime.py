@@ -90,7 +90,7 @@ class _QkvBuffers:
     def workspace(self, M, C, hidden, device):
         need = ops.transformer_block_workspace_bytes(M, C, hidden)
         if self.ws is None or self.ws.numel() < need or self.ws.device != device:
-            self.ws = torch.empty((need,), dtype=torch.uint8, device=device)
+            self.ws = ops._workspace("cmdiad_transformer_block_workspace_bytes", device, M, C, hidden)[0]
         return self.ws
 
     def get(self, B, H, T, device):

@@ -320,6 +320,41 @@ def test_cell_grid_ring_walk_covers_every_cell_once_and_axes_match_the_model(tmp
     assert out.returncode == 0 and "cell grid ok" in out.stdout, out.stdout + out.stderr
 
 
+def test_workspace_carver_sizes_and_cuts_agree(tmp_path):
+    """tests/workspace_check.cpp on csrc/workspace.h, the carver behind every workspace layout (one function per workspace gives
+    the size query its total and the launcher its pointers), compiled for the host with address + undefined sanitizers: a sizing
+    pass and a real pass over the same takes give the same total, every piece lies inside the workspace, pieces are pairwise
+    disjoint and aligned to their pad wherever the pads before them are multiples of it, a null base never becomes a pointer, and workspace_ok answers -2 with the text the
+    launchers' callers match on."""
+    import shutil
+    cxx = next((c for c in (os.environ.get("CXX"), "c++", "g++", "clang++") if c and shutil.which(c)), None)
+    assert cxx, "no host C++ compiler on PATH"
+    exe = str(tmp_path / "workspace_check")
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           os.path.join(REPO, "tests", "workspace_check.cpp"), "-o", exe]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout + out.stderr
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "workspace ok" in out.stdout, out.stdout + out.stderr
+
+
+def test_workspace_size_queries_answer_what_they_always_did():
+    """Every *_workspace_bytes query against tests/golden/workspace_sizes.json, recorded (tests/golden/make_golden_workspace.py)
+    before the layouts moved onto one carver: callers may have cached a size, so each query returns exactly the recorded value
+    for every recorded argument list -- those that answer 0 (zero, negative, over the limit), 1, both sides of every threshold
+    of its formula and the production shapes.  cmdiad_ocsvm_fit_workspace_bytes is not in the table: its hipcub term depends on
+    whether a device is visible, so a value recorded on one machine would not hold on another."""
+    import json
+    from cmdiad_amd import _native as nat
+    L = nat.lib()
+    table = json.load(open(os.path.join(REPO, "tests", "golden", "workspace_sizes.json")))
+    assert set(table) == {q for q in nat.SIZE_QUERIES if q.endswith("_workspace_bytes")} - {"cmdiad_ocsvm_fit_workspace_bytes"}
+    assert sum(len(rows) for rows in table.values()) > 1000
+    bad = [(q, args, want, int(getattr(L, q)(*args))) for q, rows in table.items() for args, want in rows
+           if int(getattr(L, q)(*args)) != want]
+    assert not bad, bad[:10]
+
+
 def test_compat_shims_register_the_cuda_wheel_module_paths():
     code = ("import sys; sys.path.insert(0, %r); import cmdiad_amd.compat as c; c.install();"
             "from pointnet2_ops import pointnet2_utils; from knn_cuda import KNN;"
