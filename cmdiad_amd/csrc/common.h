@@ -18,6 +18,15 @@ constexpr int kPersistCUs = 256;   // one persistent block per CU (MI355X)
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// The LayerNorm-fold operands of a residual-row epilogue (gemm_core.h, ResRows): all null, or ln_xb and ln_part together, both
+// 8-byte aligned; add2 only with them, 16-byte aligned; row pitches (elements) in multiples of 4.
+inline bool ln_out_operands_ok(const void* ln_xb, int ld_xb, const void* ln_part, const void* add2, int ld_add2)
+{
+    if (!ln_xb && !ln_part && !add2) return true;
+    return ln_xb && ln_part && ld_xb % 4 == 0 && ((uintptr_t)ln_xb & 7) == 0 && ((uintptr_t)ln_part & 7) == 0 &&
+           (!add2 || (aligned16(add2) && ld_add2 % 4 == 0));
+}
+
 // Last error text, returned through cmdiad_last_error().  Never throws across the C ABI.
 void cmdiad_set_error(const char* fmt, ...);
 

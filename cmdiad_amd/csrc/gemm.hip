@@ -55,15 +55,6 @@ __device__ __forceinline__ float ln_merge_chunks(const float2* __restrict__ part
     return rsqrtf(m2 / (float)(chunks * 64) + eps);
 }
 
-// sum over the 8 lanes of a half DPP row (lanes 8 h .. 8 h + 7), result in all 8
-__device__ __forceinline__ float half_row_sum(float v)
-{
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));
-    return v;
-}
-
 // rows the launch really has: the caller's M, or the device-side count of a compacted row set (block-uniform)
 __device__ __forceinline__ void live_m(StdParams& p, GlobalTile& A)
 {
@@ -177,65 +168,15 @@ __global__ __launch_bounds__(S::THREADS, S::WAVES_PER_SIMD) void gemm_std_kernel
 #pragma unroll
                     for (int j = 0; j < 4; ++j) bj[j] = *reinterpret_cast<const f32x4*>(bp + j * 16);
                 }
+                // (built here, not ahead of the K loop: see m0r below)
+                const ResRows o{p.residual, p.ldr, out32, p.ldo32, p.ln_xb, p.ld_xb, p.ln_part, p.add2, p.ld_add2, p.M};
 #pragma unroll
                 for (int i = 0; i < S::MI; ++i) {
                     int m0r = c.m0 + c.wr * (S::MI * 16) + i * 16 + rs.R;
                     // (LN_OUT has twice the row pointers: computed ahead of the K loop, as the compiler would, they spill)
                     if constexpr (LN_OUT) asm volatile("" : "+v"(m0r));
-                    const int ma = full ? m0r : min(m0r, p.M - 1), mb = full ? m0r + 8 : min(m0r + 8, p.M - 1);
-                    f32x4 o0[2], o1[2];   // the new residual values of rows R / R + 8: columns ch * 32 + 4 u .. + 3 of the wave's 64
-#pragma unroll
-                    for (int ch = 0; ch < 2; ++ch) {
-                        const int col = n0 + ch * 32 + rs.u * 4;
-                        const f32x4 r0 = *reinterpret_cast<const f32x4*>(p.residual + (size_t)ma * p.ldr + col);
-                        const f32x4 r1 = *reinterpret_cast<const f32x4*>(p.residual + (size_t)mb * p.ldr + col);
-                        f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0;
-                        if (LN_OUT && p.add2) {
-                            a0 = *reinterpret_cast<const f32x4*>(p.add2 + (size_t)ma * p.ld_add2 + col);
-                            a1 = *reinterpret_cast<const f32x4*>(p.add2 + (size_t)mb * p.ld_add2 + col);
-                        }
-                        rs.park(acc[i][2 * ch] + bj[2 * ch], acc[i][2 * ch + 1] + bj[2 * ch + 1]);
-                        f32x4 t0, t1;
-                        rs.fetch(t0, t1);
-                        o0[ch] = t0 + r0;
-                        o1[ch] = t1 + r1;
-                        if (LN_OUT && p.add2) { o0[ch] += a0; o1[ch] += a1; }   // (x + f(x)) + pos: the order of the unfused LayerNorm
-                        if (full || m0r < p.M) *reinterpret_cast<f32x4*>(out32 + (size_t)m0r * p.ldo32 + col) = o0[ch];
-                        if (full || m0r + 8 < p.M) *reinterpret_cast<f32x4*>(out32 + (size_t)(m0r + 8) * p.ldo32 + col) = o1[ch];
-                        if constexpr (LN_OUT) {
-                            const bf16x4 h0 = {f2bf(o0[ch][0]), f2bf(o0[ch][1]), f2bf(o0[ch][2]), f2bf(o0[ch][3])};
-                            const bf16x4 h1 = {f2bf(o1[ch][0]), f2bf(o1[ch][1]), f2bf(o1[ch][2]), f2bf(o1[ch][3])};
-                            if (full || m0r < p.M) *reinterpret_cast<bf16x4*>(p.ln_xb + (size_t)m0r * p.ld_xb + col) = h0;
-                            if (full || m0r + 8 < p.M) *reinterpret_cast<bf16x4*>(p.ln_xb + (size_t)(m0r + 8) * p.ld_xb + col) = h1;
-                        }
-                    }
-                    if constexpr (LN_OUT) {   // the eight lanes of a half DPP row hold one row's 64 columns
-                        float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-                        for (int ch = 0; ch < 2; ++ch)
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) { s0 += o0[ch][q]; s1 += o1[ch][q]; }
-                        s0 = half_row_sum(s0);
-                        s1 = half_row_sum(s1);
-                        const float c0 = s0 * (1.0f / 64), c1 = s1 * (1.0f / 64);
-                        float q0 = 0.f, q1 = 0.f;
-#pragma unroll
-                        for (int ch = 0; ch < 2; ++ch)
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) {
-                                const float d0 = o0[ch][q] - c0, d1 = o1[ch][q] - c1;
-                                q0 = fmaf(d0, d0, q0);
-                                q1 = fmaf(d1, d1, q1);
-                            }
-                        q0 = half_row_sum(q0);
-                        q1 = half_row_sum(q1);
-                        if (rs.u == 0) {   // (one lane of the eight)
-                            float2* part = reinterpret_cast<float2*>(p.ln_part) + (size_t)(n0 >> 6) * p.M;
-                            if (full || m0r < p.M) part[m0r] = make_float2(s0, q0);
-                            if (full || m0r + 8 < p.M) part[m0r + 8] = make_float2(s1, q1);
-                        }
-                        __builtin_amdgcn_sched_barrier(0);   // keep the next row block's loads behind this one's: 64 more live VGPRs spill
-                    }
+                    residual_rows_block<LN_OUT>(rs, acc[i], bj, o, m0r, n0, full);
+                    if constexpr (LN_OUT) __builtin_amdgcn_sched_barrier(0);   // keep the next row block's loads behind this one's: 64 more live VGPRs spill
                 }
             };
             if (c.m0 + S::BM <= p.M) emit(std::true_type{});
@@ -367,17 +308,7 @@ __global__ __launch_bounds__(512, 1) void gemm_std_pp3_kernel(GlobalTile A, Glob
             // act(acc + bias) of 16-row block i as bf16, in the MFMA layout
             auto compute = [&](int i, bf16x4 (&h)[4]) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    f32x4 v;
-                    if constexpr (RSCALE) v = __builtin_elementwise_fma(acc[i][j], f32x4{rsc[i], rsc[i], rsc[i], rsc[i]}, bias[j]);
-                    else v = acc[i][j] + bias[j];
-                    if constexpr (ACT == CMDIAD_ACT_GELU) v = gelu_erf4(v);
-                    else if constexpr (ACT == CMDIAD_ACT_RELU) {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], 0.0f);
-                    }
-                    h[j] = bf16x4{f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
-                }
+                for (int j = 0; j < 4; ++j) h[j] = act_bf16<ACT, RSCALE>(acc[i][j], RSCALE ? rsc[i] : 1.0f, bias[j]);
             };
             // software pipeline over the eight blocks: the arithmetic of block i + 1 (the GELU is ~20 VALU operations per
             // element) runs while block i makes its round trip through the scratch
@@ -1032,9 +963,8 @@ extern "C" int cmdiad_gemm_bf16(const cmdiad_gemm_args* a, cmdiad_stream_t strea
                 a->out_f32, a->ldo32, (bf16_t*)a->out_bf16, a->ldo16, (bf16_t*)a->out_pre_bf16, (const bf16_t*)a->dact_of, split, 1, 1, a->m_count,
                 a->row_scale, (bf16_t*)a->ln_xb, a->ld_xb, a->ln_part, a->add2, a->ld_add2};
     const bool ln_out = a->ln_xb || a->ln_part || a->add2;
-    CMDIAD_REQUIRE(!ln_out || (a->ln_xb && a->ln_part && a->ld_xb % 4 == 0 && ((uintptr_t)a->ln_xb & 7) == 0 && ((uintptr_t)a->ln_part & 7) == 0 &&
-                               (!a->add2 || (aligned16(a->add2) && a->ld_add2 % 4 == 0))),
-                   CMDIAD_ERR_ARG, "cmdiad_gemm_bf16: ln_xb and ln_part come together (8-byte aligned, ld_xb%%4==0); add2 only with them");
+    CMDIAD_REQUIRE(ln_out_operands_ok(a->ln_xb, a->ld_xb, a->ln_part, a->add2, a->ld_add2), CMDIAD_ERR_ARG,
+                   "cmdiad_gemm_bf16: ln_xb and ln_part come together (8-byte aligned, ld_xb%%4==0); add2 only with them");
     CMDIAD_REQUIRE(!a->row_scale || (split == 1 && !a->out_pre_bf16 && !a->dact_of && !a->m_count), CMDIAD_ERR_ARG,
                    "cmdiad_gemm_bf16: row_scale with split_k / training terms / m_count");
     CMDIAD_REQUIRE(!a->m_count || split == 1, CMDIAD_ERR_ARG, "cmdiad_gemm_bf16: m_count with split_k > 1");

@@ -306,6 +306,23 @@ __device__ __forceinline__ void run(const ALoader& A, const WLoader& W, int m0, 
     }
 }
 
+// act(acc + bias) of one accumulator as bf16; RSCALE: act(rsc * acc + bias) in one fused multiply-add per element, the consumer
+// side of the LayerNorm fold (gemm.hip).  The persistent 256 x 256 kernel's epilogue and the hidden chunk of the fused Point-MAE
+// MLP, which must give the same bits.
+template <int ACT, bool RSCALE>
+__device__ __forceinline__ bf16x4 act_bf16(const f32x4& acc, float rsc, const f32x4& bias)
+{
+    f32x4 v;
+    if constexpr (RSCALE) v = __builtin_elementwise_fma(acc, f32x4{rsc, rsc, rsc, rsc}, bias);
+    else v = acc + bias;
+    if constexpr (ACT == CMDIAD_ACT_GELU) v = gelu_erf4(v);
+    else if constexpr (ACT == CMDIAD_ACT_RELU) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], 0.0f);
+    }
+    return bf16x4{f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
+}
+
 // Row-contiguous stores from the MFMA accumulator layout.  In the swapped orientation a lane holds 4 consecutive columns of
 // ONE row, so a store instruction of a wave's 16 x 64 block touches 16 rows x 32 bytes (bf16): 64 separate line accesses for
 // the texture addresser -- measured as 30 % of the fc1 GEMM (profiles/r2_notes.md).  A wave parks the block (as bf16) in a
@@ -365,6 +382,92 @@ struct RowStore32 {
                      : "=&v"(t0), "=&v"(t1) : "v"(rd0), "v"(rd1) : "memory");
     }
 };
+
+// sum over the 8 lanes of a half DPP row (lanes 8 h .. 8 h + 7), result in all 8
+__device__ __forceinline__ float half_row_sum(float v)
+{
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));
+    return v;
+}
+
+// The residual-row epilogue: the fp32 residual stream updated in place through RowStore32 (x += proj(...), x += fc2(...) of every
+// transformer block), shared by the tile GEMM (gemm.hip, gemm_std_kernel<..., RES_ROWS>) and the fused Point-MAE MLP
+// (mlp_fused.hip), which is defined as bit-identical to the launches it replaces: this is the one place where the order of the
+// additions and of the ln_part sums is written down.  Pitches in elements.
+struct ResRows {
+    const float* residual; int ldr;
+    float* out; int ldo;
+    bf16_t* ln_xb; int ld_xb;        // LN_OUT (the LayerNorm fold, gemm.hip): bf16 copy of the new rows ...
+    float* ln_part;                  // ... and [N/64][M] (sum, M2 about the chunk mean) of every 64-column chunk of them
+    const float* add2; int ld_add2;  // LN_OUT: a second fp32 addend, or null
+    int M;                           // rows >= M are neither stored nor counted
+};
+
+// One 16-row x 64-column block of a wave: acc (+ bj, the bias of the lane's four columns of each 16-column tile) in the MFMA
+// accumulator layout; columns n0 .. n0 + 63; the lane stores rows m0r = (block's first row) + rs.R and m0r + 8, columns
+// ch * 32 + 4 u .. + 3 of each 32-column half: out = ((acc + bias) + residual) (+ add2).  full: every row of the block is below
+// M, so nothing is clamped or tested (a branch per row = a basic block per store group = s_waitcnt vmcnt(0) in front of each:
+// stores count in vmcnt on gfx9); rows past M are otherwise loaded from row M - 1, computed and not stored.
+template <bool LN_OUT>
+__device__ __forceinline__ void residual_rows_block(const RowStore32& rs, const f32x4 (&acc)[4], const f32x4 (&bj)[4], const ResRows& o,
+                                                    int m0r, int n0, bool full)
+{
+    const int ma = full ? m0r : min(m0r, o.M - 1), mb = full ? m0r + 8 : min(m0r + 8, o.M - 1);
+    f32x4 o0[2], o1[2];   // the new residual values of rows R / R + 8: columns ch * 32 + 4 u .. + 3 of the wave's 64
+#pragma unroll
+    for (int ch = 0; ch < 2; ++ch) {
+        const int col = n0 + ch * 32 + rs.u * 4;
+        const f32x4 r0 = *reinterpret_cast<const f32x4*>(o.residual + (size_t)ma * o.ldr + col);
+        const f32x4 r1 = *reinterpret_cast<const f32x4*>(o.residual + (size_t)mb * o.ldr + col);
+        f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0;
+        if (LN_OUT && o.add2) {
+            a0 = *reinterpret_cast<const f32x4*>(o.add2 + (size_t)ma * o.ld_add2 + col);
+            a1 = *reinterpret_cast<const f32x4*>(o.add2 + (size_t)mb * o.ld_add2 + col);
+        }
+        rs.park(acc[2 * ch] + bj[2 * ch], acc[2 * ch + 1] + bj[2 * ch + 1]);
+        f32x4 t0, t1;
+        rs.fetch(t0, t1);
+        o0[ch] = t0 + r0;
+        o1[ch] = t1 + r1;
+        if (LN_OUT && o.add2) { o0[ch] += a0; o1[ch] += a1; }   // (x + f(x)) + pos: the order of the unfused LayerNorm
+        if (full || m0r < o.M) *reinterpret_cast<f32x4*>(o.out + (size_t)m0r * o.ldo + col) = o0[ch];
+        if (full || m0r + 8 < o.M) *reinterpret_cast<f32x4*>(o.out + (size_t)(m0r + 8) * o.ldo + col) = o1[ch];
+        if constexpr (LN_OUT) {
+            const bf16x4 h0 = {f2bf(o0[ch][0]), f2bf(o0[ch][1]), f2bf(o0[ch][2]), f2bf(o0[ch][3])};
+            const bf16x4 h1 = {f2bf(o1[ch][0]), f2bf(o1[ch][1]), f2bf(o1[ch][2]), f2bf(o1[ch][3])};
+            if (full || m0r < o.M) *reinterpret_cast<bf16x4*>(o.ln_xb + (size_t)m0r * o.ld_xb + col) = h0;
+            if (full || m0r + 8 < o.M) *reinterpret_cast<bf16x4*>(o.ln_xb + (size_t)(m0r + 8) * o.ld_xb + col) = h1;
+        }
+    }
+    if constexpr (LN_OUT) {   // the eight lanes of a half DPP row hold one row's 64 columns
+        float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+        for (int ch = 0; ch < 2; ++ch)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { s0 += o0[ch][q]; s1 += o1[ch][q]; }
+        s0 = half_row_sum(s0);
+        s1 = half_row_sum(s1);
+        const float c0 = s0 * (1.0f / 64), c1 = s1 * (1.0f / 64);
+        float q0 = 0.f, q1 = 0.f;
+#pragma unroll
+        for (int ch = 0; ch < 2; ++ch)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float d0 = o0[ch][q] - c0, d1 = o1[ch][q] - c1;
+                q0 = fmaf(d0, d0, q0);
+                q1 = fmaf(d1, d1, q1);
+            }
+        q0 = half_row_sum(q0);
+        q1 = half_row_sum(q1);
+        if (rs.u == 0) {   // (one lane of the eight)
+            float2* part = reinterpret_cast<float2*>(o.ln_part) + (size_t)(n0 >> 6) * o.M;
+            if (full || m0r < o.M) part[m0r] = make_float2(s0, q0);
+            if (full || m0r + 8 < o.M) part[m0r + 8] = make_float2(s1, q1);
+        }
+    }
+}
 
 // XCD-aware bijective remap of the linear workgroup id (guide T1): blocks b and b+8 share an XCD
 // (and its L2), so give every XCD a CONTIGUOUS chunk of the tile order.

@@ -15,8 +15,9 @@
 // Results are bit-identical to the two launches: every accumulator sees the same v_mfma_f32_16x16x32_bf16 chain as in the
 // products it replaces -- swapped orientation (weights as the MFMA A operand), the same k of each lane's fragment, K blocks
 // of 32 in increasing order from zero (fc1 over K = 384; fc2 over the chunks in order, i.e. K = 1 536 in order) -- and the
-// epilogues are the same expressions: fma(acc, rstd, b1) -> gelu_erf4 -> bf16 for the hidden; RowStore32 and the residual-row
-// arithmetic of gemm_std_kernel<..., RES_ROWS, LN_OUT> (the 64-column ln_part sums in its lane order) for the output.
+// epilogues are the same code: act_bf16<GELU, true> (fma(acc, rstd, b1) -> gelu_erf4 -> bf16) for the hidden, as in
+// gemm_std_pp3_kernel; residual_rows_block (RowStore32, the residual-row arithmetic and the 64-column ln_part sums in their
+// lane order), as in gemm_std_kernel<..., RES_ROWS, LN_OUT>, for the output.  Both live in gemm_core.h.
 //
 // LDS: xb 8 x 12 KiB + hidden 8 x 2 KiB + ring 6 x 8 KiB = 160 KiB.
 #include "gemm_core.h"
@@ -54,15 +55,6 @@ struct MlpParams {
 };
 
 __device__ __forceinline__ void mlp_barrier() { asm volatile("s_barrier" ::: "memory"); }
-
-// sum over the 8 lanes of a half DPP row: gemm.hip's half_row_sum, step for step (the ln_part bits depend on the order)
-__device__ __forceinline__ float half_row_sum8(float v)
-{
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));
-    return v;
-}
 
 template <bool LN_OUT>
 __global__ __launch_bounds__(512, 1) void pmae_mlp_fused_kernel(MlpParams p)
@@ -159,87 +151,30 @@ __global__ __launch_bounds__(512, 1) void pmae_mlp_fused_kernel(MlpParams p)
             else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
             mlp_barrier();
             if (q == kKT1 - 1) {
-                // hidden chunk: act(row_scale * acc + bias) as in gemm_std_pp3_kernel<GELU, true>, parked as bf16 at
+                // hidden chunk: act_bf16 (gemm_core.h), the expression of gemm_std_pp3_kernel<GELU, true>, parked as bf16 at
                 // row r16, columns j * 16 + 4 g .. + 3 of the wave's [16][64] tile, read back as fc2's A fragments
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    f32x4 v = __builtin_elementwise_fma(acc1[j], f32x4{rsc, rsc, rsc, rsc}, b1v[j]);
-                    v = gelu_erf4(v);
-                    const bf16x4 hv = {f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
-                    *reinterpret_cast<bf16x4*>(hs + lds_off(r16, 2 * j + (g >> 1)) + (g & 1) * 8) = hv;
-                }
+                for (int j = 0; j < 4; ++j)
+                    *reinterpret_cast<bf16x4*>(hs + lds_off(r16, 2 * j + (g >> 1)) + (g & 1) * 8) = act_bf16<CMDIAD_ACT_GELU, true>(acc1[j], rsc, b1v[j]);
                 h0 = ldf(hs, r16, 0);
                 h1 = ldf(hs, r16, 1);
             }
         }
     }
 
-    // out = ((acc + b2) + x) (+ add2) through the row-contiguous epilogue of gemm_std_kernel<S128, NONE, false, true, LN_OUT>:
-    // per 64-column chunk nb, rows R and R + 8 of the wave's 16, columns ch * 32 + 4 u .. + 3
+    // out = ((acc + b2) + x) (+ add2) through residual_rows_block (gemm_core.h), the epilogue of gemm_std_kernel<S128, NONE, false,
+    // true, LN_OUT>: per 64-column chunk nb, rows R and R + 8 of the wave's 16
     RowStore32 rs;
     rs.init(hs, lane);   // (the hidden tile is no longer read)
+    const ResRows o{p.x, kC, p.x, kC, p.ln_xb, kC, p.ln_part, p.add2, kC, p.M};
     const bool full = mw + 16 <= p.M;
-    const int m0r = mw + rs.R;
-    const int ma = min(m0r, p.M - 1), mb = min(m0r + 8, p.M - 1);
 #pragma unroll
     for (int nb = 0; nb < kC / 64; ++nb) {
-        const int n0 = nb * 64;
         f32x4 bj[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) bj[j] = *reinterpret_cast<const f32x4*>(p.b2 + n0 + j * 16 + g * 4);
-        f32x4 o0[2], o1[2];
-#pragma unroll
-        for (int ch = 0; ch < 2; ++ch) {
-            const int col = n0 + ch * 32 + rs.u * 4;
-            const f32x4 r0 = *reinterpret_cast<const f32x4*>(p.x + (size_t)ma * kC + col);
-            const f32x4 r1 = *reinterpret_cast<const f32x4*>(p.x + (size_t)mb * kC + col);
-            f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0;
-            if (LN_OUT && p.add2) {
-                a0 = *reinterpret_cast<const f32x4*>(p.add2 + (size_t)ma * kC + col);
-                a1 = *reinterpret_cast<const f32x4*>(p.add2 + (size_t)mb * kC + col);
-            }
-            rs.park(acc2[nb][2 * ch] + bj[2 * ch], acc2[nb][2 * ch + 1] + bj[2 * ch + 1]);
-            f32x4 t0, t1;
-            rs.fetch(t0, t1);
-            o0[ch] = t0 + r0;
-            o1[ch] = t1 + r1;
-            if (LN_OUT && p.add2) { o0[ch] += a0; o1[ch] += a1; }
-            if (full || m0r < p.M) *reinterpret_cast<f32x4*>(p.x + (size_t)m0r * kC + col) = o0[ch];
-            if (full || m0r + 8 < p.M) *reinterpret_cast<f32x4*>(p.x + (size_t)(m0r + 8) * kC + col) = o1[ch];
-            if constexpr (LN_OUT) {
-                const bf16x4 v0 = {f2bf(o0[ch][0]), f2bf(o0[ch][1]), f2bf(o0[ch][2]), f2bf(o0[ch][3])};
-                const bf16x4 v1 = {f2bf(o1[ch][0]), f2bf(o1[ch][1]), f2bf(o1[ch][2]), f2bf(o1[ch][3])};
-                if (full || m0r < p.M) *reinterpret_cast<bf16x4*>(p.ln_xb + (size_t)m0r * kC + col) = v0;
-                if (full || m0r + 8 < p.M) *reinterpret_cast<bf16x4*>(p.ln_xb + (size_t)(m0r + 8) * kC + col) = v1;
-            }
-        }
-        if constexpr (LN_OUT) {   // the eight lanes of a half DPP row hold one row's 64 columns: gemm.hip's order exactly
-            float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-            for (int ch = 0; ch < 2; ++ch)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { s0 += o0[ch][q]; s1 += o1[ch][q]; }
-            s0 = half_row_sum8(s0);
-            s1 = half_row_sum8(s1);
-            const float c0 = s0 * (1.0f / 64), c1 = s1 * (1.0f / 64);
-            float q0 = 0.f, q1 = 0.f;
-#pragma unroll
-            for (int ch = 0; ch < 2; ++ch)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float d0 = o0[ch][q] - c0, d1 = o1[ch][q] - c1;
-                    q0 = fmaf(d0, d0, q0);
-                    q1 = fmaf(d1, d1, q1);
-                }
-            q0 = half_row_sum8(q0);
-            q1 = half_row_sum8(q1);
-            if (rs.u == 0) {
-                float2* part = reinterpret_cast<float2*>(p.ln_part) + (size_t)nb * p.M;
-                if (full || m0r < p.M) part[m0r] = make_float2(s0, q0);
-                if (full || m0r + 8 < p.M) part[m0r + 8] = make_float2(s1, q1);
-            }
-        }
+        for (int j = 0; j < 4; ++j) bj[j] = *reinterpret_cast<const f32x4*>(p.b2 + nb * 64 + j * 16 + g * 4);
+        residual_rows_block<LN_OUT>(rs, acc2[nb], bj, o, mw + rs.R, nb * 64, full);
     }
 }
 
@@ -252,8 +187,8 @@ int cmdiad_pmae_mlp_fused(float* x, const uint16_t* xb, const float* rstd, const
     CMDIAD_REQUIRE(x && xb && rstd && w1 && b1 && w2 && b2 && M > 0, CMDIAD_ERR_ARG, "cmdiad_pmae_mlp_fused: null operand");
     CMDIAD_REQUIRE(aligned16(x) && aligned16(xb) && aligned16(w1) && aligned16(w2) && aligned16(b1) && aligned16(b2) && (!add2 || aligned16(add2)), CMDIAD_ERR_ARG,
                    "cmdiad_pmae_mlp_fused: operands must be 16-byte aligned");
-    CMDIAD_REQUIRE(!ln_xb == !ln_part && (ln_xb || !add2) && (!ln_xb || (((uintptr_t)ln_xb & 7) == 0 && ((uintptr_t)ln_part & 7) == 0)),
-                   CMDIAD_ERR_ARG, "cmdiad_pmae_mlp_fused: ln_xb and ln_part come together (8-byte aligned); add2 only with them");
+    CMDIAD_REQUIRE(ln_out_operands_ok(ln_xb, kC, ln_part, add2, kC), CMDIAD_ERR_ARG,
+                   "cmdiad_pmae_mlp_fused: ln_xb and ln_part come together (8-byte aligned); add2 only with them");
     MlpParams p{M, (const bf16_t*)xb, rstd, (const bf16_t*)w1, b1, (const bf16_t*)w2, b2, x, (bf16_t*)ln_xb, ln_part, add2};
     const dim3 grid((unsigned)((M + kBM - 1) / kBM)), block(kWaves * 64);
     const int rc = ln_xb ? launch_lds<pmae_mlp_fused_kernel<true>>("cmdiad_pmae_mlp_fused", grid, block, kLdsBytes, (hipStream_t)stream, p)

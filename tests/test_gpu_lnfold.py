@@ -55,6 +55,68 @@ def test_residual_product_emits_rows_and_statistics(M, N, K, with_add):
         np.testing.assert_allclose(mean.cpu().numpy(), x.double().cpu().mean(1).numpy(), rtol=1e-5, atol=1e-6)
 
 
+_SENTINEL = 0x7FC5A5A5   # a quiet NaN with a payload no computation produces; the bf16 buffers carry its high half
+
+
+def _guarded(shape, dtype, live):
+    """A buffer filled with the sentinel bit pattern and its leading `live` elements (rows of a matrix, or a flat count)."""
+    if dtype == torch.bfloat16:
+        buf = torch.full(shape, _SENTINEL >> 16, dtype=torch.int16, device=DEV).view(torch.bfloat16)
+    else:
+        buf = torch.full(shape, _SENTINEL, dtype=torch.int32, device=DEV).view(torch.float32)
+    return buf, buf[:live]
+
+
+def _guard_intact(buf, live):
+    ints = buf[live:].view(torch.int16 if buf.dtype == torch.bfloat16 else torch.int32)
+    return bool((ints == (_SENTINEL >> 16 if buf.dtype == torch.bfloat16 else _SENTINEL)).all())
+
+
+@pytest.mark.parametrize("N", [64, 192])
+@pytest.mark.parametrize("M", [1, 8, 9, 120, 129, 137])
+def test_residual_rows_store_nothing_past_the_last_row(M, N):
+    """The residual-row epilogue (csrc/gemm_core.h residual_rows_block) at the edges of its row guard: a lane stores rows R and
+    R + 8 of a 16-row block, so M = 1 (one live row), 8 (every R row of the first block live, every R + 8 row dead), 9 (one
+    R + 8 row live), 120 (the tile's last block half dead), 129 and 137 (a second M tile with one R row / one R + 8 row); N = 64
+    (the tile's second wave column has nothing to store) and 192 (half of the last N tile dead).  Every output is the leading
+    part of a longer buffer whose tail must keep its bit pattern; the live part is held to the checks of
+    test_residual_product_emits_rows_and_statistics.  The plain form's values: float64; its fp32 sums of K = 64 products of
+    O(1 / 8) and two more addends of magnitude < 16 round by less than 66 * 16 * 2^-24 = 6.3e-5."""
+    K, chunks = 64, N // 64
+    g = torch.Generator().manual_seed(1000 * M + N)
+    A = _bf(torch.randn(M, K, generator=g))
+    W = _bf(torch.randn(N, K, generator=g) / K ** 0.5)
+    bias, res = torch.randn(N, generator=g), 3.0 * torch.randn(M, N, generator=g) + 0.7
+    add = 0.2 * torch.randn(M, N, generator=g)
+    dA, dW, dbias = A.to(DEV).bfloat16(), W.to(DEV).bfloat16(), bias.to(DEV)
+    add_buf, dadd = _guarded((M + 16, N), torch.float32, M)
+    dadd.copy_(add)
+
+    x0_buf, x0 = _guarded((M + 16, N), torch.float32, M)
+    x0.copy_(res)
+    ops.gemm(dA, dW, bias=dbias, residual=x0, out_f32=x0, want_bf16=False)
+    assert _guard_intact(x0_buf, M)
+    ref = A.double() @ W.double().T + bias.double() + res.double()
+    np.testing.assert_allclose(x0.cpu().numpy(), ref.numpy(), rtol=0, atol=1e-4)
+
+    for with_add in (False, True):
+        x_buf, x = _guarded((M + 16, N), torch.float32, M)
+        x.copy_(res)
+        xb_buf, xb = _guarded((M + 16, N), torch.bfloat16, M)
+        part_buf, part = _guarded((chunks * M * 2 + 64,), torch.float32, chunks * M * 2)
+        ops.gemm(dA, dW, bias=dbias, residual=x, out_f32=x, want_bf16=False, ln_xb=xb, ln_part=part, add2=dadd if with_add else None)
+        assert _guard_intact(x_buf, M) and _guard_intact(xb_buf, M) and _guard_intact(part_buf, chunks * M * 2)
+        assert _guard_intact(add_buf, M)
+        assert torch.equal(x, x0 + dadd if with_add else x0)          # (x + f(x)) + pos, in that order
+        assert torch.equal(xb, x.bfloat16())
+        part = part.reshape(chunks, M, 2)
+        xd = x.double().cpu().reshape(M, chunks, 64)
+        s_ref = xd.sum(-1).T
+        q_ref = ((xd - xd.mean(-1, keepdim=True)) ** 2).sum(-1).T
+        np.testing.assert_allclose(part[..., 0].cpu().numpy(), s_ref.numpy(), rtol=2e-5, atol=2e-4)
+        np.testing.assert_allclose(part[..., 1].cpu().numpy(), q_ref.numpy(), rtol=2e-5, atol=1e-5)
+
+
 def test_statistics_of_rows_with_a_large_common_offset():
     """Chunk partials are deviations from the CHUNK mean and are merged with Chan's formula: no E[x^2] - mean^2 cancellation
     when a row's mean is 1000 standard deviations."""

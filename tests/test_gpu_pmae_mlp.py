@@ -17,6 +17,7 @@ from oracle import nets  # noqa: E402
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 C, H, EPS, READ_AFTER = 384, 6, 1e-5, (1,)
+_SENTINEL = 0x7FC5A5A5   # a quiet NaN with a payload no computation produces
 
 
 def _heavy_tailed(sd, n_blocks):
@@ -54,7 +55,10 @@ def _chain(B, T, fused, monkeypatch, heavy=False, n_blocks=4):
     if heavy:
         x[:, [7, 100]] *= 60.0              # residual channels two orders of magnitude above the rest
         x[::97] *= 8.0                      # and high-norm tokens
-    x = x.to(DEV)
+    # the residual stream is the leading B * T rows of a buffer with 16 guard rows behind it, which no launch may touch
+    buf = torch.full((B * T + 16, C), _SENTINEL, dtype=torch.int32, device=DEV).view(torch.float32)
+    x, x_cpu = buf[:B * T], x
+    x.copy_(x_cpu)
     pos = (0.1 * torch.randn(B * T, C, generator=g)).to(DEV)
     bufs, state, taps = _QkvBuffers(), {}, []
     for i, blk in enumerate(blocks):
@@ -66,6 +70,7 @@ def _chain(B, T, fused, monkeypatch, heavy=False, n_blocks=4):
         if i in READ_AFTER:
             taps.append(x.clone())
     torch.cuda.synchronize()
+    assert bool((buf[B * T:].view(torch.int32) == _SENTINEL).all()), "rows past M were written"
     return x, taps
 
 
@@ -77,10 +82,13 @@ def _same(a, b):
     assert len(ta) == len(tb) and all(torch.equal(u, v) for u, v in zip(ta, tb))
 
 
-@pytest.mark.parametrize("B,T", [(32, 1024), (3, 1000), (1, 1024), (2, 200), (1, 1), (1, 65), (3, 43), (1, 127)])
+@pytest.mark.parametrize("B,T", [(32, 1024), (3, 1000), (1, 1024), (2, 200), (1, 1), (1, 65), (3, 43), (1, 127), (1, 9), (1, 120), (1, 137)])
 def test_fused_mlp_block_equals_separate_launches(B, T, monkeypatch):
     """CMDIAD_PMAE_MLP=1: every row count, ragged ones included (M = 3 000, 400: the last 128-row tile is partial, the last
-    waves of it have no live row at all; M = 1, 65, 127: a single partial tile; M = 129: one row in the second)."""
+    waves of it have no live row at all; M = 1, 65, 127: a single partial tile; M = 129: one row in the second; M = 9, 120, 137:
+    a wave with exactly one of its upper eight rows live, the tile's last wave with its upper eight dead, and the first case
+    again in a second tile).  The residual
+    stream has guard rows behind it (_chain): the epilogue's row test must keep every store below M."""
     _same(_chain(B, T, "1", monkeypatch), _chain(B, T, "ref", monkeypatch))
 
 

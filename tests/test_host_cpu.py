@@ -279,7 +279,7 @@ def test_isa_lint_main_loops():
         pytest.skip("hipcc not on PATH")
     out = subprocess.run([sys.executable, os.path.join(REPO, "tools", "isa_lint.py")], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout + out.stderr
-    assert out.stdout.count("main loops clean") == 5      # gemm, gemm_sk, l2min, conv, encoder_tail
+    assert out.stdout.count("main loops clean") == 6      # gemm, gemm_sk, mlp_fused, l2min, conv, encoder_tail
 
 
 def test_streamk_job_list_covers_every_unit_once_in_hand_over_order(tmp_path):
