@@ -83,8 +83,11 @@ void check_launch(int M, int N, int K, int nb, bool one_tile_each)
 
 int main()
 {
-    // the four eligible shapes of test_gemm_streamk_matches_128_tile_bit_for_bit on the stream-K grid of 256 blocks
-    const int shapes[4][3] = {{32 * 785, 768, 3072}, {32 * 785, 768, 768}, {100 * 256, 768, 1536}, {24000, 1024, 1024}};
+    // the eligible shapes of the stream-K device tests on the stream-K grid of 256 blocks: test_gemm_streamk_matches_128_tile_bit_for_bit ...
+    const int shapes[8][3] = {{32 * 785, 768, 3072}, {32 * 785, 768, 768}, {100 * 256, 768, 1536}, {24000, 1024, 1024},
+                              // the edges of the eligibility rule (test_gemm_streamk_at_the_edges_of_its_eligibility): 257 and 511 tiles of
+                              // three K-tiles (a range is barely one tile long), 258 tiles of four, 511 whole tiles
+                              {65537, 256, 192}, {130561, 256, 192}, {32924, 512, 256}, {130816, 256, 192}};
     for (const auto& s : shapes) check_launch(s[0], s[1], s[2], 256, false);
     // the residual-tiles form: one block per tile (test_gemm_residual_on_wide_tiles_matches_128_tile_bit_for_bit's shapes it is legal for)
     const int tiled[3][3] = {{32 * 785, 768, 768}, {9 * 256 + 17, 512, 1536}, {300, 256, 192}};

@@ -208,11 +208,12 @@ def test_feature_ring_on_device(tmp_path):
 
 
 @pytest.mark.parametrize("M,N1,N2,split", [(512, 768, 1920, 1), (4096, 1920, 1920, 8), (1024, 136, 72, 3), (64, 8, 8, 1),
-                                           (640, 200, 328, 16)])
+                                           (640, 200, 328, 16), (576, 200, 328, 4)])
 def test_gemm_tn_vs_torch(M, N1, N2, split):
     """cmdiad_gemm_tn_bf16 (the weight-gradient product with both operands row-major, transposing LDS reads) against
     P^T Q in float64 on the bf16-rounded operands: fp32 accumulation, error <= 1e-3 of the output scale.  Ragged N (not a
-    tile multiple), an uneven / over-long split (empty slabs must be written as zeros), the smallest legal shape."""
+    tile multiple), an uneven / over-long split, the smallest legal shape; (576, ., ., 4): nine K-steps in slabs of three leave the
+    fourth slab empty, and it must be written as zeros (slab by slab, exactly: tests/test_gpu_gemm_edges.py)."""
     from cmdiad_amd import ops
     g = torch.Generator().manual_seed(M + N1)
     P = torch.randn(M, N1, generator=g).to(torch.bfloat16)
