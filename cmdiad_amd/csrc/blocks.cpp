@@ -9,16 +9,6 @@
 int cmdiad_pmae_mlp_fused(float* x, const uint16_t* xb, const float* rstd, const uint16_t* w1, const float* b1, const uint16_t* w2,
                           const float* b2, int M, uint16_t* ln_xb, float* ln_part, const float* add2, cmdiad_stream_t stream);
 
-// The fused MLP keeps a 128-row tile per CU (one block of 8 waves, all 160 KiB of LDS); below ~3/4 of a chip's worth of
-// tiles the two launches, which spread smaller tiles over every CU, are at least as fast (B = 1: 8 tiles; the drop-in's
-// micro-batches of 16: 128).  CMDIAD_PMAE_MLP=1 / 0 forces it on / off wherever it is legal (A/B runs, parity tests).
-static bool pmae_mlp_fused_wanted(bool folded, int M, int C, int hidden)
-{
-    if (!folded || C != 384 || hidden != 1536) return false;
-    if (env_set("CMDIAD_PMAE_MLP")) return !env_is("CMDIAD_PMAE_MLP", '0');
-    return M >= 192 * 128;
-}
-
 struct BlockWs {
     uint16_t *h, *a, *m;   // [M, C]: LayerNorm output, or the raw rows as bf16 (folded) | [M, C]: attention output | [M, hidden]
     float *part, *rstd;    // LayerNorm fold: chunk partials [C/64][M][2] | 1 / sigma per row (readable up to M rounded up to 256)
@@ -72,7 +62,8 @@ extern "C" int cmdiad_transformer_block_fwd(float* x, const float* pos, const cm
     g.residual = x; g.ldr = C; g.out_f32 = x; g.ldo32 = C; g.act = CMDIAD_ACT_NONE; g.group_rows = 1; g.split_k = 1;
     if (folded) { g.ln_xb = h; g.ld_xb = C; g.ln_part = part; }
     if ((rc = cmdiad_gemm_bf16(&g, stream))) return rc;
-    if (pmae_mlp_fused_wanted(folded, M, C, hidden)) {
+    // gemm_plan.h: one kernel, or the two launches below
+    if (plan::pmae_mlp_fused_wanted(folded, M, C, hidden, env_switches())) {
         if ((rc = cmdiad_ln_stats_finalize(part, M, C / 64, eps, rstd, nullptr, stream))) return rc;
         const bool prep = flags & CMDIAD_BLOCK_PREP_NEXT;
         if ((rc = cmdiad_pmae_mlp_fused(x, h, rstd, w->fc1_wf, w->fc1_bf, w->fc2_w, w->fc2_b, M, prep ? h : nullptr, prep ? part : nullptr,

@@ -4,7 +4,12 @@
 #include <stdint.h>
 
 #include "../../include/cmdiad_hip.h"
+#include "gemm_plan.h"   // host only: the plans of the GEMM family
 #include "workspace.h"   // host only: Carve, workspace_ok
+
+using plan::aligned16;
+using plan::kPersistCUs;
+using plan::ln_out_operands_ok;
 
 typedef __bf16 bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -14,18 +19,6 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 #define CMDIAD_WAVE 64
-constexpr int kPersistCUs = 256;   // one persistent block per CU (MI355X)
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// The LayerNorm-fold operands of a residual-row epilogue (gemm_core.h, ResRows): all null, or ln_xb and ln_part together, both
-// 8-byte aligned; add2 only with them, 16-byte aligned; row pitches (elements) in multiples of 4.
-inline bool ln_out_operands_ok(const void* ln_xb, int ld_xb, const void* ln_part, const void* add2, int ld_add2)
-{
-    if (!ln_xb && !ln_part && !add2) return true;
-    return ln_xb && ln_part && ld_xb % 4 == 0 && ((uintptr_t)ln_xb & 7) == 0 && ((uintptr_t)ln_part & 7) == 0 &&
-           (!add2 || (aligned16(add2) && ld_add2 % 4 == 0));
-}
 
 // Last error text, returned through cmdiad_last_error().  Never throws across the C ABI.
 void cmdiad_set_error(const char* fmt, ...);

@@ -29,7 +29,7 @@ struct StdParams {
     bf16_t* out_pre_bf16;         // pre-activation copy (training keeps z for the GELU backward)
     const bf16_t* dact_of;        // acc *= GELU'(dact_of[m][n]) first (backward through an activation)
     int split_k;                  // > 1: block y handles K/split_k, writes slab y of out_f32 (no epilogue terms)
-    int panel;                    // N tiles walked by one block (see panel_tiles)
+    int panel;                    // N tiles walked by one block (gemm_plan.h panel_tiles)
     int group_m;                  // M tiles per L2 group (Coord)
     const int* m_count;           // device-resident live row count (rows >= it are neither computed nor stored), or null
     // LayerNorm folded into the products on either side of it (see "LayerNorm fold" below)
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(S::THREADS, S::WAVES_PER_SIMD) void gemm_std_kernel
     // accumulator layout its 16-byte loads and stores touch 16 rows x 64 bytes per instruction; on the short-K products the
     // texture addresser, not the MFMAs, then bounds the block (proj 25120 x 768 x 768: 417 TFLOP/s against fc2's 710 on the
     // same kernel).  RowStore32: 8 rows x 128 contiguous bytes per load / store.
-    // RES_ROWS is its own instantiation, chosen on the host (res_rows_epilogue()): with both epilogues in one kernel the
+    // RES_ROWS is its own instantiation, chosen on the host (gemm_plan.h res_rows_form()): with both epilogues in one kernel the
     // compiler ran out of registers and spilled the general path's row pointers (tools/isa_lint.py).
     static_assert(!RES_ROWS || (!EXTRAS && ACT == CMDIAD_ACT_NONE), "residual-row epilogue: no activation, no training terms");
     static_assert(!LN_OUT || RES_ROWS, "the LayerNorm statistics come from the residual-row epilogue");
@@ -851,8 +851,8 @@ __global__ __launch_bounds__(256) void ln_stats_finalize_kernel(const float2* __
     rstd[m] = ln_merge_chunks(part, M, chunks, m, eps, mean_out ? mean_out + m : nullptr);
 }
 
-// Every network GEMM runs the 128 x 128 shape: the tile sweep on MI355X (profiles/r1_notes.md) had it ahead of
-// 256x128x3-stage and 256x256 on every ViT / Point-MAE shape; the larger shapes serve the distance GEMM only (l2min.hip).
+// Every network GEMM runs the 128 x 128 shape unless its plan says otherwise (gemm_plan.h plan_gemm, where the rules and their
+// measurements live); the larger shapes serve the distance GEMM (l2min.hip).
 constexpr int kLdsStd = S128::LDS_BYTES + S128::WAVES * kRowStoreScratch;
 
 // the run-time activation (none, GELU, ReLU) as a compile-time constant: f(std::integral_constant<int, CMDIAD_ACT_*>)
@@ -864,178 +864,72 @@ int with_act(int act, F f)
                                     : f(std::integral_constant<int, CMDIAD_ACT_NONE>{});
 }
 
-// N tiles per block.  Short-K, tall-M products (the Point-MAE encoder: M = 4.2 M rows, K <= 512) are bound by the
-// HBM latency of each block's few K-steps, not by bandwidth or MFMA rate; walking the whole N panel in one block
-// pays that latency once and re-reads A from L2.  CMDIAD_GEMM_PANEL_MIN = smallest M-tile count that switches
-// it on (default 2048; 1 in the parity tests so small shapes cover the path; a huge value disables it).
-// M tiles per L2 group of the block order (Coord); CMDIAD_GEMM_GROUPM=1 restores the row-major order (A/B runs)
-int group_m_tiles()
-{
-    const int g = env_int("CMDIAD_GEMM_GROUPM", 8);
-    return g < 1 ? 1 : g;
-}
-
-template <class S>
-int panel_tiles(long M, long N, long K, int split)
-{
-    const long min_mt = env_long("CMDIAD_GEMM_PANEL_MIN", 2048);
-    const long mt = (M + S::BM - 1) / S::BM, ntl = (N + S::BN - 1) / S::BN;
-    if (split > 1 || ntl == 1 || K > 512 || mt < min_mt) return 1;
-    return (int)(ntl < 8 ? ntl : 8);
-}
-
-unsigned persist_blocks(long M, long N)
-{
-    const long jobs = ((M + 255) / 256) * (N / 256);
 #ifdef CMDIAD_AB_VARIANTS
-    if (const long g = env_long("CMDIAD_PP3_GRID", 0); g > 0) return (unsigned)(jobs < g ? jobs : g);
-#endif
-    // as many blocks as give every block the same number of tiles (+-1) at the same number of rounds: 1 188 tiles are five
-    // rounds on 256 CUs and on 238; the smaller grid is 1-2 % faster (fewer CUs share the fabric in the last round;
-    // tools/pp3_grid.py).  The vendor library picks its stream-K grids for these shapes the same way (198 blocks x 6 tiles).
-    const long rounds = (jobs + kPersistCUs - 1) / kPersistCUs;
-    return (unsigned)(jobs < kPersistCUs ? jobs : (jobs + rounds - 1) / rounds);
-}
-
-#ifdef CMDIAD_AB_VARIANTS
-// Wide-shape choice for a product: 0 = keep 128 x 128, 8 = 256 x 256, 4 = 256 x 128.  Measured on MI355X
-// (profiles/r1_notes.md): the 4-wave shapes pay for issuing all LDS-DMA pieces from the MFMA-issuing wave; the only shape
-// they win as a bare product (4.2M x 512 x 256: 2.34 vs 2.57 ms) they lose again inside the encoder, where that GEMM
-// carries the group-bias + ReLU epilogue (encoder 8.6-8.9 vs 7.9 ms).  So no network GEMM selects them; the distance GEMM
-// does (l2min.hip).  CMDIAD_GEMM_WIDE=4 / =8 force a shape (A/B runs and the parity tests).
-int wide_choice(long M, long N, long K, bool plain_epilogue, int split)
-{
-    const int force = env_int("CMDIAD_GEMM_WIDE", -1);
-    if (!plain_epilogue || split > 1 || force == 0) return 0;
-    if (force == 4 || force == 8) return force;
-    (void)M; (void)N; (void)K;
-    return 0;
-}
-
 template <int NJ, auto Kernel, class P>
-int launch_wide(const char* who, long M, long N, long K, P& p, const GlobalTile& A, const GlobalTile& W, hipStream_t s)
+int launch_wide(const char* who, plan::tile_grid g, P& p, const GlobalTile& A, const GlobalTile& W, hipStream_t s)
 {
-    using SW = WideShape<NJ>;
-    const long ntl = (N + SW::BN - 1) / SW::BN;
-    p.panel = (K <= 512 && ntl <= 8) ? (int)ntl : 1;  // short K: walk the whole N panel in one block
-    const long blocks = ((M + SW::BM - 1) / SW::BM) * ((ntl + p.panel - 1) / p.panel);
-    return launch_lds<Kernel>(who, dim3((unsigned)blocks), dim3(256), SW::LDS_BYTES, s, A, W, p);
+    p.panel = g.panel;
+    return launch_lds<Kernel>(who, dim3(g.x), dim3(256), WideShape<NJ>::LDS_BYTES, s, A, W, p);
 }
 #endif  // CMDIAD_AB_VARIANTS
 
-// (Round 5 tried 160-row tiles -- Shape<160,128,4,2>, 5 x 4 MFMA tiles per wave, still two blocks per CU -- for the in-place residual
-// products, whose 128-row tile count is a bad fit for 512 block slots at the ViT's batch-32 shape: 1 182 tiles = 2.31 rounds against
-// 942 = 1.84.  Bit-identical, and measured on one box, interleaved: proj 54.9 -> 56.5 us, fc2 139.1 -> 143.9 us, the whole step
-// 22.46 -> 22.72 ms: a partly filled last round is NOT a whole round -- its blocks have their CU to themselves and run ~1.5x faster,
-// and in the pipeline the other streams' kernels take the idle CUs.  Removed; profiles/r5_notes.md section 2.)
-template <class S>
-dim3 grid_for(long M, long N, int y = 1, int panel = 1)
-{
-    const long ntl = (N + S::BN - 1) / S::BN;
-    return dim3((unsigned)(((M + S::BM - 1) / S::BM) * ((ntl + panel - 1) / panel)), y);
-}
-
 }  // namespace
 
-int gemm_residual_tiles_launch(const cmdiad_gemm_args* a, hipStream_t stream);   // gemm_sk.hip
+int gemm_residual_tiles_launch(const cmdiad_gemm_args* a, unsigned tiles, hipStream_t stream);   // gemm_sk.hip
 
+// plan (gemm_plan.h: every argument check, the kernel, its grid), zero what the plan says no block will write, launch
 extern "C" int cmdiad_gemm_bf16(const cmdiad_gemm_args* a, cmdiad_stream_t stream)
 {
-    CMDIAD_REQUIRE(a && a->A && a->W, CMDIAD_ERR_ARG, "cmdiad_gemm_bf16: null operand");
-    CMDIAD_REQUIRE(a->M > 0 && a->N > 0 && a->K > 0 && a->K % 64 == 0 && a->N % 4 == 0, CMDIAD_ERR_ARG,
-                   "cmdiad_gemm_bf16: need K%%64==0 and N%%4==0 (M=%d N=%d K=%d)", a->M, a->N, a->K);
-    CMDIAD_REQUIRE(a->lda % 8 == 0 && a->ldw % 8 == 0 && aligned16(a->A) && aligned16(a->W), CMDIAD_ERR_ARG,
-                   "cmdiad_gemm_bf16: operands must be 16-byte aligned with ld%%8==0");
-    CMDIAD_REQUIRE(a->out_f32 || a->out_bf16, CMDIAD_ERR_ARG, "cmdiad_gemm_bf16: no output");
-    CMDIAD_REQUIRE((!a->out_f32 || (a->ldo32 % 4 == 0 && aligned16(a->out_f32))) &&
-                       (!a->out_bf16 || (a->ldo16 % 4 == 0 && ((uintptr_t)a->out_bf16 & 7) == 0)) &&
-                       (!a->residual || (a->ldr % 4 == 0 && aligned16(a->residual))) &&
-                       (!a->bias || aligned16(a->bias)) && (!a->group_bias || (aligned16(a->group_bias) && a->group_rows > 0)),
-                   CMDIAD_ERR_ARG, "cmdiad_gemm_bf16: epilogue operand alignment");
-    const int split = a->split_k > 1 ? a->split_k : 1;
-    CMDIAD_REQUIRE(split == 1 || (a->out_f32 && !a->out_bf16 && !a->bias && !a->group_bias && !a->residual &&
-                                  a->act == CMDIAD_ACT_NONE && !a->out_pre_bf16 && !a->dact_of),
-                   CMDIAD_ERR_ARG, "cmdiad_gemm_bf16: split_k > 1 writes raw f32 slabs only");
-    CMDIAD_REQUIRE((!a->out_pre_bf16 || ((uintptr_t)a->out_pre_bf16 & 7) == 0) && (!a->dact_of || ((uintptr_t)a->dact_of & 7) == 0),
-                   CMDIAD_ERR_ARG, "cmdiad_gemm_bf16: out_pre_bf16 / dact_of alignment");
+    using K = plan::gemm_kernel;
+    constexpr const char* who = "cmdiad_gemm_bf16";
+    CMDIAD_REQUIRE(a, CMDIAD_ERR_ARG, "cmdiad_gemm_bf16: null operand");
+    const plan::gemm_plan pl = plan::plan_gemm(*a, env_switches(), kAbBuild);
+    CMDIAD_REQUIRE(!pl.err, pl.err, "%s", pl.text);
+    hipStream_t s = (hipStream_t)stream;
+    const int split = plan::split_of(*a);
+    if (pl.first_empty_slab >= 0 &&
+        hipMemset2DAsync(a->out_f32 + (size_t)pl.first_empty_slab * a->M * a->ldo32, (size_t)a->ldo32 * sizeof(float), 0,
+                         (size_t)a->N * sizeof(float), (size_t)(split - pl.first_empty_slab) * a->M, s) != hipSuccess) {
+        cmdiad_set_error("cmdiad_gemm_bf16: hipMemset2DAsync of the empty split-K slabs failed");
+        return CMDIAD_ERR_LAUNCH;
+    }
+    if (pl.kernel == K::res_tiles) return gemm_residual_tiles_launch(a, pl.grid_x, s);
     GlobalTile A{(const bf16_t*)a->A, a->lda, a->M}, W{(const bf16_t*)a->W, a->ldw, a->N};
     StdParams p{a->M, a->N, a->K, a->bias, a->group_bias, a->group_rows, a->act, a->residual, a->ldr,
-                a->out_f32, a->ldo32, (bf16_t*)a->out_bf16, a->ldo16, (bf16_t*)a->out_pre_bf16, (const bf16_t*)a->dact_of, split, 1, 1, a->m_count,
+                a->out_f32, a->ldo32, (bf16_t*)a->out_bf16, a->ldo16, (bf16_t*)a->out_pre_bf16, (const bf16_t*)a->dact_of, split, pl.panel, pl.group_m, a->m_count,
                 a->row_scale, (bf16_t*)a->ln_xb, a->ld_xb, a->ln_part, a->add2, a->ld_add2};
-    const bool ln_out = a->ln_xb || a->ln_part || a->add2;
-    CMDIAD_REQUIRE(ln_out_operands_ok(a->ln_xb, a->ld_xb, a->ln_part, a->add2, a->ld_add2), CMDIAD_ERR_ARG,
-                   "cmdiad_gemm_bf16: ln_xb and ln_part come together (8-byte aligned, ld_xb%%4==0); add2 only with them");
-    CMDIAD_REQUIRE(!a->row_scale || (split == 1 && !a->out_pre_bf16 && !a->dact_of && !a->m_count), CMDIAD_ERR_ARG,
-                   "cmdiad_gemm_bf16: row_scale with split_k / training terms / m_count");
-    CMDIAD_REQUIRE(!a->m_count || split == 1, CMDIAD_ERR_ARG, "cmdiad_gemm_bf16: m_count with split_k > 1");
-    hipStream_t s = (hipStream_t)stream;
-    if (split > 1) {
-        // a slab holds ceil(T / split) of the T K-tiles, so slabs ceil(T / per) .. split - 1 can be left without one (T = 33, split 8:
-        // slab 7); their blocks return before any store (gemm_std_kernel), and the caller sums every slab: zero those here
-        const int T = a->K / BK, per = (T + split - 1) / split, used = (T + per - 1) / per;
-        if (used < split && hipMemset2DAsync(a->out_f32 + (size_t)used * a->M * a->ldo32, (size_t)a->ldo32 * sizeof(float), 0,
-                                             (size_t)a->N * sizeof(float), (size_t)(split - used) * a->M, s) != hipSuccess) {
-            cmdiad_set_error("cmdiad_gemm_bf16: hipMemset2DAsync of the empty split-K slabs failed");
-            return CMDIAD_ERR_LAUNCH;
-        }
-    }
-    const bool extras = a->out_pre_bf16 || a->dact_of;
-    int rc;
+    const dim3 grid(pl.grid_x, pl.grid_y), block(S128::THREADS);
+    constexpr int kLds3 = SPP3::LDS_BYTES + 8 * kPp3Scratch;
+    int rc = CMDIAD_OK;
+    switch (pl.kernel) {
+    case K::general:
+        rc = with_act(pl.act, [&](auto act) { return launch_lds<gemm_std_kernel<S128, decltype(act)::value, false>>(who, grid, block, kLdsStd, s, A, W, p); });
+        break;
+    case K::general_train:
+        rc = with_act(pl.act, [&](auto act) { return launch_lds<gemm_std_kernel<S128, decltype(act)::value, true>>(who, grid, block, kLdsStd, s, A, W, p); });
+        break;
+    case K::res_rows: rc = launch_lds<gemm_std_kernel<S128, CMDIAD_ACT_NONE, false, true>>(who, grid, block, kLdsStd, s, A, W, p); break;
+    case K::res_rows_ln: rc = launch_lds<gemm_std_kernel<S128, CMDIAD_ACT_NONE, false, true, true>>(who, grid, block, kLdsStd, s, A, W, p); break;
+    case K::pp3:
+        rc = with_act(pl.act, [&](auto act) { return launch_lds<gemm_std_pp3_kernel<decltype(act)::value>>(who, grid, dim3(512), kLds3, s, A, W, p); });
+        break;
+    case K::pp3_rscale:
+        rc = with_act(pl.act, [&](auto act) { return launch_lds<gemm_std_pp3_kernel<decltype(act)::value, true>>(who, grid, dim3(512), kLds3, s, A, W, p); });
+        break;
 #ifdef CMDIAD_AB_VARIANTS
-    const int wide = a->m_count ? 0 : wide_choice(a->M, a->N, a->K, !extras && !a->residual && !a->row_scale && !ln_out && a->ldo16 % 4 == 0, split);   // (the wide kernels know neither row_scale nor the LayerNorm outputs)
-    if (wide) {
-        rc = with_act(a->act, [&](auto act) {
-            constexpr int ACT = decltype(act)::value;
-            return wide == 8 ? launch_wide<8, gemm_std_wide_kernel<8, ACT>>("cmdiad_gemm_bf16", a->M, a->N, a->K, p, A, W, s)
-                             : launch_wide<4, gemm_std_wide_kernel<4, ACT>>("cmdiad_gemm_bf16", a->M, a->N, a->K, p, A, W, s);
-        });
-        if (rc) return rc;
-        CMDIAD_CHECK_LAUNCH();
-        return CMDIAD_OK;
-    }
+    case K::wide4:
+        rc = with_act(pl.act, [&](auto act) { return launch_wide<4, gemm_std_wide_kernel<4, decltype(act)::value>>(who, {pl.grid_x, pl.panel}, p, A, W, s); });
+        break;
+    case K::wide8:
+        rc = with_act(pl.act, [&](auto act) { return launch_wide<8, gemm_std_wide_kernel<8, decltype(act)::value>>(who, {pl.grid_x, pl.panel}, p, A, W, s); });
+        break;
+#else
+    case K::wide4: case K::wide8:   // planned in the test-only build alone
+        cmdiad_set_error("cmdiad_gemm_bf16: the plan names a kernel that only the test build (make ab) contains");
+        return CMDIAD_ERR_ARG;
 #endif
-    {
-        // residual products (out_f32 = A.W^T + bias + residual) on the two-group 256 x 256 kernel, one tile per block (gemm_sk.hip)
-        const bool legal = a->residual && a->out_f32 && !a->out_bf16 && a->bias && !extras && !ln_out && !a->group_bias && split == 1 &&
-                           a->act == CMDIAD_ACT_NONE && !a->m_count && !a->row_scale && a->N % 256 == 0 && a->K >= 192;
-        if (legal && env_is("CMDIAD_GEMM_RES_WIDE", '1')) return gemm_residual_tiles_launch(a, s);
+    case K::res_tiles: break;       // launched above
     }
-    {
-        // two-group persistent kernel: whole 256-column tiles, bias, bf16-only output; chosen when every CU gets >= 2 tiles of
-        // a wide product.  CMDIAD_GEMM_PP3=1 / 0 forces it on / off wherever it is legal (A/B runs, parity tests)
-        const bool plain3 = !extras && !ln_out && !a->group_bias && split == 1 && a->N % 256 == 0 && a->K % 64 == 0 && a->K >= 192 && a->bias &&
-                            !a->residual && !a->out_f32 && a->out_bf16 && a->ldo16 % 8 == 0 && aligned16(a->out_bf16);
-        const bool want3 = env_set("CMDIAD_GEMM_PP3") ? !env_is("CMDIAD_GEMM_PP3", '0')
-                                                      : (a->N >= 1536 && ((long)(a->M + 255) / 256) * (a->N / 256) >= 2 * kPersistCUs);
-        if (plain3 && want3) {
-            constexpr int kLds3 = SPP3::LDS_BYTES + 8 * kPp3Scratch;
-            const dim3 grid(persist_blocks(a->M, a->N));
-            rc = with_act(a->act, [&](auto act) {
-                constexpr int ACT = decltype(act)::value;
-                if (a->row_scale) return launch_lds<gemm_std_pp3_kernel<ACT, true>>("cmdiad_gemm_bf16", grid, dim3(512), kLds3, s, A, W, p);
-                return launch_lds<gemm_std_pp3_kernel<ACT>>("cmdiad_gemm_bf16", grid, dim3(512), kLds3, s, A, W, p);
-            });
-            if (rc) return rc;
-            CMDIAD_CHECK_LAUNCH();
-            return CMDIAD_OK;
-        }
-    }
-    p.panel = panel_tiles<S128>(a->M, a->N, a->K, split);
-    p.group_m = p.panel == 1 && split == 1 ? group_m_tiles() : 1;
-    // fp32 residual stream in place (proj / fc2): out_f32 = acc + bias + residual through the row-contiguous epilogue
-    const bool res_rows = !extras && a->act == CMDIAD_ACT_NONE && p.residual && p.out_f32 && !p.out_bf16 && !p.group_bias && p.bias &&
-                          split == 1 && a->N % 64 == 0 && p.panel == 1;
-    CMDIAD_REQUIRE(!ln_out || (res_rows && !a->row_scale && !a->m_count), CMDIAD_ERR_ARG,
-                   "cmdiad_gemm_bf16: ln_xb / ln_part need the in-place residual form (bias, residual, out_f32 only, N%%64==0)");
-    CMDIAD_REQUIRE(!a->row_scale || !res_rows, CMDIAD_ERR_ARG, "cmdiad_gemm_bf16: row_scale with the residual-row form");
-    const dim3 grid = grid_for<S128>(a->M, a->N, split, p.panel), block(S128::THREADS);
-    if (res_rows && ln_out) rc = launch_lds<gemm_std_kernel<S128, CMDIAD_ACT_NONE, false, true, true>>("cmdiad_gemm_bf16", grid, block, kLdsStd, s, A, W, p);
-    else if (res_rows) rc = launch_lds<gemm_std_kernel<S128, CMDIAD_ACT_NONE, false, true>>("cmdiad_gemm_bf16", grid, block, kLdsStd, s, A, W, p);
-    else rc = with_act(a->act, [&](auto act) {
-        constexpr int ACT = decltype(act)::value;
-        if (extras) return launch_lds<gemm_std_kernel<S128, ACT, true>>("cmdiad_gemm_bf16", grid, block, kLdsStd, s, A, W, p);
-        return launch_lds<gemm_std_kernel<S128, ACT, false>>("cmdiad_gemm_bf16", grid, block, kLdsStd, s, A, W, p);
-    });
     if (rc) return rc;
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
@@ -1061,9 +955,9 @@ extern "C" int cmdiad_gemm_qkv(const uint16_t* A, const uint16_t* W, const float
     const int M = B * T;
     GlobalTile At{(const bf16_t*)A, C, M}, Wt{(const bf16_t*)W, C, 3 * C};
     static const int v_rows = !env_is("CMDIAD_QKV_VROWS", '0');
-    QkvParams p{M, T, (T + 63) / 64 * 64, C, C / 64, group_m_tiles(), bias, (bf16_t*)q_out, (bf16_t*)k_out, (bf16_t*)vt_out, row_scale, v_rows};
+    QkvParams p{M, T, (T + 63) / 64 * 64, C, C / 64, plan::group_m_tiles(env_switches()), bias, (bf16_t*)q_out, (bf16_t*)k_out, (bf16_t*)vt_out, row_scale, v_rows};
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid = grid_for<S128>(M, 3 * C), block(S128::THREADS);
+    const dim3 grid(plan::grid128(M, 3 * C)), block(S128::THREADS);
     const int rc = row_scale ? launch_lds<gemm_qkv_kernel<S128, true>>("cmdiad_gemm_qkv", grid, block, kLdsStd, s, At, Wt, p)
                              : launch_lds<gemm_qkv_kernel<S128, false>>("cmdiad_gemm_qkv", grid, block, kLdsStd, s, At, Wt, p);
     if (rc) return rc;
@@ -1083,18 +977,19 @@ extern "C" int cmdiad_gemm_groupmax(const uint16_t* A, const uint16_t* W, const 
     GlobalTile At{(const bf16_t*)A, K, M}, Wt{(const bf16_t*)W, K, N};
     GroupMaxParams p{M, N, K, Mg, 1, bias, nullptr, 0, out_f32, (bf16_t*)out_bf16};
     hipStream_t s = (hipStream_t)stream;
+    const plan::switches sw = env_switches();
+    const int wide = plan::wide_choice(true, 1, sw, kAbBuild);
+    const plan::tile_grid g = plan::groupmax_grid(M, N, K, wide, sw);
+    int rc;
 #ifdef CMDIAD_AB_VARIANTS
-    const int wide = wide_choice(M, N, K, true, 1);
-    if (wide) {
-        const int rcw = wide == 8 ? launch_wide<8, gemm_groupmax_wide_kernel<8>>("cmdiad_gemm_groupmax", M, N, K, p, At, Wt, s)
-                                  : launch_wide<4, gemm_groupmax_wide_kernel<4>>("cmdiad_gemm_groupmax", M, N, K, p, At, Wt, s);
-        if (rcw) return rcw;
-        CMDIAD_CHECK_LAUNCH();
-        return CMDIAD_OK;
-    }
+    if (wide == 8) rc = launch_wide<8, gemm_groupmax_wide_kernel<8>>("cmdiad_gemm_groupmax", g, p, At, Wt, s);
+    else if (wide == 4) rc = launch_wide<4, gemm_groupmax_wide_kernel<4>>("cmdiad_gemm_groupmax", g, p, At, Wt, s);
+    else
 #endif
-    p.panel = panel_tiles<S128>(M, N, K, 1);
-    const int rc = launch_lds<gemm_groupmax_kernel<S128>>("cmdiad_gemm_groupmax", grid_for<S128>(M, N, 1, p.panel), dim3(S128::THREADS), group_max_lds<S128>(), s, At, Wt, p);
+    {
+        p.panel = g.panel;
+        rc = launch_lds<gemm_groupmax_kernel<S128>>("cmdiad_gemm_groupmax", dim3(g.x), dim3(S128::THREADS), group_max_lds<S128>(), s, At, Wt, p);
+    }
     if (rc) return rc;
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
@@ -1115,24 +1010,26 @@ extern "C" int cmdiad_encoder_stage1(const float* neigh, const float* w1, const 
     GroupMaxParams p{M, 256, 128, Mg, 1, b2, (bf16_t*)h2_out, 256, gmax_out, (bf16_t*)gmax_bf16_out};
     hipStream_t s = (hipStream_t)stream;
     CMDIAD_REQUIRE(b2, CMDIAD_ERR_ARG, "cmdiad_encoder_stage1: the second convolution's bias is required");
-    int rc;
-    bool persist = M % 128 == 0;   // the once-per-block kernel keeps the ragged case (Mg = 32 / 64 with an odd group count)
+    const plan::stage1_plan pl = plan::plan_stage1(M, Mg, env_switches(), kAbBuild);
+    const dim3 grid(pl.grid_x);
+    p.panel = pl.panel;
+    int rc = CMDIAD_OK;
+    switch (pl.kernel) {
+    case plan::stage1_kernel::persist:
+        if (pl.g64) rc = launch_lds<encoder_stage1_persist_kernel<true>>("cmdiad_encoder_stage1", grid, dim3(512), Stage1Persist::LDS_BYTES, s, neigh, (const float4*)w1, (const bf16_t*)W2, p, pl.n_tiles);
+        else rc = launch_lds<encoder_stage1_persist_kernel<false>>("cmdiad_encoder_stage1", grid, dim3(512), Stage1Persist::LDS_BYTES, s, neigh, (const float4*)w1, (const bf16_t*)W2, p, pl.n_tiles);
+        break;
+    case plan::stage1_kernel::once:
+        rc = launch_lds<encoder_stage1_once_kernel>("cmdiad_encoder_stage1", grid, dim3(S128::THREADS), group_max_lds<S128>() + 4 * kRowStoreScratch, s, At, Wt, p);
+        break;
+    case plan::stage1_kernel::generic:   // planned in the test-only build alone
 #ifdef CMDIAD_AB_VARIANTS
-    // test-only build: CMDIAD_STAGE1_PERSIST=0 selects the once-per-block kernel, CMDIAD_STAGE1_ONCE=0 the generic pipeline (A/B runs)
-    if (env_is("CMDIAD_STAGE1_PERSIST", '0')) persist = false;
-    if (env_is("CMDIAD_STAGE1_ONCE", '0')) {
-        p.panel = panel_tiles<S128>(M, 256, 128, 1);
-        rc = launch_lds<encoder_stage1_kernel<S128>>("cmdiad_encoder_stage1", grid_for<S128>(M, 256, 1, p.panel), dim3(S128::THREADS), group_max_lds<S128>(), s, At, Wt, p);
-    } else
+        rc = launch_lds<encoder_stage1_kernel<S128>>("cmdiad_encoder_stage1", grid, dim3(S128::THREADS), group_max_lds<S128>(), s, At, Wt, p);
+        break;
+#else
+        cmdiad_set_error("cmdiad_encoder_stage1: the plan names a kernel that only the test build (make ab) contains");
+        return CMDIAD_ERR_ARG;
 #endif
-    if (persist) {
-        const int n_tiles = M / 128;
-        const dim3 grid((unsigned)(n_tiles < kPersistCUs ? n_tiles : kPersistCUs));
-        if (Mg >= 64) rc = launch_lds<encoder_stage1_persist_kernel<true>>("cmdiad_encoder_stage1", grid, dim3(512), Stage1Persist::LDS_BYTES, s, neigh, (const float4*)w1, (const bf16_t*)W2, p, n_tiles);
-        else rc = launch_lds<encoder_stage1_persist_kernel<false>>("cmdiad_encoder_stage1", grid, dim3(512), Stage1Persist::LDS_BYTES, s, neigh, (const float4*)w1, (const bf16_t*)W2, p, n_tiles);
-    } else {
-        p.panel = 1;
-        rc = launch_lds<encoder_stage1_once_kernel>("cmdiad_encoder_stage1", dim3((unsigned)((M + 127) / 128)), dim3(S128::THREADS), group_max_lds<S128>() + 4 * kRowStoreScratch, s, At, Wt, p);
     }
     if (rc) return rc;
     CMDIAD_CHECK_LAUNCH();

@@ -170,14 +170,13 @@ __global__ __launch_bounds__(512, 1) void gemm_sk_kernel(GlobalTile A, GlobalTil
 // or taken over and the workspace is never touched).  Stand-alone this loses to the 128 x 128 kernel (294 tiles = a full round of
 // 256 CUs and a round of 38), but per CU-second a 256 x 256 tile is cheaper (half the LDS-DMA pieces per FLOP, the bound of the
 // 128 x 128 kernel: profiles/r4_notes.md section 12) -- and inside the pipeline the CUs its second round leaves idle are not idle:
-// the other streams' kernels take them.  Selected by cmdiad_gemm_bf16 (gemm.hip) for the residual products it is legal for.
-int gemm_residual_tiles_launch(const cmdiad_gemm_args* a, hipStream_t stream)
+// the other streams' kernels take them.  Planned by plan_gemm (gemm_plan.h: tiles = its grid) for the residual products it is legal for.
+int gemm_residual_tiles_launch(const cmdiad_gemm_args* a, unsigned tiles, hipStream_t stream)
 {
     constexpr int kLds = SPP3::LDS_BYTES + 8 * kRowStoreScratch;
     GlobalTile A{(const bf16_t*)a->A, a->lda, a->M}, W{(const bf16_t*)a->W, a->ldw, a->N};
     SkParams p{a->M, a->N, a->K, a->bias, a->residual, a->ldr, a->out_f32, a->ldo32, nullptr, nullptr};
-    const long tiles = ((long)(a->M + 255) / 256) * (a->N / 256);
-    if (const int rc = launch_lds<gemm_sk_kernel>("cmdiad_gemm_bf16", dim3((unsigned)tiles), dim3(512), kLds, stream, A, W, p)) return rc;
+    if (const int rc = launch_lds<gemm_sk_kernel>("cmdiad_gemm_bf16", dim3(tiles), dim3(512), kLds, stream, A, W, p)) return rc;
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
 }
@@ -192,23 +191,14 @@ static SkWs sk_layout(void* base)
 
 extern "C" size_t cmdiad_gemm_streamk_workspace_bytes(void) { return sk_layout(nullptr).total; }
 
-extern "C" int cmdiad_gemm_streamk_eligible(int M, int N, int K)
-{
-    if (M <= 0 || N <= 0 || K <= 0 || N % 256 != 0 || K % 64 != 0 || K < 192) return 0;
-    const long tiles = ((long)(M + 255) / 256) * (N / 256), KT = K / 64;
-    // every block's range must be at least one tile long (no block takes over and hands over the same tile), and the split
-    // must be worth it: more than one tile and less than two per CU
-    return tiles * KT / kPersistCUs >= KT && tiles > kPersistCUs && tiles < 2 * kPersistCUs ? 1 : 0;
-}
+extern "C" int cmdiad_gemm_streamk_eligible(int M, int N, int K) { return plan::streamk_eligible(M, N, K) ? 1 : 0; }
 
 extern "C" int cmdiad_gemm_streamk_bf16(const cmdiad_gemm_args* a, void* workspace, size_t workspace_bytes, cmdiad_stream_t stream)
 {
     CMDIAD_REQUIRE(a && a->A && a->W && a->bias && a->residual && a->out_f32 && workspace, CMDIAD_ERR_ARG,
                    "cmdiad_gemm_streamk_bf16: needs A, W, bias, residual, out_f32 and a workspace");
-    CMDIAD_REQUIRE(!a->out_bf16 && !a->group_bias && a->act == CMDIAD_ACT_NONE && !a->out_pre_bf16 && !a->dact_of && a->split_k <= 1 &&
-                       !a->m_count && !a->row_scale && !a->ln_xb && !a->ln_part && !a->add2,
-                   CMDIAD_ERR_ARG, "cmdiad_gemm_streamk_bf16: the residual form only (out_f32 = A.W^T + bias + residual)");
-    CMDIAD_REQUIRE(cmdiad_gemm_streamk_eligible(a->M, a->N, a->K), CMDIAD_ERR_ARG,
+    CMDIAD_REQUIRE(plan::residual_form_only(*a), CMDIAD_ERR_ARG, "cmdiad_gemm_streamk_bf16: the residual form only (out_f32 = A.W^T + bias + residual)");
+    CMDIAD_REQUIRE(plan::streamk_eligible(a->M, a->N, a->K), CMDIAD_ERR_ARG,
                    "cmdiad_gemm_streamk_bf16: shape M=%d N=%d K=%d is not eligible (cmdiad_gemm_streamk_eligible)", a->M, a->N, a->K);
     CMDIAD_REQUIRE(a->lda % 8 == 0 && a->ldw % 8 == 0 && aligned16(a->A) && aligned16(a->W) && a->ldo32 % 4 == 0 && a->ldr % 4 == 0 &&
                        aligned16(a->out_f32) && aligned16(a->residual) && aligned16(a->bias) && aligned16(workspace),

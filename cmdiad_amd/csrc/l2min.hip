@@ -561,104 +561,44 @@ struct L2Live {
     int n_seg = 0, seg_stride = 0;
 };
 
-// Library ranges per query tile of the segments launch (the W-way row-sharded search: W x the query tiles of one rank against
-// 1/W of the library).  Measured on the bagel library at W = 1 / 2 / 4 / 8 (299 / 150 / 74 / 38 library tiles, 213 live query
-// tiles per segment; tools/l2_segments_sweep.sh, profiles/r4_notes.md): ranges of ~15 tiles as in the single-library launch, but
-// never fewer than 8 ranges -- a group of 4 query tiles x 8 ranges is what one XCD's 32 CUs hold at a time, with fewer ranges its
-// L2 has to keep more query tiles than it can (W = 8: 1 range 6.35 ms, 8 ranges 5.96 ms) -- and ranges of at least 4 tiles.
-static int segment_splits(int nbt)
-{
-    int sp = nbt / 15;
-    sp = sp < 8 ? 8 : (sp > 20 ? 20 : sp);
-    const int most = nbt / 4 < 1 ? 1 : nbt / 4;
-    return sp > most ? most : sp;
-}
-
+// one planned launch (gemm_plan.h plan_l2: tile shape, library rows, nq / nbt / splits / qgroup, grid) on its kernel
 template <class S, bool F16>
-int launch_l2(const uint16_t* q, const float* q_sqnorm, const uint16_t* bank, const float* bank_sqnorm, int Q, int Nb,
-              int D, uint32_t row_offset, unsigned long long* keys, unsigned long long* keys2, hipStream_t stream,
-              const L2Live& live = L2Live())
+int launch_l2(const plan::l2_call& c, const plan::l2_launch& l, const L2Live& live, hipStream_t stream)
 {
-    // segments: the launch is sized for every segment's cap (seg_stride rows); Q = n_seg * seg_stride
-    const int nq = live.seg_counts ? live.n_seg * ((live.seg_stride + S::BM - 1) / S::BM) : (Q + S::BM - 1) / S::BM;
-    const int nbt = (Nb + S::BN - 1) / S::BN;
-    // enough blocks to fill the chip a few times over, but long bank ranges per block so the running
-    // min stays in registers and the per-block atomics stay negligible
-    static const int env_splits = env_int("CMDIAD_L2_SPLITS", 0);
-    static const int env_qgroup = env_int("CMDIAD_L2_QGROUP", 0);
-    const int env_seg_splits = env_int("CMDIAD_L2_SEG_SPLITS", 0);   // tools/l2_segments.py sweeps it
-    // measured on the bagel xyz library (profiles/r1_notes.md): 8 bank ranges for the 8-wave shapes; the 4-wave wide
-    // shape gains another 5 % from 16-32 (shorter ranges, better tail balance), as long as a range keeps >= 4 tiles.
-    // Round 3 (profiles/r3_notes.md, the two-group kernel on the de-duplicated 54 401 rows): 20 ranges of 15 tiles 5.40 ms against
-    // 5.55 ms for 30 ranges of 10 -- a block's pipeline fill and drain are paid per range, and 213 live query tiles leave no
-    // tail to balance; all 100 352 rows: within 1 % from 15 to 50 ranges.
-    int splits = env_splits > 0 ? env_splits : 8;
-    if (env_splits <= 0 && S::BM == 256 && !std::is_same<S, S2x2>::value) splits = nbt / 4 < 1 ? 1 : (nbt / 4 > 20 ? 20 : nbt / 4);
-    if (live.seg_counts && S::BM == 256) splits = env_seg_splits > 0 ? env_seg_splits : segment_splits(nbt);
-    splits = splits > nbt ? nbt : splits;
-    if ((nbt + splits - 1) / splits > 4096) splits = (nbt + 4095) / 4096;   // RowMin keeps a tile's place in 12 bits
-    int qgroup = env_qgroup > 0 ? env_qgroup : 4;
-    qgroup = qgroup > nq ? nq : qgroup;
-    GlobalTile A{(const bf16_t*)q, D, Q}, W{(const bf16_t*)bank, D, Nb};
-    L2Params p{Q, Nb, D, q_sqnorm, bank_sqnorm, row_offset, keys, keys2, nq, nbt, splits, qgroup, nullptr, -1, live.q_count,
+    GlobalTile A{(const bf16_t*)c.q, c.D, c.Q}, W{(const bf16_t*)c.bank + (size_t)l.row0 * c.D, c.D, l.rows};
+    L2Params p{c.Q, l.rows, c.D, (const float*)c.q_sqnorm, (const float*)c.bank_sqnorm + l.row0, c.row_offset + (uint32_t)l.row0,
+               (unsigned long long*)c.keys, (unsigned long long*)c.keys2, l.nq, l.nbt, l.splits, l.qgroup, nullptr, -1, live.q_count,
                live.seg_counts, live.n_seg, live.seg_stride};
-    const int ngroups = (nq + qgroup - 1) / qgroup;
-    return launch_lds<L2Kernel<S, F16>::fn>("cmdiad_l2_min_keys", dim3(ngroups * qgroup * splits), dim3(S::THREADS), S::LDS_BYTES, stream, A, W, p);
+    return launch_lds<L2Kernel<S, F16>::fn>("cmdiad_l2_min_keys", dim3(l.grid_x), dim3(S::THREADS), S::LDS_BYTES, stream, A, W, p);
 }
 
-static int l2_min_keys_impl(const uint16_t* q, const float* q_sqnorm, const L2Live& q_count, const uint16_t* bank,
+static int l2_min_keys_impl(const uint16_t* q, const float* q_sqnorm, const L2Live& live, const uint16_t* bank,
                            const float* bank_sqnorm, int Q, int Nb, int D, uint32_t row_offset,
                            unsigned long long* keys, unsigned long long* keys2, int dtype, cmdiad_stream_t stream)
 {
-    CMDIAD_REQUIRE(Q >= 0 && Nb >= 0 && D > 0 && D % 64 == 0, CMDIAD_ERR_ARG, "cmdiad_l2_min_keys: need D%%64==0 (D=%d)", D);
-    CMDIAD_REQUIRE(dtype == CMDIAD_DT_BF16 || dtype == CMDIAD_DT_F16, CMDIAD_ERR_ARG, "cmdiad_l2_min_keys: dtype");
-    // nothing to search (an empty row shard: engine.Bank on a rank beyond the library's last row; a 0-row tensor has no address):
-    // the keys stay what the caller put there
-    if (Q == 0 || Nb == 0) return CMDIAD_OK;
-    CMDIAD_REQUIRE(q && q_sqnorm && bank && bank_sqnorm && keys, CMDIAD_ERR_ARG, "cmdiad_l2_min_keys: null pointer");
-    CMDIAD_REQUIRE(aligned16(q) && aligned16(bank), CMDIAD_ERR_ARG, "cmdiad_l2_min_keys: 16-byte alignment");
-    // the runner-up is defined on groups of 16 library rows (row >> 6, (row >> 2) & 3): launches whose keys are merged must agree on them
-    CMDIAD_REQUIRE(!keys2 || row_offset % 64 == 0, CMDIAD_ERR_ARG, "cmdiad_l2_min_keys: keys2 needs row_offset %% 64 == 0 (row_offset=%u)", row_offset);
-    // production: the two-group 256 x 256 pipeline (l2_min_pp3_kernel) from Q >= 512, the 128 x 128 kernel below that, for the
-    // last Nb % 256 library rows and for D < 192 (the two-group schedule assumes >= 3 K-tiles per library tile).
-    // CMDIAD_L2_TILE (the parity tests force each shape on small inputs) = 0 / 5 for those two; the test-only
-    // build (make ab) also knows 2 = the lock-step 256 x 256 shape of gemm::run.
-    const int force = env_int("CMDIAD_L2_TILE", -1);
-    int tile = force >= 0 ? force : (Q >= 512 ? 5 : 0);
-    if (q_count.seg_counts && tile != 0) tile = 5;    // segments exist for the production shapes only
-#ifndef CMDIAD_AB_VARIANTS
-    if (tile == 2) {
-        cmdiad_set_error("cmdiad_l2_min_keys: CMDIAD_L2_TILE=2 names an A/B variant that only the test build (make ab) contains");
-        return CMDIAD_ERR_ARG;
-    }
-#endif
-    if (tile != 0 && tile != 2 && tile != 5) {
-        cmdiad_set_error("cmdiad_l2_min_keys: CMDIAD_L2_TILE=%d is not a distance-GEMM shape (0, 5; test build: 2)", tile);
-        return CMDIAD_ERR_ARG;
-    }
-    if (tile == 5 && D < 192) tile = 0;
+    const plan::l2_call c{q, q_sqnorm, bank, bank_sqnorm, keys, keys2, Q, Nb, D, live.seg_counts ? live.n_seg : 0, live.seg_stride, row_offset, dtype};
+    const plan::l2_plan pl = plan::plan_l2(c, l2_switches(), kAbBuild);
+    CMDIAD_REQUIRE(!pl.err, pl.err, "%s", pl.text);
     hipStream_t s = (hipStream_t)stream;
     const bool h = dtype == CMDIAD_DT_F16;
-    int rc;
-#define L2_ARGS q, q_sqnorm, bank, bank_sqnorm, Q, Nb, D, row_offset, keys, keys2, s, q_count
-    if (tile == 5) {
-        const int full = Nb / 256 * 256, rest = Nb - full;
-        rc = CMDIAD_OK;
-        if (full > 0) rc = h ? launch_l2<SPingPong3, true>(q, q_sqnorm, bank, bank_sqnorm, Q, full, D, row_offset, keys, keys2, s, q_count)
-                             : launch_l2<SPingPong3, false>(q, q_sqnorm, bank, bank_sqnorm, Q, full, D, row_offset, keys, keys2, s, q_count);
-        if (rc == CMDIAD_OK && rest > 0) {
-            const uint16_t* b2 = bank + (size_t)full * D;
-            rc = h ? launch_l2<S128, true>(q, q_sqnorm, b2, bank_sqnorm + full, Q, rest, D, row_offset + full, keys, keys2, s, q_count)
-                   : launch_l2<S128, false>(q, q_sqnorm, b2, bank_sqnorm + full, Q, rest, D, row_offset + full, keys, keys2, s, q_count);
-        }
-    }
+    for (int i = 0; i < pl.n; ++i) {
+        const plan::l2_launch& l = pl.launch[i];
+        int rc = CMDIAD_OK;
+        switch (l.tile) {
+        case plan::l2_tile::two_group256: rc = h ? launch_l2<SPingPong3, true>(c, l, live, s) : launch_l2<SPingPong3, false>(c, l, live, s); break;
+        case plan::l2_tile::t128: rc = h ? launch_l2<S128, true>(c, l, live, s) : launch_l2<S128, false>(c, l, live, s); break;
+        case plan::l2_tile::lockstep256:   // planned in the test-only build alone
 #ifdef CMDIAD_AB_VARIANTS
-    else if (tile == 2) rc = h ? launch_l2<S2x2, true>(L2_ARGS) : launch_l2<S2x2, false>(L2_ARGS);
+            rc = h ? launch_l2<S2x2, true>(c, l, live, s) : launch_l2<S2x2, false>(c, l, live, s);
+            break;
+#else
+            cmdiad_set_error("cmdiad_l2_min_keys: the plan names a kernel that only the test build (make ab) contains");
+            return CMDIAD_ERR_ARG;
 #endif
-    else rc = h ? launch_l2<S128, true>(L2_ARGS) : launch_l2<S128, false>(L2_ARGS);
-#undef L2_ARGS
-    if (rc) return rc;
-    CMDIAD_CHECK_LAUNCH();
+        }
+        if (rc) return rc;
+    }
+    if (pl.n) CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
 }
 

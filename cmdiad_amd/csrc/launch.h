@@ -44,9 +44,27 @@ int launch_lds(const char* who, dim3 grid, dim3 block, size_t lds, hipStream_t s
     return CMDIAD_OK;
 }
 
-// Environment switches.  A switch that tests and tools change between calls is read at its site on every call; one that is
-// fixed for the process is written `static const int x = env_int(...)` at its site.
+// Environment switches.  A switch that tests and tools change between calls is read on every call that consults it; one that is
+// fixed for the process is written `static const int x = env_int(...)` at its site.  The selection switches of the GEMM family are
+// read by gemm_plan.h (plan::switches, where each rule consults them) through env_switches() below.
 inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 inline long env_long(const char* name, long dflt) { const char* e = getenv(name); return e ? atol(e) : dflt; }
 inline bool env_set(const char* name) { return getenv(name) != nullptr; }
 inline bool env_is(const char* name, char c) { const char* e = getenv(name); return e && e[0] == c; }   // set, and starts with c
+
+// The test-only build (make ab) is the one in which CMDIAD_GEMM_WIDE, CMDIAD_PP3_GRID, CMDIAD_L2_TILE=2 and the CMDIAD_STAGE1_*
+// switches act.
+#ifdef CMDIAD_AB_VARIANTS
+constexpr bool kAbBuild = true;
+#else
+constexpr bool kAbBuild = false;
+#endif
+
+inline plan::switches env_switches() { return {[](const char* name) -> const char* { return getenv(name); }}; }
+
+// the distance GEMM's: CMDIAD_L2_SPLITS and CMDIAD_L2_QGROUP are fixed for the process
+inline plan::switches l2_switches()
+{
+    static const int splits = env_int("CMDIAD_L2_SPLITS", 0), qgroup = env_int("CMDIAD_L2_QGROUP", 0);
+    return {env_switches().get, splits, qgroup};
+}

@@ -300,6 +300,88 @@ def test_streamk_job_list_covers_every_unit_once_in_hand_over_order(tmp_path):
     assert out.returncode == 0 and "sk jobs ok" in out.stdout, out.stdout + out.stderr
 
 
+def _gemm_plan_line(shape, form, env, ab=False, pitch=None, ln=False):
+    """one `gemm` case line of tests/gemm_plan_check.cpp --lines for a (shape, Form, environment) of tests/gemm_ref.py"""
+    M, N, K = shape
+    words = ["gemm", f"M={M}", f"N={N}", f"K={K}", f"act={form.act}", f"split={form.split}", f"out={form.outs}"]
+    words += [w for w, on in (("ab", ab), ("bias", form.bias), ("res", form.residual), ("rscale", form.row_scale), ("ln", ln), ("add2", ln)) if on]
+    if form.group_rows:
+        words.append(f"gb={form.group_rows}")
+    if pitch:
+        words += [f"lda={K + pitch.a}", f"ldw={K + pitch.w}", f"ldr={N + pitch.r}", f"ldo32={N + pitch.o32}", f"ldo16={N + pitch.o16}",
+                  f"ld_xb={N + pitch.xb}", f"ld_add2={N + pitch.add2}"]
+    return " ".join(words + [f"{k}={v}" for k, v in env.items()])
+
+
+def test_gemm_plan_workload_launches_and_the_edge_tests_labels(tmp_path):
+    """tests/gemm_plan_check.cpp on csrc/gemm_plan.h, the host-only header that decides which kernel of the GEMM family runs and on
+    which grid, compiled for the host with address + undefined sanitizers.  Its own checks: the workload's launches (ViT fc1 on the
+    two-group persistent kernel with 238 blocks, proj on residual rows 1182 x 1, the distance GEMM's 20 ranges of 15 tiles, ...),
+    the switches, every argument error with its text, stream-K eligibility, the fused-MLP rule, the encoder's first stage.  Then the
+    case tables of tests/gemm_ref.py go through its line mode: every label and environment by which tests/test_gpu_gemm_edges.py
+    means to reach a particular kernel does reach it -- a changed threshold must not turn "every kernel at its edge shapes" into the
+    128 x 128 kernel five times.  The plan reads each case's switches from a stand-in environment itself, as the library reads the
+    real one, and the check counts the reads; the stream-K shapes of tests/gemm_ref.py are eligible."""
+    import shutil
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import gemm_ref as gr
+    cxx = next((c for c in (os.environ.get("CXX"), "c++", "g++", "clang++") if c and shutil.which(c)), None)
+    assert cxx, "no host C++ compiler on PATH"
+    exe = str(tmp_path / "gemm_plan_check")
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           os.path.join(REPO, "tests", "gemm_plan_check.cpp"), "-o", exe]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout + out.stderr
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "gemm plan ok" in out.stdout, out.stdout + out.stderr
+
+    cases = []                                     # (what the plan must be, line)
+    label = {"general": ("general",), "res_rows": ("res_rows",), "ln": ("res_rows_ln",), "res_wide": ("res_tiles",)}
+    for kernel, env, shape, form in gr.PITCHED_CASES:
+        want = label.get(kernel) or (("pp3_rscale",) if form.row_scale else ("pp3",))
+        cases.append((want, _gemm_plan_line(shape, form, env, pitch=gr.PITCHED, ln=kernel == "ln")))
+    for shape in gr.WIDE256_SHAPES:
+        for form in gr.PP3_FORMS:
+            cases.append(((("pp3_rscale",) if form.row_scale else ("pp3",)), _gemm_plan_line(shape, form, gr.PP3_ENV)))
+        cases.append((("res_tiles",), _gemm_plan_line(shape, gr.BIAS_RES_F32, gr.RES_WIDE_ENV)))
+    general = []                                   # (setting, shape, form) behind cases[first_general:first_wide]
+    first_general = len(cases)
+    for name, env in gr.SETTINGS:
+        for shape in gr.GENERAL_SHAPES:
+            for form in gr.GENERAL_FORMS:
+                general.append((name, shape, form))
+                cases.append((None, _gemm_plan_line(shape, form, env)))
+    first_wide = len(cases)
+    for wide in (4, 8):
+        for shape in gr.AB_WIDE_SHAPES:
+            for form in gr.AB_WIDE_FORMS:
+                cases.append(((f"wide{wide}",), _gemm_plan_line(shape, form, {"CMDIAD_GEMM_WIDE": wide}, ab=True)))
+                cases.append((("general",), _gemm_plan_line(shape, form, {"CMDIAD_GEMM_WIDE": wide})))
+    first_streamk = len(cases)
+    cases += [(("eligible",), f"streamk M={M} N={N} K={K}") for M, N, K in gr.STREAMK_SHAPES]
+    out = subprocess.run([exe, "--lines"], input="\n".join(line for _, line in cases) + "\n", capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    got = [row.split() for row in out.stdout.splitlines()]
+    assert [int(row[0]) for row in got] == list(range(len(cases))), out.stdout[:2000]
+    for (want, line), row in zip(cases, got):
+        assert row[1] != "error", (line, " ".join(row))
+        assert want is None or row[1] in want, (line, " ".join(row))
+    for (_, line), row in zip(cases[:first_streamk], got):
+        # the plan reads the case's environment itself, a switch only where a rule consults it: never more reads per call than
+        # the launcher it replaced made (1 on the persistent kernel, up to 4 elsewhere; the A/B build's two switches on top)
+        ab = " ab " in line
+        assert int(row[8]) <= (2 if row[1].startswith("pp3") else 3) + ab, (line, " ".join(row))
+        assert int(row[8]) == 1 or ab or not row[1].startswith("pp3"), (line, " ".join(row))
+    panelled = 0
+    for (name, shape, form), (_, line), row in zip(general, cases[first_general:first_wide], got[first_general:first_wide]):
+        kernel, panel, group_m = row[1], int(row[5]), int(row[6])
+        res_rows = form is gr.BIAS_RES_F32 and shape[1] % 64 == 0 and panel == 1
+        assert kernel == ("res_rows" if res_rows else "general"), (line, " ".join(row))
+        panelled += name == "panel" and panel > 1
+        assert name != "rowmajor" or group_m == 1, (line, " ".join(row))
+    assert panelled, "the \"panel\" setting plans no panel > 1 on any of GENERAL_SHAPES"
+
+
 def test_cell_grid_ring_walk_covers_every_cell_once_and_axes_match_the_model(tmp_path):
     """tests/cell_grid_check.cpp on csrc/cell_grid.h, the grid arithmetic both neighbourhood searches run on (knn_grid_*_kernel,
     interp3nn_bin / _grid_kernel), compiled for the host with address + undefined sanitizers and without contraction: for grid

@@ -1,6 +1,6 @@
 """configs[3] shard shapes on one GPU: prints bench.py's `fake_world` leg (per class and world size: the per-rank distance GEMM).
     python tools/l2_segments.py [classes] [worlds]         e.g.  bagel,peach 1,2,4,8
-CMDIAD_L2_SEG_SPLITS=<n> forces the library ranges per query tile of the segments launch (default: csrc/l2min.hip pick_splits)."""
+CMDIAD_L2_SEG_SPLITS=<n> forces the library ranges per query tile of the segments launch (default: csrc/gemm_plan.h segment_splits)."""
 import json
 import os
 import sys
