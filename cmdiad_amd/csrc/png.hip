@@ -23,6 +23,8 @@
 // arithmetic; any source byte outside [0, raw_bytes) reads as 0, so no offset makes the kernel read outside the upload buffer
 // (ops.png_unfilter checks the offsets on the host before the launch and refuses a bad one).  A filter type above 4 acts as None
 // (utils.png.read_raw refuses such a file).  Writes go to pixels of the image only.
+//
+// The encoder's direction, cmdiad_png_filter, is at the end of the file: filtering has none of these dependencies.
 #include "launch.h"
 
 namespace {
@@ -205,6 +207,78 @@ extern "C" int cmdiad_png_unfilter(const uint8_t* raw, int64_t raw_bytes, const 
     default: rc = launch_bpp<4>(waves, grid, lds, s, raw, raw_bytes, offsets, W, H, target, ring_len, out); break;
     }
     if (rc != CMDIAD_OK) return rc;
+    CMDIAD_CHECK_LAUNCH();
+    return CMDIAD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the writer's side
+// Filtering for the encoder (utils/png.py: write_many): images [n,H,W,C] uint8 -> scanlines [n, H * (1 + W * C)], the filter byte in
+// front of every row.  The sources are the UNFILTERED image, so no row or byte waits for another: one wave owns a row, lane l takes
+// bytes l, l + 64, ...  Adaptive (mode 5): a first walk sums m(b) = b < 128 ? b : 256 - b of the five candidates per lane, an
+// integer butterfly adds them over the wave (exact, order-free; a row is at most 64 KiB, so a sum stays below 2^23), the lowest
+// type among the smallest sums wins; a second walk writes it.  A forced mode takes the second walk only.
+namespace {
+
+__device__ __forceinline__ uint32_t filt_byte(uint32_t ft, uint32_t x, uint32_t a, uint32_t b, uint32_t c)
+{
+    const uint32_t pa = __builtin_amdgcn_sad_u8(b, c, 0u), pb = __builtin_amdgcn_sad_u8(a, c, 0u);
+    const uint32_t pc = (uint32_t)abs((int)(a + b) - (int)(2 * c));
+    const uint32_t paeth = (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
+    const uint32_t pred = ft == 1 ? a : ft == 2 ? b : ft == 3 ? (a + b) >> 1 : ft == 4 ? paeth : 0u;
+    return (x - pred) & 0xff;
+}
+
+__device__ __forceinline__ uint32_t filt_cost(uint32_t v) { return v < 128u ? v : 256u - v; }
+
+// grid (ceil(n H / 4)), 4 waves: wave w of workgroup g takes row 4 g + w of the batch's n * H rows
+__global__ __launch_bounds__(256) void png_filter_kernel(const uint8_t* __restrict__ img, long long rows, int H, int rb, int C, int mode,
+                                                         uint8_t* __restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;                                   // (wave-uniform; the kernel has no barrier)
+    const int r = (int)(row % H);
+    const uint8_t* __restrict__ cur = img + (size_t)row * rb;
+    const uint8_t* __restrict__ up = cur - rb;                 // read only when r > 0
+    const bool has_up = r > 0;
+    uint32_t ft = (uint32_t)mode;
+    if (mode == 5) {
+        uint32_t cost[5] = {0u, 0u, 0u, 0u, 0u};
+        for (int i = lane; i < rb; i += 64) {
+            const uint32_t x = cur[i], a = i >= C ? cur[i - C] : 0u, b = has_up ? up[i] : 0u, c = (has_up && i >= C) ? up[i - C] : 0u;
+#pragma unroll
+            for (int t = 0; t < 5; ++t) cost[t] += filt_cost(filt_byte((uint32_t)t, x, a, b, c));
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1)
+#pragma unroll
+            for (int t = 0; t < 5; ++t) cost[t] += __shfl_xor(cost[t], m, 64);
+        ft = 0;
+        uint32_t best = cost[0];
+#pragma unroll
+        for (int t = 1; t < 5; ++t)
+            if (cost[t] < best) best = cost[t], ft = (uint32_t)t;
+    }
+    uint8_t* __restrict__ o = out + (size_t)row * (1 + (size_t)rb);
+    if (lane == 0) o[0] = (uint8_t)ft;
+    for (int i = lane; i < rb; i += 64) {
+        const uint32_t x = cur[i], a = i >= C ? cur[i - C] : 0u, b = has_up ? up[i] : 0u, c = (has_up && i >= C) ? up[i - C] : 0u;
+        o[1 + i] = (uint8_t)filt_byte(ft, x, a, b, c);
+    }
+}
+
+}  // namespace
+
+extern "C" int cmdiad_png_filter(const uint8_t* images, int n, int H, int W, int C, int mode, uint8_t* scanlines, cmdiad_stream_t stream)
+{
+    CMDIAD_REQUIRE(n >= 0 && n <= 65535 && W >= 1 && W <= kMaxSide && H >= 1 && H <= kMaxSide && C >= 1 && C <= 4, CMDIAD_ERR_ARG,
+                   "cmdiad_png_filter: bad sizes n=%d (0..65535) W=%d H=%d (sides 1..%d) C=%d (1..4)", n, W, H, kMaxSide, C);
+    CMDIAD_REQUIRE(mode >= 0 && mode <= 5, CMDIAD_ERR_ARG, "cmdiad_png_filter: mode=%d (0..4 force a filter type, 5 = adaptive)", mode);
+    if (n == 0) return CMDIAD_OK;
+    CMDIAD_REQUIRE(images && scanlines, CMDIAD_ERR_ARG, "cmdiad_png_filter: null pointer");
+    const long long rows = (long long)n * H;
+    hipLaunchKernelGGL(png_filter_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, images, rows, H, W * C, C,
+                       mode, scanlines);
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
 }

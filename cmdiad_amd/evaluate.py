@@ -113,7 +113,13 @@ class ClassRun:
     the ``.cmdfit`` instead (the class is not fitted, so calibration_holdout plays no part there; where it or regions_dir is set
     and the ``.cmdcal`` is missing beside a stored fit, fit_device() raises instead of running without regions).  ``args.regions_dir`` -- when the class has a calibration, predict() ends by writing
     ``<regions_dir>/<class>.regions.json`` (thresholds, then per test image its decision and regions) and result() gains a
-    ``regions`` entry.  ``args.min_area`` / ``args.max_regions``: defaults 1 and 16."""
+    ``regions`` entry.  ``args.min_area`` / ``args.max_regions``: defaults 1 and 16.
+
+    Overlays (docs/overlay.md), read the same way, off when unset and under the same rule for the calibration:
+    ``args.overlay_dir`` -- predict() ends by writing one PNG per test image, ``<overlay_dir>/<class>/<index>.png``, in chunks of at
+    most 32: the score map coloured over the sample's own rgb tensor, the contour of the calibration's pixel threshold and the boxes
+    of the regions (min_area / max_regions) drawn in; result() gains an ``overlays`` entry (directory, file count) and ``seconds``
+    an ``overlays`` timing.  ``args.overlay_span`` (default 2.0): OverlaySpec.from_calibration's span."""
 
     def __init__(self, args, data, weights=None, method=None, extractor=None):
         from .utils.utils import set_seeds
@@ -141,6 +147,10 @@ class ClassRun:
         self.calibration = self.held_out = self.regions_summary = None
         if self.regions_dir and not self.holdout and not self.load_fit_dir:
             raise ValueError("regions_dir needs a calibration: set calibration_holdout, or load_fit_dir with a .cmdcal beside the fit")
+        self.overlay_dir, self.overlay_span = getattr(args, "overlay_dir", None), getattr(args, "overlay_span", None) or 2.0
+        self.overlays_summary = None
+        if self.overlay_dir and not self.holdout and not self.load_fit_dir:
+            raise ValueError("overlay_dir needs a calibration: set calibration_holdout, or load_fit_dir with a .cmdcal beside the fit")
 
     def _fit_file(self, directory):
         return os.path.join(directory, f"{self.data.name}.cmdfit")
@@ -173,9 +183,9 @@ class ClassRun:
             if os.path.exists(self._cal_file(self.load_fit_dir)):
                 from . import regions
                 self.calibration = regions.Calibration.load(self._cal_file(self.load_fit_dir), fit=self._fit_file(self.load_fit_dir))
-            elif self.holdout or self.regions_dir:
+            elif self.holdout or self.regions_dir or self.overlay_dir:
                 raise ValueError(f"{self._cal_file(self.load_fit_dir)} is missing: the stored fit of class {data.name} is loaded, not "
-                                 "fitted, so calibration_holdout / regions_dir need the calibration saved beside it")
+                                 "fitted, so calibration_holdout / regions_dir / overlay_dir need the calibration saved beside it")
             return self
         # the loaders are drained first (the reference's DataLoader workers prefetch beside the model; a synthetic class generates its
         # samples on this thread): "load" is reported on its own and the phase timings below are the method's
@@ -253,10 +263,35 @@ class ClassRun:
         m.calculate_metrics()
         self.sec["metrics"] = time.perf_counter() - t0
         self.phases.append("metrics")
+        if self.overlay_dir and self.calibration is not None:
+            self._write_overlays()
         self.test_items = None
         if self.regions_dir and self.calibration is not None:
             self._write_regions()
         return self
+
+    def _write_overlays(self):
+        """<overlay_dir>/<class>/<index>.png for every test image, in chunks of at most 32: per chunk the region tables on the device,
+        one render launch over the samples' normalised rgb tensors, one filter launch, and the writer threads of utils.png."""
+        from . import overlay, regions
+        m, cal = self.method, self.calibration
+        t0 = time.perf_counter()
+        folder = os.path.join(self.overlay_dir, self.data.name)
+        os.makedirs(folder, exist_ok=True)
+        spec = overlay.OverlaySpec.from_calibration(cal, self.overlay_span)
+        maps = np.stack([np.asarray(p, dtype=np.float64) for p in m.predictions])
+        files = 0
+        for at in range(0, len(maps), overlay.CHUNK):
+            part = regions._device_maps(maps[at:at + overlay.CHUNK])
+            rgb = torch.cat([it[0][0].reshape(1, 3, *it[0][0].shape[-2:]) for it in self.test_items[at:at + overlay.CHUNK]])
+            rgb = rgb.to(part.device, torch.float32)
+            thr = torch.full((1,), cal.pixel_threshold, dtype=torch.float64, device=part.device)
+            tables = regions.region_tables_device(part, thr, self.min_area, self.max_regions)
+            paths = [os.path.join(folder, f"{at + i:04d}.png") for i in range(part.shape[0])]
+            overlay.save(paths, part, spec, background=rgb if tuple(rgb.shape[-2:]) == tuple(part.shape[-2:]) else None, regions=tables)
+            files += len(paths)
+        self.overlays_summary = dict(directory=folder, files=files)
+        self.sec["overlays"] = time.perf_counter() - t0
 
     def _write_regions(self):
         """<regions_dir>/<class>.regions.json: the thresholds, then per test image its decision and its regions; the summary of
@@ -293,6 +328,8 @@ class ClassRun:
                                  if torch.is_tensor(getattr(m, f"patch_{k}_lib", None))})
         if self.regions_summary is not None:
             out["regions"] = dict(self.regions_summary)
+        if self.overlays_summary is not None:
+            out["overlays"] = dict(self.overlays_summary)
         out["_extractor"] = m.deep_feature_extractor
         return out
 

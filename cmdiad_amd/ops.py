@@ -1555,6 +1555,118 @@ def region_table(maps, labels, n_comp, comp_offset, comp_size, min_area=1, max_r
     return count, ints, vals
 
 
+# ------------------------------------------------------------------------------------ overlays (docs/overlay.md)
+OVERLAY_MAX_SIDE = 1 << 14
+OVERLAY_BACKGROUNDS = (None, torch.uint8, torch.float32)     # the index is cmdiad_overlay_render's background kind
+PNG_FILTER_MODES = ("none", "sub", "up", "average", "paeth", "adaptive")     # the index is cmdiad_png_filter's mode
+
+
+def _rgb_word(rgb, who):
+    r, g, b = (int(v) for v in rgb)
+    if not all(0 <= v <= 255 for v in (r, g, b)):
+        raise ValueError(f"{who}: a colour is three bytes, got {tuple(rgb)!r}")
+    return r | g << 8 | b << 16
+
+
+def overlay_render(maps, lohi, lut, alpha, size=None, thr=None, background=None, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0),
+                   count=None, ints=None, line_px=1, contour_rgb=(255, 255, 255), box_rgb=(0, 255, 0), canvas=None, nan_count=None):
+    """maps [n,H,W] f64 -> (canvas [n,Ho,Wo,3] u8, nan_count [1] i32), one launch (include/cmdiad_hip.h has the arithmetic).
+    lohi: f64 ON THE DEVICE, [2] or [n,2]; thr: None (no contour) or f64 on the device with 1 or n entries -- both are read by
+    the kernel, rewriting them in place changes the next launch.  lut [256,3] u8 and alpha [256] u8 on the device.  size = (Ho, Wo),
+    default the map's.  background: None, uint8 [n,Ho,Wo,3], or float32 [n,3,Ho,Wo] normalised with mean / std.  count [n] i32 and
+    ints [n,K,8] i32: cmdiad_region_table's tables (both or neither).  canvas / nan_count: buffers to write into.  No
+    synchronisation."""
+    n, H, W = _chk_maps(maps, "overlay_render")
+    dev = maps.device
+    Ho, Wo = (H, W) if size is None else (int(size[0]), int(size[1]))
+    if not (1 <= H <= OVERLAY_MAX_SIDE and 1 <= W <= OVERLAY_MAX_SIDE and 1 <= Ho <= OVERLAY_MAX_SIDE and 1 <= Wo <= OVERLAY_MAX_SIDE) \
+            or n * Ho * Wo > METRICS_MAX_TOTAL:
+        raise ValueError(f"overlay_render: maps {tuple(maps.shape)} -> canvas {Ho} x {Wo}: sides 1..2^14, n*Ho*Wo <= 2^30")
+    _chk(lohi, torch.float64, "overlay_render.lohi"); _chk(lut, torch.uint8, "overlay_render.lut"); _chk(alpha, torch.uint8, "overlay_render.alpha")
+    if lohi is None or lut is None or alpha is None:
+        raise ValueError("overlay_render: lohi, lut and alpha are required")
+    if tuple(lohi.shape) not in ((2,), (1, 2), (n, 2)) or tuple(lut.shape) != (256, 3) or tuple(alpha.shape) != (256,):
+        raise ValueError(f"overlay_render: lohi must be [2] or [{n},2], lut [256,3], alpha [256]; got {tuple(lohi.shape)}, "
+                         f"{tuple(lut.shape)}, {tuple(alpha.shape)}")
+    _chk(thr, torch.float64, "overlay_render.thr")
+    if thr is not None and thr.numel() not in (1, n):
+        raise ValueError(f"overlay_render: thr must hold 1 or n = {n} values, got {tuple(thr.shape)}")
+    kind = 0
+    if background is not None:
+        if background.dtype not in OVERLAY_BACKGROUNDS[1:]:
+            raise TypeError(f"overlay_render.background: expected uint8 [n,Ho,Wo,3] or float32 [n,3,Ho,Wo], got {background.dtype}")
+        kind = OVERLAY_BACKGROUNDS.index(background.dtype)
+        _chk(background, background.dtype, "overlay_render.background")
+        want = (n, Ho, Wo, 3) if kind == 1 else (n, 3, Ho, Wo)
+        if tuple(background.shape) != want:
+            raise ValueError(f"overlay_render: a {background.dtype} background must be {want} (the canvas size: it is not resampled), "
+                             f"got {tuple(background.shape)}")
+    if (count is None) != (ints is None):
+        raise ValueError("overlay_render: count and ints come together")
+    K = 1
+    if count is not None:
+        _chk(count, torch.int32, "overlay_render.count"); _chk(ints, torch.int32, "overlay_render.ints")
+        if count.numel() != n or ints.dim() != 3 or ints.shape[0] != n or ints.shape[2] != 8 or not 1 <= ints.shape[1] <= REGION_MAX:
+            raise ValueError(f"overlay_render: count must be [{n}] and ints [{n},K,8] with K in 1..{REGION_MAX}; got "
+                             f"{tuple(count.shape)}, {tuple(ints.shape)}")
+        K = ints.shape[1]
+    line_px = int(line_px)
+    if not 1 <= line_px <= 8:
+        raise ValueError(f"overlay_render: line_px = {line_px} (1..8)")
+    mean, std = [float(v) for v in mean], [float(v) for v in std]
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("overlay_render: mean and std are three values each")
+    if canvas is None:
+        canvas = torch.empty((n, Ho, Wo, 3), dtype=torch.uint8, device=dev)
+    if nan_count is None:
+        nan_count = torch.zeros((1,), dtype=torch.int32, device=dev)
+    _chk(canvas, torch.uint8, "overlay_render.canvas"); _chk(nan_count, torch.int32, "overlay_render.nan_count")
+    if tuple(canvas.shape) != (n, Ho, Wo, 3) or nan_count.numel() != 1:
+        raise ValueError(f"overlay_render: canvas must be {(n, Ho, Wo, 3)} and nan_count one entry")
+    for t in (lohi, lut, alpha, thr, background, count, ints, canvas, nan_count):
+        if t is not None and t.device != dev:
+            raise ValueError("overlay_render: every tensor must be on the maps' device")
+    if n:
+        _call("cmdiad_overlay_render", _p(maps), n, H, W, Ho, Wo, _p(lohi), int(lohi.numel() == 2 * n and n > 1), _p(thr),
+              int(thr is not None and thr.numel() == n and n > 1), _p(background), kind, *mean, *std, _p(lut), _p(alpha), _p(count),
+              _p(ints), K, line_px, _rgb_word(contour_rgb, "overlay_render.contour_rgb"), _rgb_word(box_rgb, "overlay_render.box_rgb"),
+              _p(canvas), _p(nan_count), _stream())
+    else:
+        nan_count.zero_()
+    return canvas, nan_count
+
+
+def png_filter(images_u8, mode="adaptive", out=None):
+    """images [n,H,W,C] uint8 (C in 1..4; [n,H,W] is one channel) -> scanlines [n, H * (1 + W * C)] uint8: every row its filter byte
+    and its filtered bytes, what utils.png.encode deflates and cmdiad_png_unfilter undoes.  mode: one of PNG_FILTER_MODES or its
+    index; 'adaptive' picks per row the type with the smallest sum of min(b, 256 - b).  No synchronisation."""
+    _chk(images_u8, torch.uint8, "png_filter.images")
+    if images_u8.dim() == 3:
+        images_u8 = images_u8.unsqueeze(-1)
+    if images_u8.dim() != 4:
+        raise ValueError(f"png_filter: images must be [n,H,W,C] or [n,H,W], got {tuple(images_u8.shape)}")
+    n, H, W, C = images_u8.shape
+    if not (1 <= H <= OVERLAY_MAX_SIDE and 1 <= W <= OVERLAY_MAX_SIDE and 1 <= C <= 4 and n <= 65535):
+        raise ValueError(f"png_filter: unsupported shape {tuple(images_u8.shape)} (n <= 65535, sides 1..2^14, C in 1..4)")
+    if isinstance(mode, str):
+        if mode not in PNG_FILTER_MODES:
+            raise ValueError(f"png_filter: mode must be one of {PNG_FILTER_MODES}, got {mode!r}")
+        mode = PNG_FILTER_MODES.index(mode)
+    mode = int(mode)
+    if not 0 <= mode <= 5:
+        raise ValueError(f"png_filter: mode = {mode} (0..5)")
+    shape = (n, H * (1 + W * C))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=images_u8.device)
+    else:
+        _chk(out, torch.uint8, "png_filter.out")
+        if tuple(out.shape) != shape or out.device != images_u8.device:
+            raise ValueError(f"png_filter: out must be {shape} on the images' device, got {tuple(out.shape)} on {out.device}")
+    if n:
+        _call("cmdiad_png_filter", _p(images_u8), n, H, W, C, mode, _p(out), _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------ content digest (stored fits)
 def digest64(tensor, seed=0, acc=None):
     """cmdiad_digest64 of a device tensor's bytes, ADDED into `acc` ([1] int64 on the tensor's device; None: a fresh zero) -> acc.

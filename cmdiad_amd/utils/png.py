@@ -5,6 +5,9 @@ device, where csrc/png.hip undoes the row filters (docs/png.md).  Pure Python + 
   supported(layout)         -> bool           the subset the device decodes; everything else stays with Pillow, it is no error
   read_raw(path, target)    -> RawImage       the inflated, still FILTERED scanlines: uint8, exactly H * (1 + row_bytes) bytes
   decode_on_device(list[RawImage], device) -> uint8 tensor [B, ...]    one pinned upload, one cmdiad_png_unfilter launch per layout
+and the way back, for the overlays (docs/overlay.md):
+  encode(scanlines, layout, level) -> bytes   signature, IHDR, one IDAT of zlib.compress, IEND
+  encode_on_device(images) / write_many(paths, images)    one cmdiad_png_filter launch, one copy down, deflate on writer threads
 
 `target` names what the caller would have done with Pillow: 'rgb' = .convert('RGB') -> [H,W,3] (alpha dropped, grey replicated),
 'l' = .convert('L') -> [H,W] (the grey byte, or (R * 19595 + G * 38470 + B * 7471 + 0x8000) >> 16), 'raw' = np.array(Image.open(p))
@@ -268,3 +271,83 @@ def decode_on_device(raws, device):
             if not whole:
                 out.index_copy_(0, torch.tensor(idx, dtype=torch.int64).pin_memory().to(dev, non_blocking=True), got)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ the writer
+_COLOR_TYPE = {1: 0, 2: 4, 3: 2, 4: 6}
+FILTER_MODES = ("none", "sub", "up", "average", "paeth", "adaptive")       # the index is cmdiad_png_filter's mode
+
+
+def _chunk(kind, body=b""):
+    return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(body, zlib.crc32(kind)))
+
+
+def write_layout(width, height, channels):
+    """The PngLayout of the 8-bit file `encode` writes for an image of this size and channel count (1 grey, 2 grey + alpha, 3 rgb,
+    4 rgb + alpha)."""
+    if channels not in _COLOR_TYPE or width < 1 or height < 1:
+        raise ValueError(f"png.write_layout: {width} x {height} with {channels} channels (sides >= 1, 1..4 channels)")
+    return PngLayout(width=int(width), height=int(height), bit_depth=8, color_type=_COLOR_TYPE[channels], channels=channels, bpp=channels,
+                     row_bytes=int(width) * channels, interlace=0, has_plte=False, has_trns=False)
+
+
+def encode(scanlines, layout, level=6):
+    """scanlines: the FILTERED rows of one image, uint8 [H * (1 + row_bytes)] (filter byte in front of every row: what `read_raw`
+    returns and ops.png_filter produces) -> the bytes of a PNG: signature, IHDR, one IDAT holding zlib.compress(scanlines, level),
+    IEND.  Runs on the calling thread; zlib releases the GIL."""
+    if not supported(layout):
+        raise ValueError("png.encode: 8-bit non-interlaced files of colour type 0 / 2 / 4 / 6 only")
+    lines = np.ascontiguousarray(scanlines, dtype=np.uint8).reshape(-1)
+    need = layout.height * (1 + layout.row_bytes)
+    if lines.size != need:
+        raise ValueError(f"png.encode: {lines.size} bytes of scanlines, {layout.height} rows of 1 + {layout.row_bytes} bytes are {need}")
+    ihdr = struct.pack(">IIBBBBB", layout.width, layout.height, 8, layout.color_type, 0, 0, 0)
+    return SIGNATURE + _chunk(b"IHDR", ihdr) + _chunk(b"IDAT", zlib.compress(memoryview(lines), level)) + _chunk(b"IEND")
+
+
+def _filtered_on_host(images_u8, mode):
+    """(scanlines [n, H * (1 + W * C)] as a numpy view of one pinned buffer, layout): one ops.png_filter launch and one copy."""
+    import torch
+    from .. import ops
+    if images_u8.dim() == 3:
+        images_u8 = images_u8.unsqueeze(-1)
+    n, H, W, C = images_u8.shape
+    lay = write_layout(W, H, C)
+    lines = ops.png_filter(images_u8.contiguous(), mode)
+    host = torch.empty(lines.shape, dtype=torch.uint8, pin_memory=True)
+    host.copy_(lines, non_blocking=True)
+    torch.cuda.current_stream(lines.device).synchronize()
+    return host.numpy(), lay
+
+
+def encode_on_device(images_u8, level=6, mode="adaptive", writers=4):
+    """images uint8 [n,H,W,C] (or [n,H,W]) ON THE DEVICE -> list of n PNG files as bytes.  The row filters run on the device
+    (cmdiad_png_filter, one launch), the scanlines come down in one copy into a pinned buffer, and `writers` threads deflate."""
+    import concurrent.futures as cf
+    lines, lay = _filtered_on_host(images_u8, mode)
+    if len(lines) <= 1 or writers <= 1:
+        return [encode(row, lay, level) for row in lines]
+    with cf.ThreadPoolExecutor(writers) as pool:
+        return list(pool.map(lambda row: encode(row, lay, level), lines))
+
+
+def write_many(paths, images_u8, level=6, mode="adaptive", writers=4):
+    """One PNG per image of the device batch images_u8 [n,H,W,C] at paths[i] (the directories exist): filtered on the device,
+    deflated and written by `writers` threads.  Returns the files' sizes in bytes."""
+    import concurrent.futures as cf
+    paths = list(paths)
+    if len(paths) != images_u8.shape[0]:
+        raise ValueError(f"png.write_many: {len(paths)} paths for {images_u8.shape[0]} images")
+    if not paths:
+        return []
+    lines, lay = _filtered_on_host(images_u8, mode)
+
+    def one(i):
+        data = encode(lines[i], lay, level)
+        with open(paths[i], "wb") as fh:
+            fh.write(data)
+        return len(data)
+    if len(paths) == 1 or writers <= 1:
+        return [one(i) for i in range(len(paths))]
+    with cf.ThreadPoolExecutor(writers) as pool:
+        return list(pool.map(one, range(len(paths))))

@@ -862,6 +862,40 @@ int cmdiad_tiff_unpack(const uint8_t* raw, int64_t raw_bytes, const int64_t* chu
 int cmdiad_png_unfilter(const uint8_t* raw, int64_t raw_bytes, const int64_t* offsets, int B, int W, int H, int bpp, int target,
                         int waves, uint8_t* out, cmdiad_stream_t stream);
 
+/* The encoder's side (utils/png.py: encode, write_many; an addition, the ABI stays 6): images [n,H,W,C] uint8, C in 1..4 ->
+ * scanlines [n, H * (1 + W * C)], every row its filter byte and then its filtered bytes -- the layout above.  mode 0..4 forces that
+ * filter type on every row; mode 5 is adaptive: per row the type with the smallest sum of m(b) = b < 128 ? b : 256 - b over its
+ * filtered bytes, ties to the lowest type.  Row 0 sees a zero prior row, bytes before the first pixel see zero, Paeth is the
+ * standard predictor.  One wave per row, integer wave reductions: the result does not depend on any order.  n in 0..65535 (0 returns
+ * CMDIAD_OK without a launch), sides in 1..16384.  No allocation, no synchronisation, no scratch. */
+int cmdiad_png_filter(const uint8_t* images, int n, int H, int W, int C, int mode, uint8_t* scanlines, cmdiad_stream_t stream);
+
+/* ---- anomaly overlays (docs/overlay.md; an addition, the ABI stays 6) ----
+ * maps [n,H,W] f64 -> canvas [n,Ho,Wo,3] uint8 in one launch.  Per canvas pixel (x, y), every floating-point step one float64
+ * operation, rounded once, in this order:
+ *   score  u = (x + 0.5) * (W / Wo) - 0.5 clamped to [0, W - 1], x0 = floor(u), x1 = min(x0 + 1, W - 1), fx = u - x0, the same for y;
+ *          s = (m[y0,x0] (1 - fx) + m[y0,x1] fx) (1 - fy) + (m[y1,x0] (1 - fx) + m[y1,x1] fx) fy, where a tap (or row) whose weight is
+ *          exactly 0 is neither read nor added: Ho == H and Wo == W reproduce the map bit for bit, infinities included.
+ *   index  d = hi - lo; t = d > 0 ? (s - lo) / d : (s > lo ? 1 : 0), clamped to [0, 1] (a NaN t is 0); a NaN s gives t = 0 and is
+ *          counted; k = (int)floor(t * 255 + 0.5).  lohi lives in DEVICE memory: [2] (lohi_per_image = 0) or [n,2] (1).
+ *   colour c = lut[k] (lut [256,3] uint8, device), a = alpha[k] (alpha [256] uint8, device); per channel
+ *          out = (c a + bg (255 - a) + 127) / 255 in integers.  bg_kind 0: no background, out = c; 1: bg uint8 [n,Ho,Wo,3];
+ *          2: bg float32 [n,3,Ho,Wo], byte = clamp(floor((v std + mean) 255 + 0.5), 0, 255) in float64 from the widened float.
+ *   contour (thr != NULL; thr in DEVICE memory, [1] or [n] by thr_per_image, as cmdiad_threshold_mask) the pixel takes contour_rgb iff
+ *          s > thr and one of its four neighbours inside the canvas has !(s > thr); strict, a NaN is never above.
+ *   boxes  (count [n] and ints [n,K,8] of cmdiad_region_table, both or neither) slot j < min(count, K) with the map box x0, y0, x1, y1:
+ *          X0 = x0 Wo / W, X1 = ((x1 + 1) Wo + W - 1) / W - 1 (integer division; Y alike), clamped to the canvas; the pixel takes
+ *          box_rgb iff it lies in the box and fewer than line_px (1..8) pixels from its border.  Boxes go over contours.
+ * Colours are r | g << 8 | b << 16.  nan_count [1] int32 (NULL: not wanted) = canvas pixels with a NaN score; zeroed first, also when
+ * n == 0.  n in 0..65535, sides in 1..16384, n H W and n Ho Wo <= 2^30, K in 1..64 (checked also without tables).  Ho Wo a multiple
+ * of 4 with a 4-byte aligned canvas (and background: 4 bytes for kind 1, 16 for kind 2) takes dword stores; anything else byte
+ * stores, with the same result.  No allocation, no synchronisation, no scratch. */
+int cmdiad_overlay_render(const double* maps, int n, int H, int W, int Ho, int Wo, const double* lohi, int lohi_per_image,
+                          const double* thr, int thr_per_image, const void* bg, int bg_kind, double mean_r, double mean_g, double mean_b,
+                          double std_r, double std_g, double std_b, const uint8_t* lut, const uint8_t* alpha, const int32_t* count,
+                          const int32_t* ints, int K, int line_px, uint32_t contour_rgb, uint32_t box_rgb, uint8_t* canvas,
+                          int32_t* nan_count, cmdiad_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Content digest (stored fits: cmdiad_amd/fitted.py, docs/fitted.md)
  * ------------------------------------------------------------------------------------------- */
