@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void blur8_maps_kernel(const float* __restrict
     float* dst = out + (size_t)blockIdx.x * H * W;
     const int SW = padded_stride(W), SH = padded_stride(H);
     unsigned char* A = lds_u8;                      // [H][SW]  row-major image
-    unsigned char* T = lds_u8 + (size_t)(H > W ? H : W) * (SW > SH ? SW : SH);  // second buffer (either orientation)
+    unsigned char* T = lds_u8 + (H * SW > W * SH ? H * SW : W * SH);  // second buffer (either orientation)
 
     // ---- map maximum (utils.py:81 img.max())
     float mx = -__builtin_inff();
@@ -136,7 +136,9 @@ __global__ __launch_bounds__(256) void ocsvm_score_maps_kernel(const float* __re
 extern "C" size_t cmdiad_blur8_lds_bytes(int H, int W)
 {
     const int SW = ((W + 3) / 4 * 4) + 4, SH = ((H + 3) / 4 * 4) + 4;
-    return (size_t)2 * (H > W ? H : W) * (SW > SH ? SW : SH);
+    // two buffers, each holding the padded image in either orientation: [H][SW] or, transposed, [W][SH]
+    const size_t rows = (size_t)H * SW, cols = (size_t)W * SH;
+    return 2 * (rows > cols ? rows : cols);
 }
 
 extern "C" int cmdiad_blur8_maps(const float* maps, int n_maps, int H, int W, float radius, float* out, cmdiad_stream_t stream)

@@ -548,7 +548,8 @@ int cmdiad_gather_points(const float* feat, const int32_t* idx, int B, int C, in
 /* KNNGaussianBlur (utils/utils.py:71-83) for n_maps maps [n_maps,H,W] f32: each map is divided by its maximum, quantised
  * like torchvision's ToPILImage (mul(255).byte()), blurred exactly as Pillow's ImageFilter.GaussianBlur(radius) does on an
  * 8-bit image (three extended-box passes per axis, 2^24 fixed point; bit-exact with oracle orc_pil_gaussian_blur_u8),
- * and mapped back (/255 * max).  H, W >= 2*floor(box radius)+2 and 2 padded 8-bit copies must fit the LDS (<= 256 x 256). */
+ * and mapped back (/255 * max).  H, W >= 2*floor(box radius)+2, and two copies of the padded 8-bit image (in the larger of its
+ * two orientations: cmdiad_blur8_lds_bytes) must fit the LDS: squares up to 284 x 284, narrow strips with a longer side. */
 int cmdiad_blur8_maps(const float* maps, int n_maps, int H, int W, float radius, float* out, cmdiad_stream_t stream);
 size_t cmdiad_blur8_lds_bytes(int H, int W);
 
