@@ -147,6 +147,7 @@ SIGNATURES = {
     "cmdiad_pro_hist": [P, I, P, P, I, I, P, P],
     "cmdiad_threshold_mask": [P, P, I, I, I, I, P, P, P],
     "cmdiad_region_table": [P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, SZ, P],
+    "cmdiad_region_measure": [P, P, P, P, c_int64, c_int64, I, I, I, I, P, P, P, P],
     "cmdiad_tiff_unpack": [P, c_int64, P, I, I, I, I, I, I, I, I, I, I, I, P, P],
     "cmdiad_png_unfilter": [P, c_int64, P, I, I, I, I, I, I, P, P],
     "cmdiad_png_filter": [P, I, I, I, I, I, P, P],

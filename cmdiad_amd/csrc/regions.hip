@@ -14,6 +14,8 @@
 //   n ceil(H/2) ceil(W/2) -- every index into them is checked against it -- and one workgroup per image that runs K rounds of
 //   "largest (key(peak), lowest label) strictly after the previous pick" over the components with area >= min_area: the order is
 //   total, so no table of taken components is needed and no rank is counted.  The launch geometry depends on n, H, W alone.
+// cmdiad_region_measure: the kept regions in the units of the organised cloud -- valid points, per-axis extent, first and second
+//   moments about the minimum corner, the area of the triangle mesh -- by one workgroup per (slot, image) in score_sum's order.
 #include <limits.h>
 
 #include "launch.h"
@@ -312,6 +314,168 @@ __global__ __launch_bounds__(256) void region_select_kernel(const double* __rest
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- measurement
+// The regions in the units of the organised cloud (docs/regions.md, "Contract of a measurement table").  A cloud is addressed
+// through two element strides, so the planar [n,3,H,W] and the interleaved [n,H,W,3] layout are one code path and give the
+// same bits; the image stride is 3 H W in both.
+struct Cloud {
+    const float* p;
+    long long pix, ch;
+};
+
+struct Pt { float x, y, z; };
+
+__device__ __forceinline__ Pt cloud_at(const Cloud& c, size_t img_base, int q)
+{
+    const float* at = c.p + img_base + (long long)q * c.pix;
+    return {at[0], at[c.ch], at[2 * c.ch]};
+}
+__device__ __forceinline__ bool finite3(const Pt& p) { return fabsf(p.x) < INFINITY && fabsf(p.y) < INFINITY && fabsf(p.z) < INFINITY; }
+// the reference's rule (all three coordinates non-zero; -0.0 is zero) and finite
+__device__ __forceinline__ bool valid_pt(const Pt& p) { return p.x != 0.f && p.y != 0.f && p.z != 0.f && finite3(p); }
+
+// 0.5 |(b - a) x (c - a)| from the widened floats, every step one float64 operation rounded once (no contraction)
+__device__ __forceinline__ double tri_area(const Pt& a, const Pt& b, const Pt& c)
+{
+#pragma clang fp contract(off)
+    const double ux = (double)b.x - (double)a.x, uy = (double)b.y - (double)a.y, uz = (double)b.z - (double)a.z;
+    const double vx = (double)c.x - (double)a.x, vy = (double)c.y - (double)a.y, vz = (double)c.z - (double)a.z;
+    const double cx = uy * vz - uz * vy, cy = uz * vx - ux * vz, cz = ux * vy - uy * vx;
+    return 0.5 * sqrt(cx * cx + cy * cy + cz * cz);
+}
+
+// grid (ceil(HW / 256), n): points with a non-finite coordinate, over the whole frames
+__global__ __launch_bounds__(256) void cloud_bad_kernel(Cloud c, int HW, int32_t* __restrict__ bad_count)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    int bad = 0;
+    if (q < HW) bad = !finite3(cloud_at(c, (size_t)blockIdx.y * 3 * HW, q));
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) bad += __shfl_xor(bad, m, 64);
+    if (bad && lane_id() == 0) atomicAdd(bad_count, bad);
+}
+
+// grid (K, n), one workgroup per (slot, image).  Two walks over the slot's box in the order of score_sum: thread t takes box
+// positions t, t + 256, ... in raster order, then the fixed 64-lane butterfly and (w0 + w1) + (w2 + w3).  Walk 1: n_pts, lo, hi
+// (minimum and maximum are exact whatever the order).  Walk 2: the sums about lo, the area, n_tri.  The table is an input that is
+// not trusted: count is clamped to [0, K], the box and the peak to the image, a label below 1 matches no pixel.
+__global__ __launch_bounds__(256) void region_measure_kernel(const int32_t* __restrict__ labels, const int32_t* __restrict__ count,
+                                                             const int32_t* __restrict__ ints, Cloud c, int H, int W, int K,
+                                                             int32_t* __restrict__ m_ints, double* __restrict__ m_vals)
+{
+#pragma clang fp contract(off)
+    __shared__ int sh_i[4];
+    __shared__ float sh_f[4][6];
+    __shared__ double sh_d[4][10];
+    const int slot = blockIdx.x, img = blockIdx.y, tid = threadIdx.x, wave = tid >> 6;
+    const int HW = H * W;
+    int32_t* oi = m_ints + ((size_t)img * K + slot) * 4;
+    double* ov = m_vals + ((size_t)img * K + slot) * 20;
+    int cnt = count[img];
+    cnt = cnt < 0 ? 0 : (cnt > K ? K : cnt);
+    const int32_t* row = ints + ((size_t)img * K + slot) * 8;
+    const int L = slot < cnt ? row[0] : 0;
+    int x0 = 0, y0 = 0, bw = 0, bh = 0;
+    if (L >= 1) {
+        x0 = max(row[2], 0), y0 = max(row[3], 0);
+        bw = min(row[4], W - 1) - x0 + 1, bh = min(row[5], H - 1) - y0 + 1;
+    }
+    const int nb = bw > 0 && bh > 0 ? bw * bh : 0;   // block-uniform
+    const size_t lbase = (size_t)img * HW, cbase = (size_t)img * 3 * HW;
+
+    int npts = 0;
+    float lox = INFINITY, loy = INFINITY, loz = INFINITY, hix = -INFINITY, hiy = -INFINITY, hiz = -INFINITY;
+    for (int j = tid; j < nb; j += 256) {
+        const int yy = j / bw;
+        const int q = (y0 + yy) * W + x0 + (j - yy * bw);
+        if (labels[lbase + q] != L) continue;
+        const Pt p = cloud_at(c, cbase, q);
+        if (!valid_pt(p)) continue;
+        ++npts;
+        lox = fminf(lox, p.x), loy = fminf(loy, p.y), loz = fminf(loz, p.z);
+        hix = fmaxf(hix, p.x), hiy = fmaxf(hiy, p.y), hiz = fmaxf(hiz, p.z);
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        npts += __shfl_xor(npts, m, 64);
+        lox = fminf(lox, __shfl_xor(lox, m, 64)), loy = fminf(loy, __shfl_xor(loy, m, 64)), loz = fminf(loz, __shfl_xor(loz, m, 64));
+        hix = fmaxf(hix, __shfl_xor(hix, m, 64)), hiy = fmaxf(hiy, __shfl_xor(hiy, m, 64)), hiz = fmaxf(hiz, __shfl_xor(hiz, m, 64));
+    }
+    if (lane_id() == 0) {
+        sh_i[wave] = npts;
+        sh_f[wave][0] = lox, sh_f[wave][1] = loy, sh_f[wave][2] = loz, sh_f[wave][3] = hix, sh_f[wave][4] = hiy, sh_f[wave][5] = hiz;
+    }
+    __syncthreads();
+    npts = (sh_i[0] + sh_i[1]) + (sh_i[2] + sh_i[3]);
+    if (npts == 0) {   // block-uniform: a dead slot, an empty box, or a region without a valid point -- every value is zero
+        if (tid < 4) oi[tid] = 0;
+        if (tid < 20) ov[tid] = 0.0;
+        return;
+    }
+    lox = fminf(fminf(sh_f[0][0], sh_f[1][0]), fminf(sh_f[2][0], sh_f[3][0]));
+    loy = fminf(fminf(sh_f[0][1], sh_f[1][1]), fminf(sh_f[2][1], sh_f[3][1]));
+    loz = fminf(fminf(sh_f[0][2], sh_f[1][2]), fminf(sh_f[2][2], sh_f[3][2]));
+    hix = fmaxf(fmaxf(sh_f[0][3], sh_f[1][3]), fmaxf(sh_f[2][3], sh_f[3][3]));
+    hiy = fmaxf(fmaxf(sh_f[0][4], sh_f[1][4]), fmaxf(sh_f[2][4], sh_f[3][4]));
+    hiz = fmaxf(fmaxf(sh_f[0][5], sh_f[1][5]), fmaxf(sh_f[2][5], sh_f[3][5]));
+    __syncthreads();   // sh_i is written again below
+
+    const double ox = (double)lox, oy = (double)loy, oz = (double)loz;
+    double sx = 0.0, sy = 0.0, sz = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0, area = 0.0;
+    int ntri = 0;
+    for (int j = tid; j < nb; j += 256) {
+        const int yy = j / bw;
+        const int y = y0 + yy, x = x0 + (j - yy * bw);
+        const int q = y * W + x;
+        if (labels[lbase + q] != L) continue;
+        const Pt a = cloud_at(c, cbase, q);
+        if (!valid_pt(a)) continue;
+        const double dx = (double)a.x - ox, dy = (double)a.y - oy, dz = (double)a.z - oz;
+        sx += dx, sy += dy, sz += dz;
+        sxx += dx * dx, sxy += dx * dy, sxz += dx * dz, syy += dy * dy, syz += dy * dz, szz += dz * dz;
+        if (y + 1 >= H || x + 1 >= W) continue;
+        // the cell below and right of (y, x): both triangles hold the diagonal a - d
+        if (labels[lbase + q + W + 1] != L) continue;
+        const Pt d = cloud_at(c, cbase, q + W + 1);
+        if (!valid_pt(d)) continue;
+        if (labels[lbase + q + 1] == L) {
+            const Pt b = cloud_at(c, cbase, q + 1);
+            if (valid_pt(b)) area += tri_area(a, b, d), ++ntri;
+        }
+        if (labels[lbase + q + W] == L) {
+            const Pt e = cloud_at(c, cbase, q + W);
+            if (valid_pt(e)) area += tri_area(a, d, e), ++ntri;
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        ntri += __shfl_xor(ntri, m, 64);
+        sx += __shfl_xor(sx, m, 64), sy += __shfl_xor(sy, m, 64), sz += __shfl_xor(sz, m, 64);
+        sxx += __shfl_xor(sxx, m, 64), sxy += __shfl_xor(sxy, m, 64), sxz += __shfl_xor(sxz, m, 64);
+        syy += __shfl_xor(syy, m, 64), syz += __shfl_xor(syz, m, 64), szz += __shfl_xor(szz, m, 64);
+        area += __shfl_xor(area, m, 64);
+    }
+    if (lane_id() == 0) {
+        sh_i[wave] = ntri;
+        double* o = sh_d[wave];
+        o[0] = sx, o[1] = sy, o[2] = sz, o[3] = sxx, o[4] = sxy, o[5] = sxz, o[6] = syy, o[7] = syz, o[8] = szz, o[9] = area;
+    }
+    __syncthreads();
+    if (tid < 10) ov[9 + tid] = (sh_d[0][tid] + sh_d[1][tid]) + (sh_d[2][tid] + sh_d[3][tid]);
+    if (tid == 10) ov[19] = 0.0;
+    if (tid == 11) {
+        // the point at the peak pixel, wherever the table puts it inside the image
+        const int px = row[6], py = row[7];
+        Pt p = {0.f, 0.f, 0.f};
+        const bool inside = px >= 0 && px < W && py >= 0 && py < H;
+        if (inside) p = cloud_at(c, cbase, py * W + px);
+        const bool ok = inside && valid_pt(p);
+        oi[0] = npts, oi[1] = (sh_i[0] + sh_i[1]) + (sh_i[2] + sh_i[3]), oi[2] = ok ? 1 : 0, oi[3] = 0;
+        ov[0] = ox, ov[1] = oy, ov[2] = oz, ov[3] = (double)hix, ov[4] = (double)hiy, ov[5] = (double)hiz;
+        ov[6] = ok ? (double)p.x : 0.0, ov[7] = ok ? (double)p.y : 0.0, ov[8] = ok ? (double)p.z : 0.0;
+    }
+}
+
 }  // namespace
 
 extern "C" int cmdiad_threshold_mask(const double* maps, const double* thr, int thr_per_image, int n, int H, int W, uint8_t* mask,
@@ -373,6 +537,36 @@ extern "C" int cmdiad_region_table(const double* maps, const int32_t* labels, co
     CMDIAD_CHECK_LAUNCH();
     hipLaunchKernelGGL(region_select_kernel, dim3((unsigned)n), dim3(256), 0, s, maps, labels, n_comp, comp_offset, comp_size, H, W, cap,
                        min_area, max_regions, T, count, ints, vals);
+    CMDIAD_CHECK_LAUNCH();
+    return CMDIAD_OK;
+}
+
+extern "C" int cmdiad_region_measure(const int32_t* labels, const int32_t* count, const int32_t* ints, const float* cloud,
+                                     long long pix_stride, long long ch_stride, int n, int H, int W, int max_regions, int32_t* m_ints,
+                                     double* m_vals, int32_t* bad_count, cmdiad_stream_t stream)
+{
+    CMDIAD_REQUIRE(sizes_ok(n, H, W) && max_regions >= 1 && max_regions <= kMaxRegions, CMDIAD_ERR_ARG,
+                   "cmdiad_region_measure: bad sizes n=%d (0..%d) H=%d W=%d (>= 1, H*W <= %d, n*H*W <= %d) max_regions=%d (1..%d)", n,
+                   kMaxImages, H, W, kMaxImagePixels, kMaxTotal, max_regions, kMaxRegions);
+    const long long HW = (long long)H * W;
+    CMDIAD_REQUIRE((pix_stride == 1 && ch_stride == HW) || (pix_stride == 3 && ch_stride == 1), CMDIAD_ERR_ARG,
+                   "cmdiad_region_measure: bad strides pix_stride=%lld ch_stride=%lld (planar [n,3,H,W]: 1 and H*W = %lld; interleaved "
+                   "[n,H,W,3]: 3 and 1)", pix_stride, ch_stride, HW);
+    CMDIAD_REQUIRE(n == 0 || (labels && count && ints && cloud && m_ints && m_vals), CMDIAD_ERR_ARG,
+                   "cmdiad_region_measure: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    if (bad_count) {
+        hipError_t e = hipMemsetAsync(bad_count, 0, sizeof(int32_t), s);
+        CMDIAD_REQUIRE(e == hipSuccess, CMDIAD_ERR_LAUNCH, "cmdiad_region_measure: hipMemsetAsync: %s", hipGetErrorString(e));
+    }
+    if (n == 0) return CMDIAD_OK;
+    const Cloud c = {cloud, pix_stride, ch_stride};
+    if (bad_count) {
+        hipLaunchKernelGGL(cloud_bad_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)n), dim3(256), 0, s, c, (int)HW, bad_count);
+        CMDIAD_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(region_measure_kernel, dim3((unsigned)max_regions, (unsigned)n), dim3(256), 0, s, labels, count, ints, c, H, W,
+                       max_regions, m_ints, m_vals);
     CMDIAD_CHECK_LAUNCH();
     return CMDIAD_OK;
 }

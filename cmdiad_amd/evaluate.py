@@ -113,7 +113,9 @@ class ClassRun:
     the ``.cmdfit`` instead (the class is not fitted, so calibration_holdout plays no part there; where it or regions_dir is set
     and the ``.cmdcal`` is missing beside a stored fit, fit_device() raises instead of running without regions).  ``args.regions_dir`` -- when the class has a calibration, predict() ends by writing
     ``<regions_dir>/<class>.regions.json`` (thresholds, then per test image its decision and regions) and result() gains a
-    ``regions`` entry.  ``args.min_area`` / ``args.max_regions``: defaults 1 and 16.
+    ``regions`` entry.  ``args.min_area`` / ``args.max_regions``: defaults 1 and 16.  ``args.measure_regions`` -- the regions are
+    also measured on the test items' organised clouds and every region of the JSON gains the 3-D fields of
+    regions.measure_fields, in the clouds' units; unset, the file is what it was.
 
     Overlays (docs/overlay.md), read the same way, off when unset and under the same rule for the calibration:
     ``args.overlay_dir`` -- predict() ends by writing one PNG per test image, ``<overlay_dir>/<class>/<index>.png``, in chunks of at
@@ -144,6 +146,7 @@ class ClassRun:
         self.holdout = getattr(args, "calibration_holdout", None)
         self.regions_dir = getattr(args, "regions_dir", None)
         self.min_area, self.max_regions = getattr(args, "min_area", None) or 1, getattr(args, "max_regions", None) or 16
+        self.measure_regions = bool(getattr(args, "measure_regions", None))
         self.calibration = self.held_out = self.regions_summary = None
         if self.regions_dir and not self.holdout and not self.load_fit_dir:
             raise ValueError("regions_dir needs a calibration: set calibration_holdout, or load_fit_dir with a .cmdcal beside the fit")
@@ -265,9 +268,11 @@ class ClassRun:
         self.phases.append("metrics")
         if self.overlay_dir and self.calibration is not None:
             self._write_overlays()
-        self.test_items = None
+        if not self.measure_regions:
+            self.test_items = None
         if self.regions_dir and self.calibration is not None:
             self._write_regions()
+        self.test_items = None
         return self
 
     def _write_overlays(self):
@@ -300,7 +305,11 @@ class ClassRun:
         from . import regions
         m, cal = self.method, self.calibration
         t0 = time.perf_counter()
-        found = regions.find_regions(m.predictions, cal.spec(self.min_area, self.max_regions))
+        clouds = None
+        if self.measure_regions:      # the test items' organised clouds (the second tensor of a sample), one xyz per map pixel
+            clouds = torch.cat([it[0][1].reshape(1, 3, *it[0][1].shape[-2:]) for it in self.test_items]).to(torch.float32)
+        found = regions.find_regions(m.predictions, cal.spec(self.min_area, self.max_regions), clouds=clouds,
+                                     layout="planar" if clouds is not None else None)
         scores = np.asarray(m.image_preds, dtype=np.float64).reshape(-1)
         labels = np.asarray(m.image_labels).reshape(-1) != 0
         names = np.asarray(m.img_name).reshape(-1)

@@ -1555,6 +1555,61 @@ def region_table(maps, labels, n_comp, comp_offset, comp_size, min_area=1, max_r
     return count, ints, vals
 
 
+def cloud_layout(cloud, H, W, layout=None, who="region_measure"):
+    """'planar' ([n,3,H,W]) or 'interleaved' ([n,H,W,3]) for an organised cloud beside maps of H x W.  The shape decides; a
+    [n,3,H,W] cloud with H == 3 or W == 3 can be read both ways and is refused unless `layout` names one."""
+    if layout not in (None, "planar", "interleaved"):
+        raise ValueError(f"{who}: layout must be 'planar', 'interleaved' or None, got {layout!r}")
+    if cloud.dim() != 4:
+        raise ValueError(f"{who}: the cloud must be [n,3,{H},{W}] or [n,{H},{W},3], got {tuple(cloud.shape)}")
+    fits = [name for name, shape in (("planar", (3, H, W)), ("interleaved", (H, W, 3))) if tuple(cloud.shape[1:]) == shape]
+    if layout is not None:
+        if layout not in fits:
+            raise ValueError(f"{who}: a {layout} cloud beside {H} x {W} maps cannot have the shape {tuple(cloud.shape)}")
+        return layout
+    if not fits:
+        raise ValueError(f"{who}: the cloud must be [n,3,{H},{W}] or [n,{H},{W},3] like the maps, got {tuple(cloud.shape)}")
+    if len(fits) == 2 or (fits[0] == "planar" and 3 in (H, W)):
+        raise ValueError(f"{who}: a cloud of shape {tuple(cloud.shape)} can be read as planar and as interleaved; pass layout=")
+    return fits[0]
+
+
+def region_measure(labels, count, ints, cloud, out=None, layout=None):
+    """labels [n,H,W] i32, count [n] i32, ints [n,K,8] i32 (ccl_label / region_table) and the organised cloud of the maps, f32,
+    planar [n,3,H,W] or interleaved [n,H,W,3] (worked out from the shape; layout= where H or W is 3) -> (m_ints [n,K,4] i32 = n_pts,
+    n_tri, peak_valid, 0; m_vals [n,K,20] f64 = lo, hi, peak_xyz, s1, s2, area, 0; bad_count [1] i32 = points with a non-finite
+    coordinate).  out: that triple, to write into.  docs/regions.md has the contract.  No synchronisation."""
+    _chk(labels, torch.int32, "region_measure.labels"); _chk(count, torch.int32, "region_measure.count")
+    _chk(ints, torch.int32, "region_measure.ints"); _chk(cloud, torch.float32, "region_measure.cloud")
+    if labels.dim() != 3:
+        raise ValueError(f"region_measure: labels must be [n,H,W], got {tuple(labels.shape)}")
+    n, H, W = labels.shape
+    if H < 1 or W < 1 or H * W > (1 << 24) or n > 65535 or n * H * W > METRICS_MAX_TOTAL:
+        raise ValueError(f"region_measure: unsupported shape {tuple(labels.shape)} (n <= 65535, H, W >= 1, H*W <= 2^24, n*H*W <= 2^30)")
+    if count.numel() != n or ints.dim() != 3 or ints.shape[0] != n or ints.shape[2] != 8 or not 1 <= ints.shape[1] <= REGION_MAX:
+        raise ValueError(f"region_measure: count must be [{n}] and ints [{n},K,8] with K in 1..{REGION_MAX}; got {tuple(count.shape)}, "
+                         f"{tuple(ints.shape)}")
+    K = ints.shape[1]
+    planar = cloud_layout(cloud, H, W, layout) == "planar"
+    if cloud.shape[0] != n:
+        raise ValueError(f"region_measure: {cloud.shape[0]} clouds for {n} label images")
+    dev = labels.device
+    if out is None:
+        out = (torch.empty((n, K, 4), dtype=torch.int32, device=dev), torch.empty((n, K, 20), dtype=torch.float64, device=dev),
+               torch.zeros((1,), dtype=torch.int32, device=dev))
+    m_ints, m_vals, bad_count = out
+    _chk(m_ints, torch.int32, "region_measure.m_ints"); _chk(m_vals, torch.float64, "region_measure.m_vals")
+    _chk(bad_count, torch.int32, "region_measure.bad_count")
+    if tuple(m_ints.shape) != (n, K, 4) or tuple(m_vals.shape) != (n, K, 20) or bad_count.numel() != 1:
+        raise ValueError(f"region_measure: out must be ([{n},{K},4] i32, [{n},{K},20] f64, [1] i32)")
+    for t in (count, ints, cloud, m_ints, m_vals, bad_count):
+        if t.device != dev:
+            raise ValueError("region_measure: every tensor must be on the labels' device")
+    _call("cmdiad_region_measure", _p(labels), _p(count), _p(ints), _p(cloud), 1 if planar else 3, H * W if planar else 1, n, H, W, K,
+          _p(m_ints), _p(m_vals), _p(bad_count), _stream())
+    return m_ints, m_vals, bad_count
+
+
 # ------------------------------------------------------------------------------------ overlays (docs/overlay.md)
 OVERLAY_MAX_SIDE = 1 << 14
 OVERLAY_BACKGROUNDS = (None, torch.uint8, torch.float32)     # the index is cmdiad_overlay_render's background kind

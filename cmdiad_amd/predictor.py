@@ -64,7 +64,8 @@ class Ticket:
     def __init__(self, host_s, host_m, event, gt, flag=None, redo=None, host_r=None, image_threshold=None):
         self._s, self._m, self._ev, self._gt = host_s, host_m, event, gt
         self._flag, self._redo = flag, redo
-        self._r, self._image_threshold = host_r, image_threshold      # pinned region tables of the slot; the threshold at submit
+        # pinned region tables of the slot (five, or eight with the measurement tables); the threshold at submit
+        self._r, self._image_threshold = host_r, image_threshold
         self._out = self._regions = None
 
     @property
@@ -88,15 +89,23 @@ class Ticket:
         return self._out
 
     def regions(self):
-        """regions.Regions of the batch (n_comp, count, ints, vals, truncated).  ValueError when a map held a NaN."""
-        from .regions import Regions
+        """regions.Regions of the batch (n_comp, count, ints, vals, truncated; .measures when the predictor was built with
+        measure=True).  ValueError when a map held a NaN or a cloud a non-finite coordinate."""
+        from .regions import Measures, Regions
         self.wait()
         if self._regions is None:
             raise RuntimeError("Ticket.regions: the predictor was built without regions=")
-        n_comp, count, ints, vals, nan = self._regions
+        n_comp, count, ints, vals, nan = self._regions[:5]
         if int(nan.reshape(-1)[0]):
             raise ValueError(f"Ticket.regions: the maps of this batch contain {int(nan.reshape(-1)[0])} NaN scores")
-        return Regions(n_comp, count, ints, vals)
+        measures = None
+        if len(self._regions) > 5:
+            m_ints, m_vals, bad = self._regions[5:]
+            if int(bad.reshape(-1)[0]):
+                raise ValueError(f"Ticket.regions: the clouds of this batch contain {int(bad.reshape(-1)[0])} points with a non-finite "
+                                 "coordinate")
+            measures = Measures(m_ints, m_vals)
+        return Regions(n_comp, count, ints, vals, measures)
 
     def decisions(self):
         """[B] bool: image score > image threshold (strict), with the threshold the predictor held when the batch was submitted."""
@@ -117,15 +126,24 @@ class BatchPredictor:
     regions: a regions.RegionSpec or regions.Calibration (docs/regions.md) -> the scoring tail ends with threshold, labelling,
     component statistics and selection on the pixel maps (on the tail's stream, behind the captured stage 2), and every Ticket
     carries the region tables and, with an image threshold, the decisions; None -> nothing of this exists: no buffer, no
-    launch.  return_maps=False: the maps are neither copied to the host nor returned (wait()[1] is None)."""
+    launch.  return_maps=False: the maps are neither copied to the host nor returned (wait()[1] is None).
+    measure=True (with regions=, gt_size == size): the regions are also measured on the step's organised clouds, in the clouds'
+    units (cmdiad_region_measure, docs/regions.md), behind the region tail; every Ticket's regions() carries .measures.  The step's
+    clouds are kept in a device copy per buffer set, made before the input buffers are released to the next load.  False ->
+    no new buffer, no new launch."""
 
     def __init__(self, engine, bank_xyz, bank_second, stats, det, seg, lambdas=(1.0, 1.0, 0.1, 0.1), batch=32, n_max=None,
                  workload="dino_pointmae", halluc=None, group=None, use_graph=True, timers=None, ring=3, size=224,
-                 gt_size=224, blur_radius=4.0, rgb_size=None, regions=None, return_maps=True):
+                 gt_size=224, blur_radius=4.0, rgb_size=None, regions=None, return_maps=True, measure=False):
         if workload not in ("dino_pointmae", "mtfi"):
             raise ValueError(f"unknown workload {workload!r}")
         if workload == "mtfi" and halluc is None:
             raise ValueError("workload 'mtfi' needs the packed hallucination network")
+        self.measure = bool(measure)
+        if self.measure and regions is None:
+            raise ValueError("BatchPredictor: measure=True measures the regions of regions=; none was given")
+        if self.measure and gt_size != size:
+            raise ValueError(f"BatchPredictor: measure=True needs one cloud point per map pixel: gt_size = {gt_size}, size = {size}")
         self.e, self.bank_xyz, self.bank_second, self.stats = engine, bank_xyz, bank_second, stats
         self.det, self.seg, self.lambdas = det, seg, tuple(float(v) for v in lambdas)
         self.B, self.n_max, self.workload, self.halluc, self.group = batch, n_max, workload, halluc, group
@@ -169,6 +187,10 @@ class BatchPredictor:
                                  torch.zeros((batch, K, 8), dtype=torch.int32, pin_memory=True),
                                  torch.zeros((batch, K, 4), dtype=torch.float64, pin_memory=True),
                                  torch.zeros((1,), dtype=torch.int32, pin_memory=True)) for _ in range(ring)]
+            if self.measure:      # every ring slot gains m_ints, m_vals, bad_count
+                self.region_ring = [r + (torch.zeros((batch, K, 4), dtype=torch.int32, pin_memory=True),
+                                         torch.zeros((batch, K, 20), dtype=torch.float64, pin_memory=True),
+                                         torch.zeros((1,), dtype=torch.int32, pin_memory=True)) for r in self.region_ring]
         # row-sharded search: one pinned flag per ring slot ("this step's live rows exceeded the gather cap on some rank")
         self.flag_ring = [torch.zeros((1,), dtype=torch.int32, pin_memory=True) for _ in range(ring)] if group is not None else None
         self.slot = 0
@@ -201,7 +223,9 @@ class BatchPredictor:
         want_rgb = self.workload == "dino_pointmae"
         return dict(rgb=torch.zeros((self.B, 3, self.rgb_size, self.rgb_size), dtype=torch.float32, device=self.dev) if want_rgb else None,
                     pcs=torch.zeros((self.B, 3, self.size, self.size), dtype=torch.float32, device=self.dev),
-                    ready=None, free=None, staged=None)
+                    ready=None, free=None, staged=None,
+                    # the step's cloud for the measurement at tail time (_keep_cloud): inp["pcs"] is released right after stage 1
+                    cloud=torch.zeros((self.B, 3, self.size, self.size), dtype=torch.float32, device=self.dev) if self.measure else None)
 
     # ---- stage 1: everything up to the 16-bit queries of both libraries
     def stage1(self, inp):
@@ -347,17 +371,28 @@ class BatchPredictor:
         img = ops.ocsvm_score_maps(s.view(B, 2, 1).contiguous(), (lam[0], lam[2]), self.det.coef_, self.det.offset_)
         return img, pix
 
-    def _tail(self, qs, keys, regions=True):
-        """stage2 and, with regions, the region tables of its maps -> (img, pix, (n_comp, count, ints, vals, nan) | None)."""
+    def _tail(self, qs, keys, regions=True, cloud=None):
+        """stage2 and, with regions, the region tables of its maps -> (img, pix, (n_comp, count, ints, vals, nan) | None); with
+        measure=True the tuple ends with (m_ints, m_vals, bad_count) of the regions on `cloud`, the step's kept cloud."""
         img, pix = self.stage2(qs, keys)
-        return img, pix, (self._region_tail(pix) if regions else None)
+        return img, pix, (self._region_tail(pix, cloud) if regions else None)
 
-    def _region_tail(self, pix):
+    def _region_tail(self, pix, cloud=None):
         if self.region_spec is None:
             return None
         from .regions import region_tables_device
         sp = self.region_spec
-        return region_tables_device(pix.view(pix.shape[0], self.gt, self.gt), self.thr, sp.min_area, sp.max_regions)
+        return region_tables_device(pix.view(pix.shape[0], self.gt, self.gt), self.thr, sp.min_area, sp.max_regions,
+                                    clouds=cloud if self.measure else None, layout="planar")
+
+    def _keep_cloud(self, inp):
+        """measure=True: the step's cloud out of the set's input buffer into the set's own copy, on the compute stream, BEFORE
+        inp["free"] is recorded.  The measurement runs at tail time, on another stream, when the copy stream may already be
+        loading the batch of two submits later into inp["pcs"]; the copy is rewritten only after the set's previous tail has
+        finished (the compute stream has waited for its `done`), so the tail always reads its own step's cloud."""
+        if self.measure:
+            inp["cloud"].copy_(inp["pcs"], non_blocking=True)
+        return inp["cloud"]
 
     def set_thresholds(self, pixel, image=None):
         """New thresholds from the next submit on: the pixel threshold is written into the device tensor in place, ordered on the
@@ -384,7 +419,7 @@ class BatchPredictor:
 
     def _capture(self):
         qs = self.stage1(self.inputs[0])  # one eager pass first: module loading / attribute setting must not happen in capture
-        self._tail(qs, self.search(qs, 0))
+        self._tail(qs, self.search(qs, 0), cloud=self._keep_cloud(self.inputs[0]))
         torch.cuda.synchronize()
         # capture_error_mode="thread_local": with a process group alive, RCCL's watchdog THREAD polls the events of earlier
         # collectives (hipEventQuery); under the default "global" mode that call from another thread invalidates this thread's
@@ -402,7 +437,7 @@ class BatchPredictor:
                 k = {n: v.contiguous() for n, v in keys.items()}
                 g2 = None
                 if self.stage2_eager:       # fp32 rows sharded too: the scoring tail holds collectives and runs eagerly
-                    out = self._tail(qs, k)
+                    out = self._tail(qs, k, cloud=self._keep_cloud(self.inputs[s]))
                 else:
                     g2 = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g2, capture_error_mode="thread_local"):
@@ -504,6 +539,7 @@ class BatchPredictor:
             if st["done"] is not None:
                 cur.wait_event(st["done"])
             st["g1"].replay()
+            cloud = self._keep_cloud(inp)
             inp["free"] = torch.cuda.Event()
             inp["free"].record()
             # The library searches go to the second stream as well and run beside the NEXT step's extraction.  MTFI workload: without
@@ -520,9 +556,9 @@ class BatchPredictor:
                     self._search_into(st, which)
                 if st["g2"] is not None:
                     st["g2"].replay()
-                    st["out"] = (st["out"][0], st["out"][1], self._region_tail(st["out"][1]))
+                    st["out"] = (st["out"][0], st["out"][1], self._region_tail(st["out"][1], cloud))
                 else:
-                    st["out"] = self._tail(st["qs"], st["k"])
+                    st["out"] = self._tail(st["qs"], st["k"], cloud=cloud)
                 self._outputs_to_host(st["out"], slot)
                 flag = self._flag_to_host()
                 ev = torch.cuda.Event()
@@ -540,7 +576,7 @@ class BatchPredictor:
             return self._ticket(host_s, host_m, ev, flag, rgb, pcs)
         self.step_no += 1
         qs = self._eager_stage1(rgb, pcs)
-        self._outputs_to_host(self._tail(qs, self.search(qs, 0)), slot)
+        self._outputs_to_host(self._tail(qs, self.search(qs, 0), cloud=self.inputs[0]["cloud"]), slot)
         flag = self._flag_to_host()
         ev = torch.cuda.Event()
         ev.record()
@@ -552,6 +588,7 @@ class BatchPredictor:
         inp = self.inputs[0]
         self._load_inputs(inp, rgb, pcs)
         qs = self.stage1(inp)
+        self._keep_cloud(inp)
         inp["free"] = torch.cuda.Event()
         inp["free"].record()
         return qs
@@ -595,7 +632,7 @@ class BatchPredictor:
         else:   # a fixed CMDIAD_SHARD_CAP below the live rows of this batch: nothing to re-read
             raise RuntimeError("BatchPredictor: the repeated batch still overflows the gather cap (CMDIAD_SHARD_CAP too small?); "
                                "its keys would be incomplete")
-        s_dev, maps_dev, reg = self._tail(qs, keys)
+        s_dev, maps_dev, reg = self._tail(qs, keys, cloud=self.inputs[0]["cloud"])
         B = s_dev.shape[0]
         return (s_dev.cpu().numpy().reshape(B).copy(),
                 maps_dev.cpu().numpy().reshape(B, self.gt, self.gt).copy() if self.return_maps else None,

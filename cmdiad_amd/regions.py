@@ -62,21 +62,50 @@ class RegionSpec:
                 f"min_area={self.min_area}, max_regions={self.max_regions})")
 
 
+def measure_fields(m_ints, m_vals):
+    """One slot of a measurement table (m_ints [4], m_vals [20]; docs/regions.md) -> the 3-D fields of a region, in the units of
+    the cloud that was measured: n_pts, n_tri, peak_valid, lo, hi, peak_xyz, area_3d, extent = hi - lo, centroid_3d = lo + s1 / n_pts,
+    covariance = s2 / n_pts - (s1 / n_pts)(s1 / n_pts)^T (3 x 3, about the centroid) and principal_sigma = the square roots of its
+    eigenvalues, ascending, clipped at 0.  The one place these are derived: the tests run it on the kernel's table and on the
+    yardstick's alike.  A region without a valid point has zeros throughout."""
+    mi, mv = np.asarray(m_ints, dtype=np.int32).reshape(4), np.asarray(m_vals, dtype=np.float64).reshape(20)
+    n = int(mi[0])
+    lo, hi = mv[0:3], mv[3:6]
+    mean = mv[9:12] / n if n else np.zeros(3)
+    s2 = np.empty((3, 3))
+    s2[np.triu_indices(3)] = mv[12:18]
+    s2 = np.triu(s2) + np.triu(s2, 1).T
+    cov = s2 / n - np.outer(mean, mean) if n else np.zeros((3, 3))
+    return dict(n_pts=n, n_tri=int(mi[1]), peak_valid=int(mi[2]), lo=lo.tolist(), hi=hi.tolist(), peak_xyz=mv[6:9].tolist(),
+                area_3d=float(mv[18]), extent=(hi - lo).tolist(), centroid_3d=(lo + mean).tolist(), covariance=cov.tolist(),
+                principal_sigma=np.sqrt(np.clip(np.linalg.eigvalsh(cov), 0.0, None)).tolist())
+
+
+class Measures:
+    """The measurement tables of n images on the host (docs/regions.md): m_ints [n,K,4] int32 (n_pts, n_tri, peak_valid, 0), m_vals
+    [n,K,20] float64 (lo, hi, peak_xyz, s1, s2, area, 0), in the units of the cloud that was passed in."""
+
+    def __init__(self, m_ints, m_vals):
+        self.m_ints, self.m_vals = np.asarray(m_ints, dtype=np.int32), np.asarray(m_vals, dtype=np.float64)
+
+
 class Regions:
     """The region tables of n images on the host: n_comp [n] (components before any filter), count [n] (components with area >=
     min_area), ints [n,K,8] int32 (label, area, x0, y0, x1, y1, peak_x, peak_y), vals [n,K,4] float64 (peak, score_sum, cx, cy),
-    truncated [n] bool (count > K).  Slots behind min(count, K) are zero."""
+    truncated [n] bool (count > K).  Slots behind min(count, K) are zero.  measures: a Measures when the regions were measured
+    on an organised cloud, else None."""
 
-    def __init__(self, n_comp, count, ints, vals):
+    def __init__(self, n_comp, count, ints, vals, measures=None):
         self.n_comp, self.count = np.asarray(n_comp, dtype=np.int32), np.asarray(count, dtype=np.int32)
         self.ints, self.vals = np.asarray(ints, dtype=np.int32), np.asarray(vals, dtype=np.float64)
         self.truncated = self.count > self.ints.shape[1]
+        self.measures = measures
 
     def __len__(self):
         return self.count.shape[0]
 
     def to_list(self):
-        """Per image a list of dicts: the twelve fields and mean = score_sum / area."""
+        """Per image a list of dicts: the twelve fields and mean = score_sum / area; with measures, the fields of measure_fields."""
         out = []
         for i in range(len(self)):
             regs = []
@@ -84,6 +113,8 @@ class Regions:
                 d = {f: int(v) for f, v in zip(INT_FIELDS, self.ints[i, k])}
                 d.update({f: float(v) for f, v in zip(VAL_FIELDS, self.vals[i, k])})
                 d["mean"] = d["score_sum"] / d["area"]
+                if self.measures is not None:
+                    d.update(measure_fields(self.measures.m_ints[i, k], self.measures.m_vals[i, k]))
                 regs.append(d)
             out.append(regs)
         return out
@@ -109,34 +140,65 @@ def _device_maps(maps):
     return m.to(torch.float64).contiguous()     # float32 widens exactly
 
 
-def region_tables_device(maps, thr, min_area, max_regions, mask=None, nan_count=None):
+def region_tables_device(maps, thr, min_area, max_regions, mask=None, nan_count=None, clouds=None, layout=None):
     """The device part, without a synchronisation: maps [n,H,W] f64 and thr (device f64, 1 or n values) -> (n_comp, count, ints,
-    vals, nan_count) as device tensors.  BatchPredictor calls this at the end of its scoring tail."""
+    vals, nan_count) as device tensors.  BatchPredictor calls this at the end of its scoring tail.  clouds: the maps' organised
+    clouds on the device (f32, [n,3,H,W] or [n,H,W,3]) -> the regions are measured on them as well and (m_ints, m_vals, bad_count)
+    of ops.region_measure are appended to the tuple."""
     from . import ops
     mask, nan_count = ops.threshold_mask(maps, thr, mask, nan_count)
     labels, n_comp, comp_offset, comp_size, _ = ops.ccl_label(mask)
     count, ints, vals = ops.region_table(maps, labels, n_comp, comp_offset, comp_size, min_area, max_regions)
-    return n_comp, count, ints, vals, nan_count
+    if clouds is None:
+        return n_comp, count, ints, vals, nan_count
+    return (n_comp, count, ints, vals, nan_count) + tuple(ops.region_measure(labels, count, ints, clouds, layout=layout))
 
 
-def find_regions(maps, spec):
-    """maps: numpy, a tensor, or a list of [H,W] maps (float32 widens exactly; host inputs are uploaded) -> Regions.  ValueError
-    when a map holds a NaN.  One host synchronisation at the end."""
+def _device_clouds(clouds, like):
+    """Organised clouds as one contiguous float32 tensor on the maps' device: a tensor, numpy, or a list of [3,H,W] / [H,W,3]."""
     import torch
+    if isinstance(clouds, (list, tuple)):
+        clouds = torch.stack([torch.as_tensor(c) for c in clouds])
+    c = torch.as_tensor(clouds)
+    if c.dtype != torch.float32:
+        raise TypeError(f"find_regions: clouds must be float32 (the scanner's stored coordinates), got {c.dtype}")
+    return c.to(like.device).contiguous()
+
+
+def find_regions(maps, spec, clouds=None, layout=None):
+    """maps: numpy, a tensor, or a list of [H,W] maps (float32 widens exactly; host inputs are uploaded) -> Regions.  ValueError
+    when a map holds a NaN.  One host synchronisation at the end.  clouds: the maps' organised clouds, float32, [n,3,H,W] or
+    [n,H,W,3] (a tensor, numpy, or a list of single clouds; layout= 'planar' | 'interleaved' where the shape does not tell) -> the
+    Regions carry .measures, the regions in the clouds' units (docs/regions.md).  ValueError when the clouds' H, W differ from the
+    maps' or a coordinate is not finite."""
+    import torch
+    from . import ops
     spec = as_spec(spec)
     m = _device_maps(maps)
     n = m.shape[0]
     pt = np.atleast_1d(np.asarray(spec.pixel_threshold, dtype=np.float64))
     if pt.size not in (1, n):
         raise ValueError(f"find_regions: {pt.size} pixel thresholds for {n} maps (one, or one per image)")
+    K = spec.max_regions
+    if clouds is not None:
+        clouds = _device_clouds(clouds, m)
+        if clouds.dim() != 4 or clouds.shape[0] != n:
+            raise ValueError(f"find_regions: {n} maps need clouds [{n},3,H,W] or [{n},H,W,3], got {tuple(clouds.shape)}")
+        layout = ops.cloud_layout(clouds, m.shape[1], m.shape[2], layout, "find_regions")
     if n == 0:
-        K = spec.max_regions
-        return Regions(np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros((0, K, 8), np.int32), np.zeros((0, K, 4)))
+        return Regions(np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros((0, K, 8), np.int32), np.zeros((0, K, 4)),
+                       Measures(np.zeros((0, K, 4), np.int32), np.zeros((0, K, 20))) if clouds is not None else None)
     thr = torch.from_numpy(pt.copy()).to(m.device)
-    n_comp, count, ints, vals, nan_count = region_tables_device(m, thr, spec.min_area, spec.max_regions)
+    out = region_tables_device(m, thr, spec.min_area, spec.max_regions, clouds=clouds, layout=layout)
+    n_comp, count, ints, vals, nan_count = out[:5]
     if int(nan_count.item()):
         raise ValueError(f"find_regions: the maps contain {int(nan_count.item())} NaN scores")
-    return Regions(n_comp.cpu().numpy(), count.cpu().numpy(), ints.cpu().numpy(), vals.cpu().numpy())
+    measures = None
+    if clouds is not None:
+        if int(out[7].item()):
+            raise ValueError(f"find_regions: the clouds contain {int(out[7].item())} points with a non-finite coordinate")
+        measures = Measures(out[5].cpu().numpy(), out[6].cpu().numpy())
+    return Regions(n_comp.cpu().numpy(), count.cpu().numpy(), ints.cpu().numpy(), vals.cpu().numpy(), measures)
 
 
 # ------------------------------------------------------------------------------------------------ calibration

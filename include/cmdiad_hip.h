@@ -838,6 +838,28 @@ int cmdiad_region_table(const double* maps, const int32_t* labels, const int32_t
                         const int32_t* comp_size, int comp_cap, int n, int H, int W, int min_area, int max_regions, int32_t* count,
                         int32_t* ints, double* vals, void* workspace, size_t workspace_bytes, cmdiad_stream_t stream);
 
+/* The regions of a table in the units of the organised cloud (docs/regions.md, "Contract of a measurement table"; an addition, the
+ * ABI stays 6).  labels [n,H,W], count [n] and ints [n,max_regions,8] as cmdiad_ccl_label / cmdiad_region_table leave them; cloud =
+ * one float32 xyz per map pixel, coordinate c of pixel q of image i at cloud[i * 3 H W + q * pix_stride + c * ch_stride].  Only
+ * planar [n,3,H,W] (pix_stride 1, ch_stride H W) and interleaved [n,H,W,3] (pix_stride 3, ch_stride 1) are accepted; both give
+ * the same bits.  A point is valid iff its three coordinates are non-zero (-0.0 is zero) and finite.  For every slot
+ * j < min(count[i], max_regions), over the pixels of its box that carry its label:
+ *   m_ints [n, max_regions, 4] int32: n_pts (valid points), n_tri (triangles counted), peak_valid (the point at peak_x, peak_y is
+ *     valid), 0;
+ *   m_vals [n, max_regions, 20] f64: lo[3], hi[3] (per-axis minimum / maximum of the valid points, the stored floats widened),
+ *     peak_xyz[3] (zeros unless peak_valid), s1[3] = sum (p - lo), s2[6] = sum (p - lo)_a (p - lo)_b for xx, xy, xz, yy, yz, zz,
+ *     area = sum over the triangles (y,x), (y,x+1), (y+1,x+1) and (y,x), (y+1,x+1), (y+1,x) whose three vertices carry the label and
+ *     are valid of 0.5 |(b - a) x (c - a)|, 0.  Every sum in float64 from the widened floats, no contraction.
+ * A slot without a valid point and the slots behind min(count, max_regions) are zero.  One workgroup of 256 per (slot, image) walks
+ * the box twice in the order of score_sum (thread t: positions t, t + 256, ...; the fixed butterfly; (w0 + w1) + (w2 + w3)): the
+ * result does not depend on n, on i, on the layout or on the run, and no float goes through an atomic.  The table is not trusted:
+ * count is clamped to [0, max_regions], boxes and peaks to the image, a label below 1 matches no pixel.  bad_count [1] int32 (NULL:
+ * not wanted) = points of the whole frames with a non-finite coordinate; zeroed first, also when n == 0.  Sizes as for
+ * cmdiad_region_table.  No allocation, no synchronisation, no workspace, no scratch. */
+int cmdiad_region_measure(const int32_t* labels, const int32_t* count, const int32_t* ints, const float* cloud, long long pix_stride,
+                          long long ch_stride, int n, int H, int W, int max_regions, int32_t* m_ints, double* m_vals,
+                          int32_t* bad_count, cmdiad_stream_t stream);
+
 /* ---- xyz TIFFs (docs/tiff.md; utils/mvtec3d_util.py:9-11 of the reference reads them with tifffile on the host) ----
  * raw [raw_bytes] = file bytes with UNCOMPRESSED chunks (dword aligned, raw_bytes a multiple of 4: the upload buffer is padded),
  * chunk_off [B, n_chunks] (device) = byte offset into raw of every chunk of every image -> out [B,H,W,C] of the files' own float type
