@@ -712,8 +712,10 @@ def rows_dedup_plan(q16, q_sq, plan=None):
     _chk(q_sq, torch.float32, "rows_dedup_plan.q_sq")
     if plan is None or plan.q16.shape != q16.shape or plan.q16.dtype != q16.dtype:
         plan = DedupPlan(Q, D, q16.dtype, q16.device)
-    _call("cmdiad_rows_dedup_plan", _p(q16), _p(q_sq), Q, D, _p(plan.work), _p(plan.slot), _p(plan.rows), _p(plan.count),
-          _p(plan.q16), _p(plan.q_sq), _stream())
+    # a 0-row tensor has no address and the entry point wants non-null pointers: at Q = 0 it reads and writes none of them but count
+    p = (lambda t: _p(plan.work)) if Q == 0 else _p
+    _call("cmdiad_rows_dedup_plan", p(q16), p(q_sq), Q, D, _p(plan.work), p(plan.slot), p(plan.rows), _p(plan.count),
+          p(plan.q16), p(plan.q_sq), _stream())
     return plan
 
 

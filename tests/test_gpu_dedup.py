@@ -1,7 +1,9 @@
 """GPU: exact removal of repeated query rows in front of the distance GEMM (csrc/dedup.hip, cmdiad_l2_min_keys_counted).
 The reference searches the library for every row of the 56 x 56 patch grid (features.py:186-190); the rows of patches without a
 foreground pixel are one repeated constant vector.  The plan is checked against its definition (include/cmdiad_hip.h) and the compacted search + key expansion against the search of every row: identical keys."""
-import numpy as np
+import os
+import sys
+
 import pytest
 import torch
 
@@ -9,34 +11,10 @@ pytestmark = pytest.mark.gpu
 
 from cmdiad_amd import ops  # noqa: E402
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from dedup_ref import check_plan  # noqa: E402
+
 DEV = "cuda"
-
-
-def check_plan(plan, q16, qsq, n_repeats):
-    """The plan is valid -- the rows kept are the others in their order, every dropped row is bit for bit its representative (16-bit
-    row and squared norm: everything the distance kernel reads) -- and it dropped the n_repeats - 1 later occurrences of the most
-    repeated row (None: whatever it found; a pair among a few hundred rows can hide behind a hash-bucket tie, which costs nothing
-    but the saving)."""
-    q = q16.view(torch.int16).cpu().numpy()
-    sq = qsq.cpu().numpy().view(np.uint32)
-    Q = q.shape[0]
-    n = int(plan.count.item())
-    rows = plan.rows[:n].cpu().numpy()
-    slot = plan.slot.cpu().numpy()
-    assert 0 <= n <= Q and (np.diff(rows) > 0).all() and (n == 0 or (0 <= rows[0] and rows[-1] < Q))
-    kept = np.zeros(Q, bool)
-    kept[rows] = True
-    assert np.array_equal(slot[rows], np.arange(n))
-    dropped = np.nonzero(~kept)[0]
-    if len(dropped):
-        rep = rows[slot[dropped]]
-        assert len(set(rep.tolist())) == 1 and (rep < dropped).all(), "one representative, the first occurrence"
-        assert (q[dropped] == q[rep]).all() and (sq[dropped] == sq[rep]).all()
-    if n_repeats is not None:
-        assert len(dropped) == max(n_repeats - 1, 0), (len(dropped), n_repeats)
-    idx = torch.from_numpy(rows).to(q16.device)
-    assert torch.equal(plan.q16[:n], q16[idx]) and torch.equal(plan.q_sq[:n], qsq[idx])
-    return n
 
 
 def make_queries(Q, D, dtype, n_const, seed, other_const=True):
