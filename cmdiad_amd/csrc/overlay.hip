@@ -12,6 +12,7 @@
 // not read; every tap index is clamped to the map; the tables are read below min(count, K) only.  Writes: canvas pixels below
 // Ho * Wo of the image, and one atomic add per wave that met a NaN.
 #include "launch.h"
+#include "overlay_color.h"   // steps 2 and 3, shared with mesh.hip
 
 namespace {
 
@@ -20,8 +21,6 @@ constexpr int kMaxImages = 65535;
 constexpr int kMaxTotal = 1 << 30;
 constexpr int kMaxBoxes = 64;
 constexpr int kMaxLine = 8;
-
-enum { kBgNone = 0, kBgU8 = 1, kBgF32 = 2 };
 
 struct OverlayArgs {
     const double* maps;
@@ -73,20 +72,6 @@ __device__ __forceinline__ double score_at(const double* __restrict__ m, int x, 
     if (ay.f != 0.0) s = s + row_of(m + (size_t)ay.i1 * A.W, ax) * ay.f;
     return s;
 }
-
-// byte of a normalised float32 background value
-__device__ __forceinline__ uint32_t bg_byte(float v, double mean, double stdv)
-{
-    double b = (double)v * stdv;
-    b = b + mean;
-    b = b * 255.0;
-    b = floor(b + 0.5);
-    b = !(b > 0.0) ? 0.0 : b;
-    b = b > 255.0 ? 255.0 : b;
-    return (uint32_t)(int)b;
-}
-
-__device__ __forceinline__ uint32_t blend(uint32_t c, uint32_t bg, uint32_t a) { return (c * a + bg * (255u - a) + 127u) / 255u; }
 
 template <bool kVec>
 __global__ __launch_bounds__(256) void overlay_render_kernel(OverlayArgs A)
@@ -169,22 +154,12 @@ __global__ __launch_bounds__(256) void overlay_render_kernel(OverlayArgs A)
         px[k] = 0u;
         if (p0 + k < HoWo) {
             const double s = score_at(m, x, y, A);
-            double t;
-            if (s != s) {
-                t = 0.0;
-                ++bad;
-            } else {
-                t = d > 0.0 ? (s - lo) / d : (s > lo ? 1.0 : 0.0);
-                t = !(t > 0.0) ? 0.0 : t;
-                t = t > 1.0 ? 1.0 : t;
-            }
-            const int kk = (int)floor(t * 255.0 + 0.5);
+            bool nan;
+            const int kk = overlay_index(s, lo, d, nan);
+            bad += nan;
             const uint32_t e = sh_lut[kk & 255];
             uint32_t c = e & 0xffffffu;
-            if (A.bg_kind != kBgNone) {
-                const uint32_t a = e >> 24, g = bgc[k];
-                c = blend(c & 0xff, g & 0xff, a) | blend((c >> 8) & 0xff, (g >> 8) & 0xff, a) << 8 | blend(c >> 16, g >> 16, a) << 16;
-            }
+            if (A.bg_kind != kBgNone) c = blend_rgb(e, bgc[k]);
             if (contour && s > thr) {
                 // the four samples do not wait for each other: a neighbour outside the canvas is sampled at the clamped
                 // coordinate (a read inside the map) and then left out

@@ -18,6 +18,7 @@
 //   moments about the minimum corner, the area of the triangle mesh -- by one workgroup per (slot, image) in score_sum's order.
 #include <limits.h>
 
+#include "cloud.h"
 #include "launch.h"
 
 namespace {
@@ -315,25 +316,8 @@ __global__ __launch_bounds__(256) void region_select_kernel(const double* __rest
 }
 
 // ---------------------------------------------------------------------------------------------------------------- measurement
-// The regions in the units of the organised cloud (docs/regions.md, "Contract of a measurement table").  A cloud is addressed
-// through two element strides, so the planar [n,3,H,W] and the interleaved [n,H,W,3] layout are one code path and give the
-// same bits; the image stride is 3 H W in both.
-struct Cloud {
-    const float* p;
-    long long pix, ch;
-};
-
-struct Pt { float x, y, z; };
-
-__device__ __forceinline__ Pt cloud_at(const Cloud& c, size_t img_base, int q)
-{
-    const float* at = c.p + img_base + (long long)q * c.pix;
-    return {at[0], at[c.ch], at[2 * c.ch]};
-}
-__device__ __forceinline__ bool finite3(const Pt& p) { return fabsf(p.x) < INFINITY && fabsf(p.y) < INFINITY && fabsf(p.z) < INFINITY; }
-// the reference's rule (all three coordinates non-zero; -0.0 is zero) and finite
-__device__ __forceinline__ bool valid_pt(const Pt& p) { return p.x != 0.f && p.y != 0.f && p.z != 0.f && finite3(p); }
-
+// The regions in the units of the organised cloud (docs/regions.md, "Contract of a measurement table"); the cloud is addressed
+// through cloud.h, so both layouts are one code path.
 // 0.5 |(b - a) x (c - a)| from the widened floats, every step one float64 operation rounded once (no contraction)
 __device__ __forceinline__ double tri_area(const Pt& a, const Pt& b, const Pt& c)
 {
@@ -549,7 +533,7 @@ extern "C" int cmdiad_region_measure(const int32_t* labels, const int32_t* count
                    "cmdiad_region_measure: bad sizes n=%d (0..%d) H=%d W=%d (>= 1, H*W <= %d, n*H*W <= %d) max_regions=%d (1..%d)", n,
                    kMaxImages, H, W, kMaxImagePixels, kMaxTotal, max_regions, kMaxRegions);
     const long long HW = (long long)H * W;
-    CMDIAD_REQUIRE((pix_stride == 1 && ch_stride == HW) || (pix_stride == 3 && ch_stride == 1), CMDIAD_ERR_ARG,
+    CMDIAD_REQUIRE(cloud_strides_ok(pix_stride, ch_stride, HW), CMDIAD_ERR_ARG,
                    "cmdiad_region_measure: bad strides pix_stride=%lld ch_stride=%lld (planar [n,3,H,W]: 1 and H*W = %lld; interleaved "
                    "[n,H,W,3]: 3 and 1)", pix_stride, ch_stride, HW);
     CMDIAD_REQUIRE(n == 0 || (labels && count && ints && cloud && m_ints && m_vals), CMDIAD_ERR_ARG,

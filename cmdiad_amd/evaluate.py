@@ -121,7 +121,14 @@ class ClassRun:
     ``args.overlay_dir`` -- predict() ends by writing one PNG per test image, ``<overlay_dir>/<class>/<index>.png``, in chunks of at
     most 32: the score map coloured over the sample's own rgb tensor, the contour of the calibration's pixel threshold and the boxes
     of the regions (min_area / max_regions) drawn in; result() gains an ``overlays`` entry (directory, file count) and ``seconds``
-    an ``overlays`` timing.  ``args.overlay_span`` (default 2.0): OverlaySpec.from_calibration's span."""
+    an ``overlays`` timing.  ``args.overlay_span`` (default 2.0): OverlaySpec.from_calibration's span.
+
+    Meshes (docs/mesh.md), read the same way, off when unset and under the same rule for the calibration: ``args.mesh_dir`` --
+    predict() ends by writing one PLY per test image, ``<mesh_dir>/<class>/<index>.ply``, in chunks of at most 32: the test item's
+    organised cloud as a triangle mesh with normals, the overlay's colours over the sample's rgb tensor, the score and the
+    component label of the region tail (the label the region tables name) per vertex; result() gains a ``meshes`` entry
+    (directory, file count) and ``seconds`` a ``meshes`` timing.  ``args.mesh_max_edge`` (default None: no edge is cut) and
+    ``args.overlay_span`` apply."""
 
     def __init__(self, args, data, weights=None, method=None, extractor=None):
         from .utils.utils import set_seeds
@@ -154,6 +161,10 @@ class ClassRun:
         self.overlays_summary = None
         if self.overlay_dir and not self.holdout and not self.load_fit_dir:
             raise ValueError("overlay_dir needs a calibration: set calibration_holdout, or load_fit_dir with a .cmdcal beside the fit")
+        self.mesh_dir, self.mesh_max_edge = getattr(args, "mesh_dir", None), getattr(args, "mesh_max_edge", None)
+        self.meshes_summary = None
+        if self.mesh_dir and not self.holdout and not self.load_fit_dir:
+            raise ValueError("mesh_dir needs a calibration: set calibration_holdout, or load_fit_dir with a .cmdcal beside the fit")
 
     def _fit_file(self, directory):
         return os.path.join(directory, f"{self.data.name}.cmdfit")
@@ -186,9 +197,9 @@ class ClassRun:
             if os.path.exists(self._cal_file(self.load_fit_dir)):
                 from . import regions
                 self.calibration = regions.Calibration.load(self._cal_file(self.load_fit_dir), fit=self._fit_file(self.load_fit_dir))
-            elif self.holdout or self.regions_dir or self.overlay_dir:
+            elif self.holdout or self.regions_dir or self.overlay_dir or self.mesh_dir:
                 raise ValueError(f"{self._cal_file(self.load_fit_dir)} is missing: the stored fit of class {data.name} is loaded, not "
-                                 "fitted, so calibration_holdout / regions_dir / overlay_dir need the calibration saved beside it")
+                                 "fitted, so calibration_holdout / regions_dir / overlay_dir / mesh_dir need the calibration saved beside it")
             return self
         # the loaders are drained first (the reference's DataLoader workers prefetch beside the model; a synthetic class generates its
         # samples on this thread): "load" is reported on its own and the phase timings below are the method's
@@ -268,6 +279,8 @@ class ClassRun:
         self.phases.append("metrics")
         if self.overlay_dir and self.calibration is not None:
             self._write_overlays()
+        if self.mesh_dir and self.calibration is not None:
+            self._write_meshes()
         if not self.measure_regions:
             self.test_items = None
         if self.regions_dir and self.calibration is not None:
@@ -297,6 +310,32 @@ class ClassRun:
             files += len(paths)
         self.overlays_summary = dict(directory=folder, files=files)
         self.sec["overlays"] = time.perf_counter() - t0
+
+    def _write_meshes(self):
+        """<mesh_dir>/<class>/<index>.ply for every test image, in chunks of at most 32: per chunk the component labels of the
+        region tail on the device, the count and the write launches over the items' organised clouds and rgb tensors, one read of
+        the counts and the writer threads of utils.ply."""
+        from . import mesh, ops, overlay, regions
+        m, cal = self.method, self.calibration
+        t0 = time.perf_counter()
+        folder = os.path.join(self.mesh_dir, self.data.name)
+        os.makedirs(folder, exist_ok=True)
+        spec = mesh.MeshSpec.from_calibration(cal, self.overlay_span, max_edge=self.mesh_max_edge)
+        maps = np.stack([np.asarray(p, dtype=np.float64) for p in m.predictions])
+        files = 0
+        for at in range(0, len(maps), overlay.CHUNK):
+            part = regions._device_maps(maps[at:at + overlay.CHUNK])
+            items = self.test_items[at:at + overlay.CHUNK]
+            clouds = torch.cat([it[0][1].reshape(1, 3, *it[0][1].shape[-2:]) for it in items]).to(part.device, torch.float32)
+            rgb = torch.cat([it[0][0].reshape(1, 3, *it[0][0].shape[-2:]) for it in items]).to(part.device, torch.float32)
+            thr = torch.full((1,), cal.pixel_threshold, dtype=torch.float64, device=part.device)
+            labels = ops.ccl_label(ops.threshold_mask(part, thr)[0])[0]        # the component labels the region tables name
+            paths = [os.path.join(folder, f"{at + i:04d}.ply") for i in range(part.shape[0])]
+            mesh.save(paths, clouds, part, spec, background=rgb if tuple(rgb.shape[-2:]) == tuple(part.shape[-2:]) else None,
+                      labels=labels, layout="planar", comments=[[f"class {self.data.name}", f"index {at + i}"] for i in range(len(paths))])
+            files += len(paths)
+        self.meshes_summary = dict(directory=folder, files=files)
+        self.sec["meshes"] = time.perf_counter() - t0
 
     def _write_regions(self):
         """<regions_dir>/<class>.regions.json: the thresholds, then per test image its decision and its regions; the summary of
@@ -339,6 +378,8 @@ class ClassRun:
             out["regions"] = dict(self.regions_summary)
         if self.overlays_summary is not None:
             out["overlays"] = dict(self.overlays_summary)
+        if self.meshes_summary is not None:
+            out["meshes"] = dict(self.meshes_summary)
         out["_extractor"] = m.deep_feature_extractor
         return out
 

@@ -1724,6 +1724,95 @@ def png_filter(images_u8, mode="adaptive", out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------ meshes (docs/mesh.md)
+MESH_CHUNK = 1024                 # pixels per entry of cmdiad_mesh_count's chunks table
+MESH_VERTEX_BYTES, MESH_FACE_BYTES = 35, 13
+MESH_MAX_TOTAL = 1 << 24
+
+
+def _mesh_geometry(cloud, maps, max_edge2, layout, who):
+    """the checks mesh_count and mesh_write share -> (n, H, W, planar, max_edge2)"""
+    n, H, W = _chk_maps(maps, who)
+    _chk(cloud, torch.float32, f"{who}.cloud")
+    if H > OVERLAY_MAX_SIDE or W > OVERLAY_MAX_SIDE or n * H * W > MESH_MAX_TOTAL:
+        raise ValueError(f"{who}: maps {tuple(maps.shape)}: sides 1..2^14, n*H*W <= 2^24")
+    planar = cloud_layout(cloud, H, W, layout, who) == "planar"
+    if cloud.shape[0] != n or cloud.device != maps.device:
+        raise ValueError(f"{who}: {cloud.shape[0]} clouds on {cloud.device} for {n} maps on {maps.device}")
+    max_edge2 = float(max_edge2)
+    if not max_edge2 > 0:
+        raise ValueError(f"{who}: max_edge2 = {max_edge2!r} must be > 0 (inf: no edge is cut)")
+    return n, H, W, planar, max_edge2
+
+
+def mesh_count(cloud, maps, max_edge2=float("inf"), out=None, layout=None):
+    """The organised cloud of the maps (f32, planar [n,3,H,W] or interleaved [n,H,W,3], worked out from the shape; layout= where H or
+    W is 3) and maps [n,H,W] f64 -> (chunks [n,C,2] i32 = vertices and faces per run of MESH_CHUNK pixels, C = ceil(H W / MESH_CHUNK);
+    counts [n,4] i32 = n_vert, n_face, bad, nan).  out: that pair, to write into.  docs/mesh.md has the contract.  No
+    synchronisation."""
+    n, H, W, planar, max_edge2 = _mesh_geometry(cloud, maps, max_edge2, layout, "mesh_count")
+    dev, C = maps.device, -(-H * W // MESH_CHUNK)
+    if out is None:
+        out = (torch.empty((n, C, 2), dtype=torch.int32, device=dev), torch.empty((n, 4), dtype=torch.int32, device=dev))
+    chunks, counts = out
+    _chk(chunks, torch.int32, "mesh_count.chunks"); _chk(counts, torch.int32, "mesh_count.counts")
+    if tuple(chunks.shape) != (n, C, 2) or tuple(counts.shape) != (n, 4) or chunks.device != dev or counts.device != dev:
+        raise ValueError(f"mesh_count: out must be ([{n},{C},2] i32, [{n},4] i32) on the maps' device")
+    if n:
+        _call("cmdiad_mesh_count", _p(cloud), 1 if planar else 3, H * W if planar else 1, _p(maps), n, H, W, max_edge2, _p(chunks),
+              _p(counts), _stream())
+    return chunks, counts
+
+
+def mesh_write(cloud, maps, chunks, lohi, lut, alpha, background=None, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), labels=None,
+               max_edge2=float("inf"), flip=False, out=None, layout=None):
+    """cloud, maps and chunks as mesh_count takes and leaves them (the same max_edge2) -> (vidx [n,H,W] i32, vertices [n, H W 35] u8,
+    faces [n, 2 (H-1) (W-1) 13] u8): image i fills the front of its rows with its counts[i,0] vertex and counts[i,1] face records.
+    lohi ([2] or [n,2] f64), lut [256,3] u8, alpha [256] u8, background (None, uint8 [n,H,W,3] or float32 [n,3,H,W] with mean / std)
+    as overlay_render takes them; labels [n,H,W] i32 or None (region 0).  out: that triple, to write into.  No synchronisation."""
+    n, H, W, planar, max_edge2 = _mesh_geometry(cloud, maps, max_edge2, layout, "mesh_write")
+    dev, C = maps.device, -(-H * W // MESH_CHUNK)
+    _chk(chunks, torch.int32, "mesh_write.chunks"); _chk(labels, torch.int32, "mesh_write.labels")
+    _chk(lohi, torch.float64, "mesh_write.lohi"); _chk(lut, torch.uint8, "mesh_write.lut"); _chk(alpha, torch.uint8, "mesh_write.alpha")
+    if chunks is None or lohi is None or lut is None or alpha is None:
+        raise ValueError("mesh_write: chunks, lohi, lut and alpha are required")
+    if tuple(chunks.shape) != (n, C, 2):
+        raise ValueError(f"mesh_write: chunks must be [{n},{C},2] (mesh_count's), got {tuple(chunks.shape)}")
+    if tuple(lohi.shape) not in ((2,), (1, 2), (n, 2)) or tuple(lut.shape) != (256, 3) or tuple(alpha.shape) != (256,):
+        raise ValueError(f"mesh_write: lohi must be [2] or [{n},2], lut [256,3], alpha [256]; got {tuple(lohi.shape)}, "
+                         f"{tuple(lut.shape)}, {tuple(alpha.shape)}")
+    if labels is not None and labels.shape != maps.shape:
+        raise ValueError(f"mesh_write: labels must have the maps' shape {tuple(maps.shape)}, got {tuple(labels.shape)}")
+    kind = 0
+    if background is not None:
+        if background.dtype not in OVERLAY_BACKGROUNDS[1:]:
+            raise TypeError(f"mesh_write.background: expected uint8 [n,H,W,3] or float32 [n,3,H,W], got {background.dtype}")
+        kind = OVERLAY_BACKGROUNDS.index(background.dtype)
+        _chk(background, background.dtype, "mesh_write.background")
+        want = (n, H, W, 3) if kind == 1 else (n, 3, H, W)
+        if tuple(background.shape) != want:
+            raise ValueError(f"mesh_write: a {background.dtype} background must be {want}, got {tuple(background.shape)}")
+    mean, std = [float(v) for v in mean], [float(v) for v in std]
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("mesh_write: mean and std are three values each")
+    shapes = ((n, H, W), (n, H * W * MESH_VERTEX_BYTES), (n, 2 * (H - 1) * (W - 1) * MESH_FACE_BYTES))
+    if out is None:
+        out = (torch.empty(shapes[0], dtype=torch.int32, device=dev), torch.empty(shapes[1], dtype=torch.uint8, device=dev),
+               torch.empty(shapes[2], dtype=torch.uint8, device=dev))
+    vidx, vertices, faces = out
+    _chk(vidx, torch.int32, "mesh_write.vidx"); _chk(vertices, torch.uint8, "mesh_write.vertices"); _chk(faces, torch.uint8, "mesh_write.faces")
+    if tuple(vidx.shape) != shapes[0] or tuple(vertices.shape) != shapes[1] or tuple(faces.shape) != shapes[2]:
+        raise ValueError(f"mesh_write: out must be ({shapes[0]} i32, {shapes[1]} u8, {shapes[2]} u8)")
+    for t in (chunks, lohi, lut, alpha, background, labels, vidx, vertices, faces):
+        if t is not None and t.device != dev:
+            raise ValueError("mesh_write: every tensor must be on the maps' device")
+    if n:
+        _call("cmdiad_mesh_write", _p(cloud), 1 if planar else 3, H * W if planar else 1, _p(maps), n, H, W, _p(lohi),
+              int(lohi.numel() == 2 * n and n > 1), _p(lut), _p(alpha), _p(background), kind, *mean, *std, _p(labels), max_edge2,
+              int(bool(flip)), _p(chunks), _p(vidx), _p(vertices), _p(faces) if faces.numel() else None, _stream())
+    return vidx, vertices, faces
+
+
 # ------------------------------------------------------------------------------------ content digest (stored fits)
 def digest64(tensor, seed=0, acc=None):
     """cmdiad_digest64 of a device tensor's bytes, ADDED into `acc` ([1] int64 on the tensor's device; None: a fresh zero) -> acc.

@@ -161,7 +161,7 @@ def _device_clouds(clouds, like):
         clouds = torch.stack([torch.as_tensor(c) for c in clouds])
     c = torch.as_tensor(clouds)
     if c.dtype != torch.float32:
-        raise TypeError(f"find_regions: clouds must be float32 (the scanner's stored coordinates), got {c.dtype}")
+        raise TypeError(f"clouds must be float32 (the scanner's stored coordinates), got {c.dtype}")
     return c.to(like.device).contiguous()
 
 

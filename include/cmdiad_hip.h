@@ -919,6 +919,36 @@ int cmdiad_overlay_render(const double* maps, int n, int H, int W, int Ho, int W
                           const int32_t* ints, int K, int line_px, uint32_t contour_rgb, uint32_t box_rgb, uint8_t* canvas,
                           int32_t* nan_count, cmdiad_stream_t stream);
 
+/* ---- scored scans as coloured PLY meshes (docs/mesh.md; an addition, the ABI stays 6) ----
+ * cloud as for cmdiad_region_measure (one float32 xyz per map pixel, the two element strides, planar or interleaved: the same
+ * bytes), maps [n,H,W] f64 at the cloud's H, W.  A point is valid iff its three coordinates are non-zero (-0.0 is zero) and finite.
+ *   vertices  the valid pixels of an image in raster order; vidx [n,H,W] int32 = each pixel's rank, -1 for an invalid pixel.
+ *   faces     cell (y, x), y + 1 < H and x + 1 < W: T0 = (y,x), (y,x+1), (y+1,x+1) and T1 = (y,x), (y+1,x+1), (y+1,x); a triangle is
+ *             emitted iff its three vertices are valid and each edge has d2 = (dx dx + dy dy) + dz dz <= max_edge2, the differences
+ *             in float64 from the widened floats, every step one float64 operation.  Cells in raster order, T0 before T1; flip = 1
+ *             stores a, c, b.  max_edge2 = +inf cuts nothing; a NaN or a value <= 0 is refused.
+ *   normal    of vertex (y, x): the sum from 0.0, per component, of (b - a) x (c - a) -- each component two products and one
+ *             difference, the triangle's own a, b, c -- over the emitted ones of cell (y-1,x-1) T0, T1, cell (y-1,x) T1, cell (y,x-1)
+ *             T0, cell (y,x) T0, T1, in this order; len = sqrt((nx nx + ny ny) + nz nz); (float)(n / len) when len > 0 and finite,
+ *             else zeros; flip = 1 negates the three floats.
+ *   colour    cmdiad_overlay_render's index and colour steps on s = maps[i,y,x]; bg at the maps' size (kind 0 | 1 | 2).
+ *   records   vertex, 35 bytes little-endian: float x y z (the stored bits), float nx ny nz, uchar red green blue, float score (the
+ *             float64 rounded once), int region (labels [n,H,W] int32, or 0 when labels is NULL).  Face, 13 bytes: uchar 3 and three
+ *             int32 vertex ranks.  Image i fills the front of its slot densely: vertices + i H W 35, faces + i 2 (H-1) (W-1) 13.
+ * cmdiad_mesh_count (one memset, one kernel): chunks [n, C, 2] int32, C = ceil(H W / 1024) = vertices and faces of every run of 1024
+ * pixels; counts [n,4] int32 = n_vert, n_face, bad (points with a non-finite coordinate), nan (valid vertices with a NaN score;
+ * they take t = 0).  cmdiad_mesh_write (two kernels; one where H or W is 1, and faces may then be NULL) takes that chunks table and
+ * writes vidx and the two record buffers; a table that does not belong to the cloud cannot make it write outside a slot.  Integer
+ * atomics only: the result does not depend on n, on i, on the layout or on the run.  n in 0..65535 (0 returns CMDIAD_OK without a
+ * launch), sides in 1..16384, n H W <= 2^24.  No workspace, no allocation, no synchronisation, no scratch. */
+int cmdiad_mesh_count(const float* cloud, long long pix_stride, long long ch_stride, const double* maps, int n, int H, int W,
+                      double max_edge2, int32_t* chunks, int32_t* counts, cmdiad_stream_t stream);
+int cmdiad_mesh_write(const float* cloud, long long pix_stride, long long ch_stride, const double* maps, int n, int H, int W,
+                      const double* lohi, int lohi_per_image, const uint8_t* lut, const uint8_t* alpha, const void* bg, int bg_kind,
+                      double mean_r, double mean_g, double mean_b, double std_r, double std_g, double std_b, const int32_t* labels,
+                      double max_edge2, int flip, const int32_t* chunks, int32_t* vidx, uint8_t* vertices, uint8_t* faces,
+                      cmdiad_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Content digest (stored fits: cmdiad_amd/fitted.py, docs/fitted.md)
  * ------------------------------------------------------------------------------------------- */
