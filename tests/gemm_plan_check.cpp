@@ -10,7 +10,7 @@
 //        -> <case> <kernel> <act> <grid.x> <grid.y> <panel> <group_m> <first empty slab or -1> <reads of the environment>
 //           |   <case> error <code> <text>
 //   l2 key=value ...     keys: ab Q Nb D nseg stride keys2 rowoff dtype, and any CMDIAD_* switch
-//        -> <case> <tile> <first row> <rows> <nq> <nbt> <splits> <qgroup> <grid.x> per launch   |   <case> nothing   |   <case> error ...
+//        -> <case> <tile> <first row> <rows> <nq> <nbt> <splits> <qgroup> <grid.x> <empty ranges> per launch   |   <case> nothing   |   <case> error ...
 //   streamk M= N= K=     -> <case> eligible | <case> not
 #include <cstdio>
 #include <cstdlib>
@@ -146,7 +146,11 @@ int lines()
             else if (!p.n) std::printf("%d nothing\n", n);
             for (int i = 0; !p.err && i < p.n; ++i) {
                 const plan::l2_launch& l = p.launch[i];
-                std::printf("%d %s %d %d %d %d %d %d %u\n", n, name_of(l.tile), l.row0, l.rows, l.nq, l.nbt, l.splits, l.qgroup, l.grid_x);
+                // the kernels cut the nbt library tiles into `splits` ranges of per = ceil(nbt / splits) tiles (csrc/l2min.hip: nt0 =
+                // split * per, ntc = min(per, nbt - nt0)): the ranges from ceil(nbt / per) on hold no tile and their blocks leave
+                const int per = (l.nbt + l.splits - 1) / l.splits;
+                std::printf("%d %s %d %d %d %d %d %d %u %d\n", n, name_of(l.tile), l.row0, l.rows, l.nq, l.nbt, l.splits, l.qgroup, l.grid_x,
+                            l.splits - (l.nbt + per - 1) / per);
             }
         } else if (c.count("streamk")) {
             std::printf("%d %s\n", n, plan::streamk_eligible((int)num(c, "M"), (int)num(c, "N"), (int)num(c, "K")) ? "eligible" : "not");

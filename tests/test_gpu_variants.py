@@ -18,7 +18,7 @@ def test_variant_parity_tests_run_in_the_test_build():
     if not os.path.exists(ab):
         pytest.skip("libcmdiad_hip_ab.so not built (python -c 'import __graft_entry__ as g; g.build()')")
     files = [f for f in ("tests/test_gpu_kernels.py", "tests/test_gpu_dedup.py", "tests/test_gpu_fullsize.py", "tests/test_gpu_nets.py",
-                        "tests/test_gpu_encoder_exact.py", "tests/test_gpu_gemm_edges.py")
+                        "tests/test_gpu_encoder_exact.py", "tests/test_gpu_gemm_edges.py", "tests/test_gpu_search_exact.py")
              if "need_ab_variants(" in open(os.path.join(REPO, f)).read().replace("import need_ab_variants", "")]
     assert files
     env = dict(os.environ, CMDIAD_TEST_AB="1")
@@ -26,7 +26,7 @@ def test_variant_parity_tests_run_in_the_test_build():
     # only the tests that HAVE a variant parametrisation (FPS "reg", kNN "block", the 4-wave GEMM shapes, the lock-step distance GEMM):
     # the rest of those files ran in the parent against the production library already; exact_variant: the encoder's superseded
     # kernels against the exact lattice reference (tests/test_gpu_encoder_exact.py, 150 cases) and the 4-wave GEMM shapes against theirs
-    # (tests/test_gpu_gemm_edges.py)
+    # (tests/test_gpu_gemm_edges.py), the lock-step distance GEMM against the integer key reference (tests/test_gpu_search_exact.py)
     select = "fps_ or knn_group_bit_exact or knn_group_ties or gemm_epilogues or pointmae_encoder_stages or l2_min or exact_variant"
     out = subprocess.run([sys.executable, "-m", "pytest", *files, "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider", "-k", select], cwd=REPO, env=env,
                          capture_output=True, text=True, timeout=1500)

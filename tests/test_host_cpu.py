@@ -382,6 +382,65 @@ def test_gemm_plan_workload_launches_and_the_edge_tests_labels(tmp_path):
     assert panelled, "the \"panel\" setting plans no panel > 1 on any of GENERAL_SHAPES"
 
 
+def test_l2_plan_reaches_what_the_search_edge_tests_labels_claim(tmp_path):
+    """The case tables of tests/search_ref.py through the line mode of tests/gemm_plan_check.cpp (csrc/gemm_plan.h plan_l2, host
+    compiler, address + undefined sanitizers): every label by which tests/test_gpu_search_exact.py means to reach a particular path
+    of the distance GEMM -- the two-group kernel on one tile and one range, the 128 kernel with more ranges than tiles (blocks that
+    leave at ntc <= 0), short and uneven ranges, the remainder launch of one row, the segments launch at a stride that is no
+    multiple of the tile -- is what the plan does with the case under each CMDIAD_L2_TILE setting.  A changed threshold must not
+    turn "every path at its edge shapes" into the same launch nineteen times."""
+    import collections
+    import shutil
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import search_ref as sr
+    cxx = next((c for c in (os.environ.get("CXX"), "c++", "g++", "clang++") if c and shutil.which(c)), None)
+    assert cxx, "no host C++ compiler on PATH"
+    exe = str(tmp_path / "gemm_plan_check")
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           os.path.join(REPO, "tests", "gemm_plan_check.cpp"), "-o", exe]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout + out.stderr
+
+    def words(setting):
+        return ([f"CMDIAD_L2_TILE={setting}"] if setting else []) + (["ab"] if setting == sr.AB_SETTING else [])
+
+    cases = []                                     # (label, line)
+    for c in sr.EDGE_CASES:
+        assert set(c.plan) == set(sr.SETTINGS) | {sr.AB_SETTING}
+        for setting, label in c.plan.items():
+            for keys2, rowoff in ((1, 0), (1, 192), (0, 7)):           # the launches of the edge table: the plan is the same for all
+                cases.append((label, " ".join(["l2", f"Q={c.Q}", f"Nb={c.Nb}", f"D={c.D}", f"keys2={keys2}", f"rowoff={rowoff}"] + words(setting))))
+    Q, Nb, D = sr.COUNTED_CASE                      # the counted launch is planned for Q_max rows
+    assert Q == sr.COUNTED_Q_MAX
+    for setting in ("0", "5"):
+        cases.append((sr.case_of(Q, Nb, D).plan[setting], " ".join(["l2", f"Q={sr.COUNTED_Q_MAX}", f"Nb={Nb}", f"D={D}", "keys2=1"] + words(setting))))
+    _, Nb, D = sr.SEGMENT_CASE
+    for setting in sr.SEGMENT_SETTINGS:
+        for counts in sr.SEGMENT_COUNTS:
+            cases.append((sr.SEGMENT_PLAN[setting], " ".join(["l2", f"nseg={len(counts)}", f"stride={sr.SEGMENT_STRIDE}", f"Nb={Nb}", f"D={D}", "keys2=1"] + words(setting))))
+    out = subprocess.run([exe, "--lines"], input="\n".join(line for _, line in cases) + "\n", capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    got = collections.defaultdict(list)
+    for row in out.stdout.splitlines():
+        n, tile, row0, rows, nq, nbt, splits, _, _, empty = row.split()
+        got[int(n)].append(f"{tile}[{row0}:{int(row0) + int(rows)}] nq={nq} nbt={nbt} splits={splits} empty={empty}")
+    for n, (label, line) in enumerate(cases):
+        assert " + ".join(got[n]) == label, (line, got[n], label)
+
+    # what the issue's table says of particular cases, in the labels' own terms
+    def launches(shape, setting):
+        return [dict(tile=t.split("[")[0], **{k: int(v) for k, v in (w.split("=") for w in t.split()[1:])})
+                for t in sr.case_of(*shape).plan[setting].split(" + ")]
+    assert launches((256, 256, 192), "5") == [dict(tile="two_group256", nq=1, nbt=1, splits=1, empty=0)]
+    assert launches((300, 1025, 64), None) == [dict(tile="t128", nq=3, nbt=9, splits=8, empty=3)]
+    assert [(la["tile"], la["nbt"]) for la in launches((257, 257, 256), "5")] == [("two_group256", 1), ("t128", 1)]
+    assert launches((512, 512, 192), None)[0]["tile"] == "two_group256" and launches((511, 511, 320), None)[0]["tile"] == "t128"
+    assert [(la["nbt"], la["splits"]) for la in launches((769, 2305, 192), None)] == [(9, 2), (1, 1)]     # ranges of 5 and 4, plus 1 row
+    assert [(la["nbt"], la["splits"]) for la in launches((513, 6018, 192), None)] == [(23, 5), (2, 2)]    # 5, 5, 5, 5, 3, plus 130 rows
+    assert sr.case_of(260, 1024, 1024).D // 64 == 16 and sr.case_of(260, 1024, 1024).amp == 4
+    assert sr.SEGMENT_STRIDE % 128 and sr.SEGMENT_STRIDE % 256 and "empty=3" in sr.SEGMENT_PLAN["0"]
+
+
 def test_cell_grid_ring_walk_covers_every_cell_once_and_axes_match_the_model(tmp_path):
     """tests/cell_grid_check.cpp on csrc/cell_grid.h, the grid arithmetic both neighbourhood searches run on (knn_grid_*_kernel,
     interp3nn_bin / _grid_kernel), compiled for the host with address + undefined sanitizers and without contraction: for grid
