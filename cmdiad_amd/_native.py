@@ -148,6 +148,10 @@ SIGNATURES = {
     "cmdiad_threshold_mask": [P, P, I, I, I, I, P, P, P],
     "cmdiad_region_table": [P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, SZ, P],
     "cmdiad_region_measure": [P, P, P, P, c_int64, c_int64, I, I, I, I, P, P, P, P],
+    "cmdiad_pr_runs": [P, I, P, I, P, P, P, I, P, P, I, P],
+    "cmdiad_pr_f1max": [P, P, P, I, I, P, P, I, P],
+    "cmdiad_region_overlap": [P, P, I, P, P, P, I, I, I, I, I, P, P, P],
+    "cmdiad_detection_counts": [P, P, I, P, P, P, I, I, I, P, P],
     "cmdiad_tiff_unpack": [P, c_int64, P, I, I, I, I, I, I, I, I, I, I, I, P, P],
     "cmdiad_png_unfilter": [P, c_int64, P, I, I, I, I, I, I, P, P],
     "cmdiad_png_filter": [P, I, I, I, I, I, P, P],
@@ -178,6 +182,7 @@ SIZE_QUERIES = {
     "cmdiad_sort_u64_tile": [],
     "cmdiad_sort_u64_workspace_bytes": [I],
     "cmdiad_region_table_workspace_bytes": [I, I, I],
+    "cmdiad_pr_tile": [],
 }
 
 

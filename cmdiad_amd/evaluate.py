@@ -117,6 +117,12 @@ class ClassRun:
     also measured on the test items' organised clouds and every region of the JSON gains the 3-D fields of
     regions.measure_fields, in the clouds' units; unset, the file is what it was.
 
+    Precision-recall numbers (docs/metrics.md), read with getattr(args, "pr_metrics", False) and off when unset: calculate_metrics
+    also computes AP and F1-max at both levels on the device and result() gains a ``pr`` entry; where a regions file is written,
+    its summary in result() gains ``detection``: ground-truth components, those hit by a reported region, reported regions and
+    those that hit no defect, at the calibrated pixel threshold and min_area.  METRICS, the table and the regions JSON stay as
+    they are.
+
     Overlays (docs/overlay.md), read the same way, off when unset and under the same rule for the calibration:
     ``args.overlay_dir`` -- predict() ends by writing one PNG per test image, ``<overlay_dir>/<class>/<index>.png``, in chunks of at
     most 32: the score map coloured over the sample's own rgb tensor, the contour of the calibration's pixel threshold and the boxes
@@ -154,6 +160,7 @@ class ClassRun:
         self.regions_dir = getattr(args, "regions_dir", None)
         self.min_area, self.max_regions = getattr(args, "min_area", None) or 1, getattr(args, "max_regions", None) or 16
         self.measure_regions = bool(getattr(args, "measure_regions", None))
+        self.pr_metrics = bool(getattr(args, "pr_metrics", False))
         self.calibration = self.held_out = self.regions_summary = None
         if self.regions_dir and not self.holdout and not self.load_fit_dir:
             raise ValueError("regions_dir needs a calibration: set calibration_holdout, or load_fit_dir with a .cmdcal beside the fit")
@@ -365,6 +372,9 @@ class ClassRun:
             json.dump(dict(class_name=self.data.name, thresholds=thresholds, images=images), f, indent=1)
         self.regions_summary = dict(thresholds, file=path, tp=int((decided & labels).sum()), fp=int((decided & ~labels).sum()),
                                     tn=int((~decided & ~labels).sum()), fn=int((~decided & labels).sum()))
+        if self.pr_metrics:       # defects, not images: ground-truth components hit by a reported region, regions that hit none
+            from . import metrics
+            self.regions_summary["detection"] = metrics.detection_counts(m.gts, m.predictions, cal.pixel_threshold, self.min_area).totals()
         self.sec["regions"] = time.perf_counter() - t0
 
     def result(self):
@@ -374,6 +384,8 @@ class ClassRun:
                    phases=list(self.phases),
                    library_rows={k: int(getattr(m, f"patch_{k}_lib").shape[0]) for k in ("xyz", "rgb", "fusion")
                                  if torch.is_tensor(getattr(m, f"patch_{k}_lib", None))})
+        if self.pr_metrics:
+            out["pr"] = dict(m.pr)
         if self.regions_summary is not None:
             out["regions"] = dict(self.regions_summary)
         if self.overlays_summary is not None:

@@ -363,8 +363,11 @@ class Features(torch.nn.Module):
 
     def calculate_metrics(self):
         """features.py:302-324.  With CMDIAD_METRICS_DEVICE=1 the three pixel-level values come from cmdiad_amd.metrics (the HIP
-        kernels of csrc/metrics.hip); image_rocauc -- about a hundred values -- stays on scikit-learn either way."""
+        kernels of csrc/metrics.hip); image_rocauc -- about a hundred values -- stays on scikit-learn either way.  With
+        args.pr_metrics set (opt-in, not a stored argument) pixel_ap, pixel_f1max, image_ap, image_f1max and the `pr` dict are set as
+        well, from cmdiad_amd.metrics whatever the switch says: there is no host implementation of them (docs/metrics.md)."""
         from ..utils.au_pro_util import calculate_au_pro
+        want_pr = bool(getattr(self.args, "pr_metrics", False))
         self.image_preds = np.stack(self.image_preds)
         self.image_labels = np.stack(self.image_labels)
         self.pixel_preds = np.array(self.pixel_preds)
@@ -376,12 +379,26 @@ class Features(torch.nn.Module):
         self.image_rocauc = roc_auc_score(self.image_labels, self.image_preds)
         if os.environ.get("CMDIAD_METRICS_DEVICE", "0") == "1":     # read at call time; docs/metrics.md
             from .. import metrics
-            m = metrics.pixel_metrics(self.gts, self.predictions)
+            m = metrics.pixel_metrics(self.gts, self.predictions, pr=True) if want_pr else metrics.pixel_metrics(self.gts, self.predictions)
             self.pixel_rocauc, self.au_pro, self.au_pro_001 = m["pixel_rocauc"], m["au_pro"], m["au_pro_001"]
+            if want_pr:
+                Features._set_pr_metrics(self, m)       # (by class: calculate_metrics is also run on bare result holders)
             return
         self.pixel_rocauc = roc_auc_score(self.pixel_labels, self.pixel_preds)
         self.au_pro, _ = calculate_au_pro(self.gts, self.predictions)
         self.au_pro_001, _ = calculate_au_pro(self.gts, self.predictions, 0.01)
+        if want_pr:
+            from .. import metrics
+            Features._set_pr_metrics(self, metrics.pixel_pr_metrics(self.gts, self.predictions))
+
+    def _set_pr_metrics(self, pixel):
+        """pixel: a dict that carries pixel_ap, pixel_f1max and pixel_f1max_threshold; the image level is computed here."""
+        from .. import metrics
+        image = metrics.image_pr_metrics(self.image_labels, self.image_preds)
+        keys = ("ap", "f1max", "f1max_threshold")
+        self.pr = {f"{lvl}_{k}": float(src[f"{lvl}_{k}"]) for lvl, src in (("pixel", pixel), ("image", image)) for k in keys}
+        self.pixel_ap, self.pixel_f1max = self.pr["pixel_ap"], self.pr["pixel_f1max"]
+        self.image_ap, self.image_f1max = self.pr["image_ap"], self.pr["image_f1max"]
 
     def run_late_fusion(self):
         """features.py:352-358 (scikit-learn on the host by default; on the device with CMDIAD_OCSVM_DEVICE=1)."""

@@ -1557,6 +1557,112 @@ def region_table(maps, labels, n_comp, comp_offset, comp_size, min_area=1, max_r
     return count, ints, vals
 
 
+# ------------------------------------------------------------------------------------ precision-recall, detection counts (docs/metrics.md)
+PR_TILE = 2048            # keys per block of the run-head passes (cmdiad_pr_tile): sizes around its multiples change the passes' shape
+PR_F1_BLOCK = 256         # runs per block-step of cmdiad_pr_f1max's first stage: runs 256 j .. 256 j + 255 meet in one block
+PR_F1_MAX_BLOCKS = 1024   # ... and block b takes j = b, b + blocks, ... with blocks = min(ceil(run_cap / 256), 1024)
+
+
+def pr_runs(def_sorted_keys, ok_sorted_keys):
+    """The SORTED keys of the defect scores [n_def] and of the defect-free scores [n_ok] -> (run_key [n_def] u64, run_first [n_def]
+    i32, run_fp [n_def] i32, n_runs [1] i32): per run of equal defect keys, in ascending key order, the key, the index of its first
+    element and the number of defect-free scores at or above it.  Entries past n_runs are not written.  No synchronisation."""
+    n_def = _chk_list(def_sorted_keys, torch.int64, "pr_runs.def_sorted_keys")
+    n_ok = _chk_list(ok_sorted_keys, torch.int64, "pr_runs.ok_sorted_keys")
+    dev = def_sorted_keys.device
+    if ok_sorted_keys.device != dev:
+        raise ValueError("pr_runs: both key lists must be on one device")
+    run_key = torch.empty((n_def,), dtype=torch.int64, device=dev)
+    run_first = torch.empty((n_def,), dtype=torch.int32, device=dev)
+    run_fp = torch.empty((n_def,), dtype=torch.int32, device=dev)
+    n_runs = torch.zeros((1,), dtype=torch.int32, device=dev)
+    if n_def:
+        tile_heads = torch.empty((2 * -(-n_def // PR_TILE),), dtype=torch.int32, device=dev)      # heads per tile | their scan
+        _call("cmdiad_pr_runs", _p(def_sorted_keys), n_def, _p(ok_sorted_keys), n_ok, _p(run_key), _p(run_first), _p(run_fp), n_def,
+              _p(n_runs), _p(tile_heads), tile_heads.numel(), _stream())
+    return run_key, run_first, run_fp, n_runs
+
+
+def pr_f1max(run_first, run_fp, n_runs, n_def):
+    """A run table as plain integers (run_first, run_fp [cap] i32, n_runs [1] i32 on the device, n_def) -> best [2] i64 = (the run
+    that maximises 2 tp / (tp + fp + n_def), tp = n_def - run_first, compared exactly, the largest index among equals; 0).  -1 when
+    the table holds no run.  No synchronisation."""
+    cap = _chk_list(run_first, torch.int32, "pr_f1max.run_first")
+    if _chk_list(run_fp, torch.int32, "pr_f1max.run_fp") != cap:
+        raise ValueError("pr_f1max: run_first and run_fp differ in length")
+    _chk(n_runs, torch.int32, "pr_f1max.n_runs")
+    n_def = int(n_def)
+    if n_runs.numel() != 1 or not 0 <= n_def <= METRICS_MAX_TOTAL:
+        raise ValueError(f"pr_f1max: n_runs must hold one entry and n_def = {n_def} lie in 0..2^30")
+    dev = run_first.device
+    if run_fp.device != dev or n_runs.device != dev:
+        raise ValueError("pr_f1max: every tensor must be on one device")
+    best = torch.tensor([-1, 0], dtype=torch.int64, device=dev)
+    if cap:
+        partial = torch.empty((min(-(-cap // PR_F1_BLOCK), PR_F1_MAX_BLOCKS),), dtype=torch.int32, device=dev)   # the first stage's winners
+        _call("cmdiad_pr_f1max", _p(run_first), _p(run_fp), _p(n_runs), cap, n_def, _p(best), _p(partial), partial.numel(), _stream())
+    return best
+
+
+def _chk_labelling(labels, comp_offset, who, what):
+    _chk(labels, torch.int32, f"{who}.{what}_labels"); _chk(comp_offset, torch.int32, f"{who}.{what}_comp_offset")
+    if labels.dim() != 3 or comp_offset.numel() != labels.shape[0] + 1:
+        raise ValueError(f"{who}: {what}_labels must be [n,H,W] and {what}_comp_offset [n+1], got {tuple(labels.shape)} and "
+                         f"{comp_offset.numel()}")
+
+
+def region_overlap(gt_labels, gt_comp_offset, pred_labels, pred_comp_offset, pred_comp_size, min_area=1):
+    """Two labellings of the same frames (ccl_label's outputs) -> (covered [n ceil(H/2) ceil(W/2)] i32 per ground-truth component = its
+    pixels inside a predicted component of at least min_area pixels, hits [len(pred_comp_size)] i32 per predicted component = the
+    ground-truth pixels inside it, 0 when it is smaller than min_area).  No synchronisation."""
+    min_area = int(min_area)
+    if min_area < 1:
+        raise ValueError(f"region_overlap: min_area = {min_area} (>= 1)")
+    _chk_labelling(gt_labels, gt_comp_offset, "region_overlap", "gt")
+    _chk_labelling(pred_labels, pred_comp_offset, "region_overlap", "pred")
+    _chk(pred_comp_size, torch.int32, "region_overlap.pred_comp_size")
+    n, H, W = gt_labels.shape
+    if H < 1 or W < 1 or H * W > (1 << 24) or n > 65535 or n * H * W > METRICS_MAX_TOTAL:
+        raise ValueError(f"region_overlap: unsupported shape {tuple(gt_labels.shape)} (n <= 65535, H, W >= 1, H*W <= 2^24, n*H*W <= 2^30)")
+    if pred_labels.shape != gt_labels.shape or pred_comp_size.dim() != 1:
+        raise ValueError(f"region_overlap: gt_labels {tuple(gt_labels.shape)} and pred_labels {tuple(pred_labels.shape)} must be the same "
+                         "[n,H,W], pred_comp_size one-dimensional")
+    dev = gt_labels.device
+    for t in (gt_comp_offset, pred_labels, pred_comp_offset, pred_comp_size):
+        if t.device != dev:
+            raise ValueError("region_overlap: every tensor must be on one device")
+    covered = torch.zeros((n * ((H + 1) // 2) * ((W + 1) // 2),), dtype=torch.int32, device=dev)
+    hits = torch.zeros((pred_comp_size.numel(),), dtype=torch.int32, device=dev)
+    if n:
+        _call("cmdiad_region_overlap", _p(gt_labels), _p(gt_comp_offset), covered.numel(), _p(pred_labels), _p(pred_comp_offset),
+              _p(pred_comp_size), hits.numel(), n, H, W, min_area, _p(covered), _p(hits), _stream())
+    return covered, hits
+
+
+def detection_counts(gt_comp_offset, covered, pred_comp_offset, pred_comp_size, hits, min_area=1):
+    """region_overlap's tables -> counts [n,4] i32 per image: ground-truth components, those with covered > 0, predicted components
+    of at least min_area pixels, those of them with hits == 0.  No synchronisation."""
+    min_area = int(min_area)
+    if min_area < 1:
+        raise ValueError(f"detection_counts: min_area = {min_area} (>= 1)")
+    for t, name in ((gt_comp_offset, "gt_comp_offset"), (covered, "covered"), (pred_comp_offset, "pred_comp_offset"),
+                    (pred_comp_size, "pred_comp_size"), (hits, "hits")):
+        _chk_list(t, torch.int32, f"detection_counts.{name}")
+    n = gt_comp_offset.numel() - 1
+    if n < 0 or n > 65535 or pred_comp_offset.numel() != n + 1 or hits.numel() != pred_comp_size.numel():
+        raise ValueError(f"detection_counts: gt_comp_offset and pred_comp_offset must both be [n+1] (n <= 65535), hits as long as "
+                         f"pred_comp_size; got {gt_comp_offset.numel()}, {pred_comp_offset.numel()}, {hits.numel()}, {pred_comp_size.numel()}")
+    dev = gt_comp_offset.device
+    for t in (covered, pred_comp_offset, pred_comp_size, hits):
+        if t.device != dev:
+            raise ValueError("detection_counts: every tensor must be on one device")
+    counts = torch.zeros((n, 4), dtype=torch.int32, device=dev)
+    if n:
+        _call("cmdiad_detection_counts", _p(gt_comp_offset), _p(covered), covered.numel(), _p(pred_comp_offset), _p(pred_comp_size),
+              _p(hits), hits.numel(), n, min_area, _p(counts), _stream())
+    return counts
+
+
 def cloud_layout(cloud, H, W, layout=None, who="region_measure"):
     """'planar' ([n,3,H,W]) or 'interleaved' ([n,H,W,3]) for an organised cloud beside maps of H x W.  The shape decides; a
     [n,3,H,W] cloud with H == 3 or W == 3 can be read both ways and is refused unless `layout` names one."""

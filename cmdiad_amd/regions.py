@@ -4,7 +4,8 @@ What scoring returns per sample is a float that means nothing by itself and a 22
 into "this part is defective, here, this big":
 
   * ``calibrate`` takes the scores of DEFECT-FREE samples and returns two thresholds, nearest-rank quantiles of the image scores
-    and of all their pixels (the pixels are sorted on the device, ``metrics.sort_values``);
+    and of all their pixels (the pixels are sorted on the device, ``metrics.sort_values``); ``calibrate_labelled`` takes LABELLED
+    samples instead and returns the two F1-max thresholds (docs/metrics.md);
   * ``find_regions`` thresholds maps on the device, labels the 8-connected components (``cmdiad_ccl_label``), and returns per
     image a fixed-size table of the strongest regions: label, area, box, peak and its position, centroid, score sum;
   * ``Calibration.save`` / ``load`` keep the thresholds in a ``.cmdcal`` file (the container of fitted.py) together with the
@@ -318,6 +319,27 @@ def calibrate(image_scores, maps, pixel_quantile=0.999, image_quantile=1.0, clas
     ordered = metrics.sort_values(m)                  # raises on NaN / infinity
     pixel_thr = float(ordered[ip:ip + 1].cpu().numpy()[0])
     return Calibration(pixel_thr, float(np.sort(s)[ii]), pixel_quantile, image_quantile, s.size, m.numel(), class_name)
+
+
+def calibrate_labelled(image_scores, image_labels, maps, gts, class_name=None):
+    """Thresholds from LABELLED samples (a validation split with ground truth): at both levels the threshold that maximises F1
+    (metrics.image_pr_metrics, metrics.pixel_pr_metrics; among equal F1 the highest), in the strict form of this module's
+    decisions -- nextafter(v, -inf) of the F1-max score v, so that `score > threshold` is `score >= v`.  pixel_quantile and
+    image_quantile record what they mean for a quantile calibration, the fraction of DEFECT-FREE values not above the threshold:
+    (n_ok - fp) / n_ok.  n_images and n_pixels count all samples.  ValueError when a level lacks one of the two classes, a mask is
+    not binary, or a score is NaN or infinite."""
+    from . import metrics
+    s = np.asarray(image_scores, dtype=np.float64).reshape(-1)
+    lab = np.asarray(image_labels).reshape(-1)
+    if s.size == 0:
+        raise ValueError("calibrate_labelled: no image scores")
+    m = metrics._stacked(maps, "maps")                # where it lives: the metric functions upload host inputs themselves
+    if m.shape[0] != s.size or lab.size != s.size:
+        raise ValueError(f"calibrate_labelled: {s.size} image scores, {lab.size} image labels and {m.shape[0]} maps")
+    img = metrics.image_pr_metrics(lab, s)
+    pix = metrics.pixel_pr_metrics(gts, m)
+    return Calibration(pix["pixel_f1max_threshold_gt"], img["image_f1max_threshold_gt"], (pix["n_ok"] - pix["fp"]) / pix["n_ok"],
+                       (img["n_ok"] - img["fp"]) / img["n_ok"], s.size, m.numel(), class_name)
 
 
 def _truncate(method, name, length):

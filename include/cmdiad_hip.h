@@ -860,6 +860,56 @@ int cmdiad_region_measure(const int32_t* labels, const int32_t* count, const int
                           long long ch_stride, int n, int H, int W, int max_regions, int32_t* m_ints, double* m_vals,
                           int32_t* bad_count, cmdiad_stream_t stream);
 
+/* ---- precision-recall numbers and defect detection counts (docs/metrics.md, "Precision-recall and detection counts"; additions,
+ * the ABI stays 6).  Every result is an integer or a stored key picked by integer work (integer atomics only), so it is bit-exact
+ * whatever the order of arrival; AP and the F1 value are float64 expressions of the caller over these integers.  Everywhere: every
+ * argument is checked before any launch, a negative size or one above 2^30 is rejected, size 0 returns CMDIAD_OK without a launch,
+ * nothing synchronises. ---- */
+
+/* The run table of the defect scores.  def_sorted_keys [n_def] and ok_sorted_keys [n_ok]: the SORTED keys (cmdiad_f64_to_keys,
+ * cmdiad_sort_u64) of the defect and of the defect-free scores.  A run is a maximal group of equal defect keys; runs are numbered in
+ * ascending key order, r = 0 .. n_runs - 1, whatever the launch geometry:
+ *   run_key [run_cap] u64 = the key, run_first [run_cap] int32 = the index of the run's first element in def_sorted_keys,
+ *   run_fp [run_cap] int32 = n_ok - #(ok keys < key) = the defect-free scores at or above the run's value; n_runs [1] int32.
+ * tp = n_def - run_first defect scores lie at or above the run's value; the run holds run_first[r + 1] - run_first[r] of them.
+ * Nothing is written past run_cap entries (n_runs still has the true number; run_cap = n_def always suffices).  n_def == 0 zeroes
+ * n_runs (where it is passed) and launches nothing.  The tile query returns the keys per block of the head count and compaction
+ * passes: sizes around its multiples are where the passes change shape.  The scratch is a typed buffer of the caller's, like the
+ * outputs, and its size is a formula, so there is no size query: tile_heads [tile_cap] int32 with tile_cap >= 2 ceil(n_def / tile)
+ * holds the run heads per tile and behind them their exclusive scan; both are left there. */
+size_t cmdiad_pr_tile(void);
+int cmdiad_pr_runs(const uint64_t* def_sorted_keys, int n_def, const uint64_t* ok_sorted_keys, int n_ok, uint64_t* run_key,
+                   int32_t* run_first, int32_t* run_fp, int run_cap, int32_t* n_runs, int32_t* tile_heads, int tile_cap,
+                   cmdiad_stream_t stream);
+
+/* best [2] int64 = (the run r that maximises F1[r] = 2 tp / (tp + fp + n_def) with tp = n_def - run_first[r], fp = run_fp[r]; 0,
+ * reserved).  Fractions are compared exactly, by cross-multiplication in unsigned 64-bit; among equal fractions the largest r (the
+ * highest threshold) wins: a total order, so the answer does not depend on the reduction tree.  n_runs [1] int32 is read on the
+ * DEVICE and clamped to 0..run_cap; a run with run_first outside 0..n_def - 1 or a negative run_fp is passed over; best[0] = -1 when
+ * no run is left.  The table is plain integers: it need not come from cmdiad_pr_runs.  Two launches: the first stage's block b takes
+ * the runs [256 j, 256 j + 256) for j = b, b + blocks, ... with blocks = min(ceil(run_cap / 256), 1024).  partial
+ * [partial_cap] int32, partial_cap >= blocks (1024 always suffices): the first stage's winners, a typed scratch buffer of the
+ * caller's.  run_cap == 0 launches nothing and leaves best alone. */
+int cmdiad_pr_f1max(const int32_t* run_first, const int32_t* run_fp, const int32_t* n_runs, int run_cap, int n_def, int64_t* best,
+                    int32_t* partial, int partial_cap, cmdiad_stream_t stream);
+
+/* Overlap of two labellings of the same n frames [n,H,W] (both as cmdiad_ccl_label leaves them): the ground truth's (gt_labels,
+ * gt_comp_offset [n + 1]) and the prediction's (pred_labels, pred_comp_offset [n + 1], pred_comp_size [pred_comp_cap]).  A predicted
+ * component is KEPT when its size is at least min_area (>= 1).  covered [gt_comp_cap] int32: per ground-truth component (global id)
+ * its pixels that lie in a kept predicted component; hits [pred_comp_cap] int32: per predicted component the ground-truth pixels
+ * inside it, 0 for one that is not kept.  Both are zeroed first.  Every id is checked against the capacity of the table it indexes;
+ * sizes as for the labelling. */
+int cmdiad_region_overlap(const int32_t* gt_labels, const int32_t* gt_comp_offset, int gt_comp_cap, const int32_t* pred_labels,
+                          const int32_t* pred_comp_offset, const int32_t* pred_comp_size, int pred_comp_cap, int n, int H, int W,
+                          int min_area, int32_t* covered, int32_t* hits, cmdiad_stream_t stream);
+
+/* counts [n,4] int32 per image: n_gt (its ground-truth components), n_detected (those with covered > 0), n_pred (its kept predicted
+ * components), n_false (kept ones with hits == 0), from the tables of cmdiad_region_overlap.  Offsets are clamped to the capacities:
+ * nothing is read outside them. */
+int cmdiad_detection_counts(const int32_t* gt_comp_offset, const int32_t* covered, int gt_comp_cap, const int32_t* pred_comp_offset,
+                            const int32_t* pred_comp_size, const int32_t* hits, int pred_comp_cap, int n, int min_area,
+                            int32_t* counts, cmdiad_stream_t stream);
+
 /* ---- xyz TIFFs (docs/tiff.md; utils/mvtec3d_util.py:9-11 of the reference reads them with tifffile on the host) ----
  * raw [raw_bytes] = file bytes with UNCOMPRESSED chunks (dword aligned, raw_bytes a multiple of 4: the upload buffer is padded),
  * chunk_off [B, n_chunks] (device) = byte offset into raw of every chunk of every image -> out [B,H,W,C] of the files' own float type
