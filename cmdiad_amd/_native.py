@@ -158,6 +158,9 @@ SIGNATURES = {
     "cmdiad_overlay_render": [P, I, I, I, I, I, P, I, P, I, P, I, D, D, D, D, D, D, P, P, P, P, I, I, U32, U32, P, P, P],
     "cmdiad_mesh_count": [P, c_int64, c_int64, P, I, I, I, D, P, P, P],
     "cmdiad_mesh_write": [P, c_int64, c_int64, P, I, I, I, P, I, P, P, P, I, D, D, D, D, D, D, P, D, I, P, P, P, P, P],
+    "cmdiad_cloud_bounds": [P, P, P, I, I, I, P, P, P],
+    "cmdiad_organize_splat": [P, P, P, I, I, I, I, I, I, P, P, P, P],
+    "cmdiad_organize_resolve": [P, P, P, P, P, I, I, I, I, I, P, P, P, P, P, P],
     "cmdiad_digest64": [P, SZ, c_uint64, P, P],
 }
 SIZE_QUERIES = {

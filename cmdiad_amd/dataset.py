@@ -26,8 +26,9 @@ Sample path (second half of this file; docs/sample_prep.md): the reference's ``T
 ``TestDataset`` / ``get_data_loader`` over an MVTec 3D-AD directory with a third ``img_process_method``, ``'hip'`` -- files decoded on
 reader threads, every transform after that in csrc/sample_prep.hip (``SamplePrep``) -- and ``MVTec3DClass``, the real-data class
 source of ``evaluate.evaluate_classes``; ``EyecandiesRawClass`` is the same over the raw Eyecandies download (csrc/eyecandies.hip,
-docs/eyecandies.md), ``MVTec3DRawClass`` over the raw MVTec 3D-AD download (csrc/preprocess.hip, docs/preprocessing.md).
-The three device sources differ in what they decode and how a batch is prepared, nothing else: ``_device_items`` is their one item
+docs/eyecandies.md), ``MVTec3DRawClass`` over the raw MVTec 3D-AD download (csrc/preprocess.hip, docs/preprocessing.md),
+``PointCloudClass`` over a tree of unorganised PLY scans (csrc/organize.hip, docs/organize.md; opt-in: ``dataset_classes`` never builds it).
+The device sources differ in what they decode and how a batch is prepared, nothing else: ``_device_items`` is their one item
 loop (utils.batching.read_ahead decodes ahead, one prepare call per batch, one pinned copy of the masks, batch-of-one items).
 """
 import math
@@ -1147,6 +1148,107 @@ class MVTec3DRawClass(_RawClassSource):
         ds = self._test
         return self._items(len(ds), lambda i: self._decode(ds.img_paths[i], ds.gt_paths[i] if ds.gt_paths[i] != 0 else None), ds.labels,
                            [str(p[0]) for p in ds.img_paths])
+
+
+class PointCloudClass(_RawClassSource):
+    """One class directory of UNORGANISED scans -- ``<class>/train/good/*.ply`` and ``<class>/test/<kind>/*.ply``, point lists with
+    optional ``red green blue`` and, in a defect scan, a per-point integer ``label`` (0: sound) -- as the data object of
+    evaluate.ClassRun / evaluate_classes, with MVTec3DClass's protocol.  Reader threads parse the files (utils.ply.read_points); every
+    batch is one ``organize`` call (csrc/organize.hip; docs/organize.md) and SamplePrep's device entry points, and it yields, sample
+    for sample and bit for bit, what MVTec3DClass with img_process_method='hip' yields over the tree ``python -m cmdiad_amd.organize``
+    writes from this directory.  ``<class>/camera.json`` (optional) fixes the camera: ``{"kind": "orthographic", "x0", "y0", "pitch"
+    [, "pitch_y"]}`` or ``{"kind": "pinhole", "fx", "fy", "cx", "cy"}``, with optional ``"T"`` (3 x 4), ``"size": [H, W]`` and ``"fill"``;
+    without it every scan gets ``fit_orthographic`` at ``args.organize_size`` (default 448) squared with a margin of 1, and
+    ``args.organize_fill`` (default 1).  Order and labels are TestDataset's (sorted directories, then sorted files; ``good`` is 0,
+    anything else 1); a file without colours gives a black image, a good sample's mask is zeros, a defect scan without ``label``
+    raises; ``rgb_path`` is the PLY's path.  There is no host path."""
+    _no_host_path = ("PointCloudClass: unorganised scans are put on the pixel grid on the device only, there is no host path: "
+                     "img_process_method must be 'hip', got {method!r} (or write the tree with python -m cmdiad_amd.organize and "
+                     "read it with MVTec3DClass)")
+
+    def __init__(self, dataset_path, class_name, args):
+        import json
+        from .organize import Camera
+        super().__init__(class_name, args)
+        root = Path(dataset_path, class_name)
+        self.train_files = [str(p) for p in _sorted_glob(root, "train", "good", "*.ply")]
+        self.test_files, self.test_labels = [], []
+        test = Path(root, "test")
+        for kind in sorted(os.listdir(test)) if test.is_dir() else []:
+            files = [str(p) for p in _sorted_glob(test, kind, "*.ply")]
+            self.test_files += files
+            self.test_labels += [0 if kind == "good" else 1] * len(files)
+        self.n_train, self.n_test = len(self.train_files), len(self.test_files)
+        size = int(getattr(args, "organize_size", 448))
+        self.camera, self.size, self.fill = None, (size, size), int(getattr(args, "organize_fill", 1))
+        cam_path = Path(root, "camera.json")
+        if cam_path.is_file():
+            with open(cam_path) as f:
+                c = json.load(f)
+            if c.get("kind") == "orthographic":
+                self.camera = Camera.orthographic(c["x0"], c["y0"], c["pitch"], c.get("pitch_y"), c.get("T"))
+            elif c.get("kind") == "pinhole":
+                self.camera = Camera.pinhole(c["fx"], c["fy"], c["cx"], c["cy"], c.get("T"))
+            else:
+                raise ValueError(f"{cam_path}: kind must be 'orthographic' or 'pinhole', got {c.get('kind')!r}")
+            self.size = tuple(int(v) for v in c.get("size", self.size))
+            self.fill = int(c.get("fill", self.fill))
+            if len(self.size) != 2:
+                raise ValueError(f"{cam_path}: size must be [H, W]")
+
+    @staticmethod
+    def decode(path, label):
+        """(points float32 [N,3], colours uint8 [N,3] or None, labels uint8 [N] or None) of one file, on a reader thread"""
+        import numpy as np
+        from .utils import ply
+        v = ply.read_points(path)
+        pts = np.stack([v["x"], v["y"], v["z"]], axis=1)
+        rgb = None
+        if all(c in v and v[c].dtype == np.uint8 for c in ("red", "green", "blue")):
+            rgb = np.stack([v["red"], v["green"], v["blue"]], axis=1)
+        lab = None
+        if label:
+            if "label" not in v:
+                raise ValueError(f"PointCloudClass: {path}: a defect scan needs a per-point integer 'label' property (0: sound)")
+            lab = (v["label"] != 0).astype(np.uint8)
+        return pts, rgb, lab
+
+    def organize_batch(self, dec):
+        """decoded scans -> the Organized of the batch: one upload of the three lists, one fit where there is no camera.json, one
+        organize call"""
+        import numpy as np
+        from . import organize as og
+        dev = self.sample_prep().device
+        lengths = [len(d[0]) for d in dec]
+        P = sum(lengths)
+        any_rgb, any_lab = any(d[1] is not None for d in dec), any(d[2] is not None for d in dec)
+        colors = np.concatenate([d[1] if d[1] is not None else np.zeros((len(d[0]), 3), np.uint8) for d in dec]) if any_rgb else None
+        labels = np.concatenate([d[2] if d[2] is not None else np.zeros(len(d[0]), np.uint8) for d in dec]) if any_lab else None
+        with torch.cuda.device(dev):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(dev, non_blocking=True) if a is not None else None
+            points = up(np.concatenate([d[0] for d in dec]).reshape(P, 3))
+            H, W = self.size
+            cams = self.camera if self.camera is not None else og.fit_orthographic(points, lengths, H, W, margin=1)
+            return og.organize(points, lengths, cams, H, W, self.fill, up(colors), up(labels))
+
+    def _prepare(self, dec):
+        """decoded scans -> [(DeviceSample, mask or None)]"""
+        prep = self.sample_prep()
+        org = self.organize_batch(dec)
+        with torch.cuda.device(prep.device):
+            imgs = prep.prepare_device_images(org.rgb)
+            clouds = prep.prepare_device_clouds(org.xyz)
+            masks = prep.prepare_device_masks(org.mask)
+        return [(DeviceSample((imgs[j], clouds[j][0], clouds[j][1]), clouds[j][2]), masks[j] if dec[j][2] is not None else None)
+                for j in range(len(dec))]
+
+    def train(self):
+        files = self.train_files
+        return self._items(self.n_train, lambda i: self.decode(files[i], 0), [0] * self.n_train)
+
+    def test(self):
+        files, labels = self.test_files, self.test_labels
+        return self._items(self.n_test, lambda i: self.decode(files[i], labels[i]), labels, files)
 
 
 def dataset_classes(args):

@@ -1919,6 +1919,125 @@ def mesh_write(cloud, maps, chunks, lohi, lut, alpha, background=None, mean=(0.0
     return vidx, vertices, faces
 
 
+# ------------------------------------------------------------------------------------ point lists into the pixel grid (docs/organize.md)
+ORGANIZE_MAX_IMAGES, ORGANIZE_MAX_PIXELS, ORGANIZE_MAX_TOTAL = 65535, 1 << 24, 1 << 30
+ORGANIZE_KEY_EMPTY = -1           # all ones, as the int64 torch shows
+
+
+def _chk_point_list(points, offsets, cams, max_len, who):
+    """the checks the three entry points share -> (n, P, max_len)"""
+    _chk(points, torch.float32, f"{who}.points"); _chk(offsets, torch.int64, f"{who}.offsets"); _chk(cams, torch.float64, f"{who}.cams")
+    if points is None or offsets is None:
+        raise ValueError(f"{who}: points and offsets are required")
+    if points.dim() != 2 or points.shape[1] != 3 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError(f"{who}: points must be [P,3] and offsets [n+1], got {tuple(points.shape)} and {tuple(offsets.shape)}")
+    n, P = offsets.numel() - 1, points.shape[0]
+    if n > ORGANIZE_MAX_IMAGES or P >= 1 << 31:
+        raise ValueError(f"{who}: {n} clouds (at most {ORGANIZE_MAX_IMAGES}) of {P} points (below 2^31)")
+    if offsets.device != points.device:
+        raise ValueError(f"{who}: offsets on {offsets.device}, points on {points.device}")
+    if cams is not None and (tuple(cams.shape) != (n, 16) or cams.device != points.device):
+        raise ValueError(f"{who}: cams must be [{n},16] float64 on the points' device, got {tuple(cams.shape)} on {cams.device}")
+    max_len = int(max_len)
+    if not 0 <= max_len < 1 << 31:
+        raise ValueError(f"{who}: max_len = {max_len} (0..2^31-1)")
+    return n, P, max_len
+
+
+def _chk_grid(n, H, W, who):
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or H * W > ORGANIZE_MAX_PIXELS or n * H * W > ORGANIZE_MAX_TOTAL:
+        raise ValueError(f"{who}: a grid of {H} x {W} for {n} clouds: sides >= 1, H*W <= 2^24, n*H*W <= 2^30")
+    return H, W
+
+
+def _chk_out(t, dtype, shape, dev, name):
+    _chk(t, dtype, name)
+    if tuple(t.shape) != tuple(shape) or t.device != dev:
+        raise ValueError(f"{name}: must be {tuple(shape)} {dtype} on {dev}, got {tuple(t.shape)} on {t.device}")
+
+
+def cloud_bounds(points, offsets, cams, max_len, out=None):
+    """points [P,3] f32, offsets [n+1] i64 (on the device), cams [n,16] f64, max_len (the longest cloud) -> (bounds [n,6] f64 = the
+    minimum of the camera coordinates c_0..c_2 over each cloud's valid points, then the maximum; count [n] i32 = the valid points).
+    An empty cloud gives +inf, -inf, 0.  out: that pair, to write into.  No synchronisation."""
+    n, P, max_len = _chk_point_list(points, offsets, cams, max_len, "cloud_bounds")
+    if cams is None:
+        raise ValueError("cloud_bounds: cams is required")
+    dev = points.device
+    if out is None:
+        out = (torch.empty((n, 6), dtype=torch.float64, device=dev), torch.empty((n,), dtype=torch.int32, device=dev))
+    bounds, count = out
+    _chk_out(bounds, torch.float64, (n, 6), dev, "cloud_bounds.bounds"); _chk_out(count, torch.int32, (n,), dev, "cloud_bounds.count")
+    if n:
+        _call("cmdiad_cloud_bounds", _p(points), _p(offsets), _p(cams), n, P, max_len, _p(bounds), _p(count), _stream())
+    return bounds, count
+
+
+def organize_splat(points, offsets, cams, max_len, kind, H, W, out=None):
+    """The projection and the nearest-point key map: -> (keys [n,H,W] i64 (the uint64 bits; ORGANIZE_KEY_EMPTY where no point fell),
+    pixel_of_point [P] i32 (-2 dropped, -1 outside, else the pixel; written for the points of the clouds only), stats [n,4] i32
+    with columns 0, 1 = dropped, outside).  kind: 0 orthographic, 1 pinhole.  out: that triple, to write into (a fresh stats is
+    zeroed; a given one keeps its columns 2, 3).  No synchronisation."""
+    n, P, max_len = _chk_point_list(points, offsets, cams, max_len, "organize_splat")
+    if cams is None:
+        raise ValueError("organize_splat: cams is required")
+    H, W = _chk_grid(n, H, W, "organize_splat")
+    kind = int(kind)
+    if kind not in (0, 1):
+        raise ValueError(f"organize_splat: kind = {kind} (0 orthographic | 1 pinhole)")
+    dev = points.device
+    if out is None:
+        out = (torch.empty((n, H, W), dtype=torch.int64, device=dev), torch.empty((P,), dtype=torch.int32, device=dev),
+               torch.zeros((n, 4), dtype=torch.int32, device=dev))
+    keys, pixel_of_point, stats = out
+    _chk_out(keys, torch.int64, (n, H, W), dev, "organize_splat.keys")
+    _chk_out(pixel_of_point, torch.int32, (P,), dev, "organize_splat.pixel_of_point")
+    _chk_out(stats, torch.int32, (n, 4), dev, "organize_splat.stats")
+    if n:
+        _call("cmdiad_organize_splat", _p(points), _p(offsets), _p(cams), n, P, max_len, kind, H, W, _p(keys), _p(pixel_of_point),
+              _p(stats), _stream())
+    return keys, pixel_of_point, stats
+
+
+def organize_resolve(points, offsets, keys, stats, fill=0, colors=None, labels=None, want_rgb=True, want_mask=True, out=None):
+    """The key map of organize_splat -> (index [n,H,W] i32, xyz [n,H,W,3] f32, rgb [n,H,W,3] u8 | None, mask [n,H,W] u8 | None); stats
+    columns 2, 3 = direct, filled pixels.  colors [P,3] u8 and labels [P] u8 are optional (absent: zeros); fill in 0..2.  out: that
+    quadruple, to write into (None in the place of an output that is not wanted).  No synchronisation."""
+    n, P, _ = _chk_point_list(points, offsets, None, 0, "organize_resolve")
+    _chk(keys, torch.int64, "organize_resolve.keys"); _chk(colors, torch.uint8, "organize_resolve.colors")
+    _chk(labels, torch.uint8, "organize_resolve.labels")
+    if keys is None or keys.dim() != 3 or keys.shape[0] != n:
+        raise ValueError(f"organize_resolve: keys must be [{n},H,W] int64")
+    H, W = _chk_grid(n, keys.shape[1], keys.shape[2], "organize_resolve")
+    fill = int(fill)
+    if fill not in (0, 1, 2):
+        raise ValueError(f"organize_resolve: fill = {fill} (0..2)")
+    dev = points.device
+    if colors is not None and (tuple(colors.shape) != (P, 3) or colors.device != dev):
+        raise ValueError(f"organize_resolve: colors must be [{P},3] uint8 on the points' device, got {tuple(colors.shape)}")
+    if labels is not None and (tuple(labels.shape) != (P,) or labels.device != dev):
+        raise ValueError(f"organize_resolve: labels must be [{P}] uint8 on the points' device, got {tuple(labels.shape)}")
+    if keys.device != dev:
+        raise ValueError("organize_resolve: keys must be on the points' device")
+    _chk_out(stats, torch.int32, (n, 4), dev, "organize_resolve.stats")
+    if out is None:
+        out = (torch.empty((n, H, W), dtype=torch.int32, device=dev), torch.empty((n, H, W, 3), dtype=torch.float32, device=dev),
+               torch.empty((n, H, W, 3), dtype=torch.uint8, device=dev) if want_rgb else None,
+               torch.empty((n, H, W), dtype=torch.uint8, device=dev) if want_mask else None)
+    index, xyz, rgb, mask = out
+    _chk_out(index, torch.int32, (n, H, W), dev, "organize_resolve.index")
+    _chk_out(xyz, torch.float32, (n, H, W, 3), dev, "organize_resolve.xyz")
+    if rgb is not None:
+        _chk_out(rgb, torch.uint8, (n, H, W, 3), dev, "organize_resolve.rgb")
+    if mask is not None:
+        _chk_out(mask, torch.uint8, (n, H, W), dev, "organize_resolve.mask")
+    if n:
+        _call("cmdiad_organize_resolve", _p(points), _p(offsets), _p(colors), _p(labels), _p(keys), n, P, H, W, fill, _p(index),
+              _p(xyz), _p(rgb), _p(mask), _p(stats), _stream())
+    return index, xyz, rgb, mask
+
+
 # ------------------------------------------------------------------------------------ content digest (stored fits)
 def digest64(tensor, seed=0, acc=None):
     """cmdiad_digest64 of a device tensor's bytes, ADDED into `acc` ([1] int64 on the tensor's device; None: a fresh zero) -> acc.

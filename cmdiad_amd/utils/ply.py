@@ -3,6 +3,9 @@ reader and a small fixed pool of writer threads.  Host only; numpy and the stand
 
 A file is the header below, then n_vert vertex records of 35 bytes (VERTEX), then n_face face records of 13 bytes (FACE: the list
 length, always 3, and three vertex indices) -- the bytes cmdiad_mesh_write leaves on the device, unchanged.
+
+`read_points` is the way in for anybody's files (docs/organize.md): the vertex element of an ascii or binary little-endian PLY as
+a dict of arrays, whatever scalar properties it has.
 """
 import os
 
@@ -121,6 +124,102 @@ def read(path):
     if n_face and (np.any(faces["n"] != 3) or faces["vertex_indices"].min() < 0 or faces["vertex_indices"].max() >= n_vert):
         raise PlyError(f"{path}: a face is not a triangle over the file's {n_vert} vertices")
     return verts, faces, comments
+
+
+# ------------------------------------------------------------------------------------------------ any file's points (docs/organize.md)
+_SCALARS = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+            "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+MAX_PROPERTIES = 256
+
+
+def _points_header(blob, path):
+    """(format, n_vert, [(name, numpy type code)], header length) of the vertex element of any PLY header"""
+    end = blob.find(b"end_header\n")
+    if not blob.startswith(b"ply\n") and not blob.startswith(b"ply\r\n") or end < 0:
+        raise PlyError(f"{path}: not a PLY file with a header of at most {MAX_HEADER} bytes")
+    try:
+        lines = [ln.strip() for ln in blob[:end].decode("ascii").split("\n")]
+    except UnicodeDecodeError:
+        raise PlyError(f"{path}: the header is not ASCII") from None
+    fmt, element, n_vert, props = None, None, None, []
+    for ln in lines[1:]:
+        tok = ln.split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            if len(tok) != 3 or tok[1] not in ("ascii", "binary_little_endian") or tok[2] != "1.0":
+                raise PlyError(f"{path}: format {' '.join(tok[1:])!r}: ascii 1.0 and binary_little_endian 1.0 are read (not big-endian)")
+            fmt = tok[1]
+        elif tok[0] == "element":
+            if len(tok) != 3 or not tok[2].isdigit() or len(tok[2]) > 12:
+                raise PlyError(f"{path}: bad header line {ln!r}")
+            if n_vert is not None:
+                break                                   # whatever follows the vertex element is not read
+            element = tok[1]
+            if element == "vertex":
+                n_vert = int(tok[2])
+        elif tok[0] == "property":
+            if len(tok) >= 2 and tok[1] == "list":
+                where = "inside the vertex element" if element == "vertex" else f"in element {element!r} in front of the vertices"
+                raise PlyError(f"{path}: a list property {where}: the vertices cannot be located without reading the payload")
+            if len(tok) != 3 or tok[1] not in _SCALARS:
+                raise PlyError(f"{path}: bad header line {ln!r}")
+            if element != "vertex":
+                raise PlyError(f"{path}: element {element!r} stands in front of the vertices: only files that start with them are read")
+            if tok[2] in [p[0] for p in props] or len(props) >= MAX_PROPERTIES:
+                raise PlyError(f"{path}: property {tok[2]!r} twice, or more than {MAX_PROPERTIES} properties")
+            props.append((tok[2], _SCALARS[tok[1]]))
+        else:
+            raise PlyError(f"{path}: bad header line {ln!r}")
+    if fmt is None or n_vert is None:
+        raise PlyError(f"{path}: the header has no format line or no vertex element")
+    return fmt, n_vert, props, end + len(b"end_header\n")
+
+
+def read_points(path):
+    """The `vertex` element of an ascii or binary_little_endian PLY file -> {property name: array [N]} in the file's types, except that
+    x, y and z (required, float or double) come back as float32: float64 coordinates are rounded.  red / green / blue and an integer
+    label are what dataset.PointCloudClass looks for; any further scalar property is returned as well.  Elements behind the vertices
+    (faces) are not read.  A list property in or in front of the vertices, any property in front of them, a big-endian file, a count
+    the file's size cannot hold and a file that ends early are PlyErrors, raised before the payload is interpreted."""
+    size = os.path.getsize(path)
+    with open(path, "rb") as f:
+        fmt, n, props, at = _points_header(f.read(min(size, MAX_HEADER)), path)
+        names = [p[0] for p in props]
+        for c in "xyz":
+            if c not in names or dict(props)[c] not in ("f4", "f8"):
+                raise PlyError(f"{path}: the vertex element needs float or double x, y and z, it has {names}")
+        if "label" in names and dict(props)["label"][0] not in "iu":
+            raise PlyError(f"{path}: label must be an integer property")
+        f.seek(at)
+        if fmt == "binary_little_endian":
+            rec = np.dtype([(nm, "<" + t) for nm, t in props])
+            if at + n * rec.itemsize > size:
+                raise PlyError(f"{path}: {n} vertices of {rec.itemsize} bytes behind a header of {at} bytes are more than the file's "
+                               f"{size} bytes")
+            data = np.frombuffer(f.read(n * rec.itemsize), dtype=rec)
+            if len(data) != n:
+                raise PlyError(f"{path}: the file ended inside the vertices")
+            cols = {nm: data[nm] for nm in names}
+        else:
+            if n * 2 * len(props) - 1 > size - at:      # a value and a separator each, at the least
+                raise PlyError(f"{path}: {n} vertices of {len(props)} values do not fit the file's {size - at} bytes behind the header")
+            rows = []
+            for _ in range(n):
+                tok = f.readline().split()
+                if len(tok) != len(props):
+                    raise PlyError(f"{path}: the file ended inside the vertices, or a vertex line has {len(tok)} values for "
+                                   f"{len(props)} properties")
+                rows.append(tok)
+            try:
+                cols = {nm: np.array([float(r[k]) if t[0] == "f" else int(r[k]) for r in rows]).astype(t) if n else np.zeros(0, t)
+                        for k, (nm, t) in enumerate(props)}
+            except (ValueError, OverflowError):
+                raise PlyError(f"{path}: a vertex line holds something that is not a number") from None
+    out = {nm: np.ascontiguousarray(cols[nm]) for nm in names}
+    for c in "xyz":
+        out[c] = out[c].astype(np.float32)
+    return out
 
 
 def write_many(paths, n_verts, vertex_rows, n_faces, face_rows, comments=None, writers=4):

@@ -999,6 +999,42 @@ int cmdiad_mesh_write(const float* cloud, long long pix_stride, long long ch_str
                       double max_edge2, int flip, const int32_t* chunks, int32_t* vidx, uint8_t* vertices, uint8_t* faces,
                       cmdiad_stream_t stream);
 
+/* ---- unordered point clouds into the pixel grid (docs/organize.md; an addition, the ABI stays 6) ----
+ * points [P,3] float32: the clouds of a batch back to back; offsets [n+1] int64 ON THE DEVICE, not trusted: cloud b is the points
+ * [lo_b, hi_b), lo_b = clamp(offsets[b], 0, P), hi_b = clamp(offsets[b+1], lo_b, P), and only its first max_len points are looked
+ * at (max_len sizes the launch: pass the longest cloud).  cams [n,16] f64: a row-major 3 x 4 transform T, then a, b, c, d.
+ *   c_k = ((T[k][0] x + T[k][1] y) + T[k][2] z) + T[k][3], k = 0, 1, 2, on the widened floats
+ *   kind 0 (orthographic, a b c d = x0 y0 sx sy): u = (c0 - x0) sx, v = (c1 - y0) sy
+ *   kind 1 (pinhole, a b c d = fx fy cx cy):      u = fx (c0 / c2) + cx, v = fy (c1 / c2) + cy, and c2 > 0 is required
+ *   uf = floor(u + 0.5), vf = floor(v + 0.5); inside iff 0 <= uf < W and 0 <= vf < H, compared as doubles (a NaN is outside), and
+ *   d32 = (float)c2 with -0.0 taken as +0.0 is finite.  Every step is one float64 operation, in this order.
+ * A point with a non-finite or a zero coordinate is dropped (the package's rule for an invalid pixel), any other point that is not
+ * inside is outside, the rest are placed: key = ord(d32) << 32 | (i - lo_b), ord the map under which unsigned order is float order
+ * (sign bit set: all bits inverted; else the sign bit set), and the pixel keeps the smallest key: the nearest d32, the lowest index
+ * among equal ones.
+ * cmdiad_cloud_bounds (three kernels): bounds [n,6] f64 = the minimum of c_0, c_1, c_2, then the maximum, over the cloud's valid (not
+ * dropped) points; count [n] int32 = their number.  A NaN c_k enters neither, a zero of either sign counts as +0.0, an empty cloud
+ * gives +inf, -inf and 0.  Between its kernels bounds holds 64-bit ordered keys: no other scratch.
+ * cmdiad_organize_splat (two kernels): keys [n,H,W] uint64 = all ones, then the minimum over the placed points; pixel_of_point [P]
+ * int32 = -2 dropped, -1 outside, vf W + uf placed, written for the points looked at only; stats [n,4] int32 columns 0 and 1 =
+ * dropped, outside (zeroed here; columns 2 and 3 are left alone).
+ * cmdiad_organize_resolve (two kernels): a pixel whose key is not all ones is a direct hit; any other takes, with fill = r in 1..2,
+ * the smallest key of the (2r+1)^2 window clipped to the image (direct hits only: fills do not cascade) and is then filled.  A key
+ * whose index is not below hi_b - lo_b is an empty pixel.  index [n,H,W] int32 = the winner's index in its cloud or -1; xyz [n,H,W,3]
+ * float32 = its three input floats, bit for bit, or zeros; rgb [n,H,W,3] uint8 (NULL: not wanted) = colors [P,3] uint8 of the winner
+ * (NULL: 0), or 0; mask [n,H,W] uint8 (NULL: not wanted) = 255 where labels [P] uint8 of the winner is not 0 (NULL: 0); stats
+ * columns 2 and 3 = direct, filled pixels (zeroed here; columns 0 and 1 are left alone).
+ * Integer atomics only (a 64-bit minimum, one 32-bit add per workgroup): the result does not depend on the run.  n in 0..65535 (0
+ * returns CMDIAD_OK without a launch), H W <= 2^24, n H W <= 2^30, P and max_len in 0..2^31-1.  No workspace, no allocation, no
+ * synchronisation, no scratch. */
+int cmdiad_cloud_bounds(const float* points, const int64_t* offsets, const double* cams, int n, int P, int max_len, double* bounds,
+                        int32_t* count, cmdiad_stream_t stream);
+int cmdiad_organize_splat(const float* points, const int64_t* offsets, const double* cams, int n, int P, int max_len, int kind, int H,
+                          int W, uint64_t* keys, int32_t* pixel_of_point, int32_t* stats, cmdiad_stream_t stream);
+int cmdiad_organize_resolve(const float* points, const int64_t* offsets, const uint8_t* colors, const uint8_t* labels,
+                            const uint64_t* keys, int n, int P, int H, int W, int fill, int32_t* index, float* xyz, uint8_t* rgb,
+                            uint8_t* mask, int32_t* stats, cmdiad_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Content digest (stored fits: cmdiad_amd/fitted.py, docs/fitted.md)
  * ------------------------------------------------------------------------------------------- */
