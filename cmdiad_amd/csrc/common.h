@@ -124,6 +124,34 @@ __device__ __forceinline__ unsigned long long pack_key(float v, unsigned idx)
     return ((unsigned long long)__float_as_uint(v) << 32) | idx;
 }
 
+// Order keys of ANY float: the unsigned order of the key is the order of the values, so integer atomicMin / atomicMax, sorts and
+// binary searches work on them.  f2ord / d2ord keep -0.0 below +0.0 (two keys); f64_key folds -0.0 into +0.0 (one key), which is
+// what a comparison of scores needs (docs/metrics.md).
+__device__ __forceinline__ uint32_t f2ord(float f)
+{
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ord2f(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
+__device__ __forceinline__ unsigned long long d2ord(double d)
+{
+    const unsigned long long u = (unsigned long long)__double_as_longlong(d);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double ord2d(unsigned long long u)
+{
+    return __longlong_as_double((long long)((u >> 63) ? (u & 0x7FFFFFFFFFFFFFFFull) : ~u));
+}
+
+constexpr unsigned long long kSign = 0x8000000000000000ull;
+__device__ __forceinline__ unsigned long long f64_key(double x)
+{
+    unsigned long long b = (unsigned long long)__double_as_longlong(x);
+    if (b == kSign) b = 0;
+    return (b & kSign) ? ~b : (b | kSign);
+}
+__device__ __forceinline__ double key_f64(unsigned long long k) { return __longlong_as_double((long long)((k & kSign) ? (k ^ kSign) : ~k)); }
+
 // max over the 16 lanes of a DPP row (lanes 16 r .. 16 r + 15), result in all 16: quad xor 1, quad xor 2, half-row mirror,
 // row mirror -- VALU only (four __shfl_xor steps are four ds_bpermute round trips through the LDS pipeline).
 __device__ __forceinline__ float row16_max(float v)

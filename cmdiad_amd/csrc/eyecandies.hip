@@ -13,11 +13,11 @@
 // square root beside 27 bytes of traffic per pixel, and it keeps the whole scan in ONE launch with nothing between the stages.
 // (The ISA of the three instantiations uses 36 / 16 / 26 VGPRs, no scratch and no LDS; the alternative -- a one-wave prologue writing
 // the anchors to a parameter block -- adds a launch per batch and a dependency between two kernels to save those operations.)
+#include "frames.h"
 #include "launch.h"
 
 namespace {
 
-constexpr int kMaxSide = 1 << 14;        // sides of a depth map, as in sample_prep.hip: H * W fits an int, B * H * W * 3 a size_t
 constexpr int kMinPixels = 513;          // both anchors (256 and n - 256) exist and are distinct
 constexpr int kMaxPoints = 1 << 28;      // points of a lone background cut (= kMaxSide squared)
 
@@ -82,8 +82,6 @@ __global__ __launch_bounds__(256) void eyecandies_kernel(const uint16_t* __restr
     }
 }
 
-inline bool side_ok(int v) { return v >= 1 && v <= kMaxSide; }
-inline dim3 pixel_grid(int pixels, int B) { return dim3((unsigned)((pixels + 255) / 256), (unsigned)B); }
 
 }  // namespace
 
@@ -91,7 +89,7 @@ extern "C" int cmdiad_eyecandies_cloud(const uint16_t* depth_u16, const cmdiad_e
                                        double* cloud_out, uint8_t* removed_out, float* depth_out, cmdiad_stream_t stream)
 {
     CMDIAD_REQUIRE(depth_u16 && params && cloud_out, CMDIAD_ERR_ARG, "cmdiad_eyecandies_cloud: null pointer");
-    CMDIAD_REQUIRE(B >= 1 && B <= 65535 && side_ok(H) && side_ok(W) && (long long)H * W >= kMinPixels, CMDIAD_ERR_ARG,
+    CMDIAD_REQUIRE(B >= 1 && B <= kMaxImages && side_ok(H) && side_ok(W) && (long long)H * W >= kMinPixels, CMDIAD_ERR_ARG,
                    "cmdiad_eyecandies_cloud: bad sizes B=%d (1..65535) H=%d W=%d (sides 1..%d, H*W >= %d: the anchors are pixels 256 "
                    "and H*W-256)", B, H, W, kMaxSide, kMinPixels);
     hipLaunchKernelGGL((eyecandies_kernel<true, true>), pixel_grid(H * W, B), dim3(256), 0, (hipStream_t)stream, depth_u16, params,
@@ -104,7 +102,7 @@ extern "C" int cmdiad_eyecandies_unproject(const uint16_t* depth_u16, const cmdi
                                            double* points_out, float* depth_out, cmdiad_stream_t stream)
 {
     CMDIAD_REQUIRE(depth_u16 && params && (points_out || depth_out), CMDIAD_ERR_ARG, "cmdiad_eyecandies_unproject: null pointer");
-    CMDIAD_REQUIRE(B >= 1 && B <= 65535 && side_ok(H) && side_ok(W), CMDIAD_ERR_ARG,
+    CMDIAD_REQUIRE(B >= 1 && B <= kMaxImages && side_ok(H) && side_ok(W), CMDIAD_ERR_ARG,
                    "cmdiad_eyecandies_unproject: bad sizes B=%d (1..65535) H=%d W=%d (sides 1..%d)", B, H, W, kMaxSide);
     hipLaunchKernelGGL((eyecandies_kernel<true, false>), pixel_grid(H * W, B), dim3(256), 0, (hipStream_t)stream, depth_u16, params,
                        (const double*)nullptr, H * W, W, points_out, (uint8_t*)nullptr, depth_out);

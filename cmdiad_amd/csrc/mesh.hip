@@ -17,14 +17,13 @@
 // not read).  Writes: vidx below H W; records below the image's counted vertices / faces, which never exceed its slot.
 #include "block_scan.h"
 #include "cloud.h"
+#include "frames.h"
 #include "launch.h"
 #include "overlay_color.h"
 
 namespace {
 
-constexpr int kMaxSide = 1 << 14;
-constexpr int kMaxImages = 65535;
-constexpr int kMaxTotal = 1 << 24;
+constexpr int kMeshMaxTotal = 1 << 24;   // n * H * W of one call: below the frames.h total, the record buffers are bytes
 constexpr int kChunk = 1024;          // pixels of a workgroup: 256 lanes x 4
 constexpr int kVertexBytes = 35;      // 6 floats, 3 bytes, 1 float, 1 int
 constexpr int kFaceBytes = 13;        // the list length (3) and three int32
@@ -90,16 +89,6 @@ __device__ __forceinline__ void tri_add(const Pt& a, const Pt& b, const Pt& c, d
 __device__ __forceinline__ void put32(uint8_t* d, uint32_t v)
 {
     d[0] = (uint8_t)v, d[1] = (uint8_t)(v >> 8), d[2] = (uint8_t)(v >> 16), d[3] = (uint8_t)(v >> 24);
-}
-
-// sum over the workgroup of an int (256 threads); one barrier, sh: 4 ints
-__device__ __forceinline__ int block_sum(int v, int* sh)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
 // column `which` of chunks [n,C,2] summed over the chunks in front of this workgroup's
@@ -306,9 +295,8 @@ __global__ __launch_bounds__(256) void mesh_face_kernel(MeshArgs A)
 
 bool geometry_ok(const char* who, int n, int H, int W, long long pix_stride, long long ch_stride, double max_edge2)
 {
-    const bool sides = H >= 1 && H <= kMaxSide && W >= 1 && W <= kMaxSide;
-    if (!(sides && n >= 0 && n <= kMaxImages && (long long)n * H * W <= kMaxTotal)) {
-        cmdiad_set_error("%s: bad sizes n=%d (0..%d) H=%d W=%d (sides 1..%d, n*H*W <= %d)", who, n, kMaxImages, H, W, kMaxSide, kMaxTotal);
+    if (!(side_ok(H) && side_ok(W) && n >= 0 && n <= kMaxImages && (long long)n * H * W <= kMeshMaxTotal)) {
+        cmdiad_set_error("%s: bad sizes n=%d (0..%d) H=%d W=%d (sides 1..%d, n*H*W <= %d)", who, n, kMaxImages, H, W, kMaxSide, kMeshMaxTotal);
         return false;
     }
     const long long HW = (long long)H * W;
@@ -345,8 +333,7 @@ extern "C" int cmdiad_mesh_count(const float* cloud, long long pix_stride, long 
     if (n == 0) return CMDIAD_OK;
     CMDIAD_REQUIRE(cloud && maps && chunks && counts, CMDIAD_ERR_ARG, "cmdiad_mesh_count: null pointer (cloud, maps, chunks, counts)");
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(counts, 0, (size_t)n * 4 * sizeof(int32_t), s);
-    CMDIAD_REQUIRE(e == hipSuccess, CMDIAD_ERR_LAUNCH, "cmdiad_mesh_count: hipMemsetAsync: %s", hipGetErrorString(e));
+    CMDIAD_CHECK_HIP("cmdiad_mesh_count", hipMemsetAsync(counts, 0, (size_t)n * 4 * sizeof(int32_t), s));
     const int C = (H * W + kChunk - 1) / kChunk;
     const Cloud c = {cloud, pix_stride, ch_stride};
     hipLaunchKernelGGL(mesh_count_kernel, dim3((unsigned)C, (unsigned)n), dim3(256), 0, s, c, maps, H, W, C, max_edge2, chunks, counts);

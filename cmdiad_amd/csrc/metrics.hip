@@ -23,56 +23,21 @@
 //   (integer order of the keys == order of the doubles), summed in the wave, one 64-bit integer atomic per wave.
 // cmdiad_pro_hist: hist[component][#thresholds strictly below the score], thresholds in LDS, integer atomics aggregated per wave.
 #include "block_scan.h"
+#include "frames.h"
 #include "launch.h"
 #include "union_find.h"
 
 namespace {
 
-constexpr int kMaxImagePixels = 1 << 24;   // per image: the union-find indices and the labels are ints
-constexpr int kMaxImages = 65535;          // grid.y
-constexpr int kMaxTotal = 1 << 30;         // n * H * W, and the length of any list: every count fits an int / a uint32
 constexpr int kCclTile = 2048;             // pixels per block of the root count / rank passes: 8 steps of 256
 constexpr int kSortTile = 4096;            // keys per block of a radix pass: 4 waves x 16 chunks of 64
 constexpr int kMaxThresholds = 1024;
-constexpr unsigned long long kSign = 0x8000000000000000ull;
 
-#define CMDIAD_CHECK_HIP(call)                                                                  \
-    do {                                                                                        \
-        hipError_t e_ = (call);                                                                 \
-        if (e_ != hipSuccess) {                                                                 \
-            cmdiad_set_error("%s:%d %s: %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); \
-            return CMDIAD_ERR_LAUNCH;                                                           \
-        }                                                                                       \
-    } while (0)
-
-__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ unsigned long long lanes_below() { return (1ull << lane_id()) - 1ull; }
 
-// float64 bits -> key whose unsigned order is the order of the doubles (-0.0 == +0.0 -> one key)
-__device__ __forceinline__ unsigned long long f64_key(double x)
-{
-    unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    if (b == kSign) b = 0;
-    return (b & kSign) ? ~b : (b | kSign);
-}
-__device__ __forceinline__ double key_f64(unsigned long long k) { return __longlong_as_double((long long)((k & kSign) ? (k ^ kSign) : ~k)); }
 __device__ __forceinline__ bool f64_nonfinite(double x)
 {
     return ((unsigned long long)__double_as_longlong(x) & 0x7FF0000000000000ull) == 0x7FF0000000000000ull;
-}
-
-// table[idx] += 1 for every active lane; lanes of the wave with the same idx share one atomic.  Every lane of the wave calls it.
-template <typename T>
-__device__ __forceinline__ void wave_agg_inc(T* table, long long idx, bool active)
-{
-    unsigned long long todo = __ballot(active);
-    while (todo) {   // wave-uniform
-        const int leader = __ffsll((long long)todo) - 1;
-        const long long lidx = __shfl(idx, leader, 64);
-        const unsigned long long same = __ballot(active && idx == lidx);
-        if (lane_id() == leader) atomicAdd(table + lidx, (T)__popcll(same));
-        todo &= ~same;
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- labelling
@@ -400,10 +365,6 @@ inline CclWs ccl_layout(void* base, int n, int HW)
     Carve c(base);
     return {tiles, c.take<int32_t>((size_t)n * HW, 256), c.take<int32_t>((size_t)n * tiles, 256), c.take<int32_t>((size_t)n * tiles, 256), c.total()};
 }
-inline bool ccl_sizes_ok(int n, int H, int W)
-{
-    return n >= 0 && n <= kMaxImages && H >= 1 && W >= 1 && (long long)H * W <= kMaxImagePixels && (long long)n * H * W <= kMaxTotal;
-}
 
 // the second copy of the keys | digit counts [256][nb] | the digit totals (not padded)
 struct SortWs { int nb; unsigned long long* alt; uint32_t* table; int32_t* totals; size_t total; };
@@ -420,19 +381,19 @@ inline unsigned blocks256(int n) { return (unsigned)((n + 255) / 256); }
 
 extern "C" size_t cmdiad_ccl_workspace_bytes(int n, int H, int W)
 {
-    return ccl_sizes_ok(n, H, W) && n > 0 ? ccl_layout(nullptr, n, H * W).total : 0;
+    return sizes_ok(n, H, W) && n > 0 ? ccl_layout(nullptr, n, H * W).total : 0;
 }
 
 extern "C" int cmdiad_ccl_label(const void* masks, int mask_is_u8, int n, int H, int W, int32_t* labels, int32_t* n_comp,
                                 int32_t* comp_offset, int32_t* comp_size, int comp_cap, int32_t* nonbinary, void* workspace,
                                 size_t workspace_bytes, cmdiad_stream_t stream)
 {
-    CMDIAD_REQUIRE(ccl_sizes_ok(n, H, W) && comp_cap >= 0 && (mask_is_u8 == 0 || mask_is_u8 == 1), CMDIAD_ERR_ARG,
+    CMDIAD_REQUIRE(sizes_ok(n, H, W) && comp_cap >= 0 && (mask_is_u8 == 0 || mask_is_u8 == 1), CMDIAD_ERR_ARG,
                    "cmdiad_ccl_label: bad sizes n=%d (0..%d) H=%d W=%d (>= 1, H*W <= %d, n*H*W <= %d) comp_cap=%d mask_is_u8=%d", n,
                    kMaxImages, H, W, kMaxImagePixels, kMaxTotal, comp_cap, mask_is_u8);
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) {
-        if (comp_offset) CMDIAD_CHECK_HIP(hipMemsetAsync(comp_offset, 0, sizeof(int32_t), s));
+        if (comp_offset) CMDIAD_CHECK_HIP("cmdiad_ccl_label", hipMemsetAsync(comp_offset, 0, sizeof(int32_t), s));
         return CMDIAD_OK;
     }
     CMDIAD_REQUIRE(masks && labels && n_comp && comp_offset && comp_size && workspace, CMDIAD_ERR_ARG, "cmdiad_ccl_label: null pointer");
@@ -444,8 +405,8 @@ extern "C" int cmdiad_ccl_label(const void* masks, int mask_is_u8, int n, int H,
     CMDIAD_REQUIRE(comp_cap >= most, CMDIAD_ERR_ARG, "cmdiad_ccl_label: comp_size holds %d components, %lld are possible (n ceil(H/2) ceil(W/2))",
                    comp_cap, most);
     const dim3 px(blocks256(HW), (unsigned)n), tl((unsigned)L.tiles, (unsigned)n);
-    CMDIAD_CHECK_HIP(hipMemsetAsync(comp_size, 0, (size_t)comp_cap * 4, s));
-    if (nonbinary) CMDIAD_CHECK_HIP(hipMemsetAsync(nonbinary, 0, sizeof(int32_t), s));
+    CMDIAD_CHECK_HIP("cmdiad_ccl_label", hipMemsetAsync(comp_size, 0, (size_t)comp_cap * 4, s));
+    if (nonbinary) CMDIAD_CHECK_HIP("cmdiad_ccl_label", hipMemsetAsync(nonbinary, 0, sizeof(int32_t), s));
     if (mask_is_u8) hipLaunchKernelGGL(ccl_init_kernel<uint8_t>, px, dim3(256), 0, s, (const uint8_t*)masks, HW, labels, nonbinary);
     else hipLaunchKernelGGL(ccl_init_kernel<float>, px, dim3(256), 0, s, (const float*)masks, HW, labels, nonbinary);
     CMDIAD_CHECK_LAUNCH();
@@ -468,7 +429,7 @@ extern "C" int cmdiad_ccl_label(const void* masks, int mask_is_u8, int n, int H,
 extern "C" int cmdiad_f64_to_keys(const double* x, int n, uint64_t* keys, int32_t* nonfinite, cmdiad_stream_t stream)
 {
     CMDIAD_REQUIRE(n >= 0 && n <= kMaxTotal, CMDIAD_ERR_ARG, "cmdiad_f64_to_keys: bad size n=%d (0..%d)", n, kMaxTotal);
-    if (nonfinite) CMDIAD_CHECK_HIP(hipMemsetAsync(nonfinite, 0, sizeof(int32_t), (hipStream_t)stream));
+    if (nonfinite) CMDIAD_CHECK_HIP("cmdiad_f64_to_keys", hipMemsetAsync(nonfinite, 0, sizeof(int32_t), (hipStream_t)stream));
     if (n == 0) return CMDIAD_OK;
     CMDIAD_REQUIRE(x && keys, CMDIAD_ERR_ARG, "cmdiad_f64_to_keys: null pointer");
     hipLaunchKernelGGL(f64_to_keys_kernel, dim3(blocks256(n)), dim3(256), 0, (hipStream_t)stream, x, n, (unsigned long long*)keys,
@@ -525,8 +486,8 @@ extern "C" int cmdiad_metrics_split(const double* preds, const int32_t* labels, 
                    "cmdiad_metrics_split: bad sizes n=%d (0..%d) HW=%d (0..%d, n*HW <= %d) ok_cap=%d def_cap=%d", n, kMaxImages, HW,
                    kMaxImagePixels, kMaxTotal, ok_cap, def_cap);
     hipStream_t s = (hipStream_t)stream;
-    if (counts) CMDIAD_CHECK_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(uint64_t), s));
-    if (nonfinite) CMDIAD_CHECK_HIP(hipMemsetAsync(nonfinite, 0, sizeof(int32_t), s));
+    if (counts) CMDIAD_CHECK_HIP("cmdiad_metrics_split", hipMemsetAsync(counts, 0, 2 * sizeof(uint64_t), s));
+    if (nonfinite) CMDIAD_CHECK_HIP("cmdiad_metrics_split", hipMemsetAsync(nonfinite, 0, sizeof(int32_t), s));
     if (n == 0 || HW == 0) return CMDIAD_OK;
     CMDIAD_REQUIRE(preds && labels && comp_offset && counts && (ok_keys || ok_cap == 0) && ((def_score && def_comp) || def_cap == 0),
                    CMDIAD_ERR_ARG, "cmdiad_metrics_split: null pointer");
@@ -541,7 +502,7 @@ extern "C" int cmdiad_auc_counts(const uint64_t* ok_sorted_keys, int n_ok, const
 {
     CMDIAD_REQUIRE(n_ok >= 0 && n_ok <= kMaxTotal && n_def >= 0 && n_def <= kMaxTotal, CMDIAD_ERR_ARG,
                    "cmdiad_auc_counts: bad sizes n_ok=%d n_def=%d (0..%d)", n_ok, n_def, kMaxTotal);
-    if (S) CMDIAD_CHECK_HIP(hipMemsetAsync(S, 0, sizeof(uint64_t), (hipStream_t)stream));
+    if (S) CMDIAD_CHECK_HIP("cmdiad_auc_counts", hipMemsetAsync(S, 0, sizeof(uint64_t), (hipStream_t)stream));
     if (n_def == 0 || n_ok == 0) return CMDIAD_OK;   // every count is 0
     CMDIAD_REQUIRE(ok_sorted_keys && def_score && S, CMDIAD_ERR_ARG, "cmdiad_auc_counts: null pointer");
     hipLaunchKernelGGL(auc_counts_kernel, dim3(blocks256(n_def)), dim3(256), 0, (hipStream_t)stream,

@@ -20,6 +20,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "common.h"
+#include "frames.h"
 
 #pragma clang fp contract(off)   // no fused multiply-adds: the x86-64 baseline build of scikit-learn has none
 
@@ -222,14 +223,13 @@ extern "C" int cmdiad_ocsvm_fit(const float* X, int n, int F, double nu, int max
     if (const int rc = workspace_ok("cmdiad_ocsvm_fit", workspace, workspace_bytes, L.total)) return rc;
     hipStream_t s = (hipStream_t)stream;
 
-#define OCSVM_HIP(call) do { if ((call) != hipSuccess) { cmdiad_set_error("cmdiad_ocsvm_fit: %s failed", #call); return CMDIAD_ERR_LAUNCH; } } while (0)
-    OCSVM_HIP(hipMemcpyAsync(L.pow2, pow2_host, 4096, hipMemcpyHostToDevice, s));
+    CMDIAD_CHECK_HIP("cmdiad_ocsvm_fit", hipMemcpyAsync(L.pow2, pow2_host, 4096, hipMemcpyHostToDevice, s));
     const unsigned sd = seed == 0 ? 1u : seed;   // our_rand_r: "seed shouldn't ever be 0"
     const int nb = (n + 255) / 256;
     hipLaunchKernelGGL(fy_targets_kernel, dim3((unsigned)(((long long)n + 64 * 256 - 1) / (64 * 256))), dim3(256), 0, s, L.pow2, sd, n, L.j);
     hipLaunchKernelGGL(fy_keys_kernel, dim3(nb), dim3(256), 0, s, L.j, n, L.keys);
     size_t sort_tmp_bytes = L.sort_tmp_bytes;
-    OCSVM_HIP(hipcub::DeviceRadixSort::SortKeys(L.sort_tmp, sort_tmp_bytes, L.keys, L.keys_sorted, n - 1, 0, 64, s));
+    CMDIAD_CHECK_HIP("cmdiad_ocsvm_fit", hipcub::DeviceRadixSort::SortKeys(L.sort_tmp, sort_tmp_bytes, L.keys, L.keys_sorted, n - 1, 0, 64, s));
     hipLaunchKernelGGL(fy_chase_kernel, dim3(nb), dim3(256), 0, s, L.j, L.keys_sorted, n, L.P);
     hipLaunchKernelGGL(iota_kernel, dim3(nb), dim3(256), 0, s, L.order_a, n);
 
@@ -243,7 +243,7 @@ extern "C" int cmdiad_ocsvm_fit(const float* X, int n, int F, double nu, int max
     h.intercept = 1.0;
     h.t = 1.0;
     h.wscale = 1.0;
-    OCSVM_HIP(hipMemcpyAsync(L.st, &h, sizeof(h), hipMemcpyHostToDevice, s));
+    CMDIAD_CHECK_HIP("cmdiad_ocsvm_fit", hipMemcpyAsync(L.st, &h, sizeof(h), hipMemcpyHostToDevice, s));
     double best_loss = INFINITY;
     int no_improve = 0, epoch = 0;
     int* oin = L.order_a;
@@ -260,8 +260,8 @@ extern "C" int cmdiad_ocsvm_fit(const float* X, int n, int F, double nu, int max
                  hipLaunchKernelGGL(ocsvm_epoch_kernel<4>, dim3(1), dim3(64), 0, s, L.xp, n, alpha, optimal_init, L.st); break;
         }
         int* tmp = oin; oin = oout; oout = tmp;
-        OCSVM_HIP(hipMemcpyAsync(&h, L.st, sizeof(h), hipMemcpyDeviceToHost, s));
-        OCSVM_HIP(hipStreamSynchronize(s));
+        CMDIAD_CHECK_HIP("cmdiad_ocsvm_fit", hipMemcpyAsync(&h, L.st, sizeof(h), hipMemcpyDeviceToHost, s));
+        CMDIAD_CHECK_HIP("cmdiad_ocsvm_fit", hipStreamSynchronize(s));
         bool finite = std::isfinite(h.intercept);
         for (int f = 0; f < F; ++f) finite = finite && std::isfinite(h.w[f]);
         if (!finite) {
@@ -273,7 +273,6 @@ extern "C" int cmdiad_ocsvm_fit(const float* X, int n, int F, double nu, int max
         if (h.sumloss < best_loss) best_loss = h.sumloss;
         if (no_improve >= n_iter_no_change) { ++epoch; break; }
     }
-#undef OCSVM_HIP
     for (int f = 0; f < F; ++f) coef_out[f] = h.w[f] * (float)h.wscale;   // w.reset_wscale(): sscal by (float)wscale
     *offset_out = 1.0 - h.intercept;
     *n_iter_out = epoch;

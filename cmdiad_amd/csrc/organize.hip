@@ -17,14 +17,13 @@
 // Reads: offsets[0..n], cams below 16 n, points / colors / labels of i in [lo_b, hi_b) only -- both ends clamped to [0, P], and a
 // key whose index does not lie in the cloud is an empty pixel.  Writes: pixel_of_point of those i; keys, index, xyz, rgb, mask below
 // n H W; stats [n,4]; nothing else.
+#include "block_scan.h"
 #include "cloud.h"
+#include "frames.h"
 #include "launch.h"
 
 namespace {
 
-constexpr int kMaxImages = 65535;
-constexpr long long kMaxPixels = 1ll << 24;       // H W
-constexpr long long kMaxTotal = 1ll << 30;        // n H W
 constexpr int kBoundsPts = 2048;                  // points of a workgroup of bounds_kernel: 256 lanes x 8
 constexpr unsigned long long kEmpty = ~0ull;
 
@@ -37,22 +36,6 @@ __device__ __forceinline__ Range cloud_range(const long long* __restrict__ offse
     lo = lo < 0 ? 0 : (lo > P ? P : lo);
     hi = hi < lo ? lo : (hi > P ? P : hi);
     return {lo, hi};
-}
-
-// the order-preserving maps of preprocess.hip, and the same on a double
-__device__ __forceinline__ uint32_t f2ord(float f)
-{
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ unsigned long long d2ord(double d)
-{
-    const unsigned long long u = (unsigned long long)__double_as_longlong(d);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double ord2d(unsigned long long u)
-{
-    return __longlong_as_double((long long)((u >> 63) ? (u & 0x7FFFFFFFFFFFFFFFull) : ~u));
 }
 
 struct Cam { double t[12], a, b, c, d; };
@@ -70,16 +53,6 @@ __device__ __forceinline__ Cam load_cam(const double* __restrict__ cams, int b)
 __device__ __forceinline__ double cam_coord(const Cam& m, int k, double x, double y, double z)
 {
     return ((m.t[4 * k] * x + m.t[4 * k + 1] * y) + m.t[4 * k + 2] * z) + m.t[4 * k + 3];
-}
-
-// sum over the workgroup of an int (256 threads); one barrier, sh: 4 ints
-__device__ __forceinline__ int block_sum(int v, int* sh)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- bounds
@@ -300,7 +273,7 @@ bool points_ok(const char* who, int n, int P, int max_len)
 
 bool grid_ok(const char* who, int n, int H, int W)
 {
-    if (!(H >= 1 && W >= 1 && (long long)H * W <= kMaxPixels && (long long)n * H * W <= kMaxTotal)) {
+    if (!sizes_ok(n, H, W)) {   // n itself has passed points_ok
         cmdiad_set_error("%s: bad grid H=%d W=%d for n=%d (sides >= 1, H*W <= 2^24, n*H*W <= 2^30)", who, H, W, n);
         return false;
     }

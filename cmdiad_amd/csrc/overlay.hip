@@ -11,14 +11,12 @@
 // clamped, into LDS.  The contour's four neighbours are sampled again from the map (L2), not staged.  Reads: a tap of weight 0 is
 // not read; every tap index is clamped to the map; the tables are read below min(count, K) only.  Writes: canvas pixels below
 // Ho * Wo of the image, and one atomic add per wave that met a NaN.
+#include "frames.h"
 #include "launch.h"
 #include "overlay_color.h"   // steps 2 and 3, shared with mesh.hip
 
 namespace {
 
-constexpr int kMaxSide = 1 << 14;
-constexpr int kMaxImages = 65535;
-constexpr int kMaxTotal = 1 << 30;
 constexpr int kMaxBoxes = 64;
 constexpr int kMaxLine = 8;
 
@@ -209,7 +207,7 @@ extern "C" int cmdiad_overlay_render(const double* maps, int n, int H, int W, in
                                      const int32_t* count, const int32_t* ints, int K, int line_px, uint32_t contour_rgb, uint32_t box_rgb,
                                      uint8_t* canvas, int32_t* nan_count, cmdiad_stream_t stream)
 {
-    const bool sides = H >= 1 && H <= kMaxSide && W >= 1 && W <= kMaxSide && Ho >= 1 && Ho <= kMaxSide && Wo >= 1 && Wo <= kMaxSide;
+    const bool sides = side_ok(H) && side_ok(W) && side_ok(Ho) && side_ok(Wo);
     CMDIAD_REQUIRE(sides && n >= 0 && n <= kMaxImages && (long long)n * H * W <= kMaxTotal && (long long)n * Ho * Wo <= kMaxTotal,
                    CMDIAD_ERR_ARG, "cmdiad_overlay_render: bad sizes n=%d (0..%d) H=%d W=%d Ho=%d Wo=%d (sides 1..%d, n*H*W and n*Ho*Wo <= %d)",
                    n, kMaxImages, H, W, Ho, Wo, kMaxSide, kMaxTotal);
@@ -220,10 +218,7 @@ extern "C" int cmdiad_overlay_render(const double* maps, int n, int H, int W, in
     CMDIAD_REQUIRE(K >= 1 && K <= kMaxBoxes && line_px >= 1 && line_px <= kMaxLine, CMDIAD_ERR_ARG,
                    "cmdiad_overlay_render: K=%d (1..%d) line_px=%d (1..%d)", K, kMaxBoxes, line_px, kMaxLine);
     hipStream_t s = (hipStream_t)stream;
-    if (nan_count) {
-        hipError_t e = hipMemsetAsync(nan_count, 0, sizeof(int32_t), s);
-        CMDIAD_REQUIRE(e == hipSuccess, CMDIAD_ERR_LAUNCH, "cmdiad_overlay_render: hipMemsetAsync: %s", hipGetErrorString(e));
-    }
+    if (nan_count) CMDIAD_CHECK_HIP("cmdiad_overlay_render", hipMemsetAsync(nan_count, 0, sizeof(int32_t), s));
     if (n == 0) return CMDIAD_OK;
     CMDIAD_REQUIRE(maps && lohi && lut && alpha && canvas && (bg_kind == kBgNone || bg) && (count == nullptr) == (ints == nullptr),
                    CMDIAD_ERR_ARG, "cmdiad_overlay_render: null pointer (maps, lohi, lut, alpha, canvas; bg with a background kind; count and "

@@ -25,11 +25,11 @@
 // (utils.png.read_raw refuses such a file).  Writes go to pixels of the image only.
 //
 // The encoder's direction, cmdiad_png_filter, is at the end of the file: filtering has none of these dependencies.
+#include "frames.h"
 #include "launch.h"
 
 namespace {
 
-constexpr int kMaxSide = 1 << 14;
 constexpr int kRing = 256;            // pixels of a wave's ring when NW > 1
 constexpr int kGroup = 4;             // steps whose source bytes are loaded ahead together
 
@@ -183,7 +183,7 @@ extern "C" int cmdiad_png_unfilter(const uint8_t* raw, int64_t raw_bytes, const 
                                    int waves, uint8_t* out, cmdiad_stream_t stream)
 {
     CMDIAD_REQUIRE(raw && offsets && out, CMDIAD_ERR_ARG, "cmdiad_png_unfilter: null pointer");
-    CMDIAD_REQUIRE(B >= 1 && B <= 65535 && W >= 1 && W <= kMaxSide && H >= 1 && H <= kMaxSide && bpp >= 1 && bpp <= 4, CMDIAD_ERR_ARG,
+    CMDIAD_REQUIRE(B >= 1 && B <= kMaxImages && side_ok(W) && side_ok(H) && bpp >= 1 && bpp <= 4, CMDIAD_ERR_ARG,
                    "cmdiad_png_unfilter: bad sizes B=%d (1..65535) W=%d H=%d (sides 1..%d) bpp=%d (1..4)", B, W, H, kMaxSide, bpp);
     CMDIAD_REQUIRE(target == kTargetRgb || target == kTargetL || target == kTargetRaw, CMDIAD_ERR_ARG,
                    "cmdiad_png_unfilter: target=%d (0 rgb | 1 l | 2 raw)", target);
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(256) void png_filter_kernel(const uint8_t* __restri
 
 extern "C" int cmdiad_png_filter(const uint8_t* images, int n, int H, int W, int C, int mode, uint8_t* scanlines, cmdiad_stream_t stream)
 {
-    CMDIAD_REQUIRE(n >= 0 && n <= 65535 && W >= 1 && W <= kMaxSide && H >= 1 && H <= kMaxSide && C >= 1 && C <= 4, CMDIAD_ERR_ARG,
+    CMDIAD_REQUIRE(n >= 0 && n <= kMaxImages && side_ok(W) && side_ok(H) && C >= 1 && C <= 4, CMDIAD_ERR_ARG,
                    "cmdiad_png_filter: bad sizes n=%d (0..65535) W=%d H=%d (sides 1..%d) C=%d (1..4)", n, W, H, kMaxSide, C);
     CMDIAD_REQUIRE(mode >= 0 && mode <= 5, CMDIAD_ERR_ARG, "cmdiad_png_filter: mode=%d (0..4 force a filter type, 5 = adaptive)", mode);
     if (n == 0) return CMDIAD_OK;

@@ -16,31 +16,14 @@
 //   the capacity of the table it indexes.
 // cmdiad_detection_counts: one workgroup per image folds the two tables into n_gt, n_detected, n_pred, n_false.
 #include "block_scan.h"
+#include "frames.h"
 #include "launch.h"
 
 namespace {
 
-constexpr int kMaxImagePixels = 1 << 24;
-constexpr int kMaxImages = 65535;
-constexpr int kMaxTotal = 1 << 30;          // list lengths, capacities, n * H * W: every count fits an int
 constexpr int kPrTile = 2048;               // keys per block of the head count / compaction passes: 8 steps of 256
 constexpr int kF1Block = 256;               // runs per block-step of the first reduction stage
 constexpr int kF1MaxBlocks = 1024;          // blocks of the first stage at most: the second stage is one block
-
-__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
-
-// table[idx] += 1 for every active lane; lanes of the wave with the same idx share one atomic.  Every lane of the wave calls it.
-__device__ __forceinline__ void wave_agg_inc(int32_t* table, int idx, bool active)
-{
-    unsigned long long todo = __ballot(active);
-    while (todo) {   // wave-uniform
-        const int leader = __ffsll((long long)todo) - 1;
-        const int lidx = __shfl(idx, leader, 64);
-        const unsigned long long same = __ballot(active && idx == lidx);
-        if (lane_id() == leader) atomicAdd(table + lidx, (int32_t)__popcll(same));
-        todo &= ~same;
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------------- run table
 __device__ __forceinline__ bool run_head(const unsigned long long* __restrict__ keys, int i, int n)
@@ -243,17 +226,7 @@ inline int f1_blocks(int run_cap)
     return want < kF1MaxBlocks ? want : kF1MaxBlocks;
 }
 
-inline bool sizes_ok(int n, int H, int W)
-{
-    return n >= 0 && n <= kMaxImages && H >= 1 && W >= 1 && (long long)H * W <= kMaxImagePixels && (long long)n * H * W <= kMaxTotal;
-}
-inline bool cap_ok(int cap) { return cap >= 0 && cap <= kMaxTotal; }
-
-#define PR_CHECK_HIP(who, call)                                                              \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        CMDIAD_REQUIRE(e_ == hipSuccess, CMDIAD_ERR_LAUNCH, who ": " #call ": %s", hipGetErrorString(e_)); \
-    } while (0)
+inline bool cap_ok(int cap) { return cap >= 0 && cap <= kMaxTotal; }   // list lengths and capacities: every count fits an int
 
 }  // namespace
 
@@ -270,7 +243,7 @@ extern "C" int cmdiad_pr_runs(const uint64_t* def_sorted_keys, int n_def, const 
                    CMDIAD_ERR_ARG, "cmdiad_pr_runs: null pointer");
     hipStream_t s = (hipStream_t)stream;
     if (n_def == 0) {
-        if (n_runs) PR_CHECK_HIP("cmdiad_pr_runs", hipMemsetAsync(n_runs, 0, sizeof(int32_t), s));
+        if (n_runs) CMDIAD_CHECK_HIP("cmdiad_pr_runs", hipMemsetAsync(n_runs, 0, sizeof(int32_t), s));
         return CMDIAD_OK;
     }
     const int tiles = pr_tiles(n_def);
@@ -318,8 +291,8 @@ extern "C" int cmdiad_region_overlap(const int32_t* gt_labels, const int32_t* gt
     CMDIAD_REQUIRE(gt_labels && gt_comp_offset && pred_labels && pred_comp_offset && (covered || gt_comp_cap == 0) &&
                        ((pred_comp_size && hits) || pred_comp_cap == 0), CMDIAD_ERR_ARG, "cmdiad_region_overlap: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    if (gt_comp_cap) PR_CHECK_HIP("cmdiad_region_overlap", hipMemsetAsync(covered, 0, (size_t)gt_comp_cap * 4, s));
-    if (pred_comp_cap) PR_CHECK_HIP("cmdiad_region_overlap", hipMemsetAsync(hits, 0, (size_t)pred_comp_cap * 4, s));
+    if (gt_comp_cap) CMDIAD_CHECK_HIP("cmdiad_region_overlap", hipMemsetAsync(covered, 0, (size_t)gt_comp_cap * 4, s));
+    if (pred_comp_cap) CMDIAD_CHECK_HIP("cmdiad_region_overlap", hipMemsetAsync(hits, 0, (size_t)pred_comp_cap * 4, s));
     if (gt_comp_cap == 0 || pred_comp_cap == 0) return CMDIAD_OK;   // no component on one side: nothing overlaps
     const int HW = H * W;
     hipLaunchKernelGGL(region_overlap_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)n), dim3(256), 0, s, gt_labels, gt_comp_offset,

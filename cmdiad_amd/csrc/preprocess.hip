@@ -28,6 +28,7 @@
 
 #include "common.h"
 #include "block_scan.h"
+#include "frames.h"
 #include "union_find.h"
 
 namespace {
@@ -253,14 +254,6 @@ inline DbscanWs dbscan_layout(void* base, int N)
             c.take<int>(n, 256), c.take<SortedPoint>(n, 256), c.take<int>(n, 256), c.take<int>(n, 256), c.take<int>(n, 256),
             c.take<int>(n, 256), c.take<int>(n + 1, 256), c.total()};
 }
-
-// order-preserving map float -> uint32 (for atomicMin / atomicMax on coordinates)
-__device__ __forceinline__ uint32_t f2ord(float f)
-{
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
 
 __global__ __launch_bounds__(256) void dbscan_bbox_kernel(const float* __restrict__ pts, int N, uint32_t* __restrict__ bbox)
 {
@@ -585,15 +578,6 @@ __global__ __launch_bounds__(256) void cluster_keep_kernel(const int32_t* __rest
     for (int k = 0; k < rgb_bytes; ++k) rgb[(size_t)at * (size_t)rgb_bytes + k] = 0;
 }
 
-#define CMDIAD_CHECK_HIP(call)                                                                  \
-    do {                                                                                        \
-        hipError_t e_ = (call);                                                                 \
-        if (e_ != hipSuccess) {                                                                 \
-            cmdiad_set_error("%s:%d %s: %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); \
-            return CMDIAD_ERR_LAUNCH;                                                           \
-        }                                                                                       \
-    } while (0)
-
 }  // namespace
 
 // the winning hypothesis' key (in 256 bytes of its own) | a plane per hypothesis
@@ -617,7 +601,7 @@ extern "C" int cmdiad_plane_ransac(const float* points, int E, int n, int iterat
     const RansacWs L = ransac_layout(workspace, iterations);
     if (const int rc = workspace_ok("cmdiad_plane_ransac", workspace, workspace_bytes, L.total)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    CMDIAD_CHECK_HIP(hipMemsetAsync(L.best, 0, sizeof(unsigned long long), s));
+    CMDIAD_CHECK_HIP("cmdiad_plane_ransac", hipMemsetAsync(L.best, 0, sizeof(unsigned long long), s));
     hipLaunchKernelGGL(plane_hypothesis_kernel, dim3(iterations), dim3(kPlaneThreads), 0, s, points, E, n, seed, distance_threshold,
                        L.planes, L.best);
     CMDIAD_CHECK_LAUNCH();
@@ -652,16 +636,16 @@ extern "C" int cmdiad_dbscan(const float* points, int N, double eps, int min_poi
     if (const int rc = workspace_ok("cmdiad_dbscan", workspace, workspace_bytes, L.total)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (N == 0) {
-        CMDIAD_CHECK_HIP(hipMemsetAsync(n_clusters, 0, sizeof(int32_t), s));
+        CMDIAD_CHECK_HIP("cmdiad_dbscan", hipMemsetAsync(n_clusters, 0, sizeof(int32_t), s));
         return CMDIAD_OK;
     }
     const double eps2 = eps * eps;
     const unsigned blocks = (unsigned)((N + 255) / 256);
-    CMDIAD_CHECK_HIP(hipMemsetAsync(L.bbox, 0xFF, 3 * sizeof(uint32_t), s));
-    CMDIAD_CHECK_HIP(hipMemsetAsync(L.bbox + 3, 0, 3 * sizeof(uint32_t), s));
-    CMDIAD_CHECK_HIP(hipMemsetAsync(L.count, 0, (size_t)L.maxc * 4, s));
-    CMDIAD_CHECK_HIP(hipMemsetAsync(L.minorig, 0x7F, (size_t)N * 4, s));
-    CMDIAD_CHECK_HIP(hipMemsetAsync(L.rank, 0, ((size_t)N + 1) * 4, s));
+    CMDIAD_CHECK_HIP("cmdiad_dbscan", hipMemsetAsync(L.bbox, 0xFF, 3 * sizeof(uint32_t), s));
+    CMDIAD_CHECK_HIP("cmdiad_dbscan", hipMemsetAsync(L.bbox + 3, 0, 3 * sizeof(uint32_t), s));
+    CMDIAD_CHECK_HIP("cmdiad_dbscan", hipMemsetAsync(L.count, 0, (size_t)L.maxc * 4, s));
+    CMDIAD_CHECK_HIP("cmdiad_dbscan", hipMemsetAsync(L.minorig, 0x7F, (size_t)N * 4, s));
+    CMDIAD_CHECK_HIP("cmdiad_dbscan", hipMemsetAsync(L.rank, 0, ((size_t)N + 1) * 4, s));
     hipLaunchKernelGGL(dbscan_bbox_kernel, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, s, points, N, L.bbox);
     CMDIAD_CHECK_LAUNCH();
     hipLaunchKernelGGL(dbscan_grid_kernel, dim3(1), dim3(64), 0, s, (const uint32_t*)L.bbox, eps, L.maxc, L.gp);
@@ -697,7 +681,7 @@ extern "C" int cmdiad_label_histogram(const int32_t* labels, int N, int32_t* his
 {
     CMDIAD_REQUIRE(labels && hist, CMDIAD_ERR_ARG, "cmdiad_label_histogram: null pointer");
     CMDIAD_REQUIRE(N >= 0 && bins >= 1, CMDIAD_ERR_ARG, "cmdiad_label_histogram: bad sizes N=%d bins=%d", N, bins);
-    CMDIAD_CHECK_HIP(hipMemsetAsync(hist, 0, (size_t)bins * 4, (hipStream_t)stream));
+    CMDIAD_CHECK_HIP("cmdiad_label_histogram", hipMemsetAsync(hist, 0, (size_t)bins * 4, (hipStream_t)stream));
     if (N == 0) return CMDIAD_OK;
     hipLaunchKernelGGL(label_histogram_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, labels, N, hist, bins);
     CMDIAD_CHECK_LAUNCH();
@@ -705,8 +689,6 @@ extern "C" int cmdiad_label_histogram(const int32_t* labels, int N, int32_t* his
 }
 
 // ---- compaction: workspace = the block counts and their scan
-constexpr int kMaxSide = 16384;
-
 struct CompactWs { int* block_count; size_t total; };   // one count per block of 256 elements, and the total
 static CompactWs compact_layout(void* base, int H, int W, int edges)
 {
@@ -715,14 +697,14 @@ static CompactWs compact_layout(void* base, int H, int W, int edges)
 }
 static size_t compact_workspace(int H, int W, int edges)
 {
-    return H < 1 || W < 1 || H > kMaxSide || W > kMaxSide ? 0 : compact_layout(nullptr, H, W, edges).total;
+    return !side_ok(H) || !side_ok(W) ? 0 : compact_layout(nullptr, H, W, edges).total;
 }
 
 static int compact_launch(const char* name, const float* pc, size_t pitch, int H, int W, int edges, float* points, int32_t* index, int cap,
                           int32_t* count, void* workspace, size_t workspace_bytes, hipStream_t s)
 {
     CMDIAD_REQUIRE(pc && points && count && workspace, CMDIAD_ERR_ARG, "%s: null pointer", name);
-    CMDIAD_REQUIRE(H >= 1 && W >= 1 && H <= kMaxSide && W <= kMaxSide && (long long)H * W <= (1ll << 26) && pitch >= (size_t)W * 3 &&
+    CMDIAD_REQUIRE(side_ok(H) && side_ok(W) && (long long)H * W <= (1ll << 26) && pitch >= (size_t)W * 3 &&
                        pitch <= ((size_t)1 << 24) && cap >= 0,
                    CMDIAD_ERR_ARG, "%s: bad sizes H=%d W=%d (1..%d, H*W <= 2^26) pitch=%zu (>= 3 W floats) cap=%d", name, H, W, kMaxSide,
                    pitch, cap);

@@ -18,26 +18,14 @@
 //   moments about the minimum corner, the area of the triangle mesh -- by one workgroup per (slot, image) in score_sum's order.
 #include <limits.h>
 
+#include "block_scan.h"
 #include "cloud.h"
+#include "frames.h"
 #include "launch.h"
 
 namespace {
 
-constexpr int kMaxImagePixels = 1 << 24;
-constexpr int kMaxImages = 65535;
-constexpr int kMaxTotal = 1 << 30;
 constexpr int kMaxRegions = 64;
-constexpr unsigned long long kSign = 0x8000000000000000ull;
-
-__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
-
-// float64 bits -> key whose unsigned order is the order of the doubles (-0.0 == +0.0 -> one key); metrics.hip's transform
-__device__ __forceinline__ unsigned long long f64_key(double x)
-{
-    unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    if (b == kSign) b = 0;
-    return (b & kSign) ? ~b : (b | kSign);
-}
 
 // per global component id, each of `cap` entries
 struct RegionTables {
@@ -62,12 +50,7 @@ inline RegionWs region_layout(void* base, long long cap)
             c.total()};
 }
 
-inline bool sizes_ok(int n, int H, int W)
-{
-    return n >= 0 && n <= kMaxImages && H >= 1 && W >= 1 && (long long)H * W <= kMaxImagePixels && (long long)n * H * W <= kMaxTotal;
-}
 inline long long most_components(int n, int H, int W) { return (long long)n * ((H + 1) / 2) * ((W + 1) / 2); }
-inline unsigned blocks512(int n) { return (unsigned)((n + 511) / 512); }
 
 // ---------------------------------------------------------------------------------------------------------------- threshold
 // grid (ceil(HW / 512), n): a lane takes pixels 2t and 2t + 1 of its image.  kVec: HW is even and both buffers are aligned, so the
@@ -470,10 +453,7 @@ extern "C" int cmdiad_threshold_mask(const double* maps, const double* thr, int 
                    H, W, kMaxImagePixels, kMaxTotal, thr_per_image);
     hipStream_t s = (hipStream_t)stream;
     CMDIAD_REQUIRE(n == 0 || (maps && thr && mask), CMDIAD_ERR_ARG, "cmdiad_threshold_mask: null pointer");
-    if (nan_count) {
-        hipError_t e = hipMemsetAsync(nan_count, 0, sizeof(int32_t), s);
-        CMDIAD_REQUIRE(e == hipSuccess, CMDIAD_ERR_LAUNCH, "cmdiad_threshold_mask: hipMemsetAsync: %s", hipGetErrorString(e));
-    }
+    if (nan_count) CMDIAD_CHECK_HIP("cmdiad_threshold_mask", hipMemsetAsync(nan_count, 0, sizeof(int32_t), s));
     if (n == 0) return CMDIAD_OK;
     const int HW = H * W;
     const bool vec = HW % 2 == 0 && ((uintptr_t)maps & 15) == 0 && ((uintptr_t)mask & 1) == 0;
@@ -539,10 +519,7 @@ extern "C" int cmdiad_region_measure(const int32_t* labels, const int32_t* count
     CMDIAD_REQUIRE(n == 0 || (labels && count && ints && cloud && m_ints && m_vals), CMDIAD_ERR_ARG,
                    "cmdiad_region_measure: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    if (bad_count) {
-        hipError_t e = hipMemsetAsync(bad_count, 0, sizeof(int32_t), s);
-        CMDIAD_REQUIRE(e == hipSuccess, CMDIAD_ERR_LAUNCH, "cmdiad_region_measure: hipMemsetAsync: %s", hipGetErrorString(e));
-    }
+    if (bad_count) CMDIAD_CHECK_HIP("cmdiad_region_measure", hipMemsetAsync(bad_count, 0, sizeof(int32_t), s));
     if (n == 0) return CMDIAD_OK;
     const Cloud c = {cloud, pix_stride, ch_stride};
     if (bad_count) {

@@ -15,12 +15,12 @@
 //   z channel three times [B,3,ds,ds], and the number of resized pixels with three non-zero coordinates (wave ballot + one vector
 //   atomic per wave).
 // cmdiad_gt_mask_prep: Pillow NEAREST through host tables, then (v / 255 > 0.5) == (v >= 128) -> 1.0 / 0.0.
+#include "frames.h"
 #include "launch.h"
 
 namespace {
 
 constexpr int kPrecisionBits = 22;   // Pillow's PRECISION_BITS for 8-bit channels (32 - 8 - 2)
-constexpr int kMaxSide = 1 << 14;    // sides of an image: far above any scan, and B * H * W * 3 still fits the index arithmetic below
 
 __device__ __forceinline__ uint8_t clip8(int acc)
 {
@@ -125,9 +125,6 @@ __global__ __launch_bounds__(256) void gt_mask_kernel(const uint8_t* __restrict_
     out[(size_t)b * S * S + i] = v >= 128 ? 1.0f : 0.0f;   // float32 v / 255 > 0.5 exactly for v >= 128
 }
 
-inline bool side_ok(int v) { return v >= 1 && v <= kMaxSide; }
-inline dim3 pixel_grid(int pixels, int B) { return dim3((unsigned)((pixels + 255) / 256), (unsigned)B); }
-
 }  // namespace
 
 extern "C" int cmdiad_resize_bicubic_u8(const uint8_t* src, int B, int H, int W, int out_h, int out_w, const int32_t* hcoef,
@@ -136,7 +133,7 @@ extern "C" int cmdiad_resize_bicubic_u8(const uint8_t* src, int B, int H, int W,
 {
     const bool horiz = W != out_w, vert = H != out_h;
     CMDIAD_REQUIRE(src && (out_u8 || out_f32) && (norm || !out_f32), CMDIAD_ERR_ARG, "cmdiad_resize_bicubic_u8: null pointer");
-    CMDIAD_REQUIRE(B >= 1 && B <= 65535 && side_ok(H) && side_ok(W) && side_ok(out_h) && side_ok(out_w), CMDIAD_ERR_ARG,
+    CMDIAD_REQUIRE(B >= 1 && B <= kMaxImages && side_ok(H) && side_ok(W) && side_ok(out_h) && side_ok(out_w), CMDIAD_ERR_ARG,
                    "cmdiad_resize_bicubic_u8: bad sizes B=%d (1..65535) %dx%d -> %dx%d (sides 1..%d)", B, H, W, out_h, out_w, kMaxSide);
     CMDIAD_REQUIRE((!horiz || (hcoef && hbounds)) && (!vert || (vcoef && vbounds)) && (!(horiz && vert) || tmp), CMDIAD_ERR_ARG,
                    "cmdiad_resize_bicubic_u8: null pointer (the tables of a pass that changes a side, tmp when both do)");
@@ -172,14 +169,11 @@ int organized_pc_prep(const char* who, const T* pc, int B, int H, int W, const i
 {
     CMDIAD_REQUIRE(pc && xyz_rows && xyz_cols && cloud_out && count_out && (!depth_out || (depth_rows && depth_cols)), CMDIAD_ERR_ARG,
                    "%s: null pointer", who);
-    CMDIAD_REQUIRE(B >= 1 && B <= 65535 && side_ok(H) && side_ok(W) && side_ok(xyz_size) && (!depth_out || side_ok(depth_size)),
+    CMDIAD_REQUIRE(B >= 1 && B <= kMaxImages && side_ok(H) && side_ok(W) && side_ok(xyz_size) && (!depth_out || side_ok(depth_size)),
                    CMDIAD_ERR_ARG, "%s: bad sizes B=%d (1..65535) H=%d W=%d xyz_size=%d depth_size=%d (1..%d)", who, B, H, W, xyz_size,
                    depth_size, kMaxSide);
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(count_out, 0, (size_t)B * sizeof(int32_t), s) != hipSuccess) {
-        cmdiad_set_error("%s: hipMemsetAsync failed", who);
-        return CMDIAD_ERR_LAUNCH;
-    }
+    CMDIAD_CHECK_HIP(who, hipMemsetAsync(count_out, 0, (size_t)B * sizeof(int32_t), s));
     hipLaunchKernelGGL(cloud_resize_kernel<T>, pixel_grid(xyz_size * xyz_size, B), dim3(256), 0, s, pc, H, W, xyz_rows, xyz_cols,
                        xyz_size, cloud_out, count_out);
     CMDIAD_CHECK_LAUNCH();
@@ -213,7 +207,7 @@ extern "C" int cmdiad_gt_mask_prep(const uint8_t* gt, int B, int H, int W, const
                                    float* out, cmdiad_stream_t stream)
 {
     CMDIAD_REQUIRE(gt && rows && cols && out, CMDIAD_ERR_ARG, "cmdiad_gt_mask_prep: null pointer");
-    CMDIAD_REQUIRE(B >= 1 && B <= 65535 && side_ok(H) && side_ok(W) && side_ok(gt_size), CMDIAD_ERR_ARG,
+    CMDIAD_REQUIRE(B >= 1 && B <= kMaxImages && side_ok(H) && side_ok(W) && side_ok(gt_size), CMDIAD_ERR_ARG,
                    "cmdiad_gt_mask_prep: bad sizes B=%d (1..65535) H=%d W=%d gt_size=%d (1..%d)", B, H, W, gt_size, kMaxSide);
     hipLaunchKernelGGL(gt_mask_kernel, pixel_grid(gt_size * gt_size, B), dim3(256), 0, (hipStream_t)stream, gt, H, W, rows, cols,
                        gt_size, out);

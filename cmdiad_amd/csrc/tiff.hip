@@ -16,11 +16,11 @@
 //   of Cc bytes, so a byte's class is its position in the segment), one block scan of the 256 segment totals with the Cc classes packed
 //   in the four bytes of a dword (byte-wise add without carries between the lanes), and a second walk that applies the running sums
 //   in place; then byte k of sample i is gathered from plane k (plane 0 = most significant) and the sample is stored.
+#include "frames.h"
 #include "launch.h"
 
 namespace {
 
-constexpr int kMaxSide = 1 << 14;
 constexpr int kThreads = 256;
 constexpr int kMaxRowBytes = 64 * 1024;
 
@@ -151,7 +151,6 @@ __global__ __launch_bounds__(kThreads) void tiff_fp_predictor_kernel(const uint3
     }
 }
 
-inline bool side_ok(int v) { return v >= 1 && v <= kMaxSide; }
 
 }  // namespace
 
@@ -160,7 +159,7 @@ extern "C" int cmdiad_tiff_unpack(const uint8_t* raw, int64_t raw_bytes, const i
                                   void* out, cmdiad_stream_t stream)
 {
     CMDIAD_REQUIRE(raw && chunk_off && out, CMDIAD_ERR_ARG, "cmdiad_tiff_unpack: null pointer");
-    CMDIAD_REQUIRE(B >= 1 && B <= 65535 && side_ok(W) && side_ok(H) && side_ok(chunk_w) && side_ok(chunk_h) && C >= 1 && C <= 4,
+    CMDIAD_REQUIRE(B >= 1 && B <= kMaxImages && side_ok(W) && side_ok(H) && side_ok(chunk_w) && side_ok(chunk_h) && C >= 1 && C <= 4,
                    CMDIAD_ERR_ARG, "cmdiad_tiff_unpack: bad sizes B=%d (1..65535) W=%d H=%d chunk_w=%d chunk_h=%d (sides 1..%d) C=%d (1..4)",
                    B, W, H, chunk_w, chunk_h, kMaxSide, C);
     CMDIAD_REQUIRE((bytes_per_sample == 4 || bytes_per_sample == 8) && (planar == 0 || planar == 1) && (big_endian == 0 || big_endian == 1) &&

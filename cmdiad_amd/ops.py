@@ -995,6 +995,85 @@ def transpose_bf16(x):
     return out
 
 
+# ------------------------------------------------------------------------------------ frames: the limits and checks of the map ops
+# csrc/frames.h's limits of a batch of n frames of H x W (tests/test_frame_limits_cpu.py holds the two together), and mesh.hip's total
+FRAME_MAX_IMAGES, FRAME_MAX_PIXELS, FRAME_MAX_TOTAL, FRAME_MAX_SIDE = 65535, 1 << 24, 1 << 30, 1 << 14
+MESH_MAX_TOTAL = 1 << 24
+METRICS_MAX_TOTAL = ORGANIZE_MAX_TOTAL = FRAME_MAX_TOTAL
+ORGANIZE_MAX_IMAGES, ORGANIZE_MAX_PIXELS, OVERLAY_MAX_SIDE = FRAME_MAX_IMAGES, FRAME_MAX_PIXELS, FRAME_MAX_SIDE
+
+
+def _frames(shape, who, side=None, pixels=FRAME_MAX_PIXELS, total=FRAME_MAX_TOTAL, least=1, msg=None):
+    """(n, H, W) of `shape` after THE frame-limit check: frames.h's sizes_ok by default.  side / pixels / total: the op's limit on a
+    side, on H W and on n H W (None: no limit); least: the smallest side; msg: the refusal's text where the op has its own."""
+    n, H, W = (int(v) for v in shape)
+    limits = ((n, FRAME_MAX_IMAGES), (max(H, W), side), (H * W, pixels), (n * H * W, total))
+    if min(H, W) < least or any(cap is not None and v > cap for v, cap in limits):
+        raise ValueError(msg or f"{who}: unsupported shape {tuple(shape)} (n <= {FRAME_MAX_IMAGES}, H, W >= 1, H*W <= 2^24, n*H*W <= 2^30)")
+    return n, H, W
+
+
+def _chk_maps(maps, who, what="maps", dtype=torch.float64):
+    _chk(maps, dtype, f"{who}.{what}")
+    if maps.dim() != 3:
+        raise ValueError(f"{who}: {what} must be [n,H,W], got {tuple(maps.shape)}")
+    return _frames(maps.shape, who)
+
+
+def _on_device(dev, who, **tensors):
+    for name, t in tensors.items():
+        if t is not None and t.device != dev:
+            raise ValueError(f"{who}.{name}: must be on {dev}, got {t.device}")
+
+
+def _chk_out(t, dtype, shape, dev, name):
+    _chk(t, dtype, name)
+    if tuple(t.shape) != tuple(shape) or t.device != dev:
+        raise ValueError(f"{name}: must be {tuple(shape)} {dtype} on {dev}, got {tuple(t.shape)} on {t.device}")
+
+
+def _out(t, dtype, shape, dev, name, zero=False):
+    """the caller's buffer after _chk_out, or a fresh one"""
+    if t is None:
+        return (torch.zeros if zero else torch.empty)(tuple(shape), dtype=dtype, device=dev)
+    _chk_out(t, dtype, shape, dev, name)
+    return t
+
+
+def _chk_region_tables(count, ints, n, who):
+    """count [n] i32 and ints [n,K,8] i32, region_table's -> K"""
+    _chk(count, torch.int32, f"{who}.count"); _chk(ints, torch.int32, f"{who}.ints")
+    if count.numel() != n or ints.dim() != 3 or ints.shape[0] != n or ints.shape[2] != 8 or not 1 <= ints.shape[1] <= REGION_MAX:
+        raise ValueError(f"{who}: count must be [{n}] and ints [{n},K,8] with K in 1..{REGION_MAX}; got {tuple(count.shape)}, "
+                         f"{tuple(ints.shape)}")
+    return ints.shape[1]
+
+
+def _chk_colours(who, n, H, W, lohi, lut, alpha, background, mean, std):
+    """the colour arguments overlay_render and mesh_write share, for an output of H x W -> (background kind, 1 where lohi is per
+    image, mean, std as floats)"""
+    _chk(lohi, torch.float64, f"{who}.lohi"); _chk(lut, torch.uint8, f"{who}.lut"); _chk(alpha, torch.uint8, f"{who}.alpha")
+    if lohi is None or lut is None or alpha is None:
+        raise ValueError(f"{who}: lohi, lut and alpha are required")
+    if tuple(lohi.shape) not in ((2,), (1, 2), (n, 2)) or tuple(lut.shape) != (256, 3) or tuple(alpha.shape) != (256,):
+        raise ValueError(f"{who}: lohi must be [2] or [{n},2], lut [256,3], alpha [256]; got {tuple(lohi.shape)}, "
+                         f"{tuple(lut.shape)}, {tuple(alpha.shape)}")
+    kind = 0
+    if background is not None:
+        if background.dtype not in OVERLAY_BACKGROUNDS[1:]:
+            raise TypeError(f"{who}.background: expected uint8 [n,{H},{W},3] or float32 [n,3,{H},{W}], got {background.dtype}")
+        kind = OVERLAY_BACKGROUNDS.index(background.dtype)
+        _chk(background, background.dtype, f"{who}.background")
+        want = (n, H, W, 3) if kind == 1 else (n, 3, H, W)
+        if tuple(background.shape) != want:
+            raise ValueError(f"{who}: a {background.dtype} background must be {want} (the output's size: it is not resampled), "
+                             f"got {tuple(background.shape)}")
+    mean, std = [float(v) for v in mean], [float(v) for v in std]
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError(f"{who}: mean and std are three values each")
+    return kind, int(lohi.numel() == 2 * n and n > 1), mean, std
+
+
 # ------------------------------------------------------------------------------------ scan preprocessing (docs/preprocessing.md)
 def plane_ransac(points, n=50, iterations=1000, distance_threshold=0.004, seed=0):
     """points [E,3] f32 -> (plane [4] f64 = (a, b, c, d) with unit normal and c >= 0, info [2] int32 = {inliers, winning hypothesis}),
@@ -1377,7 +1456,6 @@ def eyecandies_background(points):
 SORT_TILE = 4096          # keys per block of a radix pass (cmdiad_sort_u64_tile): sizes around its multiples change the passes' shape
 PRO_MAX_THRESHOLDS = 1024  # cmdiad_pro_hist keeps the thresholds in LDS
 # (the u64 keys travel in int64 tensors, bit for bit, as the search keys do: torch indexes and copies int64 everywhere)
-METRICS_MAX_TOTAL = 1 << 30
 
 
 def ccl_label(masks):
@@ -1386,12 +1464,7 @@ def ccl_label(masks):
     8-connected, numbered as scipy.ndimage.label(mask, ones((3,3))) numbers them.  No synchronisation."""
     if masks.dtype not in (torch.float32, torch.uint8):
         raise TypeError(f"ccl_label.masks: expected torch.float32 or torch.uint8, got {masks.dtype}")
-    _chk(masks, masks.dtype, "ccl_label.masks")
-    if masks.dim() != 3:
-        raise ValueError(f"ccl_label: masks must be [n,H,W], got {tuple(masks.shape)}")
-    n, H, W = masks.shape
-    if H < 1 or W < 1 or H * W > (1 << 24) or n > 65535 or n * H * W > METRICS_MAX_TOTAL:
-        raise ValueError(f"ccl_label: unsupported shape {tuple(masks.shape)} (n <= 65535, H, W >= 1, H*W <= 2^24, n*H*W <= 2^30)")
+    n, H, W = _chk_maps(masks, "ccl_label", "masks", masks.dtype)
     dev = masks.device
     cap = n * ((H + 1) // 2) * ((W + 1) // 2)
     labels = torch.empty((n, H, W), dtype=torch.int32, device=dev)
@@ -1409,7 +1482,7 @@ def ccl_label(masks):
 
 def _chk_list(t, dtype, name):
     _chk(t, dtype, name)
-    if t.dim() != 1 or t.numel() > METRICS_MAX_TOTAL:
+    if t.dim() != 1 or t.numel() > FRAME_MAX_TOTAL:
         raise ValueError(f"{name}: must be one-dimensional with at most 2^30 entries, got {tuple(t.shape)}")
     return t.numel()
 
@@ -1450,10 +1523,11 @@ def metrics_split(preds, labels, comp_offset, ok_cap, def_cap):
     if preds.dim() != 3 or preds.shape != labels.shape or comp_offset.numel() != preds.shape[0] + 1:
         raise ValueError(f"metrics_split: preds {tuple(preds.shape)} and labels {tuple(labels.shape)} must be the same [n,H,W], "
                          f"comp_offset [n+1] (got {comp_offset.numel()})")
-    n, H, W = preds.shape
+    refusal = f"metrics_split: unsupported sizes {tuple(preds.shape)} ok_cap={ok_cap} def_cap={def_cap}"
+    n, H, W = _frames(preds.shape, "metrics_split", least=0, msg=refusal)
     total = n * H * W
-    if n > 65535 or H * W > (1 << 24) or total > METRICS_MAX_TOTAL or not (0 <= ok_cap <= total and 0 <= def_cap <= total):
-        raise ValueError(f"metrics_split: unsupported sizes {tuple(preds.shape)} ok_cap={ok_cap} def_cap={def_cap}")
+    if not (0 <= ok_cap <= total and 0 <= def_cap <= total):
+        raise ValueError(refusal)
     dev = preds.device
     ok_keys = torch.empty((ok_cap,), dtype=torch.int64, device=dev)
     def_score = torch.empty((def_cap,), dtype=torch.float64, device=dev)
@@ -1497,16 +1571,6 @@ def pro_hist(thr, def_score, def_comp, total_comp):
 REGION_MAX = 64          # cmdiad_region_table: slots per image
 
 
-def _chk_maps(maps, who):
-    _chk(maps, torch.float64, f"{who}.maps")
-    if maps.dim() != 3:
-        raise ValueError(f"{who}: maps must be [n,H,W], got {tuple(maps.shape)}")
-    n, H, W = maps.shape
-    if H < 1 or W < 1 or H * W > (1 << 24) or n > 65535 or n * H * W > METRICS_MAX_TOTAL:
-        raise ValueError(f"{who}: unsupported shape {tuple(maps.shape)} (n <= 65535, H, W >= 1, H*W <= 2^24, n*H*W <= 2^30)")
-    return n, H, W
-
-
 def threshold_mask(maps, thr, mask=None, nan_count=None):
     """maps [n,H,W] f64, thr f64 ON THE DEVICE with 1 or n entries -> (mask [n,H,W] u8 = maps > thr, nan_count [1] i32 = NaN scores,
     which stay background).  -0.0 > +0.0 is false.  The threshold is read by the kernel: rewriting `thr` in place changes what the
@@ -1515,14 +1579,8 @@ def threshold_mask(maps, thr, mask=None, nan_count=None):
     _chk(thr, torch.float64, "threshold_mask.thr")
     if thr.numel() not in (1, n) or thr.device != maps.device:
         raise ValueError(f"threshold_mask: thr must hold 1 or n = {n} values on the maps' device, got {tuple(thr.shape)} on {thr.device}")
-    dev = maps.device
-    if mask is None:
-        mask = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
-    if nan_count is None:
-        nan_count = torch.zeros((1,), dtype=torch.int32, device=dev)
-    _chk(mask, torch.uint8, "threshold_mask.mask"); _chk(nan_count, torch.int32, "threshold_mask.nan_count")
-    if mask.shape != maps.shape or nan_count.numel() != 1:
-        raise ValueError("threshold_mask: mask must have the maps' shape and nan_count one entry")
+    mask = _out(mask, torch.uint8, (n, H, W), maps.device, "threshold_mask.mask")
+    nan_count = _out(nan_count, torch.int32, (1,), maps.device, "threshold_mask.nan_count", zero=True)
     if n:
         _call("cmdiad_threshold_mask", _p(maps), _p(thr), int(thr.numel() == n and n > 1), n, H, W, _p(mask), _p(nan_count), _stream())
     return mask, nan_count
@@ -1544,9 +1602,7 @@ def region_table(maps, labels, n_comp, comp_offset, comp_size, min_area=1, max_r
         raise ValueError(f"region_table: maps {tuple(maps.shape)} need labels of that shape, n_comp [n], comp_offset [n+1] and comp_size "
                          f"[>= {cap}]; got {tuple(labels.shape)}, {n_comp.numel()}, {comp_offset.numel()}, {comp_size.numel()}")
     dev = maps.device
-    for t in (labels, n_comp, comp_offset, comp_size):
-        if t.device != dev:
-            raise ValueError("region_table: every tensor must be on the maps' device")
+    _on_device(dev, "region_table", labels=labels, n_comp=n_comp, comp_offset=comp_offset, comp_size=comp_size)
     count = torch.zeros((n,), dtype=torch.int32, device=dev)
     ints = torch.zeros((n, K, 8), dtype=torch.int32, device=dev)
     vals = torch.zeros((n, K, 4), dtype=torch.float64, device=dev)
@@ -1570,8 +1626,7 @@ def pr_runs(def_sorted_keys, ok_sorted_keys):
     n_def = _chk_list(def_sorted_keys, torch.int64, "pr_runs.def_sorted_keys")
     n_ok = _chk_list(ok_sorted_keys, torch.int64, "pr_runs.ok_sorted_keys")
     dev = def_sorted_keys.device
-    if ok_sorted_keys.device != dev:
-        raise ValueError("pr_runs: both key lists must be on one device")
+    _on_device(dev, "pr_runs", ok_sorted_keys=ok_sorted_keys)
     run_key = torch.empty((n_def,), dtype=torch.int64, device=dev)
     run_first = torch.empty((n_def,), dtype=torch.int32, device=dev)
     run_fp = torch.empty((n_def,), dtype=torch.int32, device=dev)
@@ -1592,11 +1647,10 @@ def pr_f1max(run_first, run_fp, n_runs, n_def):
         raise ValueError("pr_f1max: run_first and run_fp differ in length")
     _chk(n_runs, torch.int32, "pr_f1max.n_runs")
     n_def = int(n_def)
-    if n_runs.numel() != 1 or not 0 <= n_def <= METRICS_MAX_TOTAL:
+    if n_runs.numel() != 1 or not 0 <= n_def <= FRAME_MAX_TOTAL:
         raise ValueError(f"pr_f1max: n_runs must hold one entry and n_def = {n_def} lie in 0..2^30")
     dev = run_first.device
-    if run_fp.device != dev or n_runs.device != dev:
-        raise ValueError("pr_f1max: every tensor must be on one device")
+    _on_device(dev, "pr_f1max", run_fp=run_fp, n_runs=n_runs)
     best = torch.tensor([-1, 0], dtype=torch.int64, device=dev)
     if cap:
         partial = torch.empty((min(-(-cap // PR_F1_BLOCK), PR_F1_MAX_BLOCKS),), dtype=torch.int32, device=dev)   # the first stage's winners
@@ -1621,16 +1675,13 @@ def region_overlap(gt_labels, gt_comp_offset, pred_labels, pred_comp_offset, pre
     _chk_labelling(gt_labels, gt_comp_offset, "region_overlap", "gt")
     _chk_labelling(pred_labels, pred_comp_offset, "region_overlap", "pred")
     _chk(pred_comp_size, torch.int32, "region_overlap.pred_comp_size")
-    n, H, W = gt_labels.shape
-    if H < 1 or W < 1 or H * W > (1 << 24) or n > 65535 or n * H * W > METRICS_MAX_TOTAL:
-        raise ValueError(f"region_overlap: unsupported shape {tuple(gt_labels.shape)} (n <= 65535, H, W >= 1, H*W <= 2^24, n*H*W <= 2^30)")
+    n, H, W = _frames(gt_labels.shape, "region_overlap")
     if pred_labels.shape != gt_labels.shape or pred_comp_size.dim() != 1:
         raise ValueError(f"region_overlap: gt_labels {tuple(gt_labels.shape)} and pred_labels {tuple(pred_labels.shape)} must be the same "
                          "[n,H,W], pred_comp_size one-dimensional")
     dev = gt_labels.device
-    for t in (gt_comp_offset, pred_labels, pred_comp_offset, pred_comp_size):
-        if t.device != dev:
-            raise ValueError("region_overlap: every tensor must be on one device")
+    _on_device(dev, "region_overlap", gt_comp_offset=gt_comp_offset, pred_labels=pred_labels, pred_comp_offset=pred_comp_offset,
+               pred_comp_size=pred_comp_size)
     covered = torch.zeros((n * ((H + 1) // 2) * ((W + 1) // 2),), dtype=torch.int32, device=dev)
     hits = torch.zeros((pred_comp_size.numel(),), dtype=torch.int32, device=dev)
     if n:
@@ -1649,13 +1700,11 @@ def detection_counts(gt_comp_offset, covered, pred_comp_offset, pred_comp_size, 
                     (pred_comp_size, "pred_comp_size"), (hits, "hits")):
         _chk_list(t, torch.int32, f"detection_counts.{name}")
     n = gt_comp_offset.numel() - 1
-    if n < 0 or n > 65535 or pred_comp_offset.numel() != n + 1 or hits.numel() != pred_comp_size.numel():
-        raise ValueError(f"detection_counts: gt_comp_offset and pred_comp_offset must both be [n+1] (n <= 65535), hits as long as "
+    if n < 0 or n > FRAME_MAX_IMAGES or pred_comp_offset.numel() != n + 1 or hits.numel() != pred_comp_size.numel():
+        raise ValueError(f"detection_counts: gt_comp_offset and pred_comp_offset must both be [n+1] (n <= {FRAME_MAX_IMAGES}), hits as long as "
                          f"pred_comp_size; got {gt_comp_offset.numel()}, {pred_comp_offset.numel()}, {hits.numel()}, {pred_comp_size.numel()}")
     dev = gt_comp_offset.device
-    for t in (covered, pred_comp_offset, pred_comp_size, hits):
-        if t.device != dev:
-            raise ValueError("detection_counts: every tensor must be on one device")
+    _on_device(dev, "detection_counts", covered=covered, pred_comp_offset=pred_comp_offset, pred_comp_size=pred_comp_size, hits=hits)
     counts = torch.zeros((n, 4), dtype=torch.int32, device=dev)
     if n:
         _call("cmdiad_detection_counts", _p(gt_comp_offset), _p(covered), covered.numel(), _p(pred_comp_offset), _p(pred_comp_size),
@@ -1687,39 +1736,24 @@ def region_measure(labels, count, ints, cloud, out=None, layout=None):
     planar [n,3,H,W] or interleaved [n,H,W,3] (worked out from the shape; layout= where H or W is 3) -> (m_ints [n,K,4] i32 = n_pts,
     n_tri, peak_valid, 0; m_vals [n,K,20] f64 = lo, hi, peak_xyz, s1, s2, area, 0; bad_count [1] i32 = points with a non-finite
     coordinate).  out: that triple, to write into.  docs/regions.md has the contract.  No synchronisation."""
-    _chk(labels, torch.int32, "region_measure.labels"); _chk(count, torch.int32, "region_measure.count")
-    _chk(ints, torch.int32, "region_measure.ints"); _chk(cloud, torch.float32, "region_measure.cloud")
-    if labels.dim() != 3:
-        raise ValueError(f"region_measure: labels must be [n,H,W], got {tuple(labels.shape)}")
-    n, H, W = labels.shape
-    if H < 1 or W < 1 or H * W > (1 << 24) or n > 65535 or n * H * W > METRICS_MAX_TOTAL:
-        raise ValueError(f"region_measure: unsupported shape {tuple(labels.shape)} (n <= 65535, H, W >= 1, H*W <= 2^24, n*H*W <= 2^30)")
-    if count.numel() != n or ints.dim() != 3 or ints.shape[0] != n or ints.shape[2] != 8 or not 1 <= ints.shape[1] <= REGION_MAX:
-        raise ValueError(f"region_measure: count must be [{n}] and ints [{n},K,8] with K in 1..{REGION_MAX}; got {tuple(count.shape)}, "
-                         f"{tuple(ints.shape)}")
-    K = ints.shape[1]
+    n, H, W = _chk_maps(labels, "region_measure", "labels", torch.int32)
+    K = _chk_region_tables(count, ints, n, "region_measure")
+    _chk(cloud, torch.float32, "region_measure.cloud")
     planar = cloud_layout(cloud, H, W, layout) == "planar"
     if cloud.shape[0] != n:
         raise ValueError(f"region_measure: {cloud.shape[0]} clouds for {n} label images")
     dev = labels.device
-    if out is None:
-        out = (torch.empty((n, K, 4), dtype=torch.int32, device=dev), torch.empty((n, K, 20), dtype=torch.float64, device=dev),
-               torch.zeros((1,), dtype=torch.int32, device=dev))
-    m_ints, m_vals, bad_count = out
-    _chk(m_ints, torch.int32, "region_measure.m_ints"); _chk(m_vals, torch.float64, "region_measure.m_vals")
-    _chk(bad_count, torch.int32, "region_measure.bad_count")
-    if tuple(m_ints.shape) != (n, K, 4) or tuple(m_vals.shape) != (n, K, 20) or bad_count.numel() != 1:
-        raise ValueError(f"region_measure: out must be ([{n},{K},4] i32, [{n},{K},20] f64, [1] i32)")
-    for t in (count, ints, cloud, m_ints, m_vals, bad_count):
-        if t.device != dev:
-            raise ValueError("region_measure: every tensor must be on the labels' device")
+    _on_device(dev, "region_measure", count=count, ints=ints, cloud=cloud)
+    m_ints, m_vals, bad_count = out or (None, None, None)
+    m_ints = _out(m_ints, torch.int32, (n, K, 4), dev, "region_measure.m_ints")
+    m_vals = _out(m_vals, torch.float64, (n, K, 20), dev, "region_measure.m_vals")
+    bad_count = _out(bad_count, torch.int32, (1,), dev, "region_measure.bad_count", zero=True)
     _call("cmdiad_region_measure", _p(labels), _p(count), _p(ints), _p(cloud), 1 if planar else 3, H * W if planar else 1, n, H, W, K,
           _p(m_ints), _p(m_vals), _p(bad_count), _stream())
     return m_ints, m_vals, bad_count
 
 
 # ------------------------------------------------------------------------------------ overlays (docs/overlay.md)
-OVERLAY_MAX_SIDE = 1 << 14
 OVERLAY_BACKGROUNDS = (None, torch.uint8, torch.float32)     # the index is cmdiad_overlay_render's background kind
 PNG_FILTER_MODES = ("none", "sub", "up", "average", "paeth", "adaptive")     # the index is cmdiad_png_filter's mode
 
@@ -1742,55 +1776,24 @@ def overlay_render(maps, lohi, lut, alpha, size=None, thr=None, background=None,
     n, H, W = _chk_maps(maps, "overlay_render")
     dev = maps.device
     Ho, Wo = (H, W) if size is None else (int(size[0]), int(size[1]))
-    if not (1 <= H <= OVERLAY_MAX_SIDE and 1 <= W <= OVERLAY_MAX_SIDE and 1 <= Ho <= OVERLAY_MAX_SIDE and 1 <= Wo <= OVERLAY_MAX_SIDE) \
-            or n * Ho * Wo > METRICS_MAX_TOTAL:
-        raise ValueError(f"overlay_render: maps {tuple(maps.shape)} -> canvas {Ho} x {Wo}: sides 1..2^14, n*Ho*Wo <= 2^30")
-    _chk(lohi, torch.float64, "overlay_render.lohi"); _chk(lut, torch.uint8, "overlay_render.lut"); _chk(alpha, torch.uint8, "overlay_render.alpha")
-    if lohi is None or lut is None or alpha is None:
-        raise ValueError("overlay_render: lohi, lut and alpha are required")
-    if tuple(lohi.shape) not in ((2,), (1, 2), (n, 2)) or tuple(lut.shape) != (256, 3) or tuple(alpha.shape) != (256,):
-        raise ValueError(f"overlay_render: lohi must be [2] or [{n},2], lut [256,3], alpha [256]; got {tuple(lohi.shape)}, "
-                         f"{tuple(lut.shape)}, {tuple(alpha.shape)}")
+    refusal = f"overlay_render: maps {tuple(maps.shape)} -> canvas {Ho} x {Wo}: sides 1..2^14, n*Ho*Wo <= 2^30"
+    _frames(maps.shape, "overlay_render", side=FRAME_MAX_SIDE, msg=refusal)
+    _frames((n, Ho, Wo), "overlay_render", side=FRAME_MAX_SIDE, pixels=None, msg=refusal)
+    kind, lohi_per_image, mean, std = _chk_colours("overlay_render", n, Ho, Wo, lohi, lut, alpha, background, mean, std)
     _chk(thr, torch.float64, "overlay_render.thr")
     if thr is not None and thr.numel() not in (1, n):
         raise ValueError(f"overlay_render: thr must hold 1 or n = {n} values, got {tuple(thr.shape)}")
-    kind = 0
-    if background is not None:
-        if background.dtype not in OVERLAY_BACKGROUNDS[1:]:
-            raise TypeError(f"overlay_render.background: expected uint8 [n,Ho,Wo,3] or float32 [n,3,Ho,Wo], got {background.dtype}")
-        kind = OVERLAY_BACKGROUNDS.index(background.dtype)
-        _chk(background, background.dtype, "overlay_render.background")
-        want = (n, Ho, Wo, 3) if kind == 1 else (n, 3, Ho, Wo)
-        if tuple(background.shape) != want:
-            raise ValueError(f"overlay_render: a {background.dtype} background must be {want} (the canvas size: it is not resampled), "
-                             f"got {tuple(background.shape)}")
     if (count is None) != (ints is None):
         raise ValueError("overlay_render: count and ints come together")
-    K = 1
-    if count is not None:
-        _chk(count, torch.int32, "overlay_render.count"); _chk(ints, torch.int32, "overlay_render.ints")
-        if count.numel() != n or ints.dim() != 3 or ints.shape[0] != n or ints.shape[2] != 8 or not 1 <= ints.shape[1] <= REGION_MAX:
-            raise ValueError(f"overlay_render: count must be [{n}] and ints [{n},K,8] with K in 1..{REGION_MAX}; got "
-                             f"{tuple(count.shape)}, {tuple(ints.shape)}")
-        K = ints.shape[1]
+    K = 1 if count is None else _chk_region_tables(count, ints, n, "overlay_render")
     line_px = int(line_px)
     if not 1 <= line_px <= 8:
         raise ValueError(f"overlay_render: line_px = {line_px} (1..8)")
-    mean, std = [float(v) for v in mean], [float(v) for v in std]
-    if len(mean) != 3 or len(std) != 3:
-        raise ValueError("overlay_render: mean and std are three values each")
-    if canvas is None:
-        canvas = torch.empty((n, Ho, Wo, 3), dtype=torch.uint8, device=dev)
-    if nan_count is None:
-        nan_count = torch.zeros((1,), dtype=torch.int32, device=dev)
-    _chk(canvas, torch.uint8, "overlay_render.canvas"); _chk(nan_count, torch.int32, "overlay_render.nan_count")
-    if tuple(canvas.shape) != (n, Ho, Wo, 3) or nan_count.numel() != 1:
-        raise ValueError(f"overlay_render: canvas must be {(n, Ho, Wo, 3)} and nan_count one entry")
-    for t in (lohi, lut, alpha, thr, background, count, ints, canvas, nan_count):
-        if t is not None and t.device != dev:
-            raise ValueError("overlay_render: every tensor must be on the maps' device")
+    _on_device(dev, "overlay_render", lohi=lohi, lut=lut, alpha=alpha, thr=thr, background=background, count=count, ints=ints)
+    canvas = _out(canvas, torch.uint8, (n, Ho, Wo, 3), dev, "overlay_render.canvas")
+    nan_count = _out(nan_count, torch.int32, (1,), dev, "overlay_render.nan_count", zero=True)
     if n:
-        _call("cmdiad_overlay_render", _p(maps), n, H, W, Ho, Wo, _p(lohi), int(lohi.numel() == 2 * n and n > 1), _p(thr),
+        _call("cmdiad_overlay_render", _p(maps), n, H, W, Ho, Wo, _p(lohi), lohi_per_image, _p(thr),
               int(thr is not None and thr.numel() == n and n > 1), _p(background), kind, *mean, *std, _p(lut), _p(alpha), _p(count),
               _p(ints), K, line_px, _rgb_word(contour_rgb, "overlay_render.contour_rgb"), _rgb_word(box_rgb, "overlay_render.box_rgb"),
               _p(canvas), _p(nan_count), _stream())
@@ -1808,9 +1811,11 @@ def png_filter(images_u8, mode="adaptive", out=None):
         images_u8 = images_u8.unsqueeze(-1)
     if images_u8.dim() != 4:
         raise ValueError(f"png_filter: images must be [n,H,W,C] or [n,H,W], got {tuple(images_u8.shape)}")
-    n, H, W, C = images_u8.shape
-    if not (1 <= H <= OVERLAY_MAX_SIDE and 1 <= W <= OVERLAY_MAX_SIDE and 1 <= C <= 4 and n <= 65535):
-        raise ValueError(f"png_filter: unsupported shape {tuple(images_u8.shape)} (n <= 65535, sides 1..2^14, C in 1..4)")
+    refusal = f"png_filter: unsupported shape {tuple(images_u8.shape)} (n <= {FRAME_MAX_IMAGES}, sides 1..2^14, C in 1..4)"
+    n, H, W = _frames(images_u8.shape[:3], "png_filter", side=FRAME_MAX_SIDE, pixels=None, total=None, msg=refusal)
+    C = images_u8.shape[3]
+    if not 1 <= C <= 4:
+        raise ValueError(refusal)
     if isinstance(mode, str):
         if mode not in PNG_FILTER_MODES:
             raise ValueError(f"png_filter: mode must be one of {PNG_FILTER_MODES}, got {mode!r}")
@@ -1818,13 +1823,7 @@ def png_filter(images_u8, mode="adaptive", out=None):
     mode = int(mode)
     if not 0 <= mode <= 5:
         raise ValueError(f"png_filter: mode = {mode} (0..5)")
-    shape = (n, H * (1 + W * C))
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=images_u8.device)
-    else:
-        _chk(out, torch.uint8, "png_filter.out")
-        if tuple(out.shape) != shape or out.device != images_u8.device:
-            raise ValueError(f"png_filter: out must be {shape} on the images' device, got {tuple(out.shape)} on {out.device}")
+    out = _out(out, torch.uint8, (n, H * (1 + W * C)), images_u8.device, "png_filter.out")
     if n:
         _call("cmdiad_png_filter", _p(images_u8), n, H, W, C, mode, _p(out), _stream())
     return out
@@ -1833,15 +1832,13 @@ def png_filter(images_u8, mode="adaptive", out=None):
 # ------------------------------------------------------------------------------------ meshes (docs/mesh.md)
 MESH_CHUNK = 1024                 # pixels per entry of cmdiad_mesh_count's chunks table
 MESH_VERTEX_BYTES, MESH_FACE_BYTES = 35, 13
-MESH_MAX_TOTAL = 1 << 24
 
 
 def _mesh_geometry(cloud, maps, max_edge2, layout, who):
     """the checks mesh_count and mesh_write share -> (n, H, W, planar, max_edge2)"""
     n, H, W = _chk_maps(maps, who)
     _chk(cloud, torch.float32, f"{who}.cloud")
-    if H > OVERLAY_MAX_SIDE or W > OVERLAY_MAX_SIDE or n * H * W > MESH_MAX_TOTAL:
-        raise ValueError(f"{who}: maps {tuple(maps.shape)}: sides 1..2^14, n*H*W <= 2^24")
+    _frames(maps.shape, who, side=FRAME_MAX_SIDE, total=MESH_MAX_TOTAL, msg=f"{who}: maps {tuple(maps.shape)}: sides 1..2^14, n*H*W <= 2^24")
     planar = cloud_layout(cloud, H, W, layout, who) == "planar"
     if cloud.shape[0] != n or cloud.device != maps.device:
         raise ValueError(f"{who}: {cloud.shape[0]} clouds on {cloud.device} for {n} maps on {maps.device}")
@@ -1858,12 +1855,9 @@ def mesh_count(cloud, maps, max_edge2=float("inf"), out=None, layout=None):
     synchronisation."""
     n, H, W, planar, max_edge2 = _mesh_geometry(cloud, maps, max_edge2, layout, "mesh_count")
     dev, C = maps.device, -(-H * W // MESH_CHUNK)
-    if out is None:
-        out = (torch.empty((n, C, 2), dtype=torch.int32, device=dev), torch.empty((n, 4), dtype=torch.int32, device=dev))
-    chunks, counts = out
-    _chk(chunks, torch.int32, "mesh_count.chunks"); _chk(counts, torch.int32, "mesh_count.counts")
-    if tuple(chunks.shape) != (n, C, 2) or tuple(counts.shape) != (n, 4) or chunks.device != dev or counts.device != dev:
-        raise ValueError(f"mesh_count: out must be ([{n},{C},2] i32, [{n},4] i32) on the maps' device")
+    chunks, counts = out or (None, None)
+    chunks = _out(chunks, torch.int32, (n, C, 2), dev, "mesh_count.chunks")
+    counts = _out(counts, torch.int32, (n, 4), dev, "mesh_count.counts")
     if n:
         _call("cmdiad_mesh_count", _p(cloud), 1 if planar else 3, H * W if planar else 1, _p(maps), n, H, W, max_edge2, _p(chunks),
               _p(counts), _stream())
@@ -1879,48 +1873,26 @@ def mesh_write(cloud, maps, chunks, lohi, lut, alpha, background=None, mean=(0.0
     n, H, W, planar, max_edge2 = _mesh_geometry(cloud, maps, max_edge2, layout, "mesh_write")
     dev, C = maps.device, -(-H * W // MESH_CHUNK)
     _chk(chunks, torch.int32, "mesh_write.chunks"); _chk(labels, torch.int32, "mesh_write.labels")
-    _chk(lohi, torch.float64, "mesh_write.lohi"); _chk(lut, torch.uint8, "mesh_write.lut"); _chk(alpha, torch.uint8, "mesh_write.alpha")
-    if chunks is None or lohi is None or lut is None or alpha is None:
+    if chunks is None:
         raise ValueError("mesh_write: chunks, lohi, lut and alpha are required")
     if tuple(chunks.shape) != (n, C, 2):
         raise ValueError(f"mesh_write: chunks must be [{n},{C},2] (mesh_count's), got {tuple(chunks.shape)}")
-    if tuple(lohi.shape) not in ((2,), (1, 2), (n, 2)) or tuple(lut.shape) != (256, 3) or tuple(alpha.shape) != (256,):
-        raise ValueError(f"mesh_write: lohi must be [2] or [{n},2], lut [256,3], alpha [256]; got {tuple(lohi.shape)}, "
-                         f"{tuple(lut.shape)}, {tuple(alpha.shape)}")
+    kind, lohi_per_image, mean, std = _chk_colours("mesh_write", n, H, W, lohi, lut, alpha, background, mean, std)
     if labels is not None and labels.shape != maps.shape:
         raise ValueError(f"mesh_write: labels must have the maps' shape {tuple(maps.shape)}, got {tuple(labels.shape)}")
-    kind = 0
-    if background is not None:
-        if background.dtype not in OVERLAY_BACKGROUNDS[1:]:
-            raise TypeError(f"mesh_write.background: expected uint8 [n,H,W,3] or float32 [n,3,H,W], got {background.dtype}")
-        kind = OVERLAY_BACKGROUNDS.index(background.dtype)
-        _chk(background, background.dtype, "mesh_write.background")
-        want = (n, H, W, 3) if kind == 1 else (n, 3, H, W)
-        if tuple(background.shape) != want:
-            raise ValueError(f"mesh_write: a {background.dtype} background must be {want}, got {tuple(background.shape)}")
-    mean, std = [float(v) for v in mean], [float(v) for v in std]
-    if len(mean) != 3 or len(std) != 3:
-        raise ValueError("mesh_write: mean and std are three values each")
-    shapes = ((n, H, W), (n, H * W * MESH_VERTEX_BYTES), (n, 2 * (H - 1) * (W - 1) * MESH_FACE_BYTES))
-    if out is None:
-        out = (torch.empty(shapes[0], dtype=torch.int32, device=dev), torch.empty(shapes[1], dtype=torch.uint8, device=dev),
-               torch.empty(shapes[2], dtype=torch.uint8, device=dev))
-    vidx, vertices, faces = out
-    _chk(vidx, torch.int32, "mesh_write.vidx"); _chk(vertices, torch.uint8, "mesh_write.vertices"); _chk(faces, torch.uint8, "mesh_write.faces")
-    if tuple(vidx.shape) != shapes[0] or tuple(vertices.shape) != shapes[1] or tuple(faces.shape) != shapes[2]:
-        raise ValueError(f"mesh_write: out must be ({shapes[0]} i32, {shapes[1]} u8, {shapes[2]} u8)")
-    for t in (chunks, lohi, lut, alpha, background, labels, vidx, vertices, faces):
-        if t is not None and t.device != dev:
-            raise ValueError("mesh_write: every tensor must be on the maps' device")
+    _on_device(dev, "mesh_write", chunks=chunks, lohi=lohi, lut=lut, alpha=alpha, background=background, labels=labels)
+    vidx, vertices, faces = out or (None, None, None)
+    vidx = _out(vidx, torch.int32, (n, H, W), dev, "mesh_write.vidx")
+    vertices = _out(vertices, torch.uint8, (n, H * W * MESH_VERTEX_BYTES), dev, "mesh_write.vertices")
+    faces = _out(faces, torch.uint8, (n, 2 * (H - 1) * (W - 1) * MESH_FACE_BYTES), dev, "mesh_write.faces")
     if n:
         _call("cmdiad_mesh_write", _p(cloud), 1 if planar else 3, H * W if planar else 1, _p(maps), n, H, W, _p(lohi),
-              int(lohi.numel() == 2 * n and n > 1), _p(lut), _p(alpha), _p(background), kind, *mean, *std, _p(labels), max_edge2,
+              lohi_per_image, _p(lut), _p(alpha), _p(background), kind, *mean, *std, _p(labels), max_edge2,
               int(bool(flip)), _p(chunks), _p(vidx), _p(vertices), _p(faces) if faces.numel() else None, _stream())
     return vidx, vertices, faces
 
 
 # ------------------------------------------------------------------------------------ point lists into the pixel grid (docs/organize.md)
-ORGANIZE_MAX_IMAGES, ORGANIZE_MAX_PIXELS, ORGANIZE_MAX_TOTAL = 65535, 1 << 24, 1 << 30
 ORGANIZE_KEY_EMPTY = -1           # all ones, as the int64 torch shows
 
 
@@ -1932,8 +1904,8 @@ def _chk_point_list(points, offsets, cams, max_len, who):
     if points.dim() != 2 or points.shape[1] != 3 or offsets.dim() != 1 or offsets.numel() < 1:
         raise ValueError(f"{who}: points must be [P,3] and offsets [n+1], got {tuple(points.shape)} and {tuple(offsets.shape)}")
     n, P = offsets.numel() - 1, points.shape[0]
-    if n > ORGANIZE_MAX_IMAGES or P >= 1 << 31:
-        raise ValueError(f"{who}: {n} clouds (at most {ORGANIZE_MAX_IMAGES}) of {P} points (below 2^31)")
+    if n > FRAME_MAX_IMAGES or P >= 1 << 31:
+        raise ValueError(f"{who}: {n} clouds (at most {FRAME_MAX_IMAGES}) of {P} points (below 2^31)")
     if offsets.device != points.device:
         raise ValueError(f"{who}: offsets on {offsets.device}, points on {points.device}")
     if cams is not None and (tuple(cams.shape) != (n, 16) or cams.device != points.device):
@@ -1945,16 +1917,7 @@ def _chk_point_list(points, offsets, cams, max_len, who):
 
 
 def _chk_grid(n, H, W, who):
-    H, W = int(H), int(W)
-    if H < 1 or W < 1 or H * W > ORGANIZE_MAX_PIXELS or n * H * W > ORGANIZE_MAX_TOTAL:
-        raise ValueError(f"{who}: a grid of {H} x {W} for {n} clouds: sides >= 1, H*W <= 2^24, n*H*W <= 2^30")
-    return H, W
-
-
-def _chk_out(t, dtype, shape, dev, name):
-    _chk(t, dtype, name)
-    if tuple(t.shape) != tuple(shape) or t.device != dev:
-        raise ValueError(f"{name}: must be {tuple(shape)} {dtype} on {dev}, got {tuple(t.shape)} on {t.device}")
+    return _frames((n, H, W), who, msg=f"{who}: a grid of {int(H)} x {int(W)} for {n} clouds: sides >= 1, H*W <= 2^24, n*H*W <= 2^30")[1:]
 
 
 def cloud_bounds(points, offsets, cams, max_len, out=None):
@@ -1965,10 +1928,9 @@ def cloud_bounds(points, offsets, cams, max_len, out=None):
     if cams is None:
         raise ValueError("cloud_bounds: cams is required")
     dev = points.device
-    if out is None:
-        out = (torch.empty((n, 6), dtype=torch.float64, device=dev), torch.empty((n,), dtype=torch.int32, device=dev))
-    bounds, count = out
-    _chk_out(bounds, torch.float64, (n, 6), dev, "cloud_bounds.bounds"); _chk_out(count, torch.int32, (n,), dev, "cloud_bounds.count")
+    bounds, count = out or (None, None)
+    bounds = _out(bounds, torch.float64, (n, 6), dev, "cloud_bounds.bounds")
+    count = _out(count, torch.int32, (n,), dev, "cloud_bounds.count")
     if n:
         _call("cmdiad_cloud_bounds", _p(points), _p(offsets), _p(cams), n, P, max_len, _p(bounds), _p(count), _stream())
     return bounds, count
@@ -1987,13 +1949,10 @@ def organize_splat(points, offsets, cams, max_len, kind, H, W, out=None):
     if kind not in (0, 1):
         raise ValueError(f"organize_splat: kind = {kind} (0 orthographic | 1 pinhole)")
     dev = points.device
-    if out is None:
-        out = (torch.empty((n, H, W), dtype=torch.int64, device=dev), torch.empty((P,), dtype=torch.int32, device=dev),
-               torch.zeros((n, 4), dtype=torch.int32, device=dev))
-    keys, pixel_of_point, stats = out
-    _chk_out(keys, torch.int64, (n, H, W), dev, "organize_splat.keys")
-    _chk_out(pixel_of_point, torch.int32, (P,), dev, "organize_splat.pixel_of_point")
-    _chk_out(stats, torch.int32, (n, 4), dev, "organize_splat.stats")
+    keys, pixel_of_point, stats = out or (None, None, None)
+    keys = _out(keys, torch.int64, (n, H, W), dev, "organize_splat.keys")
+    pixel_of_point = _out(pixel_of_point, torch.int32, (P,), dev, "organize_splat.pixel_of_point")
+    stats = _out(stats, torch.int32, (n, 4), dev, "organize_splat.stats", zero=True)
     if n:
         _call("cmdiad_organize_splat", _p(points), _p(offsets), _p(cams), n, P, max_len, kind, H, W, _p(keys), _p(pixel_of_point),
               _p(stats), _stream())
